@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - Groth16 proofs/sec for the confidential-transfer circuit on MI355X (BASELINE config 4 / 5).
 
-  python bench.py --gpus N --steps K --warmup W [--batch B]
+  python bench.py --gpus N --steps K --warmup W [--batch B] [--full] [--dump-outputs DIR]
 
 N > 1: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...` (RANK /
 LOCAL_RANK / WORLD_SIZE in the environment) the ranks are those processes; from a bare shell
@@ -21,18 +21,21 @@ bracketed by barrier + device synchronisation on both sides and contains the wit
 all K steps.  Ranks shard the proofs with no data-path collective; rank 0 gathers the 192-byte proofs
 of every step (RCCL gather, inside the timed region).
 
-Checked before the line is printed: a sample of proofs per rank byte-for-byte against the oracle's
-discrete-log proof of the same statement (and, on rank 0, one proof out of every rank's gathered
+A plain run sets up, warms up, times the K steps, writes the last step's proofs if --dump-outputs DIR is
+given (DIR/proofs.npy, float32, one row of 192 byte values per proof) and prints the line: the contract
+fields, `config` and `kernels` (per-kernel HIP-event totals of the timed region).
+
+With --full, checked before the line is printed: a sample of proofs per rank byte-for-byte against the
+oracle's discrete-log proof of the same statement (and, on rank 0, one proof out of every rank's gathered
 block; two proofs of EVERY step of the timed region likewise); ALL K * B proofs of the timed region by the
 product's batch verifier (outside the clock).
 
-The JSON line carries, besides the contract fields:
+With --full the JSON line also carries (cpu_baseline, secondary and micro can be turned off with --no-*):
   roofline      dominant kernel (G1 bucket accumulation): algorithmic bytes (128 B per multiexp
                 term) / its mean launch time, HIP events on the library's stream inside
                 the timed region, against the 8 TB/s HBM peak; the VALU-issue fraction beside it
   cpu_baseline  the C restatement of bellman's create_proof (oracle/c, kind "port") on this box's
                 host cores, a bounded sample
-  kernels       per-kernel HIP-event totals of the timed region
   secondary     the same batch from finished host witness vectors (no witness generation)
   micro         2^20 G1 multiexp (Mscalar/s) and the 2^20 NTT pair (GB/s) on one GPU
 """
@@ -321,7 +324,17 @@ def main():
                          "zk_anonymous_prove_batch, witness generation on the GPU: `secondary.anonymous` in the line.  The "
                          "statements come from the oracle (seconds of Python arithmetic each, cached under ZK_BENCH_CACHE): "
                          "min(N, 64) distinct ones, tiled to N, every proof with its own (r, s).  0 = off")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the parity gates (oracle proofs, the product's verifier, the circuit's "
+                         "fingerprint), roofline, CPU baseline, secondary, micro and anonymous figures.  The --no-*, "
+                         "--oracle-checks and --anonymous options act on these.  Off: set up, warm up, time the steps, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the proofs of the last timed step (rank 0: every rank's block) to "
+                         "DIR/proofs.npy as float32, one row of 192 byte values per proof; above 64 MB a fixed sample of rows "
+                         "(numpy default_rng(7)) goes to proofs.npy and their indices to proofs_index.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if args.micro_only:
         import torch
@@ -351,9 +364,9 @@ def main():
     items = None   # built natively once the library is loaded (make_statements_native); ZK_BENCH_ORACLE_STATEMENTS=1: the oracle's
     if os.environ.get("ZK_BENCH_ORACLE_STATEMENTS") == "1":
         items = make_statements(rank * args.batch, rank * args.batch + args.batch, host_threads)
-    req_items = make_requests(args.batch, host_threads) if (world == 1 and not args.no_secondary) else None
+    req_items = make_requests(args.batch, host_threads) if (args.full and world == 1 and not args.no_secondary) else None
     anon_items = None
-    if world == 1 and args.anonymous > 0 and not args.no_secondary:
+    if args.full and world == 1 and args.anonymous > 0 and not args.no_secondary:
         distinct = make_anonymous_statements(min(args.anonymous, 64), host_threads)
         anon_items = [distinct[i % len(distinct)] for i in range(args.anonymous)]
 
@@ -403,7 +416,7 @@ def main():
     lib.zk_set_host_threads(host_threads)
     t_st = time.time()
     if items is None:
-        items = make_statements_native(zk, lib, rank * args.batch, rank * args.batch + args.batch)
+        items = make_statements_native(zk, lib, rank * args.batch, rank * args.batch + args.batch, check=3 if args.full else 0)
     statements_s = time.time() - t_st
 
     B, K, W = args.batch, args.steps, args.warmup
@@ -411,11 +424,12 @@ def main():
     # the oracle's restatement of the circuit and the discrete logs of the CRS (5 s of Python) only on the rank that compares
     # proofs with the oracle byte for byte: rank 0 (its own block, and one proof out of every other rank's gathered block).
     # Every rank's proofs of the timed region are all verified by the product's verifier below.
-    oracle_checks = max(1, args.oracle_checks) if rank == 0 else 0
+    oracle_checks = max(1, args.oracle_checks) if (rank == 0 and args.full) else 0
     r1cs, P = build_circuit(host_threads) if oracle_checks > 0 else (None, None)
     mats = zk.ConstraintMatrices.transfer_circuit(device=dev_index, lib=lib)   # emitted natively (transfer_r1cs.h)
-    digest, _, _, _ = zk.transfer_r1cs_fingerprint(lib)
-    assert digest == "d23c92fb60ee547d45118e160679929cfa186957280673af62f09fa12d401784"   # confidential_transfer.rs:384
+    if args.full:
+        digest, _, _, _ = zk.transfer_r1cs_fingerprint(lib)
+        assert digest == "d23c92fb60ee547d45118e160679929cfa186957280673af62f09fa12d401784"   # confidential_transfer.rs:384
     t_setup = time.time()
     pk = zk.generate_parameters(mats, *helpers.TOXIC)   # bellman generate_parameters on the GPU (setup.cpp)
     keygen_s = time.time() - t_setup
@@ -505,8 +519,10 @@ def main():
                      "kernel_forms": {"g2_accumulate": int(x[7]), "reduce_level1": int(x[8]), "ms": [round(float(v), 4) for v in x[9:13]]},
                      "hbm_free_gb": round(float(x[13]), 1), "hbm_total_gb": round(float(x[14]), 1)}
                     for r, x in enumerate(allr)]
+    if args.dump_outputs and rank == 0:
+        dump_proofs(args.dump_outputs, gathered[-1] if world > 1 else outs[-1].tobytes())
 
-    # ---- parity gates: EVERY step of the timed region (two pipeline lanes alternate the chunks; VERDICT r2: the
+    # ---- parity gates (--full): EVERY step of the timed region (two pipeline lanes alternate the chunks; VERDICT r2: the
     # last step alone looks at one lane)
     last = outs[-1]
     last_rs = rs_ints[W + K - 1]
@@ -526,7 +542,7 @@ def main():
             checked += 1
     verified = None
     verify_ms = None
-    if hasattr(zk, "verify_transfer_batch"):
+    if args.full and hasattr(zk, "verify_transfer_batch"):
         # ALL K * B proofs of the timed region through the product's verifier (prepare_verifying_key + one verify_proof
         # per proof on the GPU; public inputs recomputed by the witness calculator from the statements) - outside the clock
         pvk = zk.prepare_verifying_key(params)
@@ -539,7 +555,7 @@ def main():
         verify_ms = (time.perf_counter() - t0) * 1e3 / K
         pvk.close()
     cross_rank = 0
-    if world > 1 and rank == 0:
+    if args.full and world > 1 and rank == 0:
         # rank 0's own block sits at the front of every gathered step; one proof out of every other rank's block of
         # the last step is re-derived here from its seed
         full = gathered[-1]
@@ -561,10 +577,11 @@ def main():
 
     total_proofs = B * world * K
     info = params.info
-    dens = [np.asarray(x, dtype=np.uint8) for x in (asg0.a_aux_density, asg0.b_input_density, asg0.b_aux_density)]
-    a_terms = N_IN + int(dens[0].sum()) + 2
-    b_terms = int(dens[1].sum()) + int(dens[2].sum()) + 1
-    g1_terms = info["n_h"] + info["n_l"] + a_terms + b_terms
+    if args.full:
+        dens = [np.asarray(x, dtype=np.uint8) for x in (asg0.a_aux_density, asg0.b_input_density, asg0.b_aux_density)]
+        a_terms = N_IN + int(dens[0].sum()) + 2
+        b_terms = int(dens[1].sum()) + int(dens[2].sum()) + 1
+        g1_terms = info["n_h"] + info["n_l"] + a_terms + b_terms
     chunk = int(os.environ.get("ZKAMD_BATCH_CHUNK", "1024"))
     roof = None
     # newest committed counter summary (tools/make_roofline.py over the rocprofv3 --pmc passes of a GPU session); it names
@@ -573,7 +590,7 @@ def main():
     cand = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]*_traffic.json")))
     TRAFFIC = os.path.relpath(cand[-1], ROOT) if cand else None
     CLOCK_HZ = 2.4e9                                            # nominal; the issue fractions below are against it
-    if "msm_accumulate_g1" in kernels:
+    if args.full and "msm_accumulate_g1" in kernels:
         k = kernels["msm_accumulate_g1"]
         n_chunks = max(1, (B + chunk - 1) // chunk) * K             # chunks proved in the timed region
         lpc = k["launches"] / n_chunks                               # launches of the dominant kernel per chunk (2: the C' set and the A set)
@@ -707,7 +724,7 @@ def main():
                 os.environ.pop("ZKAMD_NO_OVERLAP", None)
 
     cpu = None
-    if not args.no_cpu:
+    if args.full and not args.no_cpu:
         from oracle import cport
         cp = cport.Params(pk)
         n_cpu = min(max(cores, 8), 64)
@@ -751,7 +768,7 @@ def main():
                "single_proof_latency_s": round(lat, 3), "single_proof_threads": min(cores, 32)}
 
     secondary = None
-    if not args.no_secondary and world == 1:
+    if args.full and not args.no_secondary and world == 1:
         secondary = {}
         # (1) one call, nothing pipelined across calls: zk_transfer_prove_batch of one 1024-statement chunk
         zk.transfer_prove_batch(mats, params, sts, rs_ints[0])
@@ -970,7 +987,7 @@ def main():
             secondary["single_proof_error"] = repr(exc)[:200]
 
     micro = None
-    if not args.no_micro and world == 1:
+    if args.full and not args.no_micro and world == 1:
         micro = run_micro(lib, zk, dev)
     pipe.close()
     anonymous = None
@@ -1005,7 +1022,8 @@ def main():
                    "slow_ranks": [r for r in per_rank if r["proofs_per_s"] < 0.9 * sorted(x["proofs_per_s"] for x in per_rank)[len(per_rank) // 2]],
                    "proofs_checked_vs_oracle": checked, "proofs_checked_from_other_ranks": cross_rank,
                    "proofs_verified_by_product_verifier": verified, "verify_ms_per_step": None if verify_ms is None else round(verify_ms, 1), "setup_s": round(setup_s, 2), "statements_s": round(statements_s, 2), "generate_parameters_s": round(keygen_s, 2),
-                   "hbm_gb": {"total": round(hbm_total_b / 1e9, 1), "free_after_timed_region": round(hbm_free_b / 1e9, 1)}},
+                   "hbm_gb": {"total": round(hbm_total_b / 1e9, 1), "free_after_timed_region": round(hbm_free_b / 1e9, 1)},
+                   "full": args.full},
         "roofline": roof, "cpu_baseline": cpu, "kernels": kernels, "secondary": secondary, "micro": micro,
     }
     if anonymous is not None:
@@ -1013,6 +1031,23 @@ def main():
         if isinstance(line.get("secondary"), dict):
             line["secondary"]["anonymous"] = anonymous
     print(json.dumps(line), flush=True)
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_proofs(out_dir, proofs):
+    """The 192-byte proofs of one step as float32 rows (exact for byte values), at most DUMP_LIMIT_BYTES: beyond
+    that a fixed seeded sample of rows, in order, with their indices beside it."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    rows = np.frombuffer(bytes(proofs), dtype=np.uint8).reshape(-1, 192)
+    if len(rows) * 192 * 4 > DUMP_LIMIT_BYTES - 4096:      # (the .npy headers)
+        keep = (DUMP_LIMIT_BYTES - 4096) // (192 * 4 + 8)  # a float32 row and its float64 index each
+        idx = np.sort(np.random.default_rng(7).choice(len(rows), size=keep, replace=False))
+        rows = rows[idx]
+        np.save(os.path.join(out_dir, "proofs_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(out_dir, "proofs.npy"), rows.astype(np.float32))
 
 
 def splitmix_fields(seed, n, modulus):

@@ -46,3 +46,42 @@ def test_bench_line_contract(path):
         for key in ("value", "unit", "cores", "kind", "sample"):
             assert key in c, key
         assert c["kind"] in ("port", "reference") and c["cores"] >= 1
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("zk_bench_dump", os.path.join(ROOT, "bench.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    return mod
+
+
+def test_bench_options():
+    import subprocess
+    import sys
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr
+    for opt in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
+        assert opt in out.stdout, opt
+
+
+def test_dump_outputs_exact_and_bounded(tmp_path, monkeypatch):
+    """--dump-outputs: the proofs of a step as float32 byte values, row for row; above the size cap a fixed sample of rows
+    with their indices, the same on every call."""
+    import numpy as np
+    bench = _bench_module()
+    proofs = np.random.default_rng(3).integers(0, 256, size=(1000, 192), dtype=np.uint8)
+    bench.dump_proofs(str(tmp_path / "all"), proofs.tobytes())
+    assert sorted(os.listdir(tmp_path / "all")) == ["proofs.npy"]
+    got = np.load(tmp_path / "all" / "proofs.npy")
+    assert got.dtype == np.float32 and got.shape == (1000, 192)
+    assert np.array_equal(got.astype(np.uint8), proofs)
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 256 * 1024)
+    for d in ("s1", "s2"):
+        bench.dump_proofs(str(tmp_path / d), proofs.tobytes())
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= 256 * 1024
+    rows, idx = np.load(tmp_path / "s1" / "proofs.npy"), np.load(tmp_path / "s1" / "proofs_index.npy")
+    assert idx.dtype == np.float64 and len(idx) == len(rows) and 0 < len(rows) < 1000
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(rows.astype(np.uint8), proofs[idx.astype(np.int64)])
+    assert np.array_equal(rows, np.load(tmp_path / "s2" / "proofs.npy"))

@@ -1,13 +1,13 @@
 #!/bin/bash
-# A/B of library variants on the GPU box: bash tools/variants.sh <outtag> [bench args] ; variants = zero-chain_amd/variants/*.so
-TAG=$1; shift
-mkdir -p gpurun_out/$TAG
+# A/B of library variants on the GPU box: bash tools/variants.sh <outdir> [bench args] ; variants = zero-chain_amd/variants/*.so
+OUT=$1; shift
+mkdir -p $OUT
 cp zero-chain_amd/libzkamd.so /tmp/libzkamd.orig.so
 for v in zero-chain_amd/variants/libzkamd_*.so; do
   name=$(basename $v .so); name=${name#libzkamd_}
   cp $v zero-chain_amd/libzkamd.so
-  timeout 600 python bench.py --no-cpu ${VARIANT_MICRO:---no-micro} --no-secondary --oracle-checks 1 "$@" > gpurun_out/$TAG/$name.json 2> gpurun_out/$TAG/$name.err
-  python - "$name" gpurun_out/$TAG/$name.json <<'PY'
+  timeout 600 python bench.py --full --no-cpu ${VARIANT_MICRO:---no-micro} --no-secondary --oracle-checks 1 "$@" > $OUT/$name.json 2> $OUT/$name.err
+  python - "$name" $OUT/$name.json <<'PY'
 import json,sys
 try:
     d=json.load(open(sys.argv[2]))
