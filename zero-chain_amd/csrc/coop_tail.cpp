@@ -209,6 +209,97 @@ k_ct_combine(const XYZZ<F>* __restrict__ Y, XYZZ<F>* __restrict__ out, uint32_t 
     coop_store(out[job], xadd(acc, next));
 }
 
+// The tail above level 1 of a MANY-jobs launch set (a chunk of proofs: ~1 000 jobs of T = 128 - 512 nodes), one
+// workgroup of rows per job instead of a tree of one-lane launches whose upper levels hold a few waves each.  With the
+// suffix sums R_t = sum_{t' >= t} S_t' the job's sum is
+//   sum_t W_t + 2 L sum_t t S_t = sum_t W_t + 2 L sum_{t >= 1} R_t
+// - three additions per node, not the (log2 T + 1) / 2 of the bit planes: at a thousand jobs the work, not the chain,
+// is what the launch pays.  Row r walks its k = T / rows consecutive nodes [r k, r k + k) from the top down (run = local
+// suffix sum, acc = sum of the local suffix sums above the first node, w = sum of the W), then the rows are joined in
+// pairs, [lo, mid) + [mid, hi): acc = acc_lo + acc_hi + (mid - lo) run_hi, run = run_lo + run_hi, w = w_lo + w_hi.
+// w_is_a: the assembly level 1 keeps A = sum_{k >= 1} R_k per node instead of W = 2 A + S; then w sums the A and the
+// job's sum is 2 w + run + 2 L acc.  T is a power of two (nb and L are).
+template <class F>
+static __global__ void __launch_bounds__(CT_ROWS * COOP_W)
+k_ct_upper(const XYZZ<F>* __restrict__ S, uint32_t s_stride, const XYZZ<F>* __restrict__ W, XYZZ<F>* __restrict__ out, uint32_t T,
+           uint32_t log2_2l, uint32_t w_is_a) {
+    typedef CoopT<F> C;
+    ZK_SHARED XYZZ<C> sm_run[CT_ROWS * COOP_W], sm_acc[CT_ROWS * COOP_W], sm_w[CT_ROWS * COOP_W];
+    const uint32_t r = coop_row_in_block(), tid = threadIdx.x, job = blockIdx.x;
+    const uint32_t rows = T < CT_ROWS ? T : CT_ROWS, k = T / rows;
+    uint32_t lg = 0;   // log2(k): the nodes below a row's first are k 2^j apart after j joins
+    while ((1u << lg) < k) lg++;
+    XYZZ<C> run = XYZZ<C>::inf(), acc = XYZZ<C>::inf(), w = XYZZ<C>::inf();
+    if (r < rows) {
+        const XYZZ<F>* s = S + (size_t)job * T * s_stride;
+        const XYZZ<F>* wp = W + (size_t)job * T;
+        const uint32_t lo = r * k;
+        XYZZ<C> ns = coop_load(s[(size_t)(lo + k - 1) * s_stride]), nw = coop_load(wp[lo + k - 1]);
+        for (uint32_t t = lo + k; t-- > lo;) {
+            const XYZZ<C> cs = ns, cw = nw;   // (the next node in flight while this one is added)
+            if (t > lo) {
+                ns = coop_load(s[(size_t)(t - 1) * s_stride]);
+                nw = coop_load(wp[t - 1]);
+            }
+            run = xadd(run, cs);
+            if (t > lo) acc = xadd(acc, run);
+            w = xadd(w, cw);
+        }
+    }
+    for (uint32_t st = 1; st < rows; st <<= 1, lg++) {
+        const uint32_t pos = r & (2 * st - 1);
+        if (r < rows && pos == st) {   // the upper half of a pair publishes acc + 2^lg run (its own chain of doublings)
+            XYZZ<C> sc = run;
+            for (uint32_t d = 0; d < lg; d++) sc = xdbl(sc);
+            sm_acc[tid] = xadd(acc, sc);
+            sm_run[tid] = run;
+            sm_w[tid] = w;
+        }
+        __syncthreads();
+        if (r < rows && pos == 0) {
+            const uint32_t p = tid + st * COOP_W;
+            acc = xadd(acc, sm_acc[p]);
+            run = xadd(run, sm_run[p]);
+            w = xadd(w, sm_w[p]);
+        }
+        __syncthreads();
+    }
+    if (r == 0) {
+        for (uint32_t d = 0; d < log2_2l; d++) acc = xdbl(acc);
+        if (w_is_a) w = xadd(xdbl(w), run);
+        coop_store(out[job], xadd(acc, w));
+    }
+}
+
+// out[i] = s_i A[i] + B[i], one row per proof: 4-bit fixed windows over the 255-bit scalar (plain little-endian u32 words
+// at scalars + i stride_words), the 15 multiples of A in a scratch table [15][n] - msm.h k_xyzz_scale_add with a row's
+// addition (3.7 us) and doubling (2.5 us) in place of a lane's (15.3 / 9.3 us)
+template <class F>
+static __global__ void __launch_bounds__(CT_THIN * COOP_W)
+k_ct_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, const uint32_t* __restrict__ scalars,
+               uint32_t stride_words, XYZZ<F>* tbl, XYZZ<F>* __restrict__ out, uint32_t n) {
+    typedef CoopT<F> C;
+    const uint32_t i = coop_row();
+    if (i >= n) return;
+    const XYZZ<C> a = coop_load(A[i]);
+    XYZZ<C> run = xdbl(a);
+    coop_store(tbl[i], a);
+    coop_store(tbl[(size_t)n + i], run);
+    for (uint32_t k = 2; k < 15; k++) {
+        run = xadd(run, a);
+        coop_store(tbl[(size_t)k * n + i], run);   // (k + 1) A
+    }
+    const uint32_t* s = scalars + (size_t)i * stride_words;
+    XYZZ<C> acc = XYZZ<C>::inf();
+    for (int w = 63; w >= 0; w--) {
+        if (w != 63)
+            for (int d = 0; d < 4; d++) acc = xdbl(acc);
+        const uint32_t digit = (s[w >> 3] >> (4 * (w & 7))) & 15u;
+        if (digit) acc = xadd(acc, coop_load(tbl[(size_t)(digit - 1) * n + i]));
+    }
+    coop_store(out[i], xadd(acc, coop_load(B[i])));
+}
+
 }  // namespace zkdev
 
 namespace zkcoop {
@@ -264,7 +355,19 @@ void combine(const XYZZ<F>* Y, XYZZ<F>* out, uint32_t nbits, uint32_t log2_2l, u
     ZK_LAUNCH(zkdev::k_ct_combine<F>, dim3((nj + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, Y, out, nbits, log2_2l, nj);
 }
 
+template <class F>
+void upper(const XYZZ<F>* S, uint32_t s_stride, const XYZZ<F>* W, XYZZ<F>* out, uint32_t T, uint32_t log2_2l, bool w_is_a, uint32_t nj,
+           hipStream_t st) {
+    ZK_LAUNCH_SYNC(zkdev::k_ct_upper<F>, dim3(nj), dim3(CT_ROWS * COOP_W), 0, st, S, s_stride, W, out, T, log2_2l, w_is_a ? 1u : 0u);
+}
+void scale_add(const XYZZ<zkdev::Fq28>* A, const XYZZ<zkdev::Fq28>* B, const uint32_t* scalars, uint32_t stride_words,
+               XYZZ<zkdev::Fq28>* tbl, XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st) {
+    ZK_LAUNCH(zkdev::k_ct_scale_add<zkdev::Fq28>, dim3((n + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, A, B, scalars,
+              stride_words, tbl, out, n);
+}
+
 #define ZK_COOP_TAIL_INSTANTIATE(F)                                                                                                   \
+    template void upper<F>(const XYZZ<F>*, uint32_t, const XYZZ<F>*, XYZZ<F>*, uint32_t, uint32_t, bool, uint32_t, hipStream_t);      \
     template void merge<F>(const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, const uint32_t*, XYZZ<F>*, uint32_t,   \
                            uint32_t, size_t, uint32_t, uint32_t, uint32_t, hipStream_t, uint32_t);                                              \
     template void level1<F>(const XYZZ<F>*, const uint32_t*, const uint32_t*, const uint32_t*, XYZZ<F>*, XYZZ<F>*, uint32_t, uint32_t, \

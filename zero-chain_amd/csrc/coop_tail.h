@@ -4,7 +4,9 @@
 // chains of dependent point additions that a handful of waves execute: merging the task partials of a bucket, level 1
 // of the reduction, the bit planes, their weighted sum.  With one point per LANE an addition is 13 us (G1) / 40 us (G2)
 // of dependent products; with one point per 16-lane ROW it is 2 - 3 us.  The kernels are in coop_tail.cpp (its own
-// translation unit: seconds to rebuild); zkamd.cpp's MsmGroup::enqueue calls them through these four functions.
+// translation unit: seconds to rebuild); MsmGroup::enqueue (msm_group_impl.h) and zkamd.cpp call them through the
+// functions below.  A chunk of a thousand proofs uses two of them as well: upper() for the levels above level 1 of its
+// bucket reductions, scale_add() for the final fold.
 // Defined for the two fields the multiexps run on (dev_field.h Fq28, Fq2x).
 #pragma once
 #include "dev_curve.h"
@@ -39,5 +41,17 @@ void planes(const zkdev::XYZZ<F>* S, uint32_t s_stride, const zkdev::XYZZ<F>* W,
 // out[j] = 2 L * sum_i 2^i Y_i + Y_nbits   (log2_2l = log2(2 L))
 template <class F>
 void combine(const zkdev::XYZZ<F>* Y, zkdev::XYZZ<F>* out, uint32_t nbits, uint32_t log2_2l, uint32_t nj, hipStream_t st);
+
+// Many-jobs launch sets (a chunk of proofs): everything above level 1 in one launch, one workgroup of rows per job.
+// out[j] = sum_t W_t + 2 L sum_t t S_t over the T nodes of job j (S at S[(j T + t) s_stride], W at W[j T + t]; T a power
+// of two).  w_is_a: W holds A = (W - S) / 2 of the assembly level 1 (msm.h k_msm_level2_acc's form).
+template <class F>
+void upper(const zkdev::XYZZ<F>* S, uint32_t s_stride, const zkdev::XYZZ<F>* W, zkdev::XYZZ<F>* out, uint32_t T, uint32_t log2_2l,
+           bool w_is_a, uint32_t nj, hipStream_t st);
+
+// The final fold of a chunk of proofs, C = s A + C' (msm.h k_xyzz_scale_add's contract), one row per proof.  tbl: 15 n
+// points of scratch.
+void scale_add(const zkdev::XYZZ<zkdev::Fq28>* A, const zkdev::XYZZ<zkdev::Fq28>* B, const uint32_t* scalars, uint32_t stride_words,
+               zkdev::XYZZ<zkdev::Fq28>* tbl, zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);
 
 }  // namespace zkcoop

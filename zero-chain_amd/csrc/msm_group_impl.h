@@ -133,6 +133,9 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     // jobs over the same large scalar vector, which are as far from filling the machine per job as a lone job is
     const bool few = nj <= few_jobs_max() || jobs[0].vb_digit != 0;
     const bool coop = few && HasCoopTail<DF>::value && coop_tail_on();
+    // ... and a chunk of proofs folds what is above level 1 on rows too, one workgroup per job (coop_tail.h upper): the
+    // one-lane tree's upper levels are launches of 16 - 128 waves, 13.3 ms of a 1024-proof chunk for G1 and G2 together
+    const bool coop_upper = !few && HasCoopTail<DF>::value && coop_tail_on();
     // ... merge and level 1 too while the buckets of the set are few enough for rows to be the right grain: a row-addition is
     // 4 - 5 x shorter than a lane's but a wave holds four rows instead of sixty-four lanes, so a set of 278 528 buckets (the
     // seventeen digit positions of a 2^20-point variable-base multiexp) keeps the one-lane kernels for these two steps and
@@ -406,20 +409,22 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
                 fprintf(stderr, "[redo] reduction G1: %u buckets with 2..%u partials merged, %u of %zu level-1 nodes recomputed\n", v[0],
                         merge_inline, v[1], (size_t)nj * T);
             }
-            const uint32_t fan = pick_fan((uint64_t)nj * n), n_out = (n + fan - 1) / fan;
-            uint32_t log2_2m = 1;
-            while ((1u << (log2_2m - 1)) < m) log2_2m++;
-            ZK_LAUNCH(zkdev::k_msm_suffix<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)R, Rnext, n, fan, 1u);
-            ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Rnext, (const DPoint*)nullptr,
-                      red_t.as<DPoint>(), n, fan, 1u, log2_2m, 0u);
-            ZK_LAUNCH(zkdev::k_msm_level2_acc<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Wa, (const DPoint*)Rnext,
-                      (const DPoint*)red_t.as<DPoint>(), Wb, n, fan);
-            in = Wb;
-            Rcur = Rnext;
-            std::swap(Rnext, Rspare);
-            stride = fan;
-            m *= fan;
-            n = n_out;
+            if (!coop_upper) {   // (a chunk of proofs: coop_upper below takes the levels above the assembly level 1)
+                const uint32_t fan = pick_fan((uint64_t)nj * n), n_out = (n + fan - 1) / fan;
+                uint32_t log2_2m = 1;
+                while ((1u << (log2_2m - 1)) < m) log2_2m++;
+                ZK_LAUNCH(zkdev::k_msm_suffix<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)R, Rnext, n, fan, 1u);
+                ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Rnext, (const DPoint*)nullptr,
+                          red_t.as<DPoint>(), n, fan, 1u, log2_2m, 0u);
+                ZK_LAUNCH(zkdev::k_msm_level2_acc<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Wa, (const DPoint*)Rnext,
+                          (const DPoint*)red_t.as<DPoint>(), Wb, n, fan);
+                in = Wb;
+                Rcur = Rnext;
+                std::swap(Rnext, Rspare);
+                stride = fan;
+                m *= fan;
+                n = n_out;
+            }
         } else if (!coop_l1) {
             // level 1: R = suffix sums over the buckets of a node; S = R_0; W = 2 * sum_{k>=1} R_k + R_0
             ZK_LAUNCH(zkdev::k_msm_suffix_buckets<DF>, grid(T), dim3(64), 0, st, tsums.as<DPoint>(), cnt.as<uint32_t>(),
@@ -439,6 +444,15 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
                 DPoint* Y = nsplit > 1 ? parts + nj * (size_t)(nbits + 1) * nsplit : parts;   // [nj (nbits + 1)]
                 zkcoop::planes<DF>(R, coop_l1 ? 1u : L, Wa, Y, parts, T, nbits, (uint32_t)nj, st);
                 zkcoop::combine<DF>(Y, Wb, nbits, log2_2l, (uint32_t)nj, st);
+                in = Wb;
+                n = 1;
+            }
+        } else if (coop_upper) {
+            if constexpr (HasCoopTail<DF>::value) {
+                // S at R[t * L] (lane level 1) or compact (assembly level 1, whose W area holds A: W = 2 A + S)
+                uint32_t log2_2l = 1;
+                while ((1u << (log2_2l - 1)) < L) log2_2l++;
+                zkcoop::upper<DF>(R, red_asm ? 1u : L, Wa, Wb, T, log2_2l, red_asm, (uint32_t)nj, st);
                 in = Wb;
                 n = 1;
             }

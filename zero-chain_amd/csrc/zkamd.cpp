@@ -667,7 +667,8 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     // A batch keeps the chain: one lane per proof, hidden behind the other pipeline lane, no extra pairs.
     // Up to the few-jobs limit of a launch set (128 proofs): there the chain is exposed at the end of the call - 4.7 ms on
     // a call of 17.6 ms for 32 proofs - and 19 % more G1 pairs cost less.  ZKAMD_FOLD_IN_MSM_MAX overrides (measurements).
-    static const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
+    // (read at every chunk: the emulation suite sends small batches through the chunk form of the fold)
+    const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
     const bool fold_in_msm = np <= fold_max;
     const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0));
     ZK_TRY(P->cvec.ensure(np * (size_t)cstride * 32));
@@ -771,8 +772,14 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
         if (!fold_in_msm) {
             ZK_TRY(P->fold_tbl.ensure(np * 15 * sizeof(DP1)));
             ZK_TRY(P->fold_c.ensure(np * sizeof(DP1)));
-            ZK_LAUNCH(zkdev::k_xyzz_scale_add<zkdev::Fq>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, g_stream, a, cprime,
-                      (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(), P->fold_c.as<DP1>(), (uint32_t)np);
+            // one row of 16 lanes per proof (coop_tail.cpp): 256 waves, each chain 4 - 5 x shorter than a lane's; the
+            // one-lane kernel under ZKAMD_COOP_TAIL=0
+            if (coop_tail_on())
+                zkcoop::scale_add(a, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
+                                  P->fold_c.as<DP1>(), (uint32_t)np, g_stream);
+            else
+                ZK_LAUNCH(zkdev::k_xyzz_scale_add<zkdev::Fq>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, g_stream, a, cprime,
+                          (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(), P->fold_c.as<DP1>(), (uint32_t)np);
             cfin = P->fold_c.as<DP1>();
         }
         if (host_norm) {
