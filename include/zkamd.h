@@ -51,6 +51,9 @@
  *   zk_spending_key_from_seed       SpendingKey::from_seed                        core/proofs/src/no_std_aliases/keys.rs:45-58
  *   zk_jubjub_base_mul              EncryptionKey::from_decryption_key            no_std_aliases/keys.rs:250-261
  *   zk_elgamal_encrypt              elgamal::Ciphertext::encrypt                  no_std_aliases/elgamal.rs:46-63
+ *   zk_elgamal_table_create, zk_elgamal_decrypt, zk_elgamal_table_free
+ *                                   elgamal::Ciphertext::decrypt (the brute-force walk) no_std_aliases/elgamal.rs:85-108
+ *   zk_elgamal_add                  elgamal::Ciphertext::add / sub                no_std_aliases/elgamal.rs:139-158
  *   zk_transfer_derive              the derivations at the head of gen_proof      confidential.rs:105-133
  *   zk_transfer_gen_proof_batch     ProofBuilder::gen_proof (Confidential)        confidential.rs:105-172, check_proof :208-278
  *   zk_anonymous_r1cs_load          structure half of AnonymousTransfer::synthesize      circuit/anonymous_transfer.rs:56-337
@@ -316,6 +319,29 @@ zk_status zk_jubjub_base_mul(const uint8_t* scalars, size_t n, uint8_t* points_o
 zk_status zk_elgamal_encrypt(const uint32_t* values, const uint8_t* randomness, const uint8_t* enc_keys, size_t n,
                              uint8_t* left_out, uint8_t* right_out);
 zk_status zk_transfer_derive(const zk_transfer_request* req, size_t n, zk_transfer_statement* statements_out, uint8_t* rsk_out);
+/* The balance query at the head of a transfer (zface/src/utils/getter.rs:135-174): the encrypted balance and the pending
+ * transfer are added (zk_elgamal_add) and the sum is decrypted (zk_elgamal_decrypt).
+ * zk_elgamal_table_create: the baby steps { j G : j < 2^baby_bits } of a discrete-log search, built on `device` and kept there
+ *   (G = FixedGenerators::NoteCommitmentRandomness, the generator of zk_elgamal_encrypt; zface's getter calls the same index-1
+ *   generator Diversifier).  baby_bits 8 .. 24, 0 = 20: 64 MB of coordinates and 16 MB of hash slots.  Create one per
+ *   wallet process.
+ * zk_elgamal_decrypt: elgamal::Ciphertext::decrypt (no_std_aliases/elgamal.rs:85-108) for n ciphertexts (left, right: n x 32
+ *   bytes each): found_out[i] = 1 and values_out[i] = x exactly when x G == left - dk right and x < limit, else both 0 (the
+ *   reference's None).  limit = ZK_ELGAMAL_DECRYPT_LIMIT is the reference's bound; any limit 1 .. 2^32 is searched, 2^32
+ *   decrypts every u32 amount.  dec_keys: canonical Fs scalars, 32 bytes little-endian; dec_key_stride 0 = one key for all,
+ *   32 = one key per ciphertext.  Both points pass through as_prime_order as Ciphertext::read does (elgamal.rs:116-133).
+ *   left - dk right is computed on host threads; the search (one probe per ciphertext for limit <= 2^baby_bits, else
+ *   ceil(limit / 2^baby_bits) giant steps) runs on the table's device.
+ * zk_elgamal_add: Ciphertext::add, or Ciphertext::sub with subtract != 0 (elgamal.rs:139-158), for n pairs; host only.
+ * A refusal fails the whole call with ZK_ERR_INVALID_ARGUMENT naming the index and the field. */
+#define ZK_ELGAMAL_DECRYPT_LIMIT 1000000u   /* the reference's bound, elgamal.rs:100 */
+typedef struct zk_elgamal_table zk_elgamal_table;
+zk_status zk_elgamal_table_create(uint32_t baby_bits, int device, zk_elgamal_table** out);
+zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left, const uint8_t* right, const uint8_t* dec_keys,
+                             size_t dec_key_stride, uint64_t limit, uint32_t* values_out, uint8_t* found_out);
+void zk_elgamal_table_free(zk_elgamal_table* t);
+zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
+                         int subtract, uint8_t* left_out, uint8_t* right_out);
 struct zk_vk;
 zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, struct zk_vk* vk, size_t n, const zk_transfer_request* req,
                                       const uint8_t* rs, zk_confidential_xt* out);

@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -665,6 +665,103 @@ def elgamal_encrypt(values, randomness, enc_keys, lib=None):
         lib.check(lib.zk_elgamal_encrypt(_ptr(vb), _ptr(rb), _ptr(kb), n, _ptr(left), _ptr(right)))
     lb, rbb = left.tobytes(), right.tobytes()
     return [lb[i:i + 32] for i in range(0, 32 * n, 32)], [rbb[i:i + 32] for i in range(0, 32 * n, 32)]
+
+
+ELGAMAL_DECRYPT_LIMIT = 1000000                                  # the reference's bound, elgamal.rs:100
+ZERO_CIPHERTEXT = (b"\x01" + bytes(31), b"\x01" + bytes(31))     # Ciphertext::zero(): the identity twice
+
+
+def _points(encodings, n):
+    return _u8(b"".join(bytes(e) for e in encodings), 32 * n)
+
+
+class ElGamalTable:
+    """zk_elgamal_table: the baby steps { j G : j < 2^baby_bits } of the GPU discrete-log search, built once on `device` and
+    kept there (baby_bits 8 .. 24, 0 = 20).  decrypt() = Ciphertext::decrypt (elgamal.rs:85-108) over [0, limit)."""
+
+    def __init__(self, baby_bits=0, device=0, lib=None):
+        self._lib = lib or _lib.load()
+        h = C.c_void_p()
+        self._lib.check(self._lib.zk_elgamal_table_create(int(baby_bits), int(device), C.byref(h)))
+        self._h = h
+
+    def decrypt(self, left, right, dec_keys, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_elgamal_decrypt: left / right are lists of 32-byte encodings, dec_keys one Fs integer for all or a list of one
+        per ciphertext.  Returns a list of int | None (None: no x < limit with x G == left - dk right)."""
+        n = len(left)
+        if len(right) != n:
+            raise ValueError("left and right must have the same length")
+        if isinstance(dec_keys, int):
+            kb, stride = scalars_to_bytes([dec_keys]), 0
+        else:
+            if len(dec_keys) != n:
+                raise ValueError("one key for all, or one key per ciphertext")
+            kb, stride = scalars_to_bytes(dec_keys), 32
+        lb, rb = _points(left, n), _points(right, n)
+        values, found = np.zeros(n, dtype=np.uint32), np.zeros(n, dtype=np.uint8)
+        try:
+            self._lib.check(self._lib.zk_elgamal_decrypt(self._h, n, _ptr(lb), _ptr(rb), _ptr(kb), stride, int(limit), _ptr(values),
+                                                         _ptr(found)))
+        finally:
+            kb[:] = 0   # (the caller's copy of the keys is the caller's)
+        return [int(v) if f else None for v, f in zip(values, found)]
+
+    def close(self):
+        if self._h:
+            self._lib.zk_elgamal_table_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def elgamal_add(left_a, right_a, left_b, right_b, subtract=False, lib=None):
+    """zk_elgamal_add: Ciphertext::add (or ::sub, subtract=True; elgamal.rs:139-158) of lists of 32-byte encodings.
+    Returns (left encodings, right encodings)."""
+    lib = lib or _lib.load()
+    n = len(left_a)
+    if not (len(right_a) == len(left_b) == len(right_b) == n):
+        raise ValueError("the four lists must have the same length")
+    ins = [_points(x, n) for x in (left_a, right_a, left_b, right_b)]
+    left, right = np.zeros(32 * n, dtype=np.uint8), np.zeros(32 * n, dtype=np.uint8)
+    if n:
+        lib.check(lib.zk_elgamal_add(*[_ptr(a) for a in ins], n, 1 if subtract else 0, _ptr(left), _ptr(right)))
+    lb, rbb = left.tobytes(), right.tobytes()
+    return [lb[i:i + 32] for i in range(0, 32 * n, 32)], [rbb[i:i + 32] for i in range(0, 32 * n, 32)]
+
+
+def balance_query(dec_key, encrypted_balance=None, pending_transfer=None, table=None, limit=ELGAMAL_DECRYPT_LIMIT):
+    """BalanceQuery::get_balance_from_decryption_key (zface/src/utils/getter.rs:135-174): the encrypted balance plus the
+    pending transfer (each 64 bytes left || right, or a (left, right) pair; an absent part is Ciphertext::zero()), decrypted
+    with dec_key.  Returns (value or None, enc_total): the 64 bytes enc_total are what a transfer request carries as
+    enc_balance_left || enc_balance_right.  table: an ElGamalTable to search with (default: a fresh one of 20 bits)."""
+    def parts(c):
+        if c is None:
+            return ZERO_CIPHERTEXT
+        b = bytes(c) if isinstance(c, (bytes, bytearray)) else bytes(c[0]) + bytes(c[1])
+        if len(b) != 64:
+            raise ValueError("a ciphertext is 64 bytes (left || right)")
+        return b[:32], b[32:]
+    lib = table._lib if table is not None else _lib.load()
+    a, b = parts(encrypted_balance), parts(pending_transfer)
+    (left,), (right,) = elgamal_add([a[0]], [a[1]], [b[0]], [b[1]], lib=lib)
+    t = table if table is not None else ElGamalTable(lib=lib)
+    try:
+        value = t.decrypt([left], [right], int(dec_key), limit=limit)[0]
+    finally:
+        if table is None:
+            t.close()
+    return value, left + right
 
 
 def transfer_requests(items):

@@ -67,6 +67,15 @@ static inline unsigned atomicMin(unsigned* p, unsigned v) {
     while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
     return old;
 }
+static inline unsigned long long atomicMin(unsigned long long* p, unsigned long long v) {
+    unsigned long long old = __atomic_load_n(p, __ATOMIC_RELAXED);
+    while (old > v && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {}
+    return old;
+}
+static inline unsigned long long atomicCAS(unsigned long long* p, unsigned long long compare, unsigned long long v) {
+    __atomic_compare_exchange_n(p, &compare, v, false, __ATOMIC_RELAXED, __ATOMIC_RELAXED);
+    return compare;   // the value found: `compare` itself when the swap happened
+}
 static inline const char* hipGetErrorString(hipError_t) { return "emu"; }
 static inline hipError_t hipGetLastError() { return 0; }
 static inline hipError_t hipMalloc(void** p, size_t n) { *p = malloc(n ? n : 1); return *p ? 0 : 2; }

@@ -64,6 +64,26 @@ zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st,
                                    size_t index_base = 0);
 zk_status witness_anon_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base);
 
+// ------------------------------------------------------------------------------------------
+// zk_elgamal_table: the baby steps of the discrete-log search behind zk_elgamal_decrypt (elgamal_dlog.h), resident on the GPU
+// ------------------------------------------------------------------------------------------
+constexpr uint32_t ELGAMAL_BABY_BITS_DEFAULT = 20, ELGAMAL_BABY_BITS_MIN = 8, ELGAMAL_BABY_BITS_MAX = 24;
+struct zk_elgamal_table {
+    int device = 0;
+    uint32_t baby_bits = ELGAMAL_BABY_BITS_DEFAULT;
+    uint32_t fp_bits = 32;       // fingerprint width of a hash slot (the test hooks shrink it to force false hits)
+    uint32_t giant_count = 0;    // entries of the giant-step table built so far
+    // public (multiples of the generator): G, 2 d, -2^b G | j G, j < 2^b | the hash | e 2^(b+w) G, e < giant_count
+    zkrt::DevBuf consts, baby_xy, slots, giant_xy;
+    // key-derived (left - dk right, the search's points, the logarithms): zeroed before release
+    zkrt::DevBuf v, scratch, res;
+    zk_elgamal_table() { consts.is_public = baby_xy.is_public = slots.is_public = giant_xy.is_public = true; }
+};
+// witness.cpp: build the baby-step table of T (baby_bits, fp_bits and device set); the search for n points v (affine,
+// Montgomery x | y) over [0, limit): x_out[i] = the logarithm, or ~0 when there is none below the limit
+zk_status elgamal_table_build(zk_elgamal_table* T);
+zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v, uint64_t limit, uint64_t* x_out);
+
 // Groth16 verification of a batch (verify.cpp; zk_verify_batch is this with own_proofs = false).  own_proofs: the
 // proofs are this library's own fresh results (gen_proof's self-check) - decoded without the r-torsion test.
 namespace zkrt {

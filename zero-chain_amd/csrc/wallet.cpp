@@ -4,6 +4,8 @@
 //   key derivation                   core/proofs/src/no_std_aliases/keys.rs:45-198 (SpendingKey::from_seed, ProofGenerationKey,
 //                                    DecryptionKey, EncryptionKey), rvk / rsk / nonce
 //   elgamal::Ciphertext::encrypt     core/proofs/src/no_std_aliases/elgamal.rs:46-63
+//   elgamal::Ciphertext::decrypt     elgamal.rs:85-108 (the host half; the search is witness.cpp's, kernels elgamal_dlog.h)
+//   elgamal::Ciphertext::add / sub   elgamal.rs:139-158
 //   check_proof + ConfidentialXt / AnonymousXt packing   confidential.rs:208-361, anonymous.rs:200-352
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; this unit holds no kernel.
 #include <stdio.h>
@@ -16,6 +18,7 @@
 #include <utility>
 #include <chrono>
 #include <algorithm>
+#include <memory>
 
 #include "../../include/zkamd.h"
 #include "gpu_rt.h"
@@ -328,6 +331,126 @@ zk_status zk_elgamal_encrypt(const uint32_t* values, const uint8_t* randomness, 
     run_threads(nthreads, work);
     for (unsigned t = 0; t < nthreads; t++)
         if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
+    return ZK_OK;
+} ZK_ABI_CATCH
+
+// ElGamal decryption (elgamal.rs:85-108) as a baby-step giant-step search: the table and the search are witness.cpp's
+// (kernels: elgamal_dlog.h); the point work of every ciphertext - decoding, dk * right - stays on host threads here.
+zk_status zk_elgamal_table_create(uint32_t baby_bits, int device, zk_elgamal_table** out) try {
+    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    const uint32_t b = baby_bits ? baby_bits : ELGAMAL_BABY_BITS_DEFAULT;
+    if (b < ELGAMAL_BABY_BITS_MIN || b > ELGAMAL_BABY_BITS_MAX)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "baby_bits " + std::to_string(baby_bits) + " is outside 8 .. 24");
+    ZK_TRY(use_device(device));
+    std::unique_ptr<zk_elgamal_table> t(new zk_elgamal_table());
+    t->device = device;
+    t->baby_bits = b;
+    // test hook (tests/test_elgamal_decrypt.py): a narrower fingerprint, so that most probes hit slots of other points
+    if (const char* e = hook_env("ZKAMD_DEBUG_DLOG_FP_BITS")) t->fp_bits = (uint32_t)std::min(32, std::max(0, atoi(e)));
+    ZK_TRY(elgamal_table_build(t.get()));
+    *out = t.release();
+    return ZK_OK;
+} ZK_ABI_CATCH
+
+void zk_elgamal_table_free(zk_elgamal_table* t) {
+    if (!t) return;
+    try {
+        (void)use_device(t->device);   // the buffers go back (the key-derived ones zeroed) on the handle's device
+    } catch (...) {
+    }
+    delete t;
+}
+
+zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left, const uint8_t* right, const uint8_t* dec_keys,
+                             size_t dec_key_stride, uint64_t limit, uint32_t* values_out, uint8_t* found_out) try {
+    if (!t || (n && (!left || !right || !dec_keys || !values_out || !found_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (dec_key_stride != 0 && dec_key_stride != 32)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "dec_key_stride must be 0 (one key for all) or 32 (one key per ciphertext)");
+    if (limit == 0 || limit > (1ull << 32)) return fail(ZK_ERR_INVALID_ARGUMENT, "limit must be 1 .. 2^32");
+    if (n == 0) return ZK_OK;
+    ZK_TRY(use_device(t->device));
+    // v = left - dk right (elgamal.rs:92-94), affine: the value is its logarithm
+    std::vector<zkwit::JPoint> v(n);
+    WipeOnExit wipe_v{v.data(), n * sizeof(zkwit::JPoint)};
+    const unsigned nthreads = host_threads(n, 16);
+    std::vector<zk_status> sts(nthreads, ZK_OK);
+    std::vector<std::string> msgs(nthreads);
+    auto work = [&](unsigned th) {
+        const size_t i0 = n * th / nthreads, i1 = n * (th + 1) / nthreads;
+        std::vector<zkwit::EPoint> proj(i1 - i0);
+        WipeOnExit wipe_p{proj.data(), proj.size() * sizeof(zkwit::EPoint)};
+        for (size_t i = i0; i < i1; i++) {
+            uint64_t dk[4];
+            WipeOnExit wipe_dk{dk, sizeof(dk)};
+            load_scalar_le(dec_keys + dec_key_stride * i, dk);
+            const std::string who = "ciphertext " + std::to_string(i) + ": ";
+            zkwit::JPoint l, r;
+            zk_status rc = fs_lt_mod(dk) ? ZK_OK
+                                         : fail(ZK_ERR_INVALID_ARGUMENT, (dec_key_stride ? "dec_key " + std::to_string(i) : std::string("dec_key")) +
+                                                                             " is not a canonical Fs scalar");
+            if (rc == ZK_OK) rc = decode_prime_order(left + 32 * i, &l, who + "left");
+            if (rc == ZK_OK) rc = decode_prime_order(right + 32 * i, &r, who + "right");
+            if (rc != ZK_OK) {
+                sts[th] = rc;
+                msgs[th] = g_err;
+                return;
+            }
+            const zkwit::EPoint s = jubjub_var_mul(r, dk);
+            proj[i - i0] = zkwit::ext_add(zkwit::to_ext(l), zkwit::EPoint{zkhost::Fr::zero() - s.X, s.Y, s.Z, zkhost::Fr::zero() - s.T});
+        }
+        zkwit::batch_to_affine(proj.data(), v.data() + i0, i1 - i0);
+    };
+    run_threads(nthreads, work);
+    for (unsigned th = 0; th < nthreads; th++)
+        if (sts[th] != ZK_OK) return fail(sts[th], msgs[th]);
+    std::vector<uint64_t> x(n);
+    WipeOnExit wipe_x{x.data(), n * sizeof(uint64_t)};
+    static_assert(sizeof(zkwit::JPoint) == 2 * sizeof(zkhost::Fr), "x | y");
+    ZK_TRY(elgamal_dlog_search(t, n, &v[0].x, limit, x.data()));
+    for (size_t i = 0; i < n; i++) {
+        const bool found = x[i] < limit;   // (the search reports ~0 for none)
+        values_out[i] = found ? (uint32_t)x[i] : 0u;
+        found_out[i] = found ? 1 : 0;
+    }
+    return ZK_OK;
+} ZK_ABI_CATCH
+
+zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
+                         int subtract, uint8_t* left_out, uint8_t* right_out) try {
+    if (n && (!left_a || !right_a || !left_b || !right_b || !left_out || !right_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    const unsigned nthreads = host_threads(n, 16);
+    std::vector<zk_status> sts(nthreads, ZK_OK);
+    std::vector<std::string> msgs(nthreads);
+    auto work = [&](unsigned th) {
+        for (size_t i = n * th / nthreads; i < n * (th + 1) / nthreads; i++) {
+            // Ciphertext::read of both operands (elgamal.rs:116-133), then left_a +- left_b, right_a +- right_b
+            const uint8_t* in[4] = {left_a + 32 * i, right_a + 32 * i, left_b + 32 * i, right_b + 32 * i};
+            static const char* const name[4] = {"left_a", "right_a", "left_b", "right_b"};
+            zkwit::JPoint p[4];
+            zk_status rc = ZK_OK;
+            for (int k = 0; k < 4 && rc == ZK_OK; k++) rc = decode_prime_order(in[k], &p[k], "ciphertext " + std::to_string(i) + ": " + name[k]);
+            if (rc != ZK_OK) {
+                sts[th] = rc;
+                msgs[th] = g_err;
+                return;
+            }
+            if (subtract) {
+                p[2].x = zkhost::Fr::zero() - p[2].x;
+                p[3].x = zkhost::Fr::zero() - p[3].x;
+            }
+            const zkwit::EPoint sum[2] = {zkwit::ext_add(zkwit::to_ext(p[0]), zkwit::to_ext(p[2])),
+                                          zkwit::ext_add(zkwit::to_ext(p[1]), zkwit::to_ext(p[3]))};
+            zkwit::JPoint aff[2];
+            zkwit::batch_to_affine(sum, aff, 2);
+            jubjub_encode(aff[0].x, aff[0].y, left_out + 32 * i);
+            jubjub_encode(aff[1].x, aff[1].y, right_out + 32 * i);
+        }
+    };
+    run_threads(nthreads, work);
+    for (unsigned th = 0; th < nthreads; th++)
+        if (sts[th] != ZK_OK) return fail(sts[th], msgs[th]);
     return ZK_OK;
 } ZK_ABI_CATCH
 

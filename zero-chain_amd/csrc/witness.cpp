@@ -1,9 +1,12 @@
 // libzkamd, witness half: the GPU witness generator of the confidential-transfer circuit behind
-// zk_transfer_prove_batch / zk_pipeline / zk_transfer_witness_gpu (kernels: witness_gpu.h).
+// zk_transfer_prove_batch / zk_pipeline / zk_transfer_witness_gpu (kernels: witness_gpu.h), and the discrete-log search of
+// zk_elgamal_decrypt (kernels: elgamal_dlog.h; its C entries are wallet.cpp's).
+#include <algorithm>
 #include "handles.h"
 #include "transfer_witness.h"
 #include "witness_gpu.h"
 #include "witness_anon_gpu.h"
+#include "elgamal_dlog.h"
 
 using namespace zkrt;
 
@@ -159,6 +162,118 @@ zk_status witness_anon_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_
         if (code == A_BAD_GEPOCH) return fail(ZK_ERR_INVALID_ARGUMENT, who + "g_epoch is not a Jubjub point");
         const uint32_t k = (code - A_BAD_SET) / 4, set = (code - A_BAD_SET) % 4;
         return fail(ZK_ERR_INVALID_ARGUMENT, who + sets[set] + "[" + std::to_string(k) + "] is not a Jubjub point");
+    }
+    return ZK_OK;
+}
+
+
+// ---- ElGamal decryption (elgamal_dlog.h): the tables of a zk_elgamal_table and the search, on the library's stream
+// xy[j] = j (2^shift G) for j < 2^count_log (k_dlog_multiples; its walk's Zs in a scratch released here)
+static zk_status dlog_multiples(const zk_elgamal_table* T, uint32_t* xy, uint32_t count_log, uint32_t shift) {
+    using namespace zkdlog;
+    const uint32_t lanes_log = std::min(count_log, BUILD_LANES_LOG);
+    DevBuf scratch;
+    scratch.is_public = true;
+    ZK_TRY(scratch.ensure((size_t)64 << count_log));
+    {
+        ProfScope ps("elgamal_table", g_stream);
+        ZK_LAUNCH(k_dlog_multiples, dim3(((1u << lanes_log) + 63) / 64), dim3(64), 0, g_stream, xy, scratch.as<uint32_t>(),
+                  T->consts.as<uint32_t>(), shift, lanes_log, 1u << (count_log - lanes_log));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return ZK_OK;
+}
+static zkdlog::Table dlog_table(const zk_elgamal_table* T) {
+    zkdlog::Table t;
+    t.xy = T->baby_xy.as<uint32_t>();
+    t.slots = T->slots.as<unsigned long long>();
+    t.slot_mask = (2u << T->baby_bits) - 1u;
+    t.fp_mask = T->fp_bits >= 32 ? 0xffffffffu : (1u << T->fp_bits) - 1u;
+    return t;
+}
+zk_status elgamal_table_build(zk_elgamal_table* T) {
+    using namespace zkdlog;
+    const uint32_t b = T->baby_bits;
+    // G, 2 d and -M = -(2^b G), the layout of elgamal_dlog.h's consts
+    const zkwit::JPoint g = zkwit::tables().win[0][1];
+    zkwit::EPoint m = zkwit::to_ext(g);
+    for (uint32_t k = 0; k < b; k++) m = zkwit::ext_add(m, m);
+    zkwit::JPoint ma;
+    zkwit::batch_to_affine(&m, &ma, 1);
+    const zkhost::Fr c[5] = {g.x, g.y, zkwit::edwards_d().dbl(), zkhost::Fr::zero() - ma.x, ma.y};
+    static_assert(sizeof(c) == C_WORDS * 4, "consts layout");
+    ZK_TRY(T->consts.ensure(sizeof(c)));
+    HIP_TRY(hipMemcpy(T->consts.p, c, sizeof(c), hipMemcpyHostToDevice));
+    const size_t count = (size_t)1 << b;
+    ZK_TRY(T->baby_xy.ensure(count * 64));
+    ZK_TRY(T->slots.ensure(count * 16));   // 2^(b+1) slots of 8 bytes: half of them stay empty
+    HIP_TRY(hipMemsetAsync(T->slots.p, 0, count * 16, g_stream));
+    ZK_TRY(dlog_multiples(T, T->baby_xy.as<uint32_t>(), b, 0));
+    {
+        ProfScope ps("elgamal_table", g_stream);
+        ZK_LAUNCH(k_dlog_insert, dim3((unsigned)((count + 63) / 64)), dim3(64), 0, g_stream, dlog_table(T), (uint32_t)count);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return ZK_OK;
+}
+zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v, uint64_t limit, uint64_t* x_out) {
+    using namespace zkdlog;
+    static_assert(sizeof(zkhost::Fr) == 32 && sizeof(unsigned long long) == sizeof(uint64_t), "layouts");
+    const uint32_t b = T->baby_bits, w = giant_stride_log(b);
+    const uint64_t steps = (limit + (1ull << b) - 1) >> b;
+    const uint32_t chunks = (uint32_t)((steps + (1ull << w) - 1) >> w);   // <= 2^16 (giant_stride_log)
+    if (steps > 1 && chunks > T->giant_count) {   // the giant-step table: e 2^w M for e < the next power of two
+        uint32_t log = 0;
+        while ((1u << log) < chunks) log++;
+        T->giant_count = 0;
+        ZK_TRY(T->giant_xy.ensure((size_t)64 << log));
+        ZK_TRY(dlog_multiples(T, T->giant_xy.as<uint32_t>(), log, b + w));
+        T->giant_count = 1u << log;
+    }
+    constexpr size_t BLOCK = (size_t)1 << 20;   // ciphertexts per launch
+    for (size_t first = 0; first < n; first += BLOCK) {
+        const size_t nb = std::min(BLOCK, n - first);
+        ZK_TRY(T->v.ensure(nb * 64));
+        ZK_TRY(T->res.ensure(nb * 8));
+        Search s;
+        s.tab = dlog_table(T);
+        s.v = T->v.as<uint32_t>();
+        s.giant = T->giant_xy.as<uint32_t>();
+        s.consts = T->consts.as<uint32_t>();
+        s.scratch = nullptr;
+        s.res = T->res.as<unsigned long long>();
+        s.limit = limit;
+        s.steps = steps;
+        s.n = (uint32_t)nb;
+        s.baby_bits = b;
+        s.w_log = w;
+        s.chunks = chunks;
+        s.lanes = 0;
+        HIP_TRY(hipMemcpyAsync(T->v.p, v + first * 2, nb * 64, hipMemcpyHostToDevice, g_stream));
+        HIP_TRY(hipMemsetAsync(T->res.p, 0xff, nb * 8, g_stream));   // NOT_FOUND
+        size_t scratch_used = 0;
+        {
+            ProfScope ps("elgamal_dlog", g_stream);
+            if (steps == 1) {   // limit <= 2^b: the table holds the whole range
+                ZK_LAUNCH(k_dlog_probe, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, g_stream, s);
+            } else {
+                const uint64_t items = (uint64_t)nb * chunks;
+                s.lanes = (uint32_t)std::min<uint64_t>((items + 63) / 64 * 64, SEARCH_LANES);
+                scratch_used = (size_t)s.lanes * SEARCH_BATCH * 4 * 32;
+                ZK_TRY(T->scratch.ensure(scratch_used));
+                s.scratch = T->scratch.as<uint32_t>();
+                ZK_LAUNCH(k_dlog_search, dim3(s.lanes / 64), dim3(64), 0, g_stream, s);
+            }
+        }
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(x_out + first, T->res.p, nb * 8, hipMemcpyDeviceToHost, g_stream));
+        // the key-derived points do not stay on the device between calls
+        HIP_TRY(hipMemsetAsync(T->v.p, 0, nb * 64, g_stream));
+        if (scratch_used) HIP_TRY(hipMemsetAsync(T->scratch.p, 0, scratch_used, g_stream));
+        HIP_TRY(hipMemsetAsync(T->res.p, 0, nb * 8, g_stream));
+        HIP_TRY(hipStreamSynchronize(g_stream));
     }
     return ZK_OK;
 }
