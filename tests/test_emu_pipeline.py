@@ -119,7 +119,6 @@ def test_prover_batch_split_g1_launch_sets(emu_lib, monkeypatch, form):
     monkeypatch.setenv("ZKAMD_WINDOW_BITS_G2", "5")
     monkeypatch.setenv("ZKAMD_SPLIT_MIN", "1")
     pc.prover_batch(emu_lib, 6, 3, 12, 3)
-    monkeypatch.setenv("ZKAMD_G1A_STREAM", "main")
     pc.prover_batch(emu_lib, 8, 3, 12, 2)
 
 
@@ -244,8 +243,6 @@ def test_msm_variable_base_lane_merges(emu_lib, monkeypatch):
     pc.msm_variable_base(emu_lib, windows=(3,), n=700, g2_n=300, auto_n=40, g2_w=3, one_w=6)     # merge and level 1 on rows
     monkeypatch.setenv("ZKAMD_COOP_L1_MAX", "0")
     pc.msm_variable_base(emu_lib, windows=(3, 9), n=700, g2_n=300, auto_n=40, g2_w=3, one_w=6)
-    monkeypatch.setenv("ZKAMD_COOP_TAIL", "0")
-    pc.msm_variable_base(emu_lib, windows=(3,), n=700, g2_n=200, auto_n=40, g2_w=3, one_w=6)
 
 
 def test_proof_reader_subgroup_tests(emu_lib):

@@ -10,7 +10,7 @@ buckets of a node from the top down with BOTH accumulators in registers,
     run <- run + B_k            (R_k, the suffix sum)                      k = L-1 .. 0
     acc <- acc + run            (sum of R_k over k >= 1)                   k = L-1 .. 1
 
-and hands back S = run = R_0 and A = acc; the level above forms W = 2 A + S (msm.h k_msm_level2_acc).  Nothing but
+and hands back S = run = R_0 and A = acc; the tail above forms W = 2 A + S (coop_tail.cpp k_ct_upper).  Nothing but
 the bucket sums is read, nothing is written inside the loop.
 
 Group law: EFD add-2008-s on extended Jacobian XYZZ coordinates (the reference's Jacobian law for the same group

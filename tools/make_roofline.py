@@ -29,13 +29,13 @@ GROUPS = [   # substring of the rocprofv3 kernel name -> bench.py group
     ("k_ntt_pass", "ntt"), ("k_msm_sort_lds", "msm_sort_lds"),
     ("k_msm_task_hist", "msm_task_sort"), ("k_msm_task_base", "msm_task_sort"), ("k_msm_task_place", "msm_task_sort"),
     ("k_msm_merge_heavy<zkdev::Fq28>", "msm_reduce_g1"), ("k_msm_suffix_buckets<zkdev::Fq28>", "msm_reduce_g1"),
-    ("k_msm_reduce1_g1asm", "msm_reduce_g1"), ("k_msm_level2_acc<zkdev::Fq28>", "msm_reduce_g1"),
-    ("k_msm_level2_acc<zkdev::Fq2x>", "msm_reduce_g2"),
-    ("k_msm_segsum<zkdev::Fq28>", "msm_reduce_g1"), ("k_msm_suffix<zkdev::Fq28>", "msm_reduce_g1"),
+    ("k_msm_reduce1_g1asm", "msm_reduce_g1"), ("k_ct_upper<zkdev::Fq28>", "msm_reduce_g1"),
+    ("k_ct_upper<zkdev::Fq2x>", "msm_reduce_g2"),
+    ("k_msm_segsum<zkdev::Fq28>", "msm_reduce_g1"), ("k_msm_merge_light<zkdev::Fq28>", "msm_reduce_g1"),
     ("k_msm_merge_heavy<zkdev::Fq2x>", "msm_reduce_g2"), ("k_msm_suffix_buckets<zkdev::Fq2x>", "msm_reduce_g2"),
-    ("k_msm_segsum<zkdev::Fq2x>", "msm_reduce_g2"), ("k_msm_suffix<zkdev::Fq2x>", "msm_reduce_g2"),
+    ("k_msm_segsum<zkdev::Fq2x>", "msm_reduce_g2"), ("k_msm_merge_light<zkdev::Fq2x>", "msm_reduce_g2"),
     ("k_h_pointwise", "h_pointwise"), ("k_r1cs_eval", "r1cs_eval"), ("zkwitdev::k_wit_", "witness_gpu"),
-    ("k_build_scalars", "proof_fold"), ("k_xyzz_scale_add", "proof_fold"), ("k_xyzz_normalize_export", "proof_fold"),
+    ("k_build_scalars", "proof_fold"), ("k_ct_scale_add", "proof_fold"), ("k_xyzz_normalize_export", "proof_fold"),
 ]
 
 

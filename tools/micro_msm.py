@@ -43,6 +43,3 @@ def timed(tag):
 
 
 timed("default")
-if os.environ.get("MICRO_COMPARE_TREE"):
-    os.environ["ZKAMD_NO_BITSUM"] = "1"      # the full tree for the upper levels of the bucket reduction
-    timed("tree_only")

@@ -23,8 +23,7 @@ GROUPS = ("msm_sort_lds", "msm_sort_coarse", "msm_sort_fine", "msm_task_sort", "
 
 
 def run(label, env, window_bits=0):
-    for k in ("ZKAMD_MSM_SEG", "ZKAMD_NO_BITSUM"):
-        os.environ.pop(k, None)
+    os.environ.pop("ZKAMD_MSM_SEG", None)
     os.environ.update(env)
     t0 = time.perf_counter()
     ctx = zk.MultiexpContext(1, bases, window_bits=window_bits, lib=lib, variable_base=True)
@@ -52,10 +51,8 @@ if "sweep" in sys.argv:
         assert run("w = %d" % w, {}, window_bits=w) == ref
     for seg in (32, 64, 128, 256):
         assert run("seg = %d" % seg, {"ZKAMD_MSM_SEG": str(seg)}) == ref
-    assert run("no bitsum tail", {"ZKAMD_NO_BITSUM": "1"}) == ref
 # the one-shot entry: fresh bases and scalars from pageable host memory every call
-for k in ("ZKAMD_MSM_SEG", "ZKAMD_NO_BITSUM"):
-    os.environ.pop(k, None)
+os.environ.pop("ZKAMD_MSM_SEG", None)
 bb = np.frombuffer(bases, dtype=np.uint8)
 t0 = time.perf_counter()
 one = zk.multiexp(1, bb, sc, lib=lib)

@@ -272,8 +272,8 @@ k_ct_upper(const XYZZ<F>* __restrict__ S, uint32_t s_stride, const XYZZ<F>* __re
 }
 
 // out[i] = s_i A[i] + B[i], one row per proof: 4-bit fixed windows over the 255-bit scalar (plain little-endian u32 words
-// at scalars + i stride_words), the 15 multiples of A in a scratch table [15][n] - msm.h k_xyzz_scale_add with a row's
-// addition (3.7 us) and doubling (2.5 us) in place of a lane's (15.3 / 9.3 us)
+// at scalars + i stride_words), the 15 multiples of A in a scratch table [15][n]: a chain of 252 doublings and ~75
+// additions, a row's addition 3.7 us and its doubling 2.5 us (a lane's: 15.3 / 9.3 us)
 template <class F>
 static __global__ void __launch_bounds__(CT_THIN * COOP_W)
 k_ct_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, const uint32_t* __restrict__ scalars,

@@ -30,7 +30,7 @@ void level1(const zkdev::XYZZ<F>* tsums, const uint32_t* cnt, const uint32_t* to
             zkdev::XYZZ<F>* W, uint32_t nb, uint32_t L, uint32_t nj, hipStream_t st);
 
 // Y[j (nbits + 1) + i] = sum of S over the nodes whose index has bit i set (i < nbits), = sum of W (i = nbits); node t of job
-// j has its S at S[(j T + t) s_stride] (1 after level1() above; L after the one-lane level 1, whose S is the first suffix sum
+// j has its S at S[(j T + t) s_stride] (1 after level1() above; L after level 1 on lanes, whose S is the first suffix sum
 // of a node) and its W at W[j T + t].  A plane of many nodes is summed by planes_split(T) workgroups into `parts`
 // (nj (nbits + 1) planes_split(T) points) and folded.
 uint32_t planes_split(uint32_t T);
@@ -44,12 +44,13 @@ void combine(const zkdev::XYZZ<F>* Y, zkdev::XYZZ<F>* out, uint32_t nbits, uint3
 
 // Many-jobs launch sets (a chunk of proofs): everything above level 1 in one launch, one workgroup of rows per job.
 // out[j] = sum_t W_t + 2 L sum_t t S_t over the T nodes of job j (S at S[(j T + t) s_stride], W at W[j T + t]; T a power
-// of two).  w_is_a: W holds A = (W - S) / 2 of the assembly level 1 (msm.h k_msm_level2_acc's form).
+// of two).  w_is_a: the assembly level 1 (msm.h k_msm_reduce1_g1asm) leaves A = (W - S) / 2 in W's place.
 template <class F>
 void upper(const zkdev::XYZZ<F>* S, uint32_t s_stride, const zkdev::XYZZ<F>* W, zkdev::XYZZ<F>* out, uint32_t T, uint32_t log2_2l,
            bool w_is_a, uint32_t nj, hipStream_t st);
 
-// The final fold of a chunk of proofs, C = s A + C' (msm.h k_xyzz_scale_add's contract), one row per proof.  tbl: 15 n
+// The final fold of a chunk of proofs, C = s A + C', one row per proof: out[i] = s_i A[i] + B[i] through a table of the
+// 15 multiples of A[i] (4-bit windows over s_i, plain little-endian u32 words at scalars + i stride_words).  tbl: 15 n
 // points of scratch.
 void scale_add(const zkdev::XYZZ<zkdev::Fq28>* A, const zkdev::XYZZ<zkdev::Fq28>* B, const uint32_t* scalars, uint32_t stride_words,
                zkdev::XYZZ<zkdev::Fq28>* tbl, zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);

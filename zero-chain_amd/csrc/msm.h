@@ -18,7 +18,7 @@
 //     the tasks of the whole launch are ordered by length, so the 64 lanes of a wave walk
 //     equally long runs of XYZZ mixed additions (8M+2S, dev_curve.h) with no idle lanes.
 //   * buckets are reduced with chunked running sums: chunk t of length L yields
-//     sum_k (2(tL+k)+1) B_{tL+k}; chunk results are tree-summed.
+//     sum_k (2(tL+k)+1) B_{tL+k}; chunk results are summed on rows of 16 lanes (coop_tail.cpp).
 //
 // A "job" is one MSM instance (one query of one proof).  Jobs of a batch that live in the
 // same group share every launch; `MsmJob` carries the per-job pointers.
@@ -57,8 +57,8 @@ template <class F> struct MsmOcc;
 #ifndef ZK_OCC_G2_RED
 #define ZK_OCC_G2_RED 2
 #endif
-// `tail`: the kernels of the few-jobs reduction tail (k_msm_bitsum*) are chains of dependent point
-// additions run by one wave per SIMD at most - occupancy buys nothing there, spilled registers cost
+// `tail`: the normalisation kernels (k_xyzz_normalize_export*, setup.h) are chains of dependent field
+// operations run by one wave per SIMD at most - occupancy buys nothing there, spilled registers cost
 // latency - so they take the whole register file.
 #ifndef ZK_OCC_G1_TAIL
 #define ZK_OCC_G1_TAIL 2
@@ -1019,7 +1019,7 @@ k_calib_buckets(const Affine<F>* __restrict__ table, uint32_t n_table, XYZZ<F>* 
 // (k_msm_suffix_buckets + k_msm_segsum: 224 B read, 224 B written and 224 B read again per bucket), and the XYZZ full
 // addition is ~6 100 in-place instructions against the compiled one's ~9 000 through the out-of-line product routines.
 // Every bucket must hold ONE partial: the launch runs behind k_msm_merge_heavy with all multi-task buckets merged.
-// The level above forms W = 2 A + S (k_msm_level2_acc).  Equal / opposite operands and buckets that are the point at
+// The tail above it forms W = 2 A + S (coop_tail.cpp k_ct_upper, w_is_a).  Equal / opposite operands and buckets that are the point at
 // infinity leave ZZ == 0 (mod p) in the result they entered; such a node is recomputed here by the compiled addition.
 #if !defined(ZK_EMU) && !defined(ZK_NO_MADD_ASM)
 #include "red_asm.h"
@@ -1134,26 +1134,6 @@ k_msm_reduce1_redo(const XYZZ<Fq28>* __restrict__ tsums, const uint32_t* __restr
     }
 }
 #endif
-// The level above the assembly loop: children k of a parent carry S_k (suffix sums R'_k already formed by k_msm_suffix)
-// and A_k with W_k = 2 A_k + S_k, so  W(parent) = Tred + sum_k W_k = Tred + 2 sum_k A_k + R'_0  with
-// Tred = 2M sum_{k >= 1} R'_k from k_msm_segsum: one doubling per PARENT instead of one per child.
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::red)
-k_msm_level2_acc(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ Rp, const XYZZ<F>* __restrict__ Tred,
-                 XYZZ<F>* __restrict__ out, uint32_t n, uint32_t seg) {
-    const uint32_t ns = (n + seg - 1) / seg;
-    const uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= ns) return;
-    const XYZZ<F>* a = A + (size_t)blockIdx.y * n;
-    const uint32_t c0 = u * seg, c1 = c0 + seg < n ? c0 + seg : n;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t k = c0; k < c1; k++) acc = xadd(acc, a[k]);
-    acc = xdbl(acc);
-    acc = xadd(acc, Tred[(size_t)blockIdx.y * ns + u]);
-    acc = xadd(acc, Rp[(size_t)blockIdx.y * n + c0]);
-    out[(size_t)blockIdx.y * ns + u] = acc;
-}
-
 // Second pass for the tasks the assembly loop flagged: the compiled addition with every special case.  A circuit's
 // CRS holds EQUAL points (variables with identical QAP polynomials: ~100-170 flagged tasks per 1024-proof launch of
 // the transfer circuit, each time a task starts with two of them), so this pass is on the hot path: one WAVE per
@@ -1293,15 +1273,14 @@ k_msm_merge_light(const uint32_t* __restrict__ light, const uint32_t* __restrict
 // the recoding's top digit alone gives ~2^(c-6) buckets twice the average load, i.e. a run of
 // neighbouring buckets with 4 partials each.
 
-// Pass 6: bucket reduction  sum_j (2j + 1) * B_j  (bucket j holds the odd magnitude 2j + 1) as a
-// tree of running sums.  A node covering M buckets carries
+// Pass 6: bucket reduction  sum_j (2j + 1) * B_j  (bucket j holds the odd magnitude 2j + 1) by
+// running sums.  A node covering L buckets carries
 //     W = sum_b (2 (b - first) + 1) * B_b      (weights relative to the node's first bucket)
 //     S = sum_b B_b
-// With R_k = sum_{k' >= k} B_k' the suffix sums inside a node of L buckets:
+// With R_k = sum_{k' >= k} B_k' the suffix sums inside a node:
 //     level 1:    S = R_0,  W = 2 * sum_{k >= 1} R_k + R_0                       (2 additions / bucket)
-//     level l+1:  children c_0 .. c_{f-1} of M buckets each, R'_k suffix sums of S(c_k):
-//                 S = R'_0,  W = 2M * sum_{k >= 1} R'_k + sum_k W(c_k)           (3 additions / child)
-// No scalar multiplication anywhere (2M is a power of two: doublings), and every kernel below
+//     the tail:   sum_t W_t + 2L * sum_t t * S_t over the T nodes of a job, on rows of 16 lanes (coop_tail.cpp)
+// No scalar multiplication anywhere (2L is a power of two: doublings), and every kernel below
 // keeps exactly ONE point accumulator in registers: an extended-Jacobian addition with a second
 // live accumulator does not fit 168 VGPRs next to the product routine's 40, and scratch spills
 // inside these loops cost more than the arithmetic (measured: 5x on the batched prover, >100x on
@@ -1336,24 +1315,6 @@ k_msm_suffix_buckets(const XYZZ<F>* __restrict__ tsums, const uint32_t* __restri
     }
 }
 
-// k_msm_suffix: out[k] = sum_{k' >= k, same segment} in[k' * stride]; n elements per job, segments
-// of `seg`, one thread per segment.
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::red)
-k_msm_suffix(const XYZZ<F>* __restrict__ in, XYZZ<F>* __restrict__ out, uint32_t n, uint32_t seg, uint32_t stride) {
-    const uint32_t ns = (n + seg - 1) / seg;
-    uint32_t u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= ns) return;
-    const XYZZ<F>* p = in + (size_t)blockIdx.y * n * stride;
-    XYZZ<F>* q = out + (size_t)blockIdx.y * n;
-    const uint32_t c0 = u * seg, c1 = c0 + seg < n ? c0 + seg : n;
-    XYZZ<F> run = XYZZ<F>::inf();
-    for (uint32_t k = c1; k-- > c0;) {
-        run = xadd(run, p[(size_t)k * stride]);
-        q[k] = run;
-    }
-}
-
 // k_msm_segsum: per segment s of `seg` elements
 //     acc = (init ? init[s] : 0) + sum_{first <= k < seg} in[s * seg + k]
 //     out[s] = 2^dbl * acc + (plus_first ? in[s * seg] : 0)
@@ -1371,93 +1332,6 @@ k_msm_segsum(const XYZZ<F>* __restrict__ in, const XYZZ<F>* __restrict__ init, X
     for (uint32_t i = 0; i < dbl; i++) acc = xdbl(acc);
     if (plus_first) acc = xadd(acc, p[c0]);
     out[(size_t)blockIdx.y * ns + u] = acc;
-}
-
-// Few-jobs tail of the bucket reduction.  One or a few large jobs cannot fill the GPU with the
-// upper levels of the tree (each level is a chain of ~15 dependent point additions executed by a
-// handful of waves, ~13 us per addition), so after level 1 the T nodes are folded in one step:
-//     total = sum_t W_t + 2L * sum_t t * S_t,     sum_t t * S_t = sum_j 2^j * Y_j,
-//     Y_j = sum of S_t over the nodes t whose index has bit j set
-// - log2(T) + 1 independent plain sums (parallel trees in LDS, depth 8 + 8) and one Horner chain.
-// It costs (log2 T + 1) / 2 additions per node instead of 3, so it is used only when the tree's
-// latency, not its work, is what the launch waits for.
-//
-// k_msm_bitsum: grid (blocks of 512 nodes, planes, jobs).  Planes 0 .. nlow-1 (nlow = min(nbits, 9))
-// sum the S of the nodes whose index has that bit set; the bits above 8 are constant over a block, so
-// ONE further plane of plain block sums U serves all of them (k_msm_bitsum_fold masks by the block
-// index); the last plane sums W.  One wave per block: every lane adds 8 nodes from HBM, then a 6-step
-// tree in LDS (14 KB, so all blocks of a launch are resident at once: one chain of 14 additions).
-constexpr uint32_t MSM_BITSUM_LOG = 9, MSM_BITSUM_NODES = 1u << MSM_BITSUM_LOG;
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::tail)
-k_msm_bitsum(const XYZZ<F>* __restrict__ S, uint32_t s_stride, const XYZZ<F>* __restrict__ W, XYZZ<F>* __restrict__ part,
-             uint32_t T, uint32_t nbits) {
-    ZK_SHARED XYZZ<F> sm[64];
-    const uint32_t tid = threadIdx.x, plane = blockIdx.y, job = blockIdx.z;
-    const uint32_t nlow = nbits < MSM_BITSUM_LOG ? nbits : MSM_BITSUM_LOG;
-    const bool is_w = plane == gridDim.y - 1, is_bit = plane < nlow;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t e = 0; e < MSM_BITSUM_NODES / 64; e++) {
-        const uint32_t t = blockIdx.x * MSM_BITSUM_NODES + e * 64 + tid;
-        if (t >= T) break;
-        if (is_w) acc = xadd(acc, W[(size_t)job * T + t]);
-        else if (!is_bit || ((t >> plane) & 1u)) acc = xadd(acc, S[((size_t)job * T + t) * s_stride]);
-    }
-    sm[tid] = acc;
-    __syncthreads();
-    for (uint32_t st = 32; st >= 1; st >>= 1) {
-        if (tid < st) sm[tid] = xadd(sm[tid], sm[tid + st]);
-        __syncthreads();
-    }
-    if (tid == 0) part[((size_t)job * gridDim.y + plane) * gridDim.x + blockIdx.x] = sm[0];
-}
-
-// k_msm_bitsum_fold: grid (nbits + 1, jobs), one wave; Y[job][j] = plane sum over the blocks
-// (j < nbits: the nodes with bit j set; j = nbits: W).
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::tail)
-k_msm_bitsum_fold(const XYZZ<F>* __restrict__ part, XYZZ<F>* __restrict__ Y, uint32_t nblk, uint32_t nbits, uint32_t n_planes) {
-    ZK_SHARED XYZZ<F> sm[64];
-    const uint32_t tid = threadIdx.x, j = blockIdx.x, job = blockIdx.y;
-    const uint32_t nlow = nbits < MSM_BITSUM_LOG ? nbits : MSM_BITSUM_LOG;
-    const uint32_t plane = j == nbits ? n_planes - 1 : (j < nlow ? j : nlow);   // W | bit plane | U
-    const XYZZ<F>* row = part + ((size_t)job * n_planes + plane) * nblk;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (uint32_t u = tid; u < nblk; u += 64)
-        if (j == nbits || j < nlow || ((u >> (j - MSM_BITSUM_LOG)) & 1u)) acc = xadd(acc, row[u]);
-    sm[tid] = acc;
-    __syncthreads();
-    for (uint32_t st = 32; st >= 1; st >>= 1) {
-        if (tid < st) sm[tid] = xadd(sm[tid], sm[tid + st]);
-        __syncthreads();
-    }
-    if (tid == 0) Y[(size_t)job * (nbits + 1) + j] = sm[0];
-}
-
-// k_msm_bitsum_combine: one wave per job; out = 2^dbl * sum_j 2^j Y_j + Y_nbits.  The weighted sum is
-// folded pairwise (step s adds 2^(2^s) times the upper neighbour), which keeps the unavoidable
-// nbits doublings but only log2(nbits) additions on the critical path.
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::tail)
-k_msm_bitsum_combine(const XYZZ<F>* __restrict__ Y, XYZZ<F>* __restrict__ out, uint32_t nbits, uint32_t dbl) {
-    ZK_SHARED XYZZ<F> sm[64];
-    const uint32_t tid = threadIdx.x, job = blockIdx.x;
-    const XYZZ<F>* y = Y + (size_t)job * (nbits + 1);
-    sm[tid] = tid < nbits ? y[tid] : XYZZ<F>::inf();
-    __syncthreads();
-    for (uint32_t stride = 1; stride < nbits; stride <<= 1) {
-        if (tid % (2 * stride) == 0 && tid + stride < nbits) {
-            XYZZ<F> hi = sm[tid + stride];
-            for (uint32_t d = 0; d < stride; d++) hi = xdbl(hi);
-            sm[tid] = xadd(sm[tid], hi);
-        }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        XYZZ<F> acc = sm[0];
-        for (uint32_t i = 0; i < dbl; i++) acc = xdbl(acc);
-        out[job] = xadd(acc, y[nbits]);
-    }
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1877,36 +1751,9 @@ k_export_xyzz(const XYZZ<F>* __restrict__ src, uint32_t* dst, uint32_t n) {
 // ---------------------------------------------------------------------------------------------
 // Final fold of a proof on the GPU (bellman prover.rs: g_c = s * g_a + ..., then into_affine of A, B,
 // C).  On the host it cost 0.47 ms per proof - a 255-bit double-and-add plus three field inversions
-// - i.e. 30 ms per 1024-proof chunk on 16 cores with the GPU idle (8 % of the step).
+// - i.e. 30 ms per 1024-proof chunk on 16 cores with the GPU idle (8 % of the step).  The fold itself
+// is coop_tail.cpp's k_ct_scale_add; the conversions to affine form are here.
 // ---------------------------------------------------------------------------------------------
-// out[i] = s_i * A[i] + B[i].  4-bit fixed windows over the 255-bit scalar (plain little-endian u32
-// words at scalars + i * stride_words); the 15 multiples of A live in a scratch table [15][n].
-// One thread per proof: a latency chain of 252 doublings + ~75 additions.
-template <class F>
-static __global__ void __launch_bounds__(64, MsmOcc<F>::tail)
-k_xyzz_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, const uint32_t* __restrict__ scalars,
-                 uint32_t stride_words, XYZZ<F>* tbl, XYZZ<F>* __restrict__ out, uint32_t n) {
-    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const XYZZ<F> a = A[i];
-    XYZZ<F> run = xdbl(a);
-    tbl[i] = a;
-    tbl[(size_t)n + i] = run;
-    for (uint32_t k = 2; k < 15; k++) {
-        run = xadd(run, a);
-        tbl[(size_t)k * n + i] = run;   // (k + 1) * A
-    }
-    const uint32_t* s = scalars + (size_t)i * stride_words;
-    XYZZ<F> acc = XYZZ<F>::inf();
-    for (int w = 63; w >= 0; w--) {
-        if (w != 63)
-            for (int d = 0; d < 4; d++) acc = xdbl(acc);
-        const uint32_t digit = (s[w >> 3] >> (4 * (w & 7))) & 15u;
-        if (digit) acc = xadd(acc, tbl[(size_t)(digit - 1) * n + i]);
-    }
-    out[i] = xadd(acc, B[i]);
-}
-
 // dst[i] = src[i] in affine form, exported in the host's XYZZ layout with zz = zzz = 1 (all zero for
 // the point at infinity): the host only has to encode it.
 template <class F, bool GCD>

@@ -36,11 +36,6 @@ zk_status timed_best(Launch&& launch, float* best) {
 
 #ifdef ZK_HAVE_RED_ASM
 template <>
-bool asm_reduce<zkdev::Fq28>() {
-    static const bool on = !(getenv("ZKAMD_G1_RED_ASM") && atoi(getenv("ZKAMD_G1_RED_ASM")) == 0);
-    return on;
-}
-template <>
 void launch_red_asm<zkdev::Fq28>(const zkdev::XYZZ<zkdev::Fq28>* tsums, const uint32_t* cnt, const uint32_t* toff, const uint32_t* tbase,
                                  zkdev::XYZZ<zkdev::Fq28>* S, zkdev::XYZZ<zkdev::Fq28>* A, uint32_t nb, uint32_t L, dim3 grid,
                                  hipStream_t st, uint32_t* n_fallback, uint32_t* fallback) {
@@ -60,11 +55,6 @@ int persist_wgs(int group) {
     static const int v1 = getenv("ZKAMD_G1_PERSIST") ? atoi(getenv("ZKAMD_G1_PERSIST")) : 6;
     static const int v2 = getenv("ZKAMD_G2_PERSIST") ? atoi(getenv("ZKAMD_G2_PERSIST")) : 4;
     return group == 2 ? v2 : v1;
-}
-template <>
-bool asm_loop<zkdev::Fq28>() {
-    static const bool on = !(getenv("ZKAMD_G1_ASM") && atoi(getenv("ZKAMD_G1_ASM")) == 0);
-    return on;
 }
 template <>
 void launch_asm_loop<zkdev::Fq28>(const zkdev::Affine<zkdev::Fq28>* table, const uint32_t* pairs, const uint4* sorted,

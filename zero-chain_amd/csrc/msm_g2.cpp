@@ -36,11 +36,6 @@ zk_status timed_best(Launch&& launch, float* best) {
 
 #ifdef ZK_HAVE_MADD_ASM
 template <>
-bool asm_loop<zkdev::Fq2x>() {
-    static const bool on = !(getenv("ZKAMD_G2_ASM") && atoi(getenv("ZKAMD_G2_ASM")) == 0);
-    return on;
-}
-template <>
 void launch_asm_loop<zkdev::Fq2x>(const zkdev::Affine<zkdev::Fq2x>* table, const uint32_t* pairs, const uint4* sorted,
                                   const uint32_t* d_total, zkdev::XYZZ<zkdev::Fq2x>* tsums, uint32_t* d_nredo, uint32_t* redo,
                                   unsigned blocks, hipStream_t st) {
@@ -64,7 +59,7 @@ void launch_asm_loop<zkdev::Fq2x>(const zkdev::Affine<zkdev::Fq2x>* table, const
 #endif
 
 zk_status calibrate_g2_accumulate(const zkdev::Affine<DevFq2>* table, uint32_t n2, float ms[2]) {
-#if defined(ZK_HAVE_MADD_ASM) && !defined(ZK_G2_SATURATED)
+#ifdef ZK_HAVE_MADD_ASM
     // the G2 accumulation loop: 262 144 tasks of 8 pairs, the persistent launch of the prover
     typedef zkdev::XYZZ<DevFq2> P2;
     const uint32_t ntasks = 1u << 18, len = 8;

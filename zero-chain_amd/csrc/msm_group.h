@@ -27,7 +27,7 @@ using zkdev::MsmJob;
 // MSM group: window tables of a set of bases + the bucket pipeline over a list of jobs
 // ------------------------------------------------------------------------------------------
 // At most this many jobs per launch set: the latency-optimised form (many-workgroup sort, bit-plane tail of the bucket
-// reduction).  8 until round 5; a kernel trace of a 32-proof call then showed the many-jobs form's eleven k_msm_segsum<Fq2x>
+// reduction: coop_tail.h planes / combine).  8 until round 5; a kernel trace of a 32-proof call then showed the many-jobs form's eleven k_msm_segsum<Fq2x>
 // launches - 0.8 ms each whether for 32 jobs or 1024: 8.9 of the call's 16.8 ms - and the sweep of tools/few_jobs_probe.py
 // (profiles/r05end_few_jobs_probe.txt, same proof bytes under every setting): 8 proofs per call 10.5 -> 7.8 ms, 16: 14.9 -> 10.9,
 // 32: 19.9 -> 17.6, 64: 35.1 -> 30.1, 128: 51.6 -> 49.7; from 256 jobs on the many-jobs form wins (86.1 against 90.2).
@@ -120,23 +120,23 @@ inline uint32_t kernel_form(int which) {
     return g_forms[g_device & 63].form[which];   // (written once, before the device's first proving launch)
 }
 
-// The accumulation kernels run the generated assembly loops (msm.h k_msm_accumulate_g1asm / _g2asm) unless
-// ZKAMD_G1_ASM=0 / ZKAMD_G2_ASM=0 (A/B switches) or the build has none (the x86 emulation build).
+// The accumulation kernels run the generated assembly loops (msm.h k_msm_accumulate_g1asm / _g2asm) from
+// ZKAMD_ASM_MIN_PAIRS pairs per launch set on, unless the build has none (the x86 emulation build).
 template <class DF>
-bool asm_loop() { return false; }
+constexpr bool asm_loop() { return false; }
 template <class DF>
 void launch_asm_loop(const zkdev::Affine<DF>*, const uint32_t*, const uint4*, const uint32_t*, zkdev::XYZZ<DF>*, uint32_t*,
                             uint32_t*, unsigned, hipStream_t) {}
 // Level 1 of the bucket reduction as the generated assembly loop (msm.h k_msm_reduce1_g1asm): G1 only, unless
-// ZKAMD_G1_RED_ASM=0 (A/B switch) or the build has none (the x86 emulation build).
+// the build has none (the x86 emulation build).
 template <class DF>
-bool asm_reduce() { return false; }
+constexpr bool asm_reduce() { return false; }
 template <class DF>
 void launch_red_asm(const zkdev::XYZZ<DF>*, const uint32_t*, const uint32_t*, const uint32_t*, zkdev::XYZZ<DF>*, zkdev::XYZZ<DF>*,
                            uint32_t, uint32_t, dim3, hipStream_t, uint32_t*, uint32_t*) {}
-// (definitions: msm_g1.cpp / msm_g2.cpp, next to the generated assembly kernels they launch)
+// (the launchers' definitions: msm_g1.cpp / msm_g2.cpp, next to the generated assembly kernels they launch)
 #ifdef ZK_HAVE_RED_ASM
-template <> bool asm_reduce<zkdev::Fq28>();
+template <> constexpr bool asm_reduce<zkdev::Fq28>() { return true; }
 template <>
 void launch_red_asm<zkdev::Fq28>(const zkdev::XYZZ<zkdev::Fq28>* tsums, const uint32_t* cnt, const uint32_t* toff, const uint32_t* tbase,
                                  zkdev::XYZZ<zkdev::Fq28>* S, zkdev::XYZZ<zkdev::Fq28>* A, uint32_t nb, uint32_t L, dim3 grid,
@@ -144,8 +144,8 @@ void launch_red_asm<zkdev::Fq28>(const zkdev::XYZZ<zkdev::Fq28>* tsums, const ui
 #endif
 #ifdef ZK_HAVE_MADD_ASM
 int persist_wgs(int group = 1);
-template <> bool asm_loop<zkdev::Fq28>();
-template <> bool asm_loop<zkdev::Fq2x>();
+template <> constexpr bool asm_loop<zkdev::Fq28>() { return true; }
+template <> constexpr bool asm_loop<zkdev::Fq2x>() { return true; }
 template <>
 void launch_asm_loop<zkdev::Fq28>(const zkdev::Affine<zkdev::Fq28>* table, const uint32_t* pairs, const uint4* sorted,
                                   const uint32_t* d_total, zkdev::XYZZ<zkdev::Fq28>* tsums, uint32_t* d_nredo, uint32_t* redo,
@@ -155,16 +155,6 @@ void launch_asm_loop<zkdev::Fq2x>(const zkdev::Affine<zkdev::Fq2x>* table, const
                                   const uint32_t* d_total, zkdev::XYZZ<zkdev::Fq2x>* tsums, uint32_t* d_nredo, uint32_t* redo,
                                   unsigned blocks, hipStream_t st);
 #endif
-
-// The few-jobs tail of the bucket reduction on the wave-cooperative field (coop_tail.h): the two fields the multiexps run
-// on have it; ZKAMD_COOP_TAIL=0 keeps the one-lane kernels (A/B switch, read at every launch set).
-template <class DF> struct HasCoopTail { static constexpr bool value = false; };
-template <> struct HasCoopTail<zkdev::Fq28> { static constexpr bool value = true; };
-template <> struct HasCoopTail<zkdev::Fq2x> { static constexpr bool value = true; };
-inline bool coop_tail_on() {
-    const char* e = getenv("ZKAMD_COOP_TAIL");
-    return !(e && atoi(e) == 0);
-}
 
 template <class HF, class DF>
 struct MsmGroup {
@@ -239,13 +229,8 @@ struct MsmGroup {
 };
 
 typedef MsmGroup<zkhost::Fq, zkdev::Fq> MsmG1;
-// G2 runs on Fq2 over the radix-2^28 representation with the fused lazy-reduction product (dev_field.h
-// Fq2x).  -DZK_G2_SATURATED selects round 1's saturated 12 x 32-bit Fq2 (A/B measurements).
-#ifdef ZK_G2_SATURATED
-typedef zkdev::Fq2 DevFq2;
-#else
+// G2 runs on Fq2 over the radix-2^28 representation with the fused lazy-reduction product (dev_field.h Fq2x)
 typedef zkdev::Fq2x DevFq2;
-#endif
 typedef MsmGroup<zkhost::Fq2, DevFq2> MsmG2;
 typedef zkhost::Affine<zkhost::Fq> HG1A;
 typedef zkhost::Affine<zkhost::Fq2> HG2A;

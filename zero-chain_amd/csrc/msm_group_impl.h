@@ -128,23 +128,22 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     ZK_TRY(ntasks.ensure(nj * 4));
     ZK_TRY(tbase.ensure(nj * 4));
     ZK_TRY(hist.ensure((2 * n_class + 6) * 4));     // [length histogram | placement cursors | total | #heavy | #redo | next task block | #light | #level-1 nodes recomputed]
-    // the latency-optimised form of the launch set (many-workgroup sort, bit-plane tail of the bucket reduction: msm.h,
-    // passes 1-3, 5c and 6): one or a few jobs - and the digit positions of ONE variable-base multiexp, a dozen or two
-    // jobs over the same large scalar vector, which are as far from filling the machine per job as a lone job is
+    // the latency-optimised form of the launch set (many-workgroup sort, bit-plane tail of the bucket reduction: msm.h
+    // passes 1-3 and 5c, coop_tail.h planes / combine): one or a few jobs - and the digit positions of ONE variable-base
+    // multiexp, a dozen or two jobs over the same large scalar vector, which are as far from filling the machine per job
+    // as a lone job is.  Every other set is a chunk of proofs, which folds what is above level 1 on rows too, one
+    // workgroup per job (coop_tail.h upper).
     const bool few = nj <= few_jobs_max() || jobs[0].vb_digit != 0;
-    const bool coop = few && HasCoopTail<DF>::value && coop_tail_on();
-    // ... and a chunk of proofs folds what is above level 1 on rows too, one workgroup per job (coop_tail.h upper): the
-    // one-lane tree's upper levels are launches of 16 - 128 waves, 13.3 ms of a 1024-proof chunk for G1 and G2 together
-    const bool coop_upper = !few && HasCoopTail<DF>::value && coop_tail_on();
-    // ... merge and level 1 too while the buckets of the set are few enough for rows to be the right grain: a row-addition is
-    // 4 - 5 x shorter than a lane's but a wave holds four rows instead of sixty-four lanes, so a set of 278 528 buckets (the
-    // seventeen digit positions of a 2^20-point variable-base multiexp) keeps the one-lane kernels for these two steps and
-    // goes onto rows where the tree gets narrow (msm_reduce_g1 1.33 ms one-lane, 1.23 all on rows, profiles/r06m_*)
+    // A few jobs take merge and level 1 on rows as well while the buckets of the set are few enough for rows to be the right
+    // grain: a row-addition is 4 - 5 x shorter than a lane's but a wave holds four rows instead of sixty-four lanes, so a set
+    // of 278 528 buckets (the seventeen digit positions of a 2^20-point variable-base multiexp) keeps the lanes' kernels for
+    // these two steps and goes onto rows where the reduction gets narrow (msm_reduce_g1 1.33 ms on lanes, 1.23 all on rows,
+    // profiles/r06m_*)
     // (G2: 16 384 - an addition on a row is 2.4 x G1's, and the 80 k buckets of the 2^17-point variable-base G2 multiexp took
     //  1.73 ms for merge + level 1 on rows against 0.8 ms with the lanes' kernels and only the heavy buckets on rows)
     const uint64_t coop_l1_max = getenv("ZKAMD_COOP_L1_MAX") ? (uint64_t)atoll(getenv("ZKAMD_COOP_L1_MAX"))
                                                                       : (zkdev::HostWords<DF>::N == 24 ? 16384ull : 131072ull);
-    const bool coop_l1 = coop && (uint64_t)nj * nb <= coop_l1_max;
+    const bool coop_l1 = few && (uint64_t)nj * nb <= coop_l1_max;
     // rows per bucket of the cooperative merge: a power of two near a quarter of the average number of partials
     uint32_t coop_rb = 1;
     if (coop_l1) {
@@ -168,8 +167,8 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     ZK_TRY(sorted.ensure((size_t)total_tasks * sizeof(uint4)));
     ZK_TRY(tsums.ensure((size_t)total_tasks * sizeof(DPoint)));
     ZK_TRY(pairs.ensure((size_t)(total ? total : 1) * 4));
-    // nodes of 16 buckets when that still leaves the machine full of threads, narrower nodes (a
-    // shorter serial chain per thread, more levels) when one or a few jobs must fill it alone
+    // level 1 on lanes: nodes of 16 buckets when that still leaves the machine full of threads, narrower nodes (a
+    // shorter serial chain per thread) when one or a few jobs must fill it alone
     auto pick_fan = [&](uint64_t items) -> uint32_t {
         uint32_t f = MSM_RED_FAN;
         while (f > 4 && items / f < 32768) f >>= 1;
@@ -183,25 +182,20 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     const bool big_launch = total >= (min_env ? (uint64_t)atoll(min_env) : (zkdev::HostWords<DF>::N == 24 ? 1000000ull : 4000000ull));
     // level 1 of the reduction in assembly: many-jobs launches only (the few-jobs tail folds level 1 differently)
     const bool red_asm = asm_reduce<DF>() && big_launch && !few;
-    uint32_t L = coop_l1 ? zkcoop::LEVEL1_FAN : pick_fan((uint64_t)nj * nb);
-    if (red_asm) {
-        // buckets per node of the assembly loop (a power of two): 32 - half the nodes for the compiled levels above
-        // it, still eight generations of waves per launch (16 / 32 / 64 measured within noise, r04g)
-        L = 32;
-        if (const char* env = getenv("ZKAMD_RED_NODE"))
-            if (atoi(env) >= 2 && atoi(env) <= 256 && !(atoi(env) & (atoi(env) - 1))) L = (uint32_t)atoi(env);
-    }
-    if (L > nb) L = nb;
+    // buckets per node of level 1 (a power of two).  The assembly loop: 32 - half the nodes for the tail above it, still
+    // eight generations of waves per launch (16 / 32 / 64 measured within noise, r04g)
+    const uint32_t L = std::min(nb, coop_l1 ? zkcoop::LEVEL1_FAN : red_asm ? 32u : pick_fan((uint64_t)nj * nb));
     const uint32_t T = nb / L;
-    ZK_TRY(red_r.ensure(nj * ((size_t)nb + 2 * (size_t)T) * sizeof(DPoint)));   // suffix sums: level 1 | two upper-level areas
-    ZK_TRY(red_w.ensure(2 * nj * (size_t)T * sizeof(DPoint)));  // W of the nodes (ping-pong halves)
-    size_t red_t_points = (size_t)T;                            // 2M * sum R' of the level being built
-    if (coop) {   // the cooperative tail keeps the parts of its planes and their sums Y here (coop_tail.h planes)
-        uint32_t nb_ = 0;
-        while ((1u << nb_) < T) nb_++;
-        red_t_points = std::max(red_t_points, (size_t)(nb_ + 1) * (zkcoop::planes_split(T) + 1));
-    }
-    ZK_TRY(red_t.ensure(nj * red_t_points * sizeof(DPoint)));
+    uint32_t nbits = 0, log2_2l = 1;   // log2(T), log2(2 L)
+    while ((1u << nbits) < T) nbits++;
+    while ((1u << (log2_2l - 1)) < L) log2_2l++;
+    // level 1 on rows and in assembly leaves one S per node; on lanes S is the first of a node's L suffix sums
+    const uint32_t s_stride = coop_l1 || red_asm ? 1u : L;
+    ZK_TRY(red_r.ensure(nj * (size_t)T * s_stride * sizeof(DPoint)));
+    ZK_TRY(red_w.ensure(nj * ((size_t)T + 1) * sizeof(DPoint)));   // W of the nodes (assembly level 1: A) | the sum of every job
+    // a few jobs: the parts of the planes when a plane takes several workgroups, then the planes' sums Y (coop_tail.h planes)
+    const uint32_t nsplit = zkcoop::planes_split(T);
+    if (few) ZK_TRY(red_t.ensure(nj * (size_t)(nbits + 1) * (nsplit > 1 ? nsplit + 1 : 1) * sizeof(DPoint)));
     // job descriptors through page-locked staging (collect() separates consecutive launch sets)
     ZK_TRY(pin_jobs.ensure(nj * (sizeof(MsmJob) + 4)));
     memcpy(pin_jobs.p, jobs.data(), nj * sizeof(MsmJob));
@@ -279,8 +273,6 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     }
     {
         ProfScope ps(zkdev::HostWords<DF>::N > 12 ? "msm_accumulate_g2" : "msm_accumulate_g1", st);
-        // G2: one wave per SIMD with the whole register file unless ZKAMD_G2_ACC_OCC=2 (A/B switch)
-        static const bool wide_g2 = !(getenv("ZKAMD_G2_ACC_OCC") && atoi(getenv("ZKAMD_G2_ACC_OCC")) == 2);
         // the assembly loops are built for launches that fill the machine; a proof made alone (one or two jobs, 16- or
         // 32-point tasks: `total` below the short-task threshold above) keeps the compiled kernel and saves the second launch
         if (asm_loop<DF>() && big_launch) {
@@ -311,96 +303,85 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
                             pw.size() > 0 ? pw[0] : 0, pw.size() > 1 ? pw[1] : 0, pw.size() > 2 ? pw[2] : 0);
                 }
             }
-        } else if (zkdev::HostWords<DF>::N > 12 && wide_g2)
+        } else if constexpr (zkdev::HostWords<DF>::N > 12)   // G2: one wave per SIMD with the whole register file
             ZK_LAUNCH(zkdev::k_msm_accumulate_wide<DF>, dim3((unsigned)((total_tasks + 127) / 128)), dim3(128), 0, st,
                       table.as<DAffine>(), pairs.as<uint32_t>(), sorted.as<uint4>(), d_total, tsums.as<DPoint>());
         else
             ZK_LAUNCH(zkdev::k_msm_accumulate<DF>, dim3((unsigned)((total_tasks + 127) / 128)), dim3(128), 0, st,
                       table.as<DAffine>(), pairs.as<uint32_t>(), sorted.as<uint4>(), d_total, tsums.as<DPoint>());
     }
-    DPoint* R = red_r.as<DPoint>();
-    DPoint* Wa = red_w.as<DPoint>();
-    DPoint* Wb = Wa + nj * (size_t)T;
-    DPoint* in = Wa;
+    DPoint* R = red_r.as<DPoint>();          // S of the nodes of level 1: node t of job j at R[(j T + t) s_stride]
+    DPoint* W = red_w.as<DPoint>();          // W of the nodes, compact
+    DPoint* sums = W + nj * (size_t)T;       // one XYZZ per job
     {
         ProfScope ps(zkdev::HostWords<DF>::N > 12 ? "msm_reduce_g2" : "msm_reduce_g1", st);
         auto grid = [&](uint32_t threads) { return dim3((threads + 63) / 64, (unsigned)nj); };
         const uint32_t heavy_blocks = (uint32_t)std::min<size_t>(heavy_cap, few ? 512 : 4096);
-        const uint32_t light_buckets = few ? (uint32_t)n_buckets : 0u;
-        if constexpr (HasCoopTail<DF>::value) {
-            if (coop_l1) {
-                // merge and level 1 (S, W per node of L buckets) on rows of 16 lanes (coop_tail.cpp)
-                zkcoop::merge<DF>(heavy.as<uint32_t>(), d_nheavy, cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(),
-                                  tsums.as<DPoint>(), nb, seg, n_buckets, heavy_blocks, merge_inline, coop_rb, st);
-                zkcoop::level1<DF>(tsums.as<DPoint>(), cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(), R, Wa, nb, L,
-                                   (uint32_t)nj, st);
+        // ---- merge: ts[0] of every bucket with several task partials = their sum
+        if (coop_l1) {
+            // on rows of 16 lanes (coop_tail.cpp)
+            zkcoop::merge<DF>(heavy.as<uint32_t>(), d_nheavy, cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(),
+                              tsums.as<DPoint>(), nb, seg, n_buckets, heavy_blocks, merge_inline, coop_rb, st);
+        } else {
+            // on lanes.  A few jobs: the buckets with many partials (the top digit position of a variable-base multiexp:
+            // 2^(c-6) buckets with dozens of tasks each) take a workgroup of rows each all the same - 64 partials are 8
+            // additions of 9 us there, 7 of 43+ us on lanes (the 2^17-point G2 multiexp: profiles/r06z_*) - the listed
+            // buckets with up to MEDIUM_MAX partials eight lanes each (k_msm_merge_medium: the list of a variable-base
+            // multiexp can hold half of its buckets), and the buckets with 2 .. merge_inline partials one lane each in the
+            // trailing workgroups of k_msm_merge_heavy
+            // (MEDIUM_MAX: never beyond the threshold from which the split form of coop_tail.cpp takes a bucket - a test lowers
+            //  that one)
+            const uint32_t MEDIUM_MAX = std::min<uint32_t>(64u, zkcoop::merge_split_min());
+            if (hook_env("ZKAMD_DEBUG_HEAVY")) {   // diagnostics: the heavy list of the set and the partials of its buckets
+                (void)hipStreamSynchronize(st);
+                uint32_t nh = 0;
+                (void)hipMemcpy(&nh, d_nheavy, 4, hipMemcpyDeviceToHost);
+                std::vector<uint32_t> hl(nh), ch(n_buckets);
+                if (nh) (void)hipMemcpy(hl.data(), heavy.as<uint32_t>(), nh * 4, hipMemcpyDeviceToHost);
+                (void)hipMemcpy(ch.data(), cnt.as<uint32_t>(), n_buckets * 4, hipMemcpyDeviceToHost);
+                uint32_t mx = 0, le = 0;
+                uint64_t sum = 0;
+                for (uint32_t q = 0; q < nh; q++) {
+                    const uint32_t nt = (ch[hl[q]] + seg - 1) / seg;
+                    mx = std::max(mx, nt);
+                    le += nt <= MEDIUM_MAX;
+                    sum += nt;
+                }
+                fprintf(stderr, "[heavy] nj %zu nb %u seg %u merge_inline %u: %u listed buckets (%u with <= %u partials), %llu partials, largest %u\n", nj, nb,
+                        seg, merge_inline, nh, le, MEDIUM_MAX, (unsigned long long)sum, mx);
             }
-        }
-        if (!coop_l1) {
-        // the buckets with many partials (the top digit position of a variable-base multiexp: 2^(c-6) buckets with dozens of
-        // tasks each) take a workgroup of rows each when the set has the cooperative tail: 64 partials are 8 additions of 9 us
-        // there, 7 of 43+ us on lanes (the 2^17-point G2 multiexp: profiles/r06z_*); the buckets with 2 .. merge_inline
-        // partials stay with one lane each
-        // ... and the listed buckets with up to MEDIUM_MAX partials eight lanes each (k_msm_merge_medium: the list of a
-        // variable-base multiexp can hold half of its buckets)
-        // (never beyond the threshold from which the split form of coop_tail.cpp takes a bucket: a test lowers that one)
-        const uint32_t MEDIUM_MAX = std::min<uint32_t>(64u, zkcoop::merge_split_min());
-        bool heavy_on_rows = false;
-        if (hook_env("ZKAMD_DEBUG_HEAVY")) {   // diagnostics: the heavy list of the set and the partials of its buckets
-            (void)hipStreamSynchronize(st);
-            uint32_t nh = 0;
-            (void)hipMemcpy(&nh, d_nheavy, 4, hipMemcpyDeviceToHost);
-            std::vector<uint32_t> hl(nh), ch(n_buckets);
-            if (nh) (void)hipMemcpy(hl.data(), heavy.as<uint32_t>(), nh * 4, hipMemcpyDeviceToHost);
-            (void)hipMemcpy(ch.data(), cnt.as<uint32_t>(), n_buckets * 4, hipMemcpyDeviceToHost);
-            uint32_t mx = 0, le = 0;
-            uint64_t sum = 0;
-            for (uint32_t q = 0; q < nh; q++) {
-                const uint32_t nt = (ch[hl[q]] + seg - 1) / seg;
-                mx = std::max(mx, nt);
-                le += nt <= MEDIUM_MAX;
-                sum += nt;
-            }
-            fprintf(stderr, "[heavy] nj %zu nb %u seg %u merge_inline %u: %u listed buckets (%u with <= %u partials), %llu partials, largest %u\n", nj, nb,
-                    seg, merge_inline, nh, le, MEDIUM_MAX, (unsigned long long)sum, mx);
-        }
-        if (few)
-            ZK_LAUNCH_SYNC(zkdev::k_msm_merge_medium<DF>, dim3((unsigned)std::min<size_t>((heavy_cap + 7) / 8, 4096)), dim3(64), 0, st,
-                           (const uint32_t*)heavy.as<uint32_t>(), (const uint32_t*)d_nheavy, (const uint32_t*)cnt.as<uint32_t>(),
-                           (const uint32_t*)toff.as<uint32_t>(), (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg, MEDIUM_MAX);
-        const uint32_t min_heavy = few ? MEDIUM_MAX : 0u;
-        if constexpr (HasCoopTail<DF>::value) {
-            if (coop) {
+            const uint32_t min_heavy = few ? MEDIUM_MAX : 0u;
+            if (few) {
+                ZK_LAUNCH_SYNC(zkdev::k_msm_merge_medium<DF>, dim3((unsigned)std::min<size_t>((heavy_cap + 7) / 8, 4096)), dim3(64), 0, st,
+                               (const uint32_t*)heavy.as<uint32_t>(), (const uint32_t*)d_nheavy, (const uint32_t*)cnt.as<uint32_t>(),
+                               (const uint32_t*)toff.as<uint32_t>(), (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg, MEDIUM_MAX);
                 zkcoop::merge<DF>(heavy.as<uint32_t>(), d_nheavy, cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(),
                                   tsums.as<DPoint>(), nb, seg, 0, heavy_blocks, merge_inline, 1, st, min_heavy);
-                heavy_on_rows = true;
             }
+            // a chunk of proofs: the heavy list, one workgroup of lanes per bucket ...
+            const uint32_t lane_heavy_blocks = few ? 0u : heavy_blocks;
+            const uint32_t light_buckets = few ? (uint32_t)n_buckets : 0u;
+            ZK_LAUNCH_SYNC(zkdev::k_msm_merge_heavy<DF>,
+                           dim3(lane_heavy_blocks + (light_buckets + zkdev::MSM_MERGE_THREADS - 1) / zkdev::MSM_MERGE_THREADS),
+                           dim3(zkdev::MSM_MERGE_THREADS), 0, st, (const uint32_t*)heavy.as<uint32_t>(), (const uint32_t*)d_nheavy,
+                           (const uint32_t*)cnt.as<uint32_t>(), (const uint32_t*)toff.as<uint32_t>(),
+                           (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg, lane_heavy_blocks, light_buckets,
+                           merge_inline, min_heavy);
+            // ... and the listed buckets with 2 .. merge_inline partials, one thread each: level 1 then meets ONE partial
+            // per bucket
+            if (use_light)
+                ZK_LAUNCH_SYNC(zkdev::k_msm_merge_light<DF>, dim3((unsigned)std::min<size_t>((light_cap + 63) / 64, 2048)), dim3(64), 0, st,
+                               (const uint32_t*)light.as<uint32_t>(), (const uint32_t*)d_nlight, (const uint32_t*)cnt.as<uint32_t>(),
+                               (const uint32_t*)toff.as<uint32_t>(), (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg);
         }
-        const uint32_t lane_heavy_blocks = heavy_on_rows ? 0u : heavy_blocks;
-        if (lane_heavy_blocks + light_buckets)
-        ZK_LAUNCH_SYNC(zkdev::k_msm_merge_heavy<DF>,
-                       dim3(lane_heavy_blocks + (light_buckets + zkdev::MSM_MERGE_THREADS - 1) / zkdev::MSM_MERGE_THREADS),
-                       dim3(zkdev::MSM_MERGE_THREADS), 0, st, (const uint32_t*)heavy.as<uint32_t>(), (const uint32_t*)d_nheavy,
-                       (const uint32_t*)cnt.as<uint32_t>(), (const uint32_t*)toff.as<uint32_t>(),
-                       (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg, lane_heavy_blocks, light_buckets,
-                       merge_inline, min_heavy);
-        // the listed buckets with 2 .. merge_inline partials, one thread each (the heavier ones above): level 1 then
-        // meets ONE partial per bucket
-        if (use_light)
-            ZK_LAUNCH_SYNC(zkdev::k_msm_merge_light<DF>, dim3((unsigned)std::min<size_t>((light_cap + 63) / 64, 2048)), dim3(64), 0, st,
-                           (const uint32_t*)light.as<uint32_t>(), (const uint32_t*)d_nlight, (const uint32_t*)cnt.as<uint32_t>(),
-                           (const uint32_t*)toff.as<uint32_t>(), (const uint32_t*)tbase.as<uint32_t>(), tsums.as<DPoint>(), nb, seg);
-        }
-        uint32_t n = T, m = L, stride = L;   // n nodes per job of m buckets each; S(node k) = R[k * stride]
-        DPoint* Rcur = R;
-        DPoint* Rnext = R + nj * (size_t)nb;       // upper levels ping-pong between two areas behind level 1
-        DPoint* Rspare = Rnext + nj * (size_t)T;
-        if (red_asm) {
-            // level 1 in assembly: S = R_0 (compact, one per node) and A = sum_{k>=1} R_k; then the first level above
-            // it, which forms W(parent) = 2M sum_{k>=1} R'_k + 2 sum_k A_k + R'_0 (msm.h k_msm_level2_acc) - run even
-            // for a single node per job, where it is just W = 2 A + S
+        // ---- level 1: S and W of every node of L buckets
+        if (coop_l1) {
+            zkcoop::level1<DF>(tsums.as<DPoint>(), cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(), R, W, nb, L,
+                               (uint32_t)nj, st);
+        } else if (red_asm) {
+            // in assembly: S = R_0 and, in W's place, A = sum_{k>=1} R_k = (W - S) / 2
             ZK_TRY(redo.ensure(std::max((size_t)total_tasks, (size_t)nj * T) * 4));   // (the accumulation's second pass is done with its list by now)
-            launch_red_asm<DF>(tsums.as<DPoint>(), cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(), R, Wa, nb, L,
+            launch_red_asm<DF>(tsums.as<DPoint>(), cnt.as<uint32_t>(), toff.as<uint32_t>(), tbase.as<uint32_t>(), R, W, nb, L,
                                grid(T), st, d_nfallback, redo.as<uint32_t>());
             if (hook_env("ZKAMD_DEBUG_REDO")) {   // diagnostics: nodes of level 1 the assembly loop handed to the compiled addition
                 (void)hipStreamSynchronize(st);
@@ -409,99 +390,32 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
                 fprintf(stderr, "[redo] reduction G1: %u buckets with 2..%u partials merged, %u of %zu level-1 nodes recomputed\n", v[0],
                         merge_inline, v[1], (size_t)nj * T);
             }
-            if (!coop_upper) {   // (a chunk of proofs: coop_upper below takes the levels above the assembly level 1)
-                const uint32_t fan = pick_fan((uint64_t)nj * n), n_out = (n + fan - 1) / fan;
-                uint32_t log2_2m = 1;
-                while ((1u << (log2_2m - 1)) < m) log2_2m++;
-                ZK_LAUNCH(zkdev::k_msm_suffix<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)R, Rnext, n, fan, 1u);
-                ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Rnext, (const DPoint*)nullptr,
-                          red_t.as<DPoint>(), n, fan, 1u, log2_2m, 0u);
-                ZK_LAUNCH(zkdev::k_msm_level2_acc<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Wa, (const DPoint*)Rnext,
-                          (const DPoint*)red_t.as<DPoint>(), Wb, n, fan);
-                in = Wb;
-                Rcur = Rnext;
-                std::swap(Rnext, Rspare);
-                stride = fan;
-                m *= fan;
-                n = n_out;
-            }
-        } else if (!coop_l1) {
-            // level 1: R = suffix sums over the buckets of a node; S = R_0; W = 2 * sum_{k>=1} R_k + R_0
+        } else {
+            // on lanes: R = suffix sums over the buckets of a node; S = R_0; W = 2 * sum_{k>=1} R_k + R_0
             ZK_LAUNCH(zkdev::k_msm_suffix_buckets<DF>, grid(T), dim3(64), 0, st, tsums.as<DPoint>(), cnt.as<uint32_t>(),
                       toff.as<uint32_t>(), tbase.as<uint32_t>(), R, nb, L, few ? 0u : 1u /* merged by now */, seg);
-            ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(T), dim3(64), 0, st, (const DPoint*)R, (const DPoint*)nullptr, Wa, nb, L,
+            ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(T), dim3(64), 0, st, (const DPoint*)R, (const DPoint*)nullptr, W, nb, L,
                       1u, 1u, 1u);
         }
-        if (coop) {
-            if constexpr (HasCoopTail<DF>::value) {
-                // the T nodes of level 1 (S at R[t * s_stride], W compact) folded at once on rows of 16 lanes: bit planes, then
-                // their weighted sum - chains of ~15 and ~20 dependent additions of 2 - 4 us (coop_tail.cpp)
-                uint32_t nbits = 0, log2_2l = 1;
-                while ((1u << nbits) < T) nbits++;
-                while ((1u << (log2_2l - 1)) < L) log2_2l++;
-                const uint32_t nsplit = zkcoop::planes_split(T);
-                DPoint* parts = red_t.as<DPoint>();    // [nj (nbits + 1) nsplit] when a plane takes several workgroups
-                DPoint* Y = nsplit > 1 ? parts + nj * (size_t)(nbits + 1) * nsplit : parts;   // [nj (nbits + 1)]
-                zkcoop::planes<DF>(R, coop_l1 ? 1u : L, Wa, Y, parts, T, nbits, (uint32_t)nj, st);
-                zkcoop::combine<DF>(Y, Wb, nbits, log2_2l, (uint32_t)nj, st);
-                in = Wb;
-                n = 1;
-            }
-        } else if (coop_upper) {
-            if constexpr (HasCoopTail<DF>::value) {
-                // S at R[t * L] (lane level 1) or compact (assembly level 1, whose W area holds A: W = 2 A + S)
-                uint32_t log2_2l = 1;
-                while ((1u << (log2_2l - 1)) < L) log2_2l++;
-                zkcoop::upper<DF>(R, red_asm ? 1u : L, Wa, Wb, T, log2_2l, red_asm, (uint32_t)nj, st);
-                in = Wb;
-                n = 1;
-            }
-        } else if (few && T >= 2 && !getenv("ZKAMD_NO_BITSUM")) {
-            // few large jobs: fold the T nodes of level 1 at once (msm.h, k_msm_bitsum)
-            uint32_t nbits = 0, log2_2l = 1;
-            while ((1u << nbits) < T) nbits++;
-            while ((1u << (log2_2l - 1)) < L) log2_2l++;
-            const uint32_t nblk = (T + zkdev::MSM_BITSUM_NODES - 1) / zkdev::MSM_BITSUM_NODES;
-            const uint32_t nlow = std::min(nbits, zkdev::MSM_BITSUM_LOG);
-            const uint32_t n_planes = nlow + (nbits > nlow ? 1u : 0u) + 1u;   // bit planes | block sums U | W
-            DPoint* part = red_t.as<DPoint>();   // n_planes * nblk <= T partials per job
-            ZK_LAUNCH_SYNC(zkdev::k_msm_bitsum<DF>, dim3(nblk, n_planes, (unsigned)nj), dim3(64), 0, st, (const DPoint*)R, L,
-                           (const DPoint*)Wa, part, T, nbits);
-            ZK_LAUNCH_SYNC(zkdev::k_msm_bitsum_fold<DF>, dim3(nbits + 1, (unsigned)nj), dim3(64), 0, st, (const DPoint*)part, Wb,
-                           nblk, nbits, n_planes);
-            ZK_LAUNCH_SYNC(zkdev::k_msm_bitsum_combine<DF>, dim3((unsigned)nj), dim3(64), 0, st, (const DPoint*)Wb, Rnext, nbits,
-                           log2_2l);
-            in = Rnext;
-            n = 1;
-        }
-        while (n > 1) {
-            const uint32_t fan = pick_fan((uint64_t)nj * n), n_out = (n + fan - 1) / fan;
-            uint32_t log2_2m = 1;
-            while ((1u << (log2_2m - 1)) < m) log2_2m++;
-            // R' = suffix sums of S over the children of a parent
-            ZK_LAUNCH(zkdev::k_msm_suffix<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Rcur, Rnext, n, fan, stride);
-            // T = 2M * sum_{k>=1} R'_k ;  W(parent) = T + sum_k W(c_k)
-            ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)Rnext, (const DPoint*)nullptr,
-                      red_t.as<DPoint>(), n, fan, 1u, log2_2m, 0u);
-            DPoint* outW = in == Wa ? Wb : Wa;
-            ZK_LAUNCH(zkdev::k_msm_segsum<DF>, grid(n_out), dim3(64), 0, st, (const DPoint*)in,
-                      (const DPoint*)red_t.as<DPoint>(), outW, n, fan, 0u, 0u, 0u);
-            in = outW;
-            // the parents' S are R'[first child of each parent]
-            Rcur = Rnext;
-            std::swap(Rnext, Rspare);
-            stride = fan;
-            m *= fan;
-            n = n_out;
+        // ---- tail: sums[j] = sum_t W_t + 2 L sum_t t S_t over the T nodes of job j, on rows of 16 lanes (coop_tail.cpp)
+        if (few) {
+            // folded at once: bit planes, then their weighted sum - chains of ~15 and ~20 dependent additions of 2 - 4 us
+            DPoint* parts = red_t.as<DPoint>();    // [nj (nbits + 1) nsplit] when a plane takes several workgroups
+            DPoint* Y = nsplit > 1 ? parts + nj * (size_t)(nbits + 1) * nsplit : parts;   // [nj (nbits + 1)]
+            zkcoop::planes<DF>(R, s_stride, W, Y, parts, T, nbits, (uint32_t)nj, st);
+            zkcoop::combine<DF>(Y, sums, nbits, log2_2l, (uint32_t)nj, st);
+        } else {
+            // a chunk of proofs: one workgroup per job walks its nodes (three additions per node, not (nbits + 1) / 2)
+            zkcoop::upper<DF>(R, s_stride, W, sums, T, log2_2l, red_asm, (uint32_t)nj, st);
         }
     }
-    res_dev = in;   // one XYZZ per job, valid until the next enqueue on this group
+    res_dev = sums;   // one XYZZ per job, valid until the next enqueue on this group
     if (!to_host) {
         HIP_TRY(hipGetLastError());
         return ZK_OK;
     }
     ZK_TRY(result.ensure(nj * sizeof(HPoint)));
-    ZK_LAUNCH(zkdev::k_export_xyzz<DF>, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, st, (const DPoint*)in,
+    ZK_LAUNCH(zkdev::k_export_xyzz<DF>, dim3((unsigned)((nj + 63) / 64)), dim3(64), 0, st, (const DPoint*)sums,
               result.as<uint32_t>(), (uint32_t)nj);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpyAsync(out.data(), result.p, nj * sizeof(HPoint), hipMemcpyDeviceToHost, st));

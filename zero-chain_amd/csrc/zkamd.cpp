@@ -4,7 +4,7 @@
 // un-vendored bellman 0.1.0 crate; restated in SURVEY.md Appendix A):
 //   create_proof step 3  (EvaluationDomain H pipeline)   -> ntt.h kernels, NttPlan below
 //   create_proof step 4  (8 x multiexp)                  -> msm.h kernels, MsmGroup below
-//   create_proof step 6  (final fold, into_affine)       -> k_xyzz_scale_add / k_xyzz_normalize_export (msm.h)
+//   create_proof step 6  (final fold, into_affine)       -> k_ct_scale_add (coop_tail.cpp) / k_xyzz_normalize_export (msm.h)
 //   Parameters::read                                     -> Params::load below
 //   Proof::write                                         -> host_math.h g1/g2_to_compressed
 #include <stdio.h>
@@ -300,7 +300,6 @@ struct zk_params {
     // own size (one width for both held the large job at c = 15).  g1 = the C' set; g1a = the A set;
     // g1_lone = both jobs in one set under the width of their average, for a few proofs made alone (fewer launches).
     MsmG1 g1a, g1_lone;
-    bool split_g1 = true;
     MsmG2 g2;
     // the G2 group again over the SAME table with a narrower recoding, for a proof made alone: its side stream is the
     // critical path and the depth of the bucket reduction (bit planes, doublings) is what it waits for - 256 buckets
@@ -436,9 +435,8 @@ zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk
     // two G1 jobs per proof: A, and the merged C' = H + L + r * B1 - each with the width of its own size
     // (a few proofs made alone never reach the assembly level 1 of the reduction: bucket cost of the compiled few-jobs
     //  path, group 4 - ADVICE r4; the split launch sets below: group 1 / 3)
-    const uint32_t c_avg = pick_window(((size_t)P->n_h + P->n_l + P->n_a + P->n_b1) / 2, getenv("ZKAMD_SPLIT_G1") && atoi(getenv("ZKAMD_SPLIT_G1")) == 0 ? 1 : 4);
-    P->split_g1 = !(getenv("ZKAMD_SPLIT_G1") && atoi(getenv("ZKAMD_SPLIT_G1")) == 0);
-    const uint32_t c1 = P->split_g1 ? pick_window((size_t)P->n_h + P->n_l + P->n_b1, 1) : c_avg;
+    const uint32_t c_avg = pick_window(((size_t)P->n_h + P->n_l + P->n_a + P->n_b1) / 2, 4);
+    const uint32_t c1 = pick_window((size_t)P->n_h + P->n_l + P->n_b1, 1);
     const uint32_t c2 = pick_window(P->n_b2, 2);
     {
         // both groups decoded side by side, then both tables of doublings built side by side (each is one thread per base
@@ -522,7 +520,6 @@ zk_params* params_clone_for_lane(const zk_params* P) {
     Q->g1.alias(P->g1, P->g1.c);
     Q->g1a.alias(P->g1, P->g1a.c);
     Q->g1_lone.alias(P->g1, P->g1_lone.c);
-    Q->split_g1 = P->split_g1;
     Q->g2.c = P->g2.c; Q->g2.maxd = P->g2.maxd; Q->g2.nb = P->g2.nb; Q->g2.n_points = P->g2.n_points;
     Q->g2.table.borrow(P->g2.table);
     Q->g2_lone.alias(P->g2, P->g2_lone.c);
@@ -629,7 +626,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // complete, the alpha and r*delta terms rode along in the A multiexp) and
 // C' = h + l + r*(beta_1 + sum_B1) from the merged multiexp,
 //   C = s*A + C'   ==  rs*delta + s*alpha + r*beta_1 + s*sum_A + r*sum_B1 + h + l.
-// (prove_chunk: the fold and the three into_affine run on the GPU, k_xyzz_scale_add /
+// (prove_chunk: the fold and the three into_affine run on the GPU, k_ct_scale_add /
 // k_xyzz_normalize_export; the host encodes the 192 bytes.)
 
 zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out) {
@@ -662,9 +659,9 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
     // A few proofs made alone carry the final fold C = s * A + C' INSIDE the C multiexp: s * A = s alpha_1 + sum (s z_i) A_i +
     // (r s) delta_1 is 15.6 k more terms over bases whose doublings are in the table (+19 % pairs in a launch whose duration is
-    // the length of its longest task, not their number), where k_xyzz_scale_add is a chain of 252 doublings and ~75 additions
+    // the length of its longest task, not their number), where the fold's kernel (k_ct_scale_add) is a chain of 252 doublings and ~75 additions
     // of ONE point: 4.7 ms of a 7.4 ms proof under a 255-bit s (profiles/r06c_lone_baseline_random_rs_launch_list.txt).
-    // A batch keeps the chain: one lane per proof, hidden behind the other pipeline lane, no extra pairs.
+    // A batch keeps the chain: one row per proof, hidden behind the other pipeline lane, no extra pairs.
     // Up to the few-jobs limit of a launch set (128 proofs): there the chain is exposed at the end of the call - 4.7 ms on
     // a call of 17.6 ms for 32 proofs - and 19 % more G1 pairs cost less.  ZKAMD_FOLD_IN_MSM_MAX overrides (measurements).
     // (read at every chunk: the emulation suite sends small batches through the chunk form of the fold)
@@ -729,11 +726,11 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
                         (const uint32_t*)C, (uint32_t)m));
     // A batch runs the two G1 jobs of its proofs as two launch sets, each under the recoding width of its own size: the
     // C' jobs (65 k terms) here on the main stream behind the H pipeline, the A jobs (15.6 k terms, witness scalars only)
-    // on the side stream behind the G2 set (ZKAMD_G1A_STREAM=main: behind the C' set).  A few proofs made alone keep
+    // on the side stream behind the G2 set.  A few proofs made alone keep
     // ONE set (fewer launches on their critical path): all C' jobs, then all A jobs - workgroup i of a launch runs on XCD
     // i mod 8 and the sort is one workgroup per job, so alternating A, C' would put every large job on the odd XCDs.
     const size_t split_min = getenv("ZKAMD_SPLIT_MIN") ? (size_t)atoll(getenv("ZKAMD_SPLIT_MIN")) : 64;   // tests: 1
-    const bool split = P->split_g1 && np >= split_min;
+    const bool split = np >= split_min;
     MsmG1& G1C = split ? P->g1 : P->g1_lone;
     for (size_t p = 0; p < np; p++) {
         MsmJob jc = {cvec + p * (size_t)cstride * 8, (fold_in_msm ? P->map_cf : P->map_c).as<int32_t>(), cstride, 0, npts1, 0, 0, 0};
@@ -748,21 +745,16 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     typedef zkdev::XYZZ<zkdev::Fq> DP1;
     const DP1* a_dev = nullptr;
     if (split) {
-        const bool a_on_main = getenv("ZKAMD_G1A_STREAM") && !strcmp(getenv("ZKAMD_G1A_STREAM"), "main");
-        const hipStream_t sa = a_on_main ? g_stream : side;
-        if (a_on_main) ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
-        ZK_TRY(P->g1a.enqueue(P->jobs1a, P->res1a, sa, false));
+        ZK_TRY(P->g1a.enqueue(P->jobs1a, P->res1a, side, false));
         a_dev = P->g1a.res_dev;
-        if (!a_on_main) {
-            HIP_TRY(hipEventRecord(g_ev_join, sa));
-            ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
-            HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when ZKAMD_NO_OVERLAP made the side stream the main one)
-        }
+        HIP_TRY(hipEventRecord(g_ev_join, side));
+        ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
+        HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when ZKAMD_NO_OVERLAP made the side stream the main one)
     } else {
         ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
         a_dev = G1C.res_dev + np;
     }
-    // ---- final fold on the GPU: C = s * A + C' (k_xyzz_scale_add), A and C to affine form; the host
+    // ---- final fold on the GPU: C = s * A + C' (coop_tail.h scale_add), A and C to affine form; the host
     // only encodes.  (On the host the fold was 0.47 ms per proof with the GPU idle: 8 % of the step.)
     {
         ProfScope ps("proof_fold", g_stream);
@@ -772,14 +764,9 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
         if (!fold_in_msm) {
             ZK_TRY(P->fold_tbl.ensure(np * 15 * sizeof(DP1)));
             ZK_TRY(P->fold_c.ensure(np * sizeof(DP1)));
-            // one row of 16 lanes per proof (coop_tail.cpp): 256 waves, each chain 4 - 5 x shorter than a lane's; the
-            // one-lane kernel under ZKAMD_COOP_TAIL=0
-            if (coop_tail_on())
-                zkcoop::scale_add(a, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
-                                  P->fold_c.as<DP1>(), (uint32_t)np, g_stream);
-            else
-                ZK_LAUNCH(zkdev::k_xyzz_scale_add<zkdev::Fq>, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, g_stream, a, cprime,
-                          (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(), P->fold_c.as<DP1>(), (uint32_t)np);
+            // one row of 16 lanes per proof (coop_tail.cpp): 256 waves, each chain 4 - 5 x shorter than a lane's
+            zkcoop::scale_add(a, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
+                              P->fold_c.as<DP1>(), (uint32_t)np, g_stream);
             cfin = P->fold_c.as<DP1>();
         }
         if (host_norm) {
@@ -1644,7 +1631,7 @@ zk_status zk_params_get_info(const zk_params* p, zk_params_info* info) try {
 zk_status zk_params_get_windows(const zk_params* p, uint32_t out[4]) try {
     if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     out[0] = p->g1.c;
-    out[1] = p->split_g1 ? p->g1a.c : p->g1.c;
+    out[1] = p->g1a.c;
     out[2] = p->g1_lone.c;
     out[3] = p->g2.c;
     return ZK_OK;
