@@ -5,35 +5,6 @@
 
 namespace zkrt {
 
-namespace {
-// one machine-filling launch, three times, the first not counted: the best of the other two in ms
-template <class Launch>
-zk_status timed_best(Launch&& launch, float* best) {
-    hipEvent_t ev[2];
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } evg{ev};
-    *best = 1e30f;
-    for (int rep = 0; rep < 3; rep++) {   // (the first repetition warms the instruction cache and is not counted)
-        HIP_TRY(hipEventRecord(ev[0], g_stream));
-        launch();
-        HIP_TRY(hipEventRecord(ev[1], g_stream));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        if (rep && ms < *best) *best = ms;
-    }
-    HIP_TRY(hipGetLastError());
-    return ZK_OK;
-}
-}  // namespace
-
 #ifdef ZK_HAVE_RED_ASM
 template <>
 void launch_red_asm<zkdev::Fq28>(const zkdev::XYZZ<zkdev::Fq28>* tsums, const uint32_t* cnt, const uint32_t* toff, const uint32_t* tbase,
@@ -115,3 +86,37 @@ template zk_status check_points_dev<zkhost::Fq, zkdev::Fq>(const zkdev::Affine<z
 template zk_status check_points_host<zkhost::Fq, zkdev::Fq>(const std::vector<zkhost::Affine<zkhost::Fq>>&, const char*);
 
 }  // namespace zkrt
+
+#ifdef ZK_TEST_HOOKS
+// Test hook, NOT part of the ABI (absent from libzkamd.so): the plan of the launch set that n_jobs jobs of n[k] scalars each
+// would be in a group of window c (msm_plan.h; vb_digit != 0: the digit positions of a variable-base multiexp), under the
+// environment of the call.  has_asm_loop / has_asm_reduce stand for the build (the emulation has neither loop, the product
+// both).  out[0 .. 48) = the plan's fields in the order of the list below, then n_jobs x pair_base, n_jobs x tbase; a
+// refused set returns the refusal, its wording in zk_last_error().
+extern "C" zk_status zk_hook_msm_plan(int is_g2, uint32_t c, const uint32_t* n, size_t n_jobs, uint32_t vb_digit, int has_asm_loop,
+                                      int has_asm_reduce, uint64_t* out, size_t out_words) try {
+    using namespace zkrt;
+    if (!n || !n_jobs || !out || c < 2 || c > 22) return fail(ZK_ERR_INVALID_ARGUMENT, "bad argument");
+    std::vector<MsmJob> jobs(n_jobs, MsmJob{});
+    for (size_t k = 0; k < n_jobs; k++) {
+        jobs[k].n = n[k];
+        jobs[k].vb_digit = vb_digit;
+    }
+    MsmPlan p;
+    if (msm_plan(p, is_g2 != 0, c, 1u << (c - 2), vb_digit ? 1u : zkdev::msm_max_digits(c), jobs.data(), n_jobs, has_asm_loop != 0,
+                 has_asm_reduce != 0, MsmTunables::read(is_g2 != 0)) != ZK_OK)
+        return fail(p.status, p.refusal);
+    const MsmPlan::Bytes& b = p.bytes;
+    const uint64_t f[] = {p.seg, p.few, p.coop_l1, p.coop_rb, p.merge_inline, p.heavy_cap, p.light_cap, p.use_light, p.big_launch, p.acc_asm,
+                          p.red_asm, p.L, p.T, p.nbits, p.log2_2l, p.s_stride, p.nsplit, p.lds_sort, p.fine_log, p.n_coarse, p.coarse_wgs,
+                          p.heavy_blocks, p.medium_max, p.max_n, p.total, p.total_tasks, p.n_buckets, p.n_class,
+                          b.jobs_d, b.bucket, b.per_job, b.hist, b.heavy, b.light, b.tclass, b.sorted, b.tsums, b.pairs, b.red_r, b.red_w, b.red_t,
+                          b.pin_jobs, b.rank, b.blockbase, b.coarse, b.redo, b.result, n_jobs};
+    const size_t nf = sizeof(f) / sizeof(f[0]);
+    if (out_words < nf + 2 * n_jobs) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    std::copy(f, f + nf, out);
+    std::copy(p.pair_base.begin(), p.pair_base.end(), out + nf);
+    std::copy(p.tbase.begin(), p.tbase.end(), out + nf + n_jobs);
+    return ZK_OK;
+} ZK_ABI_CATCH
+#endif

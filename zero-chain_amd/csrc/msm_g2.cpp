@@ -5,35 +5,6 @@
 
 namespace zkrt {
 
-namespace {
-// one machine-filling launch, three times, the first not counted: the best of the other two in ms
-template <class Launch>
-zk_status timed_best(Launch&& launch, float* best) {
-    hipEvent_t ev[2];
-    HIP_TRY(hipEventCreate(&ev[0]));
-    HIP_TRY(hipEventCreate(&ev[1]));
-    struct EvGuard {
-        hipEvent_t* e;
-        ~EvGuard() {
-            (void)hipEventDestroy(e[0]);
-            (void)hipEventDestroy(e[1]);
-        }
-    } evg{ev};
-    *best = 1e30f;
-    for (int rep = 0; rep < 3; rep++) {   // (the first repetition warms the instruction cache and is not counted)
-        HIP_TRY(hipEventRecord(ev[0], g_stream));
-        launch();
-        HIP_TRY(hipEventRecord(ev[1], g_stream));
-        HIP_TRY(hipEventSynchronize(ev[1]));
-        float ms = 0;
-        HIP_TRY(hipEventElapsedTime(&ms, ev[0], ev[1]));
-        if (rep && ms < *best) *best = ms;
-    }
-    HIP_TRY(hipGetLastError());
-    return ZK_OK;
-}
-}  // namespace
-
 #ifdef ZK_HAVE_MADD_ASM
 template <>
 void launch_asm_loop<zkdev::Fq2x>(const zkdev::Affine<zkdev::Fq2x>* table, const uint32_t* pairs, const uint4* sorted,

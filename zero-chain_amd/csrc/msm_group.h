@@ -11,6 +11,7 @@
 #include <string>
 #include <vector>
 #include <algorithm>
+#include <utility>
 #include <mutex>
 #include "../../include/zkamd.h"
 #include "gpu_rt.h"
@@ -18,25 +19,9 @@
 #include "host_math.h"
 #include "msm.h"
 #include "coop_tail.h"
+#include "msm_plan.h"
 
 namespace zkrt {
-
-using zkdev::MsmJob;
-
-// ------------------------------------------------------------------------------------------
-// MSM group: window tables of a set of bases + the bucket pipeline over a list of jobs
-// ------------------------------------------------------------------------------------------
-// At most this many jobs per launch set: the latency-optimised form (many-workgroup sort, bit-plane tail of the bucket
-// reduction: coop_tail.h planes / combine).  8 until round 5; a kernel trace of a 32-proof call then showed the many-jobs form's eleven k_msm_segsum<Fq2x>
-// launches - 0.8 ms each whether for 32 jobs or 1024: 8.9 of the call's 16.8 ms - and the sweep of tools/few_jobs_probe.py
-// (profiles/r05end_few_jobs_probe.txt, same proof bytes under every setting): 8 proofs per call 10.5 -> 7.8 ms, 16: 14.9 -> 10.9,
-// 32: 19.9 -> 17.6, 64: 35.1 -> 30.1, 128: 51.6 -> 49.7; from 256 jobs on the many-jobs form wins (86.1 against 90.2).
-constexpr size_t MSM_FEW_JOBS = 128;
-inline size_t few_jobs_max() {           // ZKAMD_FEW_JOBS: override for measurements and for the tests (read at every launch set:
-    const char* env = getenv("ZKAMD_FEW_JOBS");   // the emulation suite runs its batches under both forms)
-    return env && atoll(env) > 0 ? (size_t)atoll(env) : MSM_FEW_JOBS;
-}
-constexpr uint32_t MSM_RED_FAN = 16;   // buckets per level-1 node and children per upper node (bucket reduction)
 
 // Width of the NAF recoding for jobs of about n scalars: minimise, in units of one mixed addition,
 //   n * 254 / (c + 1)  (bucket accumulation)  +  beta * 2^(c-2)  (bucket reduction),
@@ -167,24 +152,33 @@ struct MsmGroup {
     static_assert(sizeof(HAffine) == 2 * 4 * zkdev::HostWords<DF>::N, "host affine layout");
     static_assert(sizeof(HPoint) == 4 * 4 * zkdev::HostWords<DF>::N, "host point layout");
 
+    static constexpr bool IS_G2 = zkdev::HostWords<DF>::N == 24;
+
     uint32_t c = 0, maxd = 0, nb = 0;
     size_t n_points = 0;
     DevBuf table;
     DevBuf jobs_d, cnt, off, toff, ntasks, hist, tclass, sorted, heavy, light, blockbase, coarse, tbase, rank, pairs, tsums, red_r, red_w, red_t, result, redo;
     DPoint* res_dev = nullptr;
     PinBuf pin_jobs;
-    std::vector<uint32_t> tbase_h;
     size_t bytes = 0;
     DevBuf dstat;   // [first refused encoding | points at infinity] of the last decode_enqueue (msm.h k_decode_uncompressed)
 
-    // with_table = false: variable-base mode - only the bases themselves are kept (slice 0), every job takes ONE
-    // digit of every scalar (msm.h msm_digits)
+    // the recoding width and what follows from it.  with_table = false: variable-base mode - only the bases themselves are
+    // kept (slice 0), every job takes ONE digit of every scalar (msm.h msm_digits)
+    zk_status set_geometry(uint32_t c_, size_t n, bool with_table) {
+        c = c_;
+        maxd = with_table ? zkdev::msm_max_digits(c) : 1u;
+        nb = 1u << (c - 2);
+        n_points = n;
+        const uint32_t npos = with_table ? zkdev::MSM_NPOS : 1u;
+        if ((uint64_t)n_points * npos >= (1ull << 31)) return fail(ZK_ERR_INVALID_ARGUMENT, "doubling table too large");
+        bytes = sizeof(DAffine) * n_points * npos;
+        return ZK_OK;
+    }
     // the same bases (borrowed doubling table) under another recoding width; workspaces are this object's own
     void alias(const MsmGroup& o, uint32_t c_) {
-        c = c_;
-        maxd = zkdev::msm_max_digits(c);
-        nb = 1u << (c - 2);
-        n_points = o.n_points;
+        (void)set_geometry(c_, o.n_points, true);   // (the table it borrows passed the size test when it was built)
+        bytes = 0;                                    // (... and is accounted for by its owner)
         table.borrow(o.table);
     }
     // Slice 0 of the table from the reference's uncompressed encodings (n x 96 / 192 bytes on the HOST), decoded on the
@@ -198,7 +192,7 @@ struct MsmGroup {
         HIP_TRY(hipMemcpy(v, dstat.p, 8, hipMemcpyDeviceToHost));
         if (v[0] != 0xffffffffu) {
             if (bad_index) *bad_index = v[0];
-            return fail(ZK_ERR_IO, std::string("invalid ") + (sizeof(HAffine) == 96 ? "G1" : "G2") + " encoding at " + what + " " + std::to_string(v[0]));
+            return fail(ZK_ERR_IO, std::string("invalid ") + (IS_G2 ? "G2" : "G1") + " encoding at " + what + " " + std::to_string(v[0]));
         }
         *n_inf = v[1];
         return ZK_OK;
@@ -226,6 +220,30 @@ struct MsmGroup {
         return ZK_OK;
     }
     zk_status run(std::vector<MsmJob>& jobs, std::vector<HPoint>& out);
+
+private:
+    // the table of doublings over slice 0, enqueued on st
+    zk_status launch_table_build(DevBuf& scratch, hipStream_t st);
+    // the stages of enqueue(), in its order, each over the plan of the set (msm_plan.h)
+    zk_status reserve(const MsmPlan& p, bool to_host);
+    zk_status upload_jobs(const std::vector<MsmJob>& jobs, const MsmPlan& p, hipStream_t st);
+    zk_status sort_pairs(const MsmPlan& p, hipStream_t st);
+    zk_status order_tasks(const MsmPlan& p, hipStream_t st);
+    zk_status accumulate(const MsmPlan& p, hipStream_t st);
+    zk_status merge_partials(const MsmPlan& p, hipStream_t st);
+    zk_status level1(const MsmPlan& p, hipStream_t st);
+    zk_status tail(const MsmPlan& p, hipStream_t st);
+    // the end of the *_to_host functions: the launch is checked, `stage` (n points in the host's layout) goes to `out`
+    zk_status copy_to_host(const DevBuf& stage, size_t n, HPoint* out, hipStream_t st);
+    // diagnostics of the hooks build (ZKAMD_DEBUG_REDO, ZKAMD_DEBUG_HEAVY)
+    void dump_redo(const MsmPlan& p, hipStream_t st, bool after_level1);
+    void dump_heavy(const MsmPlan& p, hipStream_t st);
+    // the counters behind the two class arrays of `hist` (its layout: msm_plan.h Bytes::hist)
+    enum Counter { N_TASKS = 0, N_HEAVY = 1, N_REDO = 2, N_LIGHT = 4, N_FALLBACK = 5 };
+    uint32_t* counter(const MsmPlan& p, Counter k) const { return hist.as<uint32_t>() + 2 * p.n_class + k; }
+    DPoint* node_s() const { return red_r.as<DPoint>(); }   // S of the nodes of level 1: node t of job j at [(j T + t) s_stride]
+    DPoint* node_w() const { return red_w.as<DPoint>(); }   // W of the nodes, compact
+    DPoint* job_sums(const MsmPlan& p) const { return node_w() + p.nj * (size_t)p.T; }   // one XYZZ per job
 };
 
 typedef MsmGroup<zkhost::Fq, zkdev::Fq> MsmG1;
