@@ -69,6 +69,9 @@
  *   zk_verify_proof / zk_verify_batch   verify_proof                              verifier.rs:32-63; callers confidential.rs:271, modules/zk-system/src/lib.rs:57-108
  *   zk_verify_batch_rlc             - (bellman's batch verifier): the same verdicts, one final exponentiation
  *   zk_proof_read_batch             Proof::read                                   core/bellman-verifier/src/lib.rs:67-110
+ *   zk_jubjub_into_xy               IntoXY of the primitives (Point::read + as_prime_order + into_xy)   core/primitives/src/enc_key.rs:89, core/jubjub/src/curve/edwards.rs:92-165, :319-330
+ *   zk_confidential_verify_batch    zk_system::verify_confidential_proof          modules/zk-system/src/lib.rs:56-115, input_builder.rs:15-27
+ *   zk_anonymous_verify_batch       zk_system::verify_anonymous_proof             modules/zk-system/src/lib.rs:118-165
  *   zk_msm_create, zk_msm_create_variable, zk_msm_run, zk_msm_run_dev, zk_msm_free, zk_msm_g1, zk_msm_g2, zk_msm_cache_release
  *                                   bellman multiexp(FullDensity); group law core/pairing/src/bls12_381/ec.rs:296-526
  *   zk_ntt_fr, zk_ntt_create, zk_ntt_run_dev, zk_ntt_free
@@ -465,6 +468,35 @@ zk_status zk_verify_proof(zk_vk* vk, const uint8_t proof[192], const uint8_t* pu
  * the workspaces; its key material is not used. */
 enum { ZK_PROOF_BAD_ENCODING = 1, ZK_PROOF_NOT_ON_CURVE = 2, ZK_PROOF_NOT_IN_SUBGROUP = 3, ZK_PROOF_INFINITY = 4 };
 zk_status zk_proof_read_batch(zk_vk* vk, size_t n, const uint8_t* proofs, uint8_t* status_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Verification of transfer extrinsics from their bytes (the runtime's side: modules/zk-system/src/lib.rs:56-165).
+ * The public inputs of a transfer proof are the affine coordinates of the Jubjub points the extrinsic carries;
+ * PublicInputBuilder::push (modules/zk-system/src/input_builder.rs:15-27) forms them with IntoXY, which is where a
+ * verifier that starts from bytes spends its time (a square root in Fr and a 252-bit scalar multiplication per point).
+ * ------------------------------------------------------------------------------------------ */
+/* IntoXY (core/primitives/src/{enc_key,nonce,..}.rs into_xy; edwards.rs:92-165 read, :319-330 as_prime_order) for n encodings.
+ * points: n x 32 bytes.  xy_out: n x 64 bytes, x then y, each 32 bytes little-endian canonical (two consecutive public
+ * inputs of zk_verify_batch); zeroed where refused.  status_out[i]: 0, or 1 = y not in the field (io::Error::NotInField),
+ * 2 = no x for that y (NotOnCurve), 3 = not in the prime-order subgroup.  A refusal is a status, never an error.
+ * device < 0, or n <= ZKAMD_INTO_XY_HOST_MAX (default 384): on the host threads (zk_set_host_threads); else one lane per point on
+ * `device` (csrc/xt_inputs.h).  The bytes written do not depend on the form. */
+enum { ZK_INTO_XY_NOT_IN_FIELD = 1, ZK_INTO_XY_NOT_ON_CURVE = 2, ZK_INTO_XY_NOT_PRIME_ORDER = 3 };
+zk_status zk_jubjub_into_xy(const uint8_t* points, size_t n, int device, uint8_t* xy_out, uint8_t* status_out);
+/* zk_system::verify_confidential_proof (modules/zk-system/src/lib.rs:56-115) for n extrinsics: the eleven points in the
+ * reference's push order - 1 enc_key_sender, 2 enc_key_recipient, 3 left_amount_sender, 4 left_amount_recipient,
+ * 5 right_randomness, 6 left_fee, 7 balance left, 8 balance right, 9 rvk, 10 g_epoch, 11 nonce - through IntoXY, then
+ * verify_proof.  enc_balances: n x 64 bytes (the chain's stored Ciphertext of the sender; Ciphertext::zero() is two
+ * identity encodings), NULL = each xt's own enc_balance field.  g_epochs: one 32-byte encoding (stride 0, decoded once)
+ * or one per xt (stride 32).  ok_out[i] = 1 iff every input formed and the proof verifies.  refusal_out (may be NULL):
+ * 0 when all inputs formed, else (field 1..11) | (status << 6) of the first point in push order that IntoXY refuses.
+ * ZK_ERR_MALFORMED_VERIFYING_KEY unless the key has 22 inputs. */
+zk_status zk_confidential_verify_batch(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* enc_balances,
+                                       const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out);
+/* verify_anonymous_proof (:118-165): fields 1..12 enc_keys, 13..24 left_ciphertexts, 25..36 balances left, 37..48 balances
+ * right, 49 right_ciphertext, 50 rvk, 51 g_epoch, 52 nonce; enc_balances: n x 12 x 64 bytes, required; 104 inputs. */
+zk_status zk_anonymous_verify_batch(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* enc_balances,
+                                    const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone kernels (micro-benchmark / test entries)

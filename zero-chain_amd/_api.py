@@ -24,7 +24,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
                    ZK_NTT_OUT_BITREV)
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
-           "verify_transfer_batch", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
+           "verify_transfer_batch", "jubjub_into_xy", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
@@ -410,6 +410,93 @@ def verify_transfer_batch(pvk, statements, proofs, lib=None):
     w = transfer_witness(statements, lib=lib).reshape(n, nv * 32)
     inputs = np.ascontiguousarray(w[:, 32:TRANSFER_N_INPUTS * 32])
     return sum(verify_proofs(pvk, proofs if isinstance(proofs, np.ndarray) else list(proofs), inputs))
+
+
+INTO_XY_REASONS = {1: "not in the field", 2: "not on the curve", 3: "not in the prime-order subgroup"}
+# the points of an extrinsic in the reference's push order (modules/zk-system/src/lib.rs:56-165): field k is name k - 1
+CONFIDENTIAL_XT_POINTS = ("enc_key_sender", "enc_key_recipient", "left_amount_sender", "left_amount_recipient", "right_randomness",
+                          "left_fee", "enc_balance_left", "enc_balance_right", "rvk", "g_epoch", "nonce")
+ANONYMOUS_XT_POINTS = tuple("%s[%d]" % (f, i) for f in ("enc_keys", "left_ciphertexts", "enc_balances_left", "enc_balances_right")
+                            for i in range(12)) + ("right_ciphertext", "rvk", "g_epoch", "nonce")
+
+
+def jubjub_into_xy(points, device=None, lib=None):
+    """zk_jubjub_into_xy = IntoXY of the reference's primitives (Point::read, as_prime_order, into_xy) for a list of
+    32-byte encodings (or one n x 32 byte array).  device None: the host form (device = -1); else the device whose kernel
+    runs once the batch is larger than ZKAMD_INTO_XY_HOST_MAX.  Returns ([(x, y) or None], [status]): status 0, or
+    1 / 2 / 3 = y not in the field / no x for that y / not in the prime-order subgroup."""
+    lib = lib or _lib.load()
+    pb = _u8(points) if isinstance(points, np.ndarray) else _u8(b"".join(bytes(p) for p in points))
+    if pb.size % 32:
+        raise ValueError("points: %d bytes is not a whole number of 32-byte encodings" % pb.size)
+    n = pb.size // 32
+    xy, st = np.zeros(max(n, 1) * 64, dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    lib.check(lib.zk_jubjub_into_xy(_ptr(pb) if n else None, n, -1 if device is None else int(device), _ptr(xy), _ptr(st)))
+    raw = xy.tobytes()
+    vals = [None if st[i] else (int.from_bytes(raw[64 * i:64 * i + 32], "little"), int.from_bytes(raw[64 * i + 32:64 * i + 64], "little"))
+            for i in range(n)]
+    return vals, [int(v) for v in st[:n]]
+
+
+def _xt_array(xts, ctype, fill):
+    if isinstance(xts, C.Array) and xts._type_ is ctype:
+        return xts
+    arr = (ctype * len(xts))()
+    for dst, x in zip(arr, xts):
+        if isinstance(x, ctype):
+            C.memmove(C.byref(dst), C.byref(x), C.sizeof(ctype))
+        else:
+            fill(dst, x)
+    return arr
+
+
+def _fill_confidential_xt(dst, d):
+    for f in XT_FIELDS:
+        getattr(dst, f)[:] = bytes(d[f])
+
+
+def _fill_anonymous_xt(dst, d):
+    for f in ("proof", "right_ciphertext", "nonce", "rsk", "rvk"):
+        getattr(dst, f)[:] = bytes(d[f])
+    for f in ("enc_keys", "left_ciphertexts"):
+        for k in range(ANONYMOUS_SIZE):
+            getattr(dst, f)[k][:] = bytes(d[f][k])
+
+
+def _verify_xts(pvk, fn, arr, names, g_epoch, balances):
+    n = len(arr)
+    if isinstance(g_epoch, (bytes, bytearray)):
+        ge, stride = _u8(bytes(g_epoch), 32), 0
+    else:
+        ge, stride = _u8(b"".join(bytes(e) for e in g_epoch), 32 * n), 32
+    ok, ref = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    pvk._lib.check(fn(pvk._h, n, arr, None if balances is None else _ptr(balances), _ptr(ge) if ge.size else None, stride, _ptr(ok), _ptr(ref)))
+    return ([bool(v) for v in ok[:n]],
+            [None if not v else (names[(int(v) & 63) - 1], INTO_XY_REASONS[int(v) >> 6]) for v in ref[:n]])
+
+
+def verify_confidential_xts(pvk, xts, g_epoch, enc_balances=None):
+    """zk_confidential_verify_batch = zk_system::verify_confidential_proof (modules/zk-system/src/lib.rs:56-115) for a
+    block of ConfidentialXt: the array gen_proofs(..., raw=True) returns (or a list of such structures / of the dicts of
+    xt_fields).  g_epoch: one 32-byte encoding for all, or one per xt.  enc_balances: per xt the (left, right) encodings of
+    the sender's stored balance; None = each xt's own enc_balance field.  Returns (verdicts, refusals): a refusal is None,
+    or (field name, reason) of the first point in push order that IntoXY refuses (then the verdict is False)."""
+    arr = _xt_array(xts, _lib.ConfidentialXt, _fill_confidential_xt)
+    bal = None
+    if enc_balances is not None:
+        bal = _u8(b"".join(bytes(l) + bytes(r) for l, r in enc_balances), 64 * len(arr))
+    return _verify_xts(pvk, pvk._lib.zk_confidential_verify_batch, arr, CONFIDENTIAL_XT_POINTS, g_epoch, bal)
+
+
+def verify_anonymous_xts(pvk, xts, g_epoch, enc_balances):
+    """zk_anonymous_verify_batch = verify_anonymous_proof (modules/zk-system/src/lib.rs:118-165) for a block of AnonymousXt:
+    the dicts anonymous_gen_proofs returns (or AnonymousXt structures).  enc_balances: per xt the twelve (left, right)
+    encodings of the set members' stored balances.  Returns (verdicts, refusals) as verify_confidential_xts."""
+    arr = _xt_array(xts, _lib.AnonymousXt, _fill_anonymous_xt)
+    if len(enc_balances) != len(arr) or any(len(b) != ANONYMOUS_SIZE for b in enc_balances):
+        raise ValueError("enc_balances: %d (left, right) pairs per xt" % ANONYMOUS_SIZE)
+    bal = _u8(b"".join(bytes(l) + bytes(r) for b in enc_balances for l, r in b), 64 * ANONYMOUS_SIZE * len(arr))
+    return _verify_xts(pvk, pvk._lib.zk_anonymous_verify_batch, arr, ANONYMOUS_XT_POINTS, g_epoch, bal)
 
 
 class ProvingAssignment:

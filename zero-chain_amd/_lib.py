@@ -149,6 +149,11 @@ _PROTOS = {
     "zk_verify_batch_rlc": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "zk_verify_proof": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_int)]),
     "zk_proof_read_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zk_jubjub_into_xy": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "zk_confidential_verify_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_void_p, C.c_size_t,
+                                                 C.c_void_p, C.c_void_p]),
+    "zk_anonymous_verify_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_void_p, C.c_size_t,
+                                              C.c_void_p, C.c_void_p]),
     "zk_anonymous_prove_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousStatement), C.c_void_p,
                                              C.c_void_p]),
     "zk_msm_create": (C.c_int32, [C.c_int, C.c_void_p, C.c_size_t, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_void_p)]),

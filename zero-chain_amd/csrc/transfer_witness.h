@@ -560,5 +560,20 @@ inline bool decode_point(const uint8_t b[32], JPoint* out) {
     *out = JPoint{x, y};
     return true;
 }
+// Point<E, Unknown>::as_prime_order (core/jubjub/src/curve/edwards.rs:319-330): [s]P == O for the order s of the
+// prime-order subgroup.  Doubling: dbl-2008-hwcd for a = -1 (4M + 4S).
+inline bool is_prime_order(const JPoint& p) {
+    static const uint64_t FS[4] = ZK_JUBJUB_FS_MODULUS_64;
+    EPoint acc = ext_zero();
+    const EPoint base = to_ext(p);
+    for (int bit = 251; bit >= 0; bit--) {
+        const Fr a = acc.X.sqr(), b = acc.Y.sqr(), c = acc.Z.sqr().dbl();
+        const Fr d = Fr::zero() - a;                       // a = -1
+        const Fr e = (acc.X + acc.Y).sqr() - a - b, g = d + b, f = g - c, h = d - b;
+        acc = EPoint{e * f, g * h, f * g, e * h};
+        if ((FS[bit >> 6] >> (bit & 63)) & 1) acc = ext_add(acc, base);
+    }
+    return acc.X.is_zero() && acc.Y == acc.Z;
+}
 
 }  // namespace zkwit

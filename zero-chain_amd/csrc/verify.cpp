@@ -6,6 +6,8 @@
 //                                    modules/zk-system/src/lib.rs:57-108)
 //   PreparedVerifyingKey::read/write core/bellman-verifier/src/lib.rs:175-236 (zface/params/conf_vk.dat)
 //   Proof::read                      core/bellman-verifier/src/lib.rs:67-110 (compressed points, into_affine)
+//   verify_confidential_proof / verify_anonymous_proof   modules/zk-system/src/lib.rs:56-165 (the public inputs from the
+//                                    extrinsic's bytes: PublicInputBuilder::push, IntoXY - xt_inputs.h)
 // Device side: pairing.h.  Host side here: byte formats, the handle, the launch sequence.
 #include <algorithm>
 #include <new>
@@ -15,6 +17,7 @@
 #include "blake2s.h"
 #include "pairing.h"
 #include "coop_verify.h"
+#include "xt_inputs.h"
 
 using namespace zkrt;
 using zkdev::F12;
@@ -128,6 +131,7 @@ struct zk_vk {
     // its partial sums, the accumulator, flags, the exponent and e(alpha, beta)^S, the product tree, two Fq12 ones
     DevBuf rlc_rho, rlc_s, rlc_pts, rlc_c, rlc_csum, rlc_acc, rlc_inf, rlc_all, rlc_exp, rlc_want, rlc_prod, rlc_fe;
     DevBuf rlc_ab_lambda;   // e(alpha, beta)^lambda, lambda = -x^2 (the coefficients are a_i + b_i lambda: pairing.h k_rlc_scale)
+    zkxt::IntoXyBufs xt;    // IntoXY of the extrinsics' points (xt_inputs.h)
     // the G1 decoder and the input accumulator run beside the G2 decoder on the lane's side streams
     hipEvent_t ev_join[2] = {nullptr, nullptr};
     // Blake2s over e(alpha, beta), the prepared -gamma / -delta coefficients and ic: the domain separation of the combined
@@ -940,6 +944,52 @@ zk_status verify_batch(zk_vk* vk, size_t n, const uint8_t* proofs, const uint8_t
 }
 }  // namespace zkrt
 
+namespace {
+// verify_confidential_proof / verify_anonymous_proof (modules/zk-system/src/lib.rs:56-165) for n extrinsics: the n_fields
+// points of each, in the reference's push order, through IntoXY (xt_inputs.h), then verify_batch.  field(i, k): the encoding
+// of field k = 1 .. n_fields of extrinsic i; with a shared g_epoch (stride 0) that one encoding is decoded once.
+template <class Xt, class Field>
+zk_status xt_verify_batch(zk_vk* vk, size_t n, const Xt* xts, const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out,
+                          uint8_t* refusal_out, size_t n_fields, size_t epoch_field, Field field) {
+    if (!vk) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (vk->ic.size() != 2 * n_fields + 1)
+        return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "the key does not have " + std::to_string(2 * n_fields) + " public inputs");
+    if (!n) return ZK_OK;
+    if (!xts || !g_epochs || !ok_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (g_epoch_stride != 0 && g_epoch_stride != 32) return fail(ZK_ERR_INVALID_ARGUMENT, "g_epoch_stride must be 0 or 32");
+    const bool shared = g_epoch_stride == 0;
+    const size_t per = n_fields - (shared ? 1 : 0);
+    for (size_t first = 0; first < n; first += VERIFY_CHUNK) {
+        const size_t np = std::min(VERIFY_CHUNK, n - first), total = np * per + (shared ? 1 : 0);
+        std::vector<uint8_t> pts(total * 32), xy(total * 64), st(total), proofs(np * 192), inputs(np * n_fields * 64, 0), refusal(np, 0);
+        size_t at = 0;
+        if (shared) memcpy(&pts[32 * at++], g_epochs, 32);
+        for (size_t i = 0; i < np; i++) {
+            memcpy(&proofs[i * 192], xts[first + i].proof, 192);
+            for (size_t k = 1; k <= n_fields; k++)
+                if (!(shared && k == epoch_field)) memcpy(&pts[32 * at++], field(first + i, k), 32);
+        }
+        ZK_TRY(zkxt::into_xy(pts.data(), total, vk->device, &vk->xt, xy.data(), st.data()));
+        at = shared ? 1 : 0;
+        for (size_t i = 0; i < np; i++) {
+            uint8_t* row = &inputs[i * n_fields * 64];
+            for (size_t k = 1; k <= n_fields; k++) {
+                const size_t idx = shared && k == epoch_field ? 0 : at++;
+                if (st[idx] && !refusal[i]) refusal[i] = (uint8_t)(k | ((size_t)st[idx] << 6));
+                memcpy(row + (k - 1) * 64, &xy[idx * 64], 64);
+            }
+            if (refusal[i]) memset(row, 0, n_fields * 64);   // the reference never reaches verify_proof with it
+        }
+        ZK_TRY(zkrt::verify_batch(vk, np, proofs.data(), inputs.data(), 2 * n_fields, ok_out + first, false, zkrt::VERIFY_AUTO, nullptr));
+        for (size_t i = 0; i < np; i++) {
+            if (refusal[i]) ok_out[first + i] = 0;
+            if (refusal_out) refusal_out[first + i] = refusal[i];
+        }
+    }
+    return ZK_OK;
+}
+}  // namespace
+
 extern "C" {
 
 zk_status zk_vk_prepare(const uint8_t* vk_bytes, size_t len, int device, zk_vk** out) try {
@@ -1076,6 +1126,51 @@ zk_status zk_verify_proof(zk_vk* vk, const uint8_t proof[192], const uint8_t* pu
     zk_status st = zk_verify_batch(vk, 1, proof, public_inputs, n_inputs, &v);
     *ok = v;
     return st;
+} ZK_ABI_CATCH
+
+zk_status zk_jubjub_into_xy(const uint8_t* points, size_t n, int device, uint8_t* xy_out, uint8_t* status_out) try {
+    if (n && (!points || !xy_out || !status_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    return zkxt::into_xy(points, n, device, nullptr, xy_out, status_out);
+} ZK_ABI_CATCH
+zk_status zk_confidential_verify_batch(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* enc_balances,
+                                       const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out) try {
+    auto field = [&](size_t i, size_t k) -> const uint8_t* {
+        const zk_confidential_xt& x = xts[i];
+        const uint8_t* bal = enc_balances ? enc_balances + i * 64 : x.enc_balance;
+        switch (k) {
+            case 1: return x.enc_key_sender;
+            case 2: return x.enc_key_recipient;
+            case 3: return x.left_amount_sender;
+            case 4: return x.left_amount_recipient;
+            case 5: return x.right_randomness;
+            case 6: return x.left_fee;
+            case 7: return bal;
+            case 8: return bal + 32;
+            case 9: return x.rvk;
+            case 10: return g_epochs + i * g_epoch_stride;
+            default: return x.nonce;
+        }
+    };
+    return xt_verify_batch(vk, n, xts, g_epochs, g_epoch_stride, ok_out, refusal_out, 11, 10, field);
+} ZK_ABI_CATCH
+zk_status zk_anonymous_verify_batch(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* enc_balances,
+                                    const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out) try {
+    if (n && !enc_balances) return fail(ZK_ERR_INVALID_ARGUMENT, "enc_balances is required");
+    auto field = [&](size_t i, size_t k) -> const uint8_t* {
+        const zk_anonymous_xt& x = xts[i];
+        const size_t S = ZK_ANONYMOUS_SIZE;
+        if (k <= S) return x.enc_keys[k - 1];
+        if (k <= 2 * S) return x.left_ciphertexts[k - 1 - S];
+        if (k <= 3 * S) return enc_balances + (i * S + (k - 1 - 2 * S)) * 64;
+        if (k <= 4 * S) return enc_balances + (i * S + (k - 1 - 3 * S)) * 64 + 32;
+        switch (k - 4 * S) {
+            case 1: return x.right_ciphertext;
+            case 2: return x.rvk;
+            case 3: return g_epochs + i * g_epoch_stride;
+            default: return x.nonce;
+        }
+    };
+    return xt_verify_batch(vk, n, xts, g_epochs, g_epoch_stride, ok_out, refusal_out, 4 * ZK_ANONYMOUS_SIZE + 4, 4 * ZK_ANONYMOUS_SIZE + 3, field);
 } ZK_ABI_CATCH
 
 #ifdef ZK_TEST_HOOKS

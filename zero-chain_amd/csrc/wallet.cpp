@@ -143,25 +143,11 @@ struct WipeOnExit {
 // Point<E, Unknown>::as_prime_order (core/jubjub/src/curve/edwards.rs:319-330): [s]P == O for the order s of the
 // prime-order subgroup.  The reference's typed inputs (EncryptionKey::read keys.rs:269-276, Ciphertext::read
 // elgamal.rs:117-133, g_epoch.rs:75) pass through it, so a point with a torsion component is refused by the wallet-level
-// entries here too.  Doubling: dbl-2008-hwcd for a = -1 (4M + 4S).
-bool jubjub_is_prime_order(const zkwit::JPoint& p) {
-    static const uint64_t FS[4] = ZK_JUBJUB_FS_MODULUS_64;
-    using zkhost::Fr;
-    zkwit::EPoint acc = zkwit::ext_zero();
-    const zkwit::EPoint base = zkwit::to_ext(p);
-    for (int bit = 251; bit >= 0; bit--) {
-        const Fr a = acc.X.sqr(), b = acc.Y.sqr(), c = acc.Z.sqr().dbl();
-        const Fr d = Fr::zero() - a;                       // a = -1
-        const Fr e = (acc.X + acc.Y).sqr() - a - b, g = d + b, f = g - c, h = d - b;
-        acc = zkwit::EPoint{e * f, g * h, f * g, e * h};
-        if ((FS[bit >> 6] >> (bit & 63)) & 1) acc = zkwit::ext_add(acc, base);
-    }
-    return acc.X.is_zero() && acc.Y == acc.Z;
-}
+// entries here too.  The test itself: zkwit::is_prime_order (transfer_witness.h), shared with IntoXY's host form.
 zk_status decode_prime_order(const uint8_t b[32], zkwit::JPoint* out, const std::string& what) {
     zkwit::JPoint p;
     if (!zkwit::decode_point(b, &p)) return fail(ZK_ERR_INVALID_ARGUMENT, what + " is not a Jubjub point");
-    if (!jubjub_is_prime_order(p)) return fail(ZK_ERR_INVALID_ARGUMENT, what + " is not in the prime-order subgroup");
+    if (!zkwit::is_prime_order(p)) return fail(ZK_ERR_INVALID_ARGUMENT, what + " is not in the prime-order subgroup");
     if (out) *out = p;
     return ZK_OK;
 }
