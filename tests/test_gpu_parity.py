@@ -338,7 +338,7 @@ def test_verifier_small_circuit(gpu_lib):
 
 
 def test_verifier_chunk_sizes(gpu_lib):
-    pc.verifier_chunk_sizes(gpu_lib, sizes=(65, 300, 1100))
+    pc.verifier_chunk_sizes(gpu_lib, sizes=(65, 300, 1100, 2049))
 
 
 def test_fq_inverse_on_rows(gpu_hooks_lib):

@@ -18,6 +18,7 @@
 #include "pairing.h"
 #include "coop_verify.h"
 #include "xt_inputs.h"
+#include "verify_plan.h"
 
 using namespace zkrt;
 using zkdev::F12;
@@ -214,14 +215,15 @@ zk_status build_ic_table(zk_vk* V) {
     return ZK_OK;
 }
 
+struct VkGuard {   // a key under construction: freed on every way out but the last
+    zk_vk* p;
+    ~VkGuard() { delete p; }
+};
 zk_status vk_prepare(const uint8_t* bytes, size_t len, int device, zk_vk** out) {
     ZK_TRY(use_device(device));
     zk_vk* V = new (std::nothrow) zk_vk();
     if (!V) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
-    struct Guard {
-        zk_vk* p;
-        ~Guard() { delete p; }
-    } guard{V};
+    VkGuard guard{V};
     V->device = device;
     Reader r{bytes, len};
     HG1A alpha_g1, beta_g1, delta_g1, tmp;
@@ -318,10 +320,7 @@ zk_status vk_read_prepared(const uint8_t* bytes, size_t len, int device, zk_vk**
     ZK_TRY(use_device(device));
     zk_vk* V = new (std::nothrow) zk_vk();
     if (!V) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
-    struct Guard {
-        zk_vk* p;
-        ~Guard() { delete p; }
-    } guard{V};
+    VkGuard guard{V};
     V->device = device;
     Reader r{bytes, len};
     zkhost::Fq2 c;
@@ -371,114 +370,223 @@ zk_status vk_read_prepared(const uint8_t* bytes, size_t len, int device, zk_vk**
     return ZK_OK;
 }
 
-// one element of a Proof: compressed encoding -> plain x words + flags (bit 0 infinity, bit 1 larger y); false =
-// malformed (Proof::read fails: ec.rs:776-868, :1429-1548)
-bool parse_g1_compressed(const uint8_t* b, uint32_t* x, uint32_t* flags) {
+// one element of a Proof: compressed encoding of `len` bytes (48: G1, 96: G2) -> plain x words + flags (bit 0 infinity, bit 1
+// larger y); false = malformed (Proof::read fails: ec.rs:776-868, :1429-1548)
+bool parse_compressed(const uint8_t* b, size_t len, uint32_t* x, uint32_t* flags) {
     if (!(b[0] & 0x80)) return false;   // not the compressed form
     if (b[0] & 0x40) {
-        if (b[0] & 0x3f) return false;
-        for (int i = 1; i < 48; i++)
-            if (b[i]) return false;
+        if ((b[0] & 0x3f) || std::any_of(b + 1, b + len, [](uint8_t v) { return v != 0; })) return false;
         *flags = 1;
-        memset(x, 0, 48);
+        memset(x, 0, len);
         return true;
     }
     *flags = (b[0] & 0x20) ? 2u : 0u;
-    return fq_words_from_be(b, x, 0x1f);
-}
-bool parse_g2_compressed(const uint8_t* b, uint32_t* x, uint32_t* flags) {
-    if (!(b[0] & 0x80)) return false;
-    if (b[0] & 0x40) {
-        if (b[0] & 0x3f) return false;
-        for (int i = 1; i < 96; i++)
-            if (b[i]) return false;
-        *flags = 1;
-        memset(x, 0, 96);
-        return true;
-    }
-    *flags = (b[0] & 0x20) ? 2u : 0u;
+    if (len == 48) return fq_words_from_be(b, x, 0x1f);
     return fq_words_from_be(b, x + 12, 0x1f) && fq_words_from_be(b + 48, x, 0xff);   // c1 first on the wire
 }
+bool parse_g1_compressed(const uint8_t* b, uint32_t* x, uint32_t* flags) { return parse_compressed(b, 48, x, flags); }
+bool parse_g2_compressed(const uint8_t* b, uint32_t* x, uint32_t* flags) { return parse_compressed(b, 96, x, flags); }
 
-// own_proofs: A, B, C were computed by this library's prover a moment ago (the self-check of gen_proof): group elements
-// by construction, as the in-memory Proof the reference hands to verify_proof in check_proof (confidential.rs:208-278,
-// no deserialisation there) - the decoders then skip the r-torsion test, which only a foreign byte string needs.
-// own_affine (with own_proofs): the affine coordinates of A, B, C as the prover had them (host_common.h OWN_AFFINE_BYTES per
-// proof) - uploaded where the decoders would have left them, the decoders skipped.
-zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out, bool own_proofs,
-                       const uint8_t* own_affine = nullptr) {
-    const uint32_t ni = V->n_ic - 1;
-    if (!own_proofs) own_affine = nullptr;
-    std::vector<uint32_t> g1((size_t)2 * n * 12), g2((size_t)n * 24), f1(2 * n), f2(n), bad(n, 0), sc((size_t)n * ni * 8);
-    static const uint64_t RMOD[4] = ZK_FR_P_64;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* p = proofs + i * 192;
-        bool good;
-        if (own_affine) {
-            // a point at infinity in A, B or C is what Proof::read refuses (x = y = 0 stands for it in the host's affine form)
-            const uint8_t* a = own_affine + i * OWN_AFFINE_BYTES;
-            auto zero = [](const uint8_t* q, size_t len) {
-                for (size_t k = 0; k < len; k++)
-                    if (q[k]) return false;
-                return true;
+// The front end of a chunk (verify_chunk, verify_chunk_rlc, zk_proof_read_batch), what the host makes of n proofs:
+// x words and flag words of A | C (g1, f1: C behind the n A's) and of B (g2, f2); enc[i] bit k: the ENCODING of point k (0 = A,
+// 1 = B, 2 = C) is refused, that point decodes to nothing
+struct Staged {
+    std::vector<uint32_t> g1, g2, f1, f2;
+    std::vector<uint8_t> enc;
+    // every point is parsed on its own: Proof::read finishes A (decode, curve, subgroup, infinity) before it touches B, so a
+    // device-side failure of A must win over a malformed B.  proofs == nullptr: nothing to parse, all zero
+    Staged(size_t n, const uint8_t* proofs) : g1((size_t)2 * n * 12), g2((size_t)n * 24), f1(2 * n), f2(n), enc(n, 0) {
+        for (size_t i = 0; proofs && i < n; i++) {
+            const uint8_t* p = proofs + i * 192;
+            auto refused = [&](int k, uint32_t* x, size_t words, uint32_t* flag) {
+                enc[i] |= (uint8_t)(1u << k);
+                *flag = 1;   // decode nothing
+                memset(x, 0, words * 4);
             };
-            good = !zero(a, 96) && !zero(a + 96, 192) && !zero(a + 288, 96);
-        } else {
-            good = parse_g1_compressed(p, &g1[i * 12], &f1[i]) && parse_g2_compressed(p + 48, &g2[i * 24], &f2[i]) &&
-                   parse_g1_compressed(p + 144, &g1[(n + i) * 12], &f1[n + i]);
-        }
-        for (uint32_t j = 0; j < ni && good; j++) {
-            const uint8_t* s = inputs + (i * ni + j) * 32;
-            uint64_t v[4];
-            for (int k = 0; k < 4; k++) {
-                uint64_t w = 0;
-                for (int b = 7; b >= 0; b--) w = (w << 8) | s[k * 8 + b];
-                v[k] = w;
-            }
-            bool lt = false;
-            for (int k = 3; k >= 0; k--) {
-                if (v[k] < RMOD[k]) {
-                    lt = true;
-                    break;
-                }
-                if (v[k] > RMOD[k]) break;
-            }
-            if (!lt) good = false;   // not a canonical Fr: the reference cannot even form the input
-            memcpy(&sc[(i * ni + j) * 8], s, 32);
-        }
-        if (!good) {
-            bad[i] = 1;
-            f1[i] = f1[n + i] = f2[i] = 1;   // decode nothing
-            if (ni) memset(&sc[i * ni * 8], 0, (size_t)ni * 32);   // (no inputs: `sc` is empty, nothing to index - UBSan, round 4)
+            if (!parse_g1_compressed(p, &g1[i * 12], &f1[i])) refused(0, &g1[i * 12], 12, &f1[i]);
+            if (!parse_g2_compressed(p + 48, &g2[i * 24], &f2[i])) refused(1, &g2[i * 24], 24, &f2[i]);
+            if (!parse_g1_compressed(p + 144, &g1[(n + i) * 12], &f1[n + i])) refused(2, &g1[(n + i) * 12], 12, &f1[n + i]);
         }
     }
-    ZK_TRY(upload(V->in_g1, g1.data(), g1.size() * 4));
-    ZK_TRY(upload(V->in_g2, g2.data(), g2.size() * 4));
-    ZK_TRY(upload(V->fl_g1, f1.data(), f1.size() * 4));
-    ZK_TRY(upload(V->fl_g2, f2.data(), f2.size() * 4));
-    ZK_TRY(upload(V->host_bad, bad.data(), bad.size() * 4));
-    ZK_TRY(upload(V->scal, sc.data(), sc.size() * 4));
+};
+// ni public inputs of one proof, 32 little-endian bytes each: all canonical Fr?  (Of another the reference cannot even form the input.)
+bool inputs_canonical(const uint8_t* row, uint32_t ni) {
+    for (uint32_t j = 0; j < ni; j++) {
+        uint64_t v[4];
+        load_scalar_le(row + j * 32, v);
+        if (zkhost::Fr::geq_p(v)) return false;
+    }
+    return true;
+}
+// the staged words uploaded, the decoders' outputs reserved; bad: the host's verdict per proof, of the callers that have one
+zk_status upload_staged(zk_vk* V, size_t n, const Staged& s, const std::vector<uint32_t>* bad) {
+    ZK_TRY(upload(V->in_g1, s.g1.data(), s.g1.size() * 4));
+    ZK_TRY(upload(V->in_g2, s.g2.data(), s.g2.size() * 4));
+    ZK_TRY(upload(V->fl_g1, s.f1.data(), s.f1.size() * 4));
+    ZK_TRY(upload(V->fl_g2, s.f2.data(), s.f2.size() * 4));
+    if (bad) ZK_TRY(upload(V->host_bad, bad->data(), bad->size() * 4));
     ZK_TRY(V->aff_g1.ensure((size_t)2 * n * 96));
     ZK_TRY(V->aff_g2.ensure(n * 192));
     ZK_TRY(V->st_g1.ensure(2 * n * 4));
     ZK_TRY(V->st_g2.ensure(n * 4));
-    if (own_affine) {
-        // [A | C] and B where the decoders write them, "decoded" in every state word
-        std::vector<uint8_t> a1((size_t)2 * n * 96), a2(n * 192);
-        for (size_t i = 0; i < n; i++) {
-            const uint8_t* a = own_affine + i * OWN_AFFINE_BYTES;
-            memcpy(&a1[i * 96], a, 96);
-            memcpy(&a1[(n + i) * 96], a + 288, 96);
-            memcpy(&a2[i * 192], a + 96, 192);
-        }
-        ZK_TRY(upload(V->in_g1, a1.data(), a1.size()));   // (staged through the buffers the encodings would have used)
-        ZK_TRY(upload(V->in_g2, a2.data(), a2.size()));
-        HIP_TRY(hipMemcpyAsync(V->aff_g1.p, V->in_g1.p, a1.size(), hipMemcpyDeviceToDevice, g_stream));
-        HIP_TRY(hipMemcpyAsync(V->aff_g2.p, V->in_g2.p, a2.size(), hipMemcpyDeviceToDevice, g_stream));
-        HIP_TRY(hipMemsetAsync(V->st_g1.p, 0, 2 * n * 4, g_stream));
-        HIP_TRY(hipMemsetAsync(V->st_g2.p, 0, n * 4, g_stream));
-        HIP_TRY(hipStreamSynchronize(g_stream));   // (a1 / a2 are about to go out of scope: pageable sources of asynchronous copies)
+    return ZK_OK;
+}
+// B decoded and its lines prepared on `main`, A | C decoded on `side`, in the forms the plan names
+zk_status enqueue_head(zk_vk* V, size_t n, const VerifyPlan& pl, hipStream_t main, hipStream_t side) {
+    const uint32_t *in_g1 = V->in_g1.as<const uint32_t>(), *in_g2 = V->in_g2.as<const uint32_t>();
+    const uint32_t *fl_g1 = V->fl_g1.as<const uint32_t>(), *fl_g2 = V->fl_g2.as<const uint32_t>();
+    uint32_t *aff_g1 = V->aff_g1.as<uint32_t>(), *aff_g2 = V->aff_g2.as<uint32_t>(), *st_g1 = V->st_g1.as<uint32_t>(), *st_g2 = V->st_g2.as<uint32_t>();
+    {
+        ProfScope ps("verify_decode", main);
+        if (pl.decode == VDecode::ROWS)
+            zkcoop::verify_decode_g2(in_g2, fl_g2, aff_g2, st_g2, (uint32_t)n, main);
+        else if (pl.decode == VDecode::LANES)
+            ZK_LAUNCH(zkdev::k_decode_g2, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, main, in_g2, fl_g2, aff_g2, st_g2, (uint32_t)n,
+                      pl.b_torsion_in_decoder ? 1u : 0u);
     }
+    static_assert(zkcoop::VERIFY_NCOEF == zkdev::PAIRING_NCOEF, "coop_verify.cpp restates the loop constants");
+    if (pl.prepare != VPrepare::NONE) {
+        uint32_t* st_b = pl.subgroup_tests ? st_g2 : nullptr;   // (it skips what did not decode and settles B's r-torsion test)
+        if (pl.prep_b_points) ZK_TRY(V->prep_b.ensure(pl.prep_b_points * COEF_WORDS * 4));
+        if (pl.prepare == VPrepare::ROWS) ZK_TRY(V->coop_stage.ensure(zkcoop::g2_prepare_stage_bytes((uint32_t)n)));
+        ProfScope ps("verify_prepare", main);
+        if (pl.prepare == VPrepare::ROWS)
+            zkcoop::verify_g2_prepare(aff_g2, V->coop_stage.p, pl.prep_b_points ? V->prep_b.as<uint32_t>() : nullptr, (uint32_t)n, st_b, main);
+        else
+            ZK_LAUNCH_SYNC(zkdev::k_g2_prepare_tri, dim3((unsigned)((n + zkdev::TL_POINTS - 1) / zkdev::TL_POINTS)), dim3(64), 0, main,
+                           (const uint32_t*)aff_g2, V->prep_b.as<uint32_t>(), (uint32_t)n, st_b);
+    }
+    {
+        ProfScope ps("verify_decode_g1", side);
+        const uint32_t check = pl.subgroup_tests ? 1u : 0u;
+        if (pl.decode == VDecode::ROWS)
+            zkcoop::verify_decode_g1(in_g1, fl_g1, aff_g1, st_g1, (uint32_t)(2 * n), check, side);
+        else if (pl.decode == VDecode::LANES)
+            ZK_LAUNCH(zkdev::k_decode_g1, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, side, in_g1, fl_g1, aff_g1, st_g1, (uint32_t)(2 * n), check);
+    }
+    return ZK_OK;
+}
+// the prover's affine A, B, C (host_common.h OWN_AFFINE_BYTES per proof) uploaded where the decoders would have left them:
+// [A | C] and B, "decoded" in every state word
+zk_status stage_own_affine(zk_vk* V, size_t n, const uint8_t* own_affine) {
+    std::vector<uint8_t> a1((size_t)2 * n * 96), a2(n * 192);
+    for (size_t i = 0; i < n; i++) {
+        const uint8_t* a = own_affine + i * OWN_AFFINE_BYTES;
+        memcpy(&a1[i * 96], a, 96);
+        memcpy(&a1[(n + i) * 96], a + 288, 96);
+        memcpy(&a2[i * 192], a + 96, 192);
+    }
+    ZK_TRY(upload(V->in_g1, a1.data(), a1.size()));   // (staged through the buffers the encodings would have used)
+    ZK_TRY(upload(V->in_g2, a2.data(), a2.size()));
+    HIP_TRY(hipMemcpyAsync(V->aff_g1.p, V->in_g1.p, a1.size(), hipMemcpyDeviceToDevice, g_stream));
+    HIP_TRY(hipMemcpyAsync(V->aff_g2.p, V->in_g2.p, a2.size(), hipMemcpyDeviceToDevice, g_stream));
+    HIP_TRY(hipMemsetAsync(V->st_g1.p, 0, 2 * n * 4, g_stream));
+    HIP_TRY(hipMemsetAsync(V->st_g2.p, 0, n * 4, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));   // (a1 / a2 are about to go out of scope: pageable sources of asynchronous copies)
+    return ZK_OK;
+}
+// acc[p] = ic_0 + sum_j x_pj ic_j for the n proofs of the chunk, on `st`
+zk_status enqueue_inputs(zk_vk* V, size_t n, const VerifyPlan& pl, hipStream_t st) {
+    const uint32_t ni = V->n_ic - 1;
+    const DG1A* table = V->ic_table.as<const DG1A>();
+    const uint32_t* scal = V->scal.as<const uint32_t>();
+    DG1* part = V->part.as<DG1>();
+    uint32_t *acc = V->acc.as<uint32_t>(), *acc_inf = V->acc_inf.as<uint32_t>();
+    ProfScope ps("verify_inputs", st);
+    if (pl.inputs == VInputs::ROWS) {
+        zkcoop::verify_inputs(V->ic_table.p, scal, V->part.p, acc, acc_inf, V->n_ic, (uint32_t)n, st);
+        return ZK_OK;
+    }
+    // on lanes: the products of the pieces of every scalar with its base ...
+    const bool sixteen = pl.inputs == VInputs::SIXTEEN;
+    if (pl.inputs == VInputs::WINDOWS) {   // (four chains of eight additions per scalar)
+        if (!V->ic_win.cap) {
+            V->ic_win.is_public = true;
+            ZK_TRY(V->ic_win.ensure((size_t)V->n_ic * 32 * 256 * sizeof(DG1A)));
+            ZK_LAUNCH(zkdev::k_inputs_window_table, dim3((unsigned)(V->n_ic * 32 * 256 / 64)), dim3(64), 0, st, table, V->ic_win.as<DG1A>(), V->n_ic);
+        }
+        ZK_LAUNCH(zkdev::k_inputs_mul_win<4>, dim3((unsigned)((4 * n * ni + 63) / 64)), dim3(64), 0, st, V->ic_win.as<const DG1A>(), scal, part,
+                  V->n_ic, (uint32_t)n);
+    } else if (pl.inputs_mul && sixteen) {
+        ZK_LAUNCH(zkdev::k_inputs_mul<16>, dim3((unsigned)((16 * n * ni + 63) / 64)), dim3(64), 0, st, table, scal, part, V->n_ic, (uint32_t)n);
+    } else if (pl.inputs_mul) {
+        ZK_LAUNCH(zkdev::k_inputs_mul<4>, dim3((unsigned)((4 * n * ni + 63) / 64)), dim3(64), 0, st, table, scal, part, V->n_ic, (uint32_t)n);
+    }
+    if (sixteen)   // ... and their sum: a wave per proof
+        ZK_LAUNCH_SYNC((zkdev::k_inputs_sum<16, 64>), dim3((unsigned)n), dim3(64), 0, st, table, (const DG1*)part, acc, acc_inf, V->n_ic, (uint32_t)n);
+    else
+        ZK_LAUNCH_SYNC((zkdev::k_inputs_sum<4, 8>), dim3((unsigned)((n + 7) / 8)), dim3(64), 0, st, table, (const DG1*)part, acc, acc_inf, V->n_ic,
+                       (uint32_t)n);
+    return ZK_OK;
+}
+// e(A, B) e(acc, -gamma) e(C, -delta) == e(alpha, beta) per proof: three Miller loops each, then the final exponentiations
+zk_status enqueue_pairing(zk_vk* V, size_t n, const VerifyPlan& pl) {
+    const uint32_t *a = V->aff_g1.as<const uint32_t>(), *c = a + n * 24, *acc = V->acc.as<const uint32_t>();
+    const uint32_t *skip = V->skip.as<const uint32_t>(), *valid = V->valid.as<const uint32_t>(), *gam = V->gam.as<const uint32_t>();
+    const uint32_t* prep_gamma = V->gamma_inf ? nullptr : V->prep[0].as<const uint32_t>();
+    const uint32_t* prep_delta = V->delta_inf ? nullptr : V->prep[1].as<const uint32_t>();
+    const F12* alpha_beta = V->alpha_beta.as<const F12>();
+    uint32_t* ok = V->ok.as<uint32_t>();
+    const unsigned b64 = (unsigned)((n + 63) / 64), bw = (unsigned)((n + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS);
+    if (pl.pairing == VPairing::ROWS)   // the key's prepared lines in the rows' representation, once per key
+        for (int k = 0; k < 2; k++) {
+            if ((k == 0 ? V->gamma_inf : V->delta_inf) || V->lines28[k].cap) continue;
+            V->lines28[k].is_public = true;
+            ZK_TRY(V->lines28[k].ensure(zkcoop::LINE_TABLE_BYTES));
+            zkcoop::verify_import_coefs(V->prep[k].as<const uint32_t>(), V->lines28[k].p, (uint32_t)zkcoop::VERIFY_NCOEF * 6, g_stream);
+        }
+    {
+        ProfScope ps("verify_miller");
+        if (pl.pairing == VPairing::ROWS)
+            zkcoop::verify_miller(a, V->coop_stage.p, acc, V->gamma_inf ? nullptr : V->lines28[0].p, c, V->delta_inf ? nullptr : V->lines28[1].p, skip,
+                                  V->f.p, (uint32_t)n, g_stream);
+        else if (pl.pairing == VPairing::LANES18)
+            ZK_LAUNCH_SYNC(zkdev::k_miller_loop_wide, dim3(bw, 3), dim3(zkdev::W3_THREADS), 0, g_stream, a, V->prep_b.as<const uint32_t>(), acc,
+                           prep_gamma, c, prep_delta, skip, V->f.as<F12>(), (uint32_t)n);
+        else
+            ZK_LAUNCH(zkdev::k_miller_loop, dim3(b64, 3), dim3(64), 0, g_stream, a, V->aff_g2.as<const uint32_t>(), acc, prep_gamma, c, prep_delta, skip,
+                      V->f.as<F12>(), (uint32_t)n);
+    }
+    {
+        ProfScope ps("verify_final");
+        if (pl.pairing == VPairing::ROWS)
+            zkcoop::verify_final_exp(V->f.p, gam, V->alpha_beta.p, valid, ok, nullptr, (uint32_t)n, g_stream);
+        else if (pl.pairing == VPairing::LANES18)
+            ZK_LAUNCH_SYNC(zkdev::k_final_exp_wide, dim3(bw), dim3(zkdev::W3_THREADS), 0, g_stream, V->f.as<const F12>(), gam, alpha_beta, valid, ok,
+                           (F12*)nullptr, (uint32_t)n);
+        else
+            ZK_LAUNCH(zkdev::k_final_exp, dim3(b64), dim3(64), 0, g_stream, V->f.as<const F12>(), gam, alpha_beta, valid, ok, (F12*)nullptr, (uint32_t)n);
+    }
+    return ZK_OK;
+}
+
+// own_proofs: A, B, C were computed by this library's prover a moment ago (the self-check of gen_proof): group elements
+// by construction, as the in-memory Proof the reference hands to verify_proof in check_proof (confidential.rs:208-278,
+// no deserialisation there) - no r-torsion test, which only a foreign byte string needs; own_affine: see stage_own_affine
+zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok_out, bool own_proofs,
+                       const uint8_t* own_affine, const VerifyTunables& tun) {
+    const uint32_t ni = V->n_ic - 1;
+    if (!own_proofs) own_affine = nullptr;
+    const VerifyPlan pl = verify_plan(n, ni, own_proofs, own_affine != nullptr, tun);
+    Staged s(n, own_affine ? nullptr : proofs);
+    // a point at infinity in A, B or C is what Proof::read refuses (x = y = 0 stands for it in the host's affine form)
+    auto zero = [](const uint8_t* q, size_t len) { return std::all_of(q, q + len, [](uint8_t b) { return b == 0; }); };
+    for (size_t i = 0; own_affine && i < n; i++) {
+        const uint8_t* a = own_affine + i * OWN_AFFINE_BYTES;
+        s.enc[i] = zero(a, 96) || zero(a + 96, 192) || zero(a + 288, 96);
+    }
+    std::vector<uint32_t> bad(n, 0), sc((size_t)n * ni * 8, 0);
+    for (size_t i = 0; i < n; i++) {
+        if (s.enc[i] || !inputs_canonical(inputs + i * ni * 32, ni)) {
+            bad[i] = 1;
+            s.f1[i] = s.f1[n + i] = s.f2[i] = 1;   // decode nothing; its scalars stay zero
+        } else if (ni) {   // (no inputs: `sc` is empty, nothing to index - UBSan, round 4)
+            memcpy(&sc[i * ni * 8], inputs + i * ni * 32, (size_t)ni * 32);
+        }
+    }
+    ZK_TRY(upload_staged(V, n, s, &bad));
+    ZK_TRY(upload(V->scal, sc.data(), sc.size() * 4));
+    if (own_affine) ZK_TRY(stage_own_affine(V, n, own_affine));
     ZK_TRY(V->part.ensure((size_t)n * (ni ? 16 * ni : 1) * sizeof(DG1)));   // (sixteen pieces per scalar from INPUTS_FINE_MIN proofs)
     ZK_TRY(V->acc.ensure(n * 96));
     ZK_TRY(V->acc_inf.ensure(n * 4));
@@ -486,7 +594,6 @@ zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t*
     ZK_TRY(V->valid.ensure(n * 4));
     ZK_TRY(V->f.ensure(3 * n * sizeof(F12)));   // one Miller function per pair
     ZK_TRY(V->ok.ensure(n * 4));
-    const unsigned b64 = (unsigned)((n + 63) / 64);
     // three independent bundles of serial chains - the G2 decoder, the G1 decoder, the input accumulator - side by side
     // on the lane's three streams (each is a few dozen waves; one after the other they were 60 % of a verification)
     for (int k = 0; k < 2; k++)
@@ -494,155 +601,16 @@ zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t*
     HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
     HIP_TRY(hipStreamWaitEvent(g_stream2, g_ev_fork, 0));
     HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_ev_fork, 0));
-    // eighteen lanes per (proof, pair) and per final exponentiation (pairing.h "Lane-parallel Fq12"; six in round 3): the chains
-    // are ~9x shorter than one thread's; ZKAMD_VERIFY_WIDE=0 keeps one thread per pair / per proof (A/B; the key's e(alpha,
-    // beta) always takes it)
-    const char* wide_env = getenv("ZKAMD_VERIFY_WIDE");
-    const bool wide = !(wide_env && atoi(wide_env) == 0);
-    // Rows of 16 lanes instead of one value per lane (coop_verify.cpp, coop_pairing.cpp) - the same tables, accumulators and
-    // Fq12 words, the same verdicts:
-    //  - the input accumulator for a handful of proofs (88 rows per proof: work-bound beyond COOP_INPUTS_MAX);
-    //  - the decoders, the line preparation of B, the Miller loops and the final exponentiation (3 + 1 + 18 + 6 rows per
-    //    proof) up to COOP_PAIRING_MAX proofs per chunk: shorter chains AND fewer instructions than the eighteen-lane form.
-    // ZKAMD_COOP_VERIFY=0 keeps the one-lane head, ZKAMD_COOP_PAIRING=0 the eighteen-lane pairing (A/B; *_MAX: the limits).
-    auto env_n = [](const char* name, size_t dflt) {
-        const char* e = getenv(name);
-        return e && *e ? (size_t)strtoull(e, nullptr, 10) : dflt;
-    };
-    const bool coop_on = wide && env_n("ZKAMD_COOP_VERIFY", 1) != 0;
-    const bool coop_inputs = coop_on && n <= env_n("ZKAMD_COOP_INPUTS_MAX", zkcoop::VERIFY_MAX);
-    const bool coop_head = coop_on && n <= std::max(env_n("ZKAMD_COOP_PAIRING_MAX", zkcoop::PAIRING_MAX), env_n("ZKAMD_COOP_INPUTS_MAX", zkcoop::VERIFY_MAX));
-    const bool coop_pairing = coop_head && n <= env_n("ZKAMD_COOP_PAIRING_MAX", zkcoop::PAIRING_MAX) && env_n("ZKAMD_COOP_PAIRING", 1) != 0;
-    {
-        // the lane-parallel Miller loop reads the lines of B prepared, and the preparation's last point settles B's r-torsion
-        // test (k_g2_prepare): the decoder leaves it out there
-        ProfScope ps("verify_decode");
-        if (own_affine) {
-        } else if (coop_head)
-            zkcoop::verify_decode_g2((const uint32_t*)V->in_g2.as<uint32_t>(), (const uint32_t*)V->fl_g2.as<uint32_t>(), V->aff_g2.as<uint32_t>(),
-                                     V->st_g2.as<uint32_t>(), (uint32_t)n, g_stream);
-        else
-        ZK_LAUNCH(zkdev::k_decode_g2, dim3(b64), dim3(64), 0, g_stream, (const uint32_t*)V->in_g2.as<uint32_t>(),
-                  (const uint32_t*)V->fl_g2.as<uint32_t>(), V->aff_g2.as<uint32_t>(), V->st_g2.as<uint32_t>(), (uint32_t)n,
-                  (own_proofs || wide) ? 0u : 1u);
-    }
-    static_assert(zkcoop::VERIFY_NCOEF == zkdev::PAIRING_NCOEF, "coop_verify.cpp restates the loop constants");
-    if (coop_pairing)
-        for (int k = 0; k < 2; k++) {
-            if ((k == 0 ? V->gamma_inf : V->delta_inf) || V->lines28[k].cap) continue;
-            V->lines28[k].is_public = true;
-            ZK_TRY(V->lines28[k].ensure(zkcoop::LINE_TABLE_BYTES));
-            zkcoop::verify_import_coefs((const uint32_t*)V->prep[k].as<uint32_t>(), V->lines28[k].p, (uint32_t)zkcoop::VERIFY_NCOEF * 6, g_stream);
-        }
-    if (coop_head) {
-        if (!coop_pairing) ZK_TRY(V->prep_b.ensure(n * COEF_WORDS * 4));
-        ZK_TRY(V->coop_stage.ensure(zkcoop::g2_prepare_stage_bytes((uint32_t)n)));
-        ProfScope ps("verify_prepare");
-        zkcoop::verify_g2_prepare((const uint32_t*)V->aff_g2.as<uint32_t>(), V->coop_stage.p, coop_pairing ? (uint32_t*)nullptr : V->prep_b.as<uint32_t>(),
-                                  (uint32_t)n, own_proofs ? (uint32_t*)nullptr : V->st_g2.as<uint32_t>(), g_stream);
-    } else if (wide) {
-        ZK_TRY(V->prep_b.ensure(n * COEF_WORDS * 4));
-        ProfScope ps("verify_prepare");
-        ZK_LAUNCH_SYNC(zkdev::k_g2_prepare_tri, dim3((unsigned)((n + zkdev::TL_POINTS - 1) / zkdev::TL_POINTS)), dim3(64), 0, g_stream,
-                       (const uint32_t*)V->aff_g2.as<uint32_t>(), V->prep_b.as<uint32_t>(), (uint32_t)n,
-                       own_proofs ? (uint32_t*)nullptr : V->st_g2.as<uint32_t>());
-    }
-    {
-        ProfScope ps("verify_decode_g1", g_stream2);
-        if (own_affine) {
-        } else if (coop_head)
-            zkcoop::verify_decode_g1((const uint32_t*)V->in_g1.as<uint32_t>(), (const uint32_t*)V->fl_g1.as<uint32_t>(), V->aff_g1.as<uint32_t>(),
-                                     V->st_g1.as<uint32_t>(), (uint32_t)(2 * n), own_proofs ? 0u : 1u, g_stream2);
-        else
-        ZK_LAUNCH(zkdev::k_decode_g1, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, g_stream2,
-                  (const uint32_t*)V->in_g1.as<uint32_t>(), (const uint32_t*)V->fl_g1.as<uint32_t>(), V->aff_g1.as<uint32_t>(),
-                  V->st_g1.as<uint32_t>(), (uint32_t)(2 * n), own_proofs ? 0u : 1u);
-    }
+    ZK_TRY(enqueue_head(V, n, pl, g_stream, g_stream2));
     HIP_TRY(hipEventRecord(V->ev_join[0], g_stream2));
-    {
-        ProfScope ps("verify_inputs", g_copy_stream);
-        if (coop_inputs)
-            zkcoop::verify_inputs(V->ic_table.p, (const uint32_t*)V->scal.as<uint32_t>(), V->part.p, V->acc.as<uint32_t>(),
-                                  V->acc_inf.as<uint32_t>(), V->n_ic, (uint32_t)n, g_copy_stream);
-        else {
-        if (ni && n >= env_n("ZKAMD_INPUTS_FINE_MIN", zkdev::INPUTS_FINE_MIN) && env_n("ZKAMD_INPUTS_WINDOWS", 1) != 0) {
-            // products from the table of 8-bit windows: four chains of eight additions per scalar
-            if (!V->ic_win.cap) {
-                V->ic_win.is_public = true;
-                ZK_TRY(V->ic_win.ensure((size_t)V->n_ic * 32 * 256 * sizeof(DG1A)));
-                ZK_LAUNCH(zkdev::k_inputs_window_table, dim3((unsigned)(V->n_ic * 32 * 256 / 64)), dim3(64), 0, g_copy_stream,
-                          (const DG1A*)V->ic_table.as<DG1A>(), V->ic_win.as<DG1A>(), V->n_ic);
-            }
-            ZK_LAUNCH(zkdev::k_inputs_mul_win<4>, dim3((unsigned)((4 * n * ni + 63) / 64)), dim3(64), 0, g_copy_stream,
-                      (const DG1A*)V->ic_win.as<DG1A>(), (const uint32_t*)V->scal.as<uint32_t>(), V->part.as<DG1>(), V->n_ic, (uint32_t)n);
-            ZK_LAUNCH_SYNC((zkdev::k_inputs_sum<4, 8>), dim3((unsigned)((n + 7) / 8)), dim3(64), 0, g_copy_stream, (const DG1A*)V->ic_table.as<DG1A>(),
-                           (const DG1*)V->part.as<DG1>(), V->acc.as<uint32_t>(), V->acc_inf.as<uint32_t>(), V->n_ic, (uint32_t)n);
-        } else if (n >= env_n("ZKAMD_INPUTS_FINE_MIN", zkdev::INPUTS_FINE_MIN)) {   // sixteen pieces per scalar, a wave per proof for the sum
-            if (ni)
-                ZK_LAUNCH(zkdev::k_inputs_mul<16>, dim3((unsigned)((16 * n * ni + 63) / 64)), dim3(64), 0, g_copy_stream,
-                          (const DG1A*)V->ic_table.as<DG1A>(), (const uint32_t*)V->scal.as<uint32_t>(), V->part.as<DG1>(), V->n_ic, (uint32_t)n);
-            ZK_LAUNCH_SYNC((zkdev::k_inputs_sum<16, 64>), dim3((unsigned)n), dim3(64), 0, g_copy_stream, (const DG1A*)V->ic_table.as<DG1A>(),
-                           (const DG1*)V->part.as<DG1>(), V->acc.as<uint32_t>(), V->acc_inf.as<uint32_t>(), V->n_ic, (uint32_t)n);
-        } else {
-        if (ni)
-            ZK_LAUNCH(zkdev::k_inputs_mul<4>, dim3((unsigned)((4 * n * ni + 63) / 64)), dim3(64), 0, g_copy_stream,
-                      (const DG1A*)V->ic_table.as<DG1A>(), (const uint32_t*)V->scal.as<uint32_t>(), V->part.as<DG1>(), V->n_ic,
-                      (uint32_t)n);
-        ZK_LAUNCH_SYNC((zkdev::k_inputs_sum<4, 8>), dim3((unsigned)((n + 7) / 8)), dim3(64), 0, g_copy_stream, (const DG1A*)V->ic_table.as<DG1A>(),
-                  (const DG1*)V->part.as<DG1>(), V->acc.as<uint32_t>(), V->acc_inf.as<uint32_t>(), V->n_ic, (uint32_t)n);
-        }
-        }
-    }
+    ZK_TRY(enqueue_inputs(V, n, pl, g_copy_stream));
     HIP_TRY(hipEventRecord(V->ev_join[1], g_copy_stream));
     HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[0], 0));
     HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[1], 0));
-    ZK_LAUNCH(zkdev::k_verify_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)V->st_g1.as<uint32_t>(),
-              (const uint32_t*)V->st_g2.as<uint32_t>(), (const uint32_t*)V->acc_inf.as<uint32_t>(),
-              (const uint32_t*)V->host_bad.as<uint32_t>(), V->skip.as<uint32_t>(), V->valid.as<uint32_t>(), (uint32_t)n);
-    const uint32_t* prep_gamma = V->gamma_inf ? (const uint32_t*)nullptr : (const uint32_t*)V->prep[0].as<uint32_t>();
-    const uint32_t* prep_delta = V->delta_inf ? (const uint32_t*)nullptr : (const uint32_t*)V->prep[1].as<uint32_t>();
-    if (coop_pairing) {
-        {
-            ProfScope ps("verify_miller");
-            zkcoop::verify_miller((const uint32_t*)V->aff_g1.as<uint32_t>(), V->coop_stage.p, (const uint32_t*)V->acc.as<uint32_t>(),
-                                  V->gamma_inf ? nullptr : V->lines28[0].p, (const uint32_t*)(V->aff_g1.as<uint32_t>() + n * 24),
-                                  V->delta_inf ? nullptr : V->lines28[1].p, (const uint32_t*)V->skip.as<uint32_t>(), V->f.p, (uint32_t)n, g_stream);
-        }
-        {
-            ProfScope ps("verify_final");
-            zkcoop::verify_final_exp(V->f.p, (const uint32_t*)V->gam.as<uint32_t>(), V->alpha_beta.p, (const uint32_t*)V->valid.as<uint32_t>(),
-                                     V->ok.as<uint32_t>(), nullptr, (uint32_t)n, g_stream);
-        }
-    } else if (wide) {
-        const unsigned bw = (unsigned)((n + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS);
-        {
-            ProfScope ps("verify_miller");
-            ZK_LAUNCH_SYNC(zkdev::k_miller_loop_wide, dim3(bw, 3), dim3(zkdev::W3_THREADS), 0, g_stream,
-                           (const uint32_t*)V->aff_g1.as<uint32_t>(), (const uint32_t*)V->prep_b.as<uint32_t>(),
-                           (const uint32_t*)V->acc.as<uint32_t>(), prep_gamma, (const uint32_t*)(V->aff_g1.as<uint32_t>() + n * 24),
-                           prep_delta, (const uint32_t*)V->skip.as<uint32_t>(), V->f.as<F12>(), (uint32_t)n);
-        }
-        {
-            ProfScope ps("verify_final");
-            ZK_LAUNCH_SYNC(zkdev::k_final_exp_wide, dim3(bw), dim3(zkdev::W3_THREADS), 0, g_stream, (const F12*)V->f.as<F12>(),
-                           (const uint32_t*)V->gam.as<uint32_t>(), (const F12*)V->alpha_beta.as<F12>(),
-                           (const uint32_t*)V->valid.as<uint32_t>(), V->ok.as<uint32_t>(), (F12*)nullptr, (uint32_t)n);
-        }
-    } else {
-        {
-            ProfScope ps("verify_miller");
-            ZK_LAUNCH(zkdev::k_miller_loop, dim3(b64, 3), dim3(64), 0, g_stream, (const uint32_t*)V->aff_g1.as<uint32_t>(),
-                      (const uint32_t*)V->aff_g2.as<uint32_t>(), (const uint32_t*)V->acc.as<uint32_t>(), prep_gamma,
-                      (const uint32_t*)(V->aff_g1.as<uint32_t>() + n * 24), prep_delta, (const uint32_t*)V->skip.as<uint32_t>(),
-                      V->f.as<F12>(), (uint32_t)n);
-        }
-        {
-            ProfScope ps("verify_final");
-            ZK_LAUNCH(zkdev::k_final_exp, dim3(b64), dim3(64), 0, g_stream, (const F12*)V->f.as<F12>(), (const uint32_t*)V->gam.as<uint32_t>(),
-                      (const F12*)V->alpha_beta.as<F12>(), (const uint32_t*)V->valid.as<uint32_t>(), V->ok.as<uint32_t>(), (F12*)nullptr,
-                      (uint32_t)n);
-        }
-    }
+    ZK_LAUNCH(zkdev::k_verify_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, V->st_g1.as<const uint32_t>(),
+              V->st_g2.as<const uint32_t>(), V->acc_inf.as<const uint32_t>(), V->host_bad.as<const uint32_t>(), V->skip.as<uint32_t>(),
+              V->valid.as<uint32_t>(), (uint32_t)n);
+    ZK_TRY(enqueue_pairing(V, n, pl));
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> okv(n);
     HIP_TRY(hipStreamSynchronize(g_stream));
@@ -657,32 +625,16 @@ zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t*
 // weigh (Fiat-Shamir), no randomness source is needed and a run can be repeated.  *decided = true: every proof of the
 // chunk verifies (probability of a wrong accept 2^-128 per attempt).  *decided = false: a proof of the chunk is malformed
 // or invalid, or the combined check failed - the caller runs the per-proof verifier, which names the culprits.
-zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t* inputs, bool own_proofs, bool* decided) {
+zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t* inputs, bool own_proofs, bool* decided,
+                           const VerifyTunables& tun) {
     *decided = false;
     const uint32_t ni = V->n_ic - 1;
     if (V->gamma_inf || V->delta_inf || !ni) return ZK_OK;   // degenerate keys: the per-proof path knows them
-    std::vector<uint32_t> g1((size_t)2 * n * 12), g2((size_t)n * 24), f1(2 * n), f2(n), bad(n, 0);
+    const Staged staged(n, proofs);
+    const std::vector<uint32_t> bad(n, 0);
     static const uint64_t RMOD[4] = ZK_FR_P_64;
-    for (size_t i = 0; i < n; i++) {
-        const uint8_t* p = proofs + i * 192;
-        if (!(parse_g1_compressed(p, &g1[i * 12], &f1[i]) && parse_g2_compressed(p + 48, &g2[i * 24], &f2[i]) &&
-              parse_g1_compressed(p + 144, &g1[(n + i) * 12], &f1[n + i])))
-            return ZK_OK;
-        for (uint32_t j = 0; j < ni; j++) {
-            const uint8_t* s = inputs + (i * ni + j) * 32;
-            uint64_t v[4];
-            memcpy(v, s, 32);
-            bool lt = false;
-            for (int k = 3; k >= 0; k--) {
-                if (v[k] < RMOD[k]) {
-                    lt = true;
-                    break;
-                }
-                if (v[k] > RMOD[k]) break;
-            }
-            if (!lt) return ZK_OK;   // not a canonical Fr
-        }
-    }
+    for (size_t i = 0; i < n; i++)   // a refused encoding, an input that is not a canonical Fr: undecided
+        if (staged.enc[i] || !inputs_canonical(inputs + i * ni * 32, ni)) return ZK_OK;
     // seed = Blake2s(n | digests of the leaves), a leaf = 256 consecutive proofs with their inputs: the leaves are hashed by
     // the host threads side by side (7 MB in one stream was 7 ms of the 8192-proof call), the seed does not depend on how many
     uint8_t seed[32];
@@ -773,22 +725,14 @@ zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint
     memcpy(&ev[0], &sa, 16);
     memcpy(&ev[4], &sb, 16);
     const size_t m = n + 2;
-    ZK_TRY(upload(V->in_g1, g1.data(), g1.size() * 4));
-    ZK_TRY(upload(V->in_g2, g2.data(), g2.size() * 4));
-    ZK_TRY(upload(V->fl_g1, f1.data(), f1.size() * 4));
-    ZK_TRY(upload(V->fl_g2, f2.data(), f2.size() * 4));
-    ZK_TRY(upload(V->host_bad, bad.data(), bad.size() * 4));
+    ZK_TRY(upload_staged(V, n, staged, &bad));
     ZK_TRY(upload(V->rlc_rho, rho.data(), rho.size() * 4));
     ZK_TRY(upload(V->rlc_s, sv.data(), sv.size() * 4));
     ZK_TRY(upload(V->rlc_exp, ev.data(), 32));
-    ZK_TRY(V->aff_g1.ensure((size_t)2 * n * 96));
-    ZK_TRY(V->aff_g2.ensure(n * 192));
-    ZK_TRY(V->st_g1.ensure(2 * n * 4));
-    ZK_TRY(V->st_g2.ensure(n * 4));
     ZK_TRY(V->skip.ensure(m * 4));
     ZK_TRY(V->f.ensure(3 * m * sizeof(F12)));
     ZK_TRY(V->ok.ensure(4));
-    ZK_TRY(V->prep_b.ensure(m * COEF_WORDS * 4));
+    ZK_TRY(V->prep_b.ensure(m * COEF_WORDS * 4));   // (the key's two tables behind the n of the batch: before enqueue_head reserves n)
     ZK_TRY(V->rlc_pts.ensure(m * 96));
     ZK_TRY(V->rlc_c.ensure(n * sizeof(zkdev::XYZZ<zkdev::Fq32>)));
     ZK_TRY(V->rlc_csum.ensure(((n + 255) / 256 + 1) * sizeof(zkdev::XYZZ<zkdev::Fq32>)));
@@ -803,31 +747,15 @@ zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint
         for (int k = 1; k < 3; k++) memcpy(&ones[(size_t)k * 144], R32, 48);
         ZK_TRY(upload(V->rlc_fe, ones.data(), ones.size() * 4));
     }
-    const unsigned b64 = (unsigned)((n + 63) / 64);
     for (int k = 0; k < 2; k++)
         if (!V->ev_join[k]) HIP_TRY(hipEventCreate(&V->ev_join[k]));
     HIP_TRY(hipMemsetAsync(V->rlc_all.p, 0xff, 4, g_stream));
     HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
     HIP_TRY(hipStreamWaitEvent(g_stream2, g_ev_fork, 0));
     HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_ev_fork, 0));
-    {   // main stream: B decoded, its lines prepared (the r-torsion test rides on the preparation)
-        ProfScope ps("verify_decode");
-        ZK_LAUNCH(zkdev::k_decode_g2, dim3(b64), dim3(64), 0, g_stream, (const uint32_t*)V->in_g2.as<uint32_t>(),
-                  (const uint32_t*)V->fl_g2.as<uint32_t>(), V->aff_g2.as<uint32_t>(), V->st_g2.as<uint32_t>(), (uint32_t)n, 0u);
-    }
-    {
-        ProfScope ps("verify_prepare");
-        ZK_LAUNCH_SYNC(zkdev::k_g2_prepare_tri, dim3((unsigned)((n + zkdev::TL_POINTS - 1) / zkdev::TL_POINTS)), dim3(64), 0, g_stream,
-                       (const uint32_t*)V->aff_g2.as<uint32_t>(), V->prep_b.as<uint32_t>(), (uint32_t)n,
-                       own_proofs ? (uint32_t*)nullptr : V->st_g2.as<uint32_t>());
-    }
-    {   // side stream: A and C decoded, scaled by rho_i, the C's summed
-        ProfScope ps("verify_decode_g1", g_stream2);
-        ZK_LAUNCH(zkdev::k_decode_g1, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, g_stream2,
-                  (const uint32_t*)V->in_g1.as<uint32_t>(), (const uint32_t*)V->fl_g1.as<uint32_t>(), V->aff_g1.as<uint32_t>(),
-                  V->st_g1.as<uint32_t>(), (uint32_t)(2 * n), own_proofs ? 0u : 1u);
-    }
-    {
+    // main stream: B decoded, its lines prepared (the r-torsion test rides on the preparation); side stream: A and C decoded ...
+    ZK_TRY(enqueue_head(V, n, verify_plan_lane_head(n, own_proofs, tun, true), g_stream, g_stream2));
+    {   // ... scaled by rho_i, the C's summed
         ProfScope ps("verify_rlc_scale", g_stream2);
         typedef zkdev::XYZZ<zkdev::Fq32> P32;
         ZK_LAUNCH(zkdev::k_rlc_scale, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, g_stream2, (const uint32_t*)V->aff_g1.as<uint32_t>(),
@@ -912,33 +840,27 @@ zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint
 }  // namespace
 
 namespace zkrt {
-// rlc: try the random-linear-combination check on every chunk first (verify_chunk_rlc) and fall back to the per-proof
-// verifier only for a chunk it cannot vouch for
-// form: VERIFY_PER_PROOF | VERIFY_COMBINED (every chunk of 8 or more) | VERIFY_AUTO: the combined check for the chunks it is the
-// faster form for.  It saves WORK (n + 2 Miller loops and one final exponentiation instead of 3 n and n), and work is what
-// a verification costs only once the chunk fills the machine: 1024 proofs 8.0 ms per proof against 12.7 combined, 2048: 9.2 /
-// 13.1, 8192: 22.5 / 16.0 (profiles/r05final_verify_probe.txt) - the two meet near 4000.
-constexpr size_t VERIFY_RLC_AUTO_MIN = 4096;
+// the random-linear-combination check first (verify_chunk_rlc) on the chunks verify_plan.h names for it, the per-proof
+// verifier for the others and for a chunk the combined check cannot vouch for
 zk_status verify_batch(zk_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_inputs, uint8_t* ok_out,
                        bool own_proofs, int form, const uint8_t* own_affine) {
-    static const size_t auto_min = getenv("ZKAMD_VERIFY_RLC_MIN") ? (size_t)atoll(getenv("ZKAMD_VERIFY_RLC_MIN")) : VERIFY_RLC_AUTO_MIN;
     if (!vk || (n && (!proofs || !ok_out)) || (n && n_inputs && !public_inputs)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     // verifier.rs:38-40
     if (n_inputs + 1 != vk->ic.size()) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "number of public inputs + 1 differs from ic");
     ZK_TRY(use_device(vk->device));
     for (size_t first = 0; first < n; first += VERIFY_CHUNK) {
         const size_t np = std::min(VERIFY_CHUNK, n - first);
-        const bool rlc = form == VERIFY_COMBINED || (form == VERIFY_AUTO && np >= auto_min);
-        if (rlc && np >= 8) {
+        const VerifyTunables tun = VerifyTunables::read();
+        if (verify_takes_combined(form, np, tun)) {
             bool decided = false;
-            ZK_TRY(verify_chunk_rlc(vk, np, proofs + first * 192, public_inputs + first * n_inputs * 32, own_proofs, &decided));
+            ZK_TRY(verify_chunk_rlc(vk, np, proofs + first * 192, public_inputs + first * n_inputs * 32, own_proofs, &decided, tun));
             if (decided) {
                 memset(ok_out + first, 1, np);
                 continue;
             }
         }
         ZK_TRY(verify_chunk(vk, np, proofs + first * 192, public_inputs + first * n_inputs * 32, ok_out + first, own_proofs,
-                            own_affine ? own_affine + first * OWN_AFFINE_BYTES : nullptr));
+                            own_affine ? own_affine + first * OWN_AFFINE_BYTES : nullptr, tun));
     }
     return ZK_OK;
 }
@@ -1054,51 +976,10 @@ zk_status zk_proof_read_batch(zk_vk* vk, size_t n, const uint8_t* proofs, uint8_
     for (size_t first = 0; first < n; first += VERIFY_CHUNK) {
         const size_t np = std::min(VERIFY_CHUNK, n - first);
         const uint8_t* pr = proofs + first * 192;
-        std::vector<uint32_t> g1((size_t)2 * np * 12), g2((size_t)np * 24), f1(2 * np), f2(np);
-        std::vector<uint8_t> enc(np, 0);   // bit k: the ENCODING of point k (0 = A, 1 = B, 2 = C) is refused on the host
-        for (size_t i = 0; i < np; i++) {
-            const uint8_t* p = pr + i * 192;
-            // every point is parsed on its own: Proof::read finishes A (decode, curve, subgroup, infinity) before it
-            // touches B, so a device-side failure of A must win over a malformed B
-            if (!parse_g1_compressed(p, &g1[i * 12], &f1[i])) {
-                enc[i] |= 1;
-                f1[i] = 1;   // decode nothing
-                memset(&g1[i * 12], 0, 48);
-            }
-            if (!parse_g2_compressed(p + 48, &g2[i * 24], &f2[i])) {
-                enc[i] |= 2;
-                f2[i] = 1;
-                memset(&g2[i * 24], 0, 96);
-            }
-            if (!parse_g1_compressed(p + 144, &g1[(np + i) * 12], &f1[np + i])) {
-                enc[i] |= 4;
-                f1[np + i] = 1;
-                memset(&g1[(np + i) * 12], 0, 48);
-            }
-        }
-        ZK_TRY(upload(vk->in_g1, g1.data(), g1.size() * 4));
-        ZK_TRY(upload(vk->in_g2, g2.data(), g2.size() * 4));
-        ZK_TRY(upload(vk->fl_g1, f1.data(), f1.size() * 4));
-        ZK_TRY(upload(vk->fl_g2, f2.data(), f2.size() * 4));
-        ZK_TRY(vk->aff_g1.ensure((size_t)2 * np * 96));
-        ZK_TRY(vk->aff_g2.ensure(np * 192));
-        ZK_TRY(vk->st_g1.ensure(2 * np * 4));
-        ZK_TRY(vk->st_g2.ensure(np * 4));
-        // B as zk_verify_batch treats it: decoded, then the r-torsion test either inside the decoder or at the end of the
-        // line preparation (ZKAMD_VERIFY_WIDE, verify_chunk) - the reader reports what the verifier would act on
-        const char* wide_env = getenv("ZKAMD_VERIFY_WIDE");
-        const bool wide = !(wide_env && atoi(wide_env) == 0);
-        ZK_LAUNCH(zkdev::k_decode_g2, dim3((unsigned)((np + 63) / 64)), dim3(64), 0, g_stream, (const uint32_t*)vk->in_g2.as<uint32_t>(),
-                  (const uint32_t*)vk->fl_g2.as<uint32_t>(), vk->aff_g2.as<uint32_t>(), vk->st_g2.as<uint32_t>(), (uint32_t)np,
-                  wide ? 0u : 1u);
-        if (wide) {
-            ZK_TRY(vk->prep_b.ensure(np * COEF_WORDS * 4));
-            ZK_LAUNCH_SYNC(zkdev::k_g2_prepare_tri, dim3((unsigned)((np + zkdev::TL_POINTS - 1) / zkdev::TL_POINTS)), dim3(64), 0, g_stream,
-                           (const uint32_t*)vk->aff_g2.as<uint32_t>(), vk->prep_b.as<uint32_t>(), (uint32_t)np, vk->st_g2.as<uint32_t>());
-        }
-        ZK_LAUNCH(zkdev::k_decode_g1, dim3((unsigned)((2 * np + 63) / 64)), dim3(64), 0, g_stream,
-                  (const uint32_t*)vk->in_g1.as<uint32_t>(), (const uint32_t*)vk->fl_g1.as<uint32_t>(), vk->aff_g1.as<uint32_t>(),
-                  vk->st_g1.as<uint32_t>(), (uint32_t)(2 * np), 1u);
+        const Staged s(np, pr);
+        ZK_TRY(upload_staged(vk, np, s, nullptr));
+        // B as zk_verify_batch treats it: the reader reports what the verifier would act on
+        ZK_TRY(enqueue_head(vk, np, verify_plan_lane_head(np, false, VerifyTunables::read(), false), g_stream, g_stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));
         std::vector<uint32_t> s1(2 * np), s2(np);
@@ -1110,7 +991,7 @@ zk_status zk_proof_read_batch(zk_vk* vk, size_t n, const uint8_t* proofs, uint8_
             // (core/bellman-verifier/src/lib.rs:67-110): bad encoding, then the decoder's verdict on that point
             const uint32_t d[3] = {s1[i], s2[i], s1[np + i]};
             for (int k = 0; k < 3 && !st; k++) {
-                if (enc[i] & (1u << k))
+                if (s.enc[i] & (1u << k))
                     st = (uint8_t)((k + 1) | (ZK_PROOF_BAD_ENCODING << 2));
                 else if (d[k])   // decoder states 1 / 2 / 3 = not on the curve / not in the subgroup / infinity
                     st = (uint8_t)((k + 1) | ((d[k] == 1 ? ZK_PROOF_NOT_ON_CURVE : d[k] == 2 ? ZK_PROOF_NOT_IN_SUBGROUP : ZK_PROOF_INFINITY) << 2));
@@ -1187,6 +1068,17 @@ zk_status zk_hook_fq_inverse(const uint32_t* in, uint32_t* out, size_t n) try {
     zkcoop::test_inverse((const uint32_t*)a.p, (uint32_t*)b.p, (uint32_t)n, g_stream);
     HIP_TRY(hipStreamSynchronize(g_stream));
     HIP_TRY(hipMemcpy(out, b.p, n * 48, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_ABI_CATCH
+// ... and the plan of a chunk of n proofs (verify_plan.h) under the environment of the call, no GPU involved: out[0 .. 9) =
+// the fields of VerifyPlan in their order, the enumerators as numbers, then whether verify_batch tries the combined check first
+zk_status zk_hook_verify_plan(size_t n, size_t n_inputs, int own_proofs, int have_own_affine, int form, uint64_t* out, size_t out_words) try {
+    if (!out || out_words < 9) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    const VerifyTunables tun = VerifyTunables::read();
+    const VerifyPlan p = verify_plan(n, n_inputs, own_proofs != 0, have_own_affine != 0, tun);
+    const uint64_t f[9] = {(uint64_t)p.decode, p.b_torsion_in_decoder, p.subgroup_tests, (uint64_t)p.prepare, p.prep_b_points, (uint64_t)p.inputs,
+                           p.inputs_mul, (uint64_t)p.pairing, verify_takes_combined(form, n, tun)};
+    std::copy(f, f + 9, out);
     return ZK_OK;
 } ZK_ABI_CATCH
 #endif
