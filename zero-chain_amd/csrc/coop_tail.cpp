@@ -271,25 +271,19 @@ k_ct_upper(const XYZZ<F>* __restrict__ S, uint32_t s_stride, const XYZZ<F>* __re
     }
 }
 
-// out[i] = s_i A[i] + B[i], one row per proof: 4-bit fixed windows over the 255-bit scalar (plain little-endian u32 words
-// at scalars + i stride_words), the 15 multiples of A in a scratch table [15][n]: a chain of 252 doublings and ~75
-// additions, a row's addition 3.7 us and its doubling 2.5 us (a lane's: 15.3 / 9.3 us)
+// s a for row i of n: 4-bit fixed windows over the 255-bit scalar (eight plain little-endian u32 words at s), the 15 multiples
+// of a in column i of a scratch table [15][n]: a chain of 252 doublings and ~75 additions, a row's addition 3.7 us and its
+// doubling 2.5 us (a lane's: 15.3 / 9.3 us)
 template <class F>
-static __global__ void __launch_bounds__(CT_THIN * COOP_W)
-k_ct_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, const uint32_t* __restrict__ scalars,
-               uint32_t stride_words, XYZZ<F>* tbl, XYZZ<F>* __restrict__ out, uint32_t n) {
+ZK_DI XYZZ<CoopT<F>> ct_scale(const XYZZ<CoopT<F>>& a, const uint32_t* __restrict__ s, XYZZ<F>* tbl, uint32_t n, uint32_t i) {
     typedef CoopT<F> C;
-    const uint32_t i = coop_row();
-    if (i >= n) return;
-    const XYZZ<C> a = coop_load(A[i]);
     XYZZ<C> run = xdbl(a);
     coop_store(tbl[i], a);
     coop_store(tbl[(size_t)n + i], run);
     for (uint32_t k = 2; k < 15; k++) {
         run = xadd(run, a);
-        coop_store(tbl[(size_t)k * n + i], run);   // (k + 1) A
+        coop_store(tbl[(size_t)k * n + i], run);   // (k + 1) a
     }
-    const uint32_t* s = scalars + (size_t)i * stride_words;
     XYZZ<C> acc = XYZZ<C>::inf();
     for (int w = 63; w >= 0; w--) {
         if (w != 63)
@@ -297,7 +291,73 @@ k_ct_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, con
         const uint32_t digit = (s[w >> 3] >> (4 * (w & 7))) & 15u;
         if (digit) acc = xadd(acc, coop_load(tbl[(size_t)(digit - 1) * n + i]));
     }
+    return acc;
+}
+
+// out[i] = s_i A[i] + B[i], one row per proof (scalars at scalars + i stride_words)
+template <class F>
+static __global__ void __launch_bounds__(CT_THIN * COOP_W)
+k_ct_scale_add(const XYZZ<F>* __restrict__ A, const XYZZ<F>* __restrict__ B, const uint32_t* __restrict__ scalars,
+               uint32_t stride_words, XYZZ<F>* tbl, XYZZ<F>* __restrict__ out, uint32_t n) {
+    typedef CoopT<F> C;
+    const uint32_t i = coop_row();
+    if (i >= n) return;
+    const XYZZ<C> acc = ct_scale<F>(coop_load(A[i]), scalars + (size_t)i * stride_words, tbl, n, i);
     coop_store(out[i], xadd(acc, coop_load(B[i])));
+}
+
+// ---- the derived bases of a (key, circuit) pair (coop_tail.h basis_*): transforms "in the exponent", one row per point
+
+// out[i] = tbl[idx[i]] as an XYZZ point, the identity for idx[i] < 0 (one lane per point)
+template <class F>
+static __global__ void __launch_bounds__(128)
+k_ct_gather_affine(const Affine<F>* __restrict__ tbl, const int32_t* __restrict__ idx, XYZZ<F>* __restrict__ out, uint32_t n) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    out[i] = idx[i] < 0 ? XYZZ<F>::inf() : XYZZ<F>::from_affine(tbl[idx[i]]);
+}
+
+// out[i] = s_i A[idx ? idx[i] : i]  (scalars: eight words each, one per row)
+template <class F>
+static __global__ void __launch_bounds__(CT_THIN * COOP_W)
+k_ct_scale_rows(const XYZZ<F>* __restrict__ A, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ scalars, XYZZ<F>* tbl,
+                XYZZ<F>* __restrict__ out, uint32_t n) {
+    const uint32_t i = coop_row();
+    if (i >= n) return;
+    coop_store(out[i], ct_scale<F>(coop_load(A[idx ? idx[i] : i]), scalars + (size_t)i * 8, tbl, n, i));
+}
+
+// One decimation-in-time stage of a transform of n = 2^log_n points, out of place, one row per butterfly: with half =
+// 2^log_half, the pair (x, y) = (in[b 2 half + lo], in[b 2 half + half + lo]) and t = w^e y, e = lo << (log_n - 1 - log_half),
+// out[.. + lo] = x + t and out[.. + half + lo] = x - t.  tw holds w^e for e < n / 2 (plain words).  -t negates Y (< BY p ->
+// < (BY + 1) p) and is consumed once, as the second operand of an addition, whose products take operands up to 13 p.
+template <class F>
+static __global__ void __launch_bounds__(CT_THIN * COOP_W)
+k_ct_dft_stage(const XYZZ<F>* __restrict__ in, XYZZ<F>* __restrict__ out, const uint32_t* __restrict__ tw, XYZZ<F>* tbl,
+               uint32_t log_n, uint32_t log_half) {
+    typedef CoopT<F> C;
+    const uint32_t i = coop_row(), nbf = 1u << (log_n - 1);
+    if (i >= nbf) return;
+    const uint32_t half = 1u << log_half, lo = i & (half - 1);
+    const uint32_t ix = ((i >> log_half) << (log_half + 1)) | lo, iy = ix | half;
+    const uint32_t e = lo << (log_n - 1 - log_half);
+    XYZZ<C> t = ct_scale<F>(coop_load(in[iy]), tw + (size_t)e * 8, tbl, nbf, i);
+    const XYZZ<C> x = coop_load(in[ix]);
+    coop_store(out[ix], xadd(x, t));
+    t.y = neg_b<XYZZ<C>::BY>(t.y);
+    coop_store(out[iy], xadd(x, t));
+}
+
+// out[i] = base[i] + terms[ptr[i]] + ... + terms[ptr[i + 1] - 1], one row per i
+template <class F>
+static __global__ void __launch_bounds__(CT_THIN * COOP_W)
+k_ct_segment_sums(const XYZZ<F>* __restrict__ base, const XYZZ<F>* __restrict__ terms, const uint32_t* __restrict__ ptr,
+                  XYZZ<F>* __restrict__ out, uint32_t n) {
+    const uint32_t i = coop_row();
+    if (i >= n) return;
+    auto acc = coop_load(base[i]);
+    for (uint32_t k = ptr[i]; k < ptr[i + 1]; k++) acc = xadd(acc, coop_load(terms[k]));
+    coop_store(out[i], acc);
 }
 
 }  // namespace zkdev
@@ -364,6 +424,26 @@ void scale_add(const XYZZ<zkdev::Fq28>* A, const XYZZ<zkdev::Fq28>* B, const uin
                XYZZ<zkdev::Fq28>* tbl, XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st) {
     ZK_LAUNCH(zkdev::k_ct_scale_add<zkdev::Fq28>, dim3((n + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, A, B, scalars,
               stride_words, tbl, out, n);
+}
+
+void basis_gather(const zkdev::Affine<zkdev::Fq28>* tbl, const int32_t* idx, XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st) {
+    ZK_LAUNCH(zkdev::k_ct_gather_affine<zkdev::Fq28>, dim3((n + 127) / 128), dim3(128), 0, st, tbl, idx, out, n);
+}
+void basis_scale(const XYZZ<zkdev::Fq28>* A, const uint32_t* idx, const uint32_t* scalars, XYZZ<zkdev::Fq28>* tbl,
+                 XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st) {
+    ZK_LAUNCH(zkdev::k_ct_scale_rows<zkdev::Fq28>, dim3((n + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, A, idx, scalars, tbl,
+              out, n);
+}
+void basis_dft_stage(const XYZZ<zkdev::Fq28>* in, XYZZ<zkdev::Fq28>* out, const uint32_t* tw, XYZZ<zkdev::Fq28>* tbl, uint32_t log_n,
+                     uint32_t log_half, hipStream_t st) {
+    const uint32_t n = 1u << (log_n - 1);   // butterflies
+    ZK_LAUNCH(zkdev::k_ct_dft_stage<zkdev::Fq28>, dim3((n + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, in, out, tw, tbl,
+              log_n, log_half);
+}
+void basis_segment_sums(const XYZZ<zkdev::Fq28>* base, const XYZZ<zkdev::Fq28>* terms, const uint32_t* ptr, XYZZ<zkdev::Fq28>* out,
+                        uint32_t n, hipStream_t st) {
+    ZK_LAUNCH(zkdev::k_ct_segment_sums<zkdev::Fq28>, dim3((n + CT_THIN - 1) / CT_THIN), dim3(CT_THIN * COOP_W), 0, st, base, terms, ptr,
+              out, n);
 }
 
 #define ZK_COOP_TAIL_INSTANTIATE(F)                                                                                                   \

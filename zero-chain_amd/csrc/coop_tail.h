@@ -55,4 +55,19 @@ void upper(const zkdev::XYZZ<F>* S, uint32_t s_stride, const zkdev::XYZZ<F>* W, 
 void scale_add(const zkdev::XYZZ<zkdev::Fq28>* A, const zkdev::XYZZ<zkdev::Fq28>* B, const uint32_t* scalars, uint32_t stride_words,
                zkdev::XYZZ<zkdev::Fq28>* tbl, zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);
 
+// The derived bases of a (key, circuit) pair (zkamd.cpp ensure_derived): group transforms of the key's H query, built once.
+// One row per point; `tbl` is 15 n points of scratch as for scale_add.
+//   basis_gather        out[i] = tbl[idx[i]] (affine table entry) as an XYZZ point, the identity where idx[i] < 0
+//   basis_scale         out[i] = s_i A[idx ? idx[i] : i], scalars eight plain words each
+//   basis_dft_stage     one decimation-in-time stage (pairs 2^log_half apart) of a size-2^log_n transform, in -> out;
+//                       tw[e] = w^e for e < 2^(log_n - 1), plain words
+//   basis_segment_sums  out[i] = base[i] + sum of terms[ptr[i] .. ptr[i + 1])
+void basis_gather(const zkdev::Affine<zkdev::Fq28>* tbl, const int32_t* idx, zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);
+void basis_scale(const zkdev::XYZZ<zkdev::Fq28>* A, const uint32_t* idx, const uint32_t* scalars, zkdev::XYZZ<zkdev::Fq28>* tbl,
+                 zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);
+void basis_dft_stage(const zkdev::XYZZ<zkdev::Fq28>* in, zkdev::XYZZ<zkdev::Fq28>* out, const uint32_t* tw, zkdev::XYZZ<zkdev::Fq28>* tbl,
+                     uint32_t log_n, uint32_t log_half, hipStream_t st);
+void basis_segment_sums(const zkdev::XYZZ<zkdev::Fq28>* base, const zkdev::XYZZ<zkdev::Fq28>* terms, const uint32_t* ptr,
+                        zkdev::XYZZ<zkdev::Fq28>* out, uint32_t n, hipStream_t st);
+
 }  // namespace zkcoop

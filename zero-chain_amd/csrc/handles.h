@@ -10,6 +10,7 @@
 struct zk_r1cs {
     int device = 0;
     uint32_t n_in = 0, n_aux = 0, n_con = 0;
+    uint64_t id = 0;   // one per loaded system (a lane's clone keeps it): what a key's derived bases are bound to
     zkrt::DevBuf row_ptr[3], col[3], coeff[3];
     std::vector<uint8_t> a_aux_density, b_input_density, b_aux_density;
     // host copy of the matrices (the parameter generator transposes them): CSR, Montgomery coefficients

@@ -203,6 +203,10 @@ struct MsmGroup {
     zk_status finish_build(bool checked, const char* what, bool with_table);
     zk_status build(const std::vector<HAffine>& pts, uint32_t c_, bool checked, const char* what, bool with_table = true);
 
+    // A derived base set: slice 0 = [pts | entries [from, from + count) of slice 0 of `o`], then the table of doublings.  A point
+    // at infinity among pts stays (0, 0) through the table, as in a key file: the caller maps it out.
+    zk_status build_with_tail(const std::vector<HAffine>& pts, const MsmGroup& o, size_t from, size_t count, uint32_t c_);
+
     // jobs[i].pair_base is filled in here.  Everything, including the copy of the results (one XYZZ
     // per job) into `out`, is enqueued on `st`; collect() waits for it.
     zk_status enqueue(std::vector<MsmJob>& jobs, std::vector<HPoint>& out, hipStream_t st, bool to_host = true);

@@ -97,6 +97,28 @@ zk_status MsmGroup<HF, DF>::build(const std::vector<typename MsmGroup<HF, DF>::H
     return finish_build(checked, what, with_table);
 }
 
+template <class HF, class DF>
+zk_status MsmGroup<HF, DF>::build_with_tail(const std::vector<typename MsmGroup<HF, DF>::HAffine>& pts, const MsmGroup& o, size_t from,
+                                            size_t count, uint32_t c_) {
+    if (from + count > o.n_points) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: tail outside the borrowed table");
+    ZK_TRY(set_geometry(c_, pts.size() + count, true));
+    table.is_public = true;   // images of a key's bases under public maps
+    ZK_TRY(table.ensure(bytes ? bytes : 1));
+    if (!pts.empty()) {
+        DevBuf stage;
+        stage.is_public = true;
+        ZK_TRY(stage.ensure(sizeof(HAffine) * pts.size()));
+        HIP_TRY(hipMemcpy(stage.p, pts.data(), sizeof(HAffine) * pts.size(), hipMemcpyHostToDevice));
+        ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3((unsigned)((pts.size() + 127) / 128)), dim3(128), 0, g_stream,
+                  (const uint32_t*)stage.as<uint32_t>(), table.as<DAffine>(), (uint32_t)pts.size());
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(g_stream));
+    }
+    if (count)
+        HIP_TRY(hipMemcpy(table.as<DAffine>() + pts.size(), o.table.template as<DAffine>() + from, sizeof(DAffine) * count, hipMemcpyDeviceToDevice));
+    return finish_build(false, "derived bases", true);
+}
+
 // One launch set: plan (msm_plan.h: every decision about its shape, nothing enqueued before a refusal), then the stages
 // below in this order.
 template <class HF, class DF>

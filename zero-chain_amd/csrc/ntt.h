@@ -192,6 +192,8 @@ k_ntt_pass(uint32_t* data, const uint32_t* __restrict__ src, const uint32_t* __r
 // coefficient by coefficient - for ANY a, b, c, satisfied constraints or not: the same vector as bellman's, one
 // transform of size m less (6 instead of 7).  The coefficients of c come out of its inverse transform scaled by
 // 1 / (m (g^m - 1)) (NttPlan sc_*) and are subtracted in the store of the last pass (k_ntt_pass `minus`).
+// Over the derived bases of a (key, circuit) pair the product IS the scalar: `zinv` then points at the plain words of
+// 1 / (g^m - 1), the result leaves Montgomery form in the same multiplication and no transform follows (prove_chunk).
 static __global__ void __launch_bounds__(256)
 k_h_pointwise(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
               const uint32_t* __restrict__ zinv, uint32_t* out, uint32_t m, uint32_t out_stride, size_t count) {
@@ -323,10 +325,13 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 //                fold != 0 appends [ s * z (nv) | s | r * s ] over the bases of the A query, alpha_1 and delta_1: the job is
 //                then C = s * A + C' itself (A = alpha_1 + sum z_i A_i + r delta_1) - for a few proofs made alone, whose
 //                final fold would otherwise be a 255-bit double-and-add chain on the critical path (zkamd.cpp prove_chunk)
+//                in_tail != 0 appends [ inputs (n_in) ] at that position: the job over the derived bases of a (key, circuit)
+//                pair, whose input variables carry the c part of H (zkamd.cpp ensure_derived)
 // tail[p] = (1, r, s).  Witness scalars are converted out of Montgomery form when `mont` is set.
 static __global__ void __launch_bounds__(256)
 k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ wit, const uint32_t* __restrict__ tail,
-                uint32_t nv, uint32_t n_in, uint32_t m, uint32_t cstride, uint32_t mont, uint32_t* bad, uint32_t fold) {
+                uint32_t nv, uint32_t n_in, uint32_t m, uint32_t cstride, uint32_t mont, uint32_t* bad, uint32_t fold,
+                uint32_t in_tail = 0) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= nv + 3) return;
     const size_t p = blockIdx.y;
@@ -354,6 +359,7 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
         if (i >= n_in) st_fr(cv + (size_t)(m + (i - n_in)) * 8, v);
         st_fr(cv + (size_t)(m + n_aux + i) * 8, rz);
         if (fold) st_fr(cv + (size_t)(m + n_aux + nv + 1 + i) * 8, mul(v, sR));   // (z)(s R) / R = z s
+        if (in_tail && i < n_in) st_fr(cv + (size_t)(in_tail + i) * 8, v);
     } else {
         v = ld_fr(tail + (p * 3 + (i - nv)) * 8);
         if (i == nv) st_fr(cv + (size_t)(m + n_aux + nv) * 8, r);   // r * 1 for beta_1

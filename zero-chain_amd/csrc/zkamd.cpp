@@ -65,7 +65,8 @@ struct NttPlan {
     DevBuf s1_plain, s1_mont, s2;    // prover tables, bit-reversed order (see prove_chunk)
     DevBuf sc_plain, sc_mont;        // constant 1 / (n (g^n - 1)): the scaling of c's coefficients (k_h_pointwise)
     DevBuf coset_fwd, coset_inv;     // g^i and g^-i / n, natural order (Montgomery)
-    DevBuf consts;                   // [0] = 1/n, [1] = 1/(g^n - 1)   (Montgomery)
+    DevBuf consts;                   // [0] = 1/n, [1] = 1/(g^n - 1)   (Montgomery), [2] = 1/(g^n - 1) in plain words
+    Fr w_inv;                        // w^-1 (Montgomery): the transforms of the derived bases make their own table of it
     DevBuf scratch;                  // permutation scratch for the stand-alone entry
     size_t bytes = 0;
 
@@ -174,8 +175,9 @@ struct NttPlan {
         Fr gn = g;
         for (uint32_t i = 0; i < k; i++) gn = gn.sqr();
         Fr zinv = zkhost::fr_inv(gn - Fr::one());   // divide_by_z_on_coset
-        Fr cs[2] = {ninv, zinv};
-        ZK_TRY(upload_fr(consts, cs, 2));
+        Fr cs[3] = {ninv, zinv, zinv.from_mont()};
+        ZK_TRY(upload_fr(consts, cs, 3));
+        w_inv = winv;
         ZK_TRY(pow_table(tw_fwd, w, Fr::one(), 0, 0, n / 2));
         ZK_TRY(pow_table(tw_inv, winv, Fr::one(), 0, 0, n / 2));
         // after the first inverse transform: * g^i / n, and lift the (plain or Montgomery) input
@@ -306,6 +308,19 @@ struct zk_params {
     // instead of 2048 (c = 10 against the throughput optimum 13) cut a lone proof from 3.54 to 3.16 ms
     MsmG2 g2_lone;
     NttPlan ntt;
+    // The derived bases of this key and ONE circuit (ensure_derived): the H query on the coset-Lagrange basis with the c part
+    // of H folded into the bases of the variables.  g1d = [G' (m) | D (inputs, aux) | a | alpha_1 | delta_1 | b_g1 | beta_1]
+    // with its own table of doublings; g1d_lone = the same table under the width of a few proofs made alone.
+    struct Derived {
+        bool ready = false;
+        uint64_t circuit = 0;       // zk_r1cs::id it was built for
+        uint32_t serial = 0;        // changes with every build: part of the key of the cached maps
+        uint32_t off_a = 0, off_b1 = 0;
+        std::vector<int32_t> pos;   // [G' | D]: position in slice 0, or -1 for a base that came out as the identity
+        double bind_ms = 0;
+    } drv;
+    MsmG1 g1d, g1d_lone;
+    DevBuf map_cd, map_cfd;         // map_c / map_cf over the derived bases
     // cached per-circuit index maps (keyed by the density bytes)
     std::vector<uint8_t> dens_key;
     DevBuf map_a, map_b2, map_c, map_cf;   // (map_cf: the C job with the fold s * A inside, for a few proofs made alone)
@@ -523,6 +538,11 @@ zk_params* params_clone_for_lane(const zk_params* P) {
     Q->g2.c = P->g2.c; Q->g2.maxd = P->g2.maxd; Q->g2.nb = P->g2.nb; Q->g2.n_points = P->g2.n_points;
     Q->g2.table.borrow(P->g2.table);
     Q->g2_lone.alias(P->g2, P->g2_lone.c);
+    if (P->drv.ready) {
+        Q->drv = P->drv;
+        Q->g1d.alias(P->g1d, P->g1d.c);
+        Q->g1d_lone.alias(P->g1d, P->g1d_lone.c);
+    }
     Q->ntt.log_n = P->ntt.log_n;
     Q->ntt.n = P->ntt.n;
     Q->ntt.tw_fwd.borrow(P->ntt.tw_fwd);
@@ -544,6 +564,7 @@ zk_r1cs* r1cs_clone_for_lane(const zk_r1cs* R) {
     zk_r1cs* Q = new (std::nothrow) zk_r1cs();
     if (!Q) return nullptr;
     Q->device = R->device;
+    Q->id = R->id;
     Q->n_in = R->n_in; Q->n_aux = R->n_aux; Q->n_con = R->n_con;
     for (int m = 0; m < 3; m++) {
         Q->row_ptr[m].borrow(R->row_ptr[m]);
@@ -566,6 +587,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     key.insert(key.end(), a_aux_d, a_aux_d + n_aux);
     key.insert(key.end(), b_in_d, b_in_d + n_in);
     key.insert(key.end(), b_aux_d, b_aux_d + n_aux);
+    for (int i = 0; i < 4; i++) key.push_back((uint8_t)((P->drv.ready ? P->drv.serial : 0u) >> (8 * i)));
     if (key == P->dens_key) return ZK_OK;
     const uint32_t nv = n_in + n_aux;
     // scalar layout per proof: [inputs | aux | 1 | r | s]
@@ -609,6 +631,26 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     // the folded form of the job (ntt.h k_build_scalars, fold): + [s z (nv) | s | r s] over the A query, alpha_1, delta_1
     std::vector<int32_t> mcf(mc);
     for (uint32_t i = 0; i < nv + 2; i++) mcf.push_back(ma[i] < 0 ? -1 : (int32_t)(P->off_a + ma[i]));
+    if (P->drv.ready && P->drv.pos.size() == P->m + nv) {
+        // the same job over the derived bases: [u (m, natural order) | aux | r z | r | fold | inputs (n_in)]
+        const zk_params::Derived& D = P->drv;
+        std::vector<int32_t> md;
+        md.reserve(mcf.size() + n_in);
+        for (size_t j = 0; j < P->m; j++) md.push_back(D.pos[j]);
+        for (uint32_t j = 0; j < n_aux; j++) md.push_back(D.pos[P->m + n_in + j]);
+        for (uint32_t i = 0; i < nv; i++) md.push_back(mb1[i] < 0 ? -1 : (int32_t)(D.off_b1 + mb1[i]));
+        md.push_back(P->beta_g1_inf ? -1 : (int32_t)(D.off_b1 + P->n_b1));
+        std::vector<int32_t> mdf(md);
+        for (uint32_t i = 0; i < nv + 2; i++) mdf.push_back(ma[i] < 0 ? -1 : (int32_t)(D.off_a + ma[i]));
+        for (uint32_t i = 0; i < n_in; i++) {
+            md.push_back(D.pos[P->m + i]);
+            mdf.push_back(D.pos[P->m + i]);
+        }
+        ZK_TRY(P->map_cd.ensure(md.size() * 4));
+        ZK_TRY(P->map_cfd.ensure(mdf.size() * 4));
+        HIP_TRY(hipMemcpy(P->map_cd.p, md.data(), md.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(P->map_cfd.p, mdf.data(), mdf.size() * 4, hipMemcpyHostToDevice));
+    }
     ZK_TRY(P->map_cf.ensure(mcf.size() * 4));
     HIP_TRY(hipMemcpy(P->map_cf.p, mcf.data(), mcf.size() * 4, hipMemcpyHostToDevice));
     ZK_TRY(P->map_a.ensure(ma.size() * 4));
@@ -629,7 +671,9 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // (prove_chunk: the fold and the three into_affine run on the GPU, k_ct_scale_add /
 // k_xyzz_normalize_export; the host encodes the 192 bytes.)
 
-zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out) {
+// derived: a, b are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over the
+// derived bases (ensure_derived); c is not read.
+zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
     const auto t_begin = std::chrono::steady_clock::now();
     const uint32_t n_in = bt->n_inputs, n_aux = bt->n_aux, nv = n_in + n_aux, n_rows = bt->n_rows;
     const size_t m = P->m;
@@ -667,12 +711,13 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     // (read at every chunk: the emulation suite sends small batches through the chunk form of the fold)
     const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
     const bool fold_in_msm = np <= fold_max;
-    const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0));
+    const uint32_t in_tail = derived ? (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0)) : 0u;   // (the inputs carry their K_i)
+    const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0));
     ZK_TRY(P->cvec.ensure(np * (size_t)cstride * 32));
     uint32_t* cvec = P->cvec.as<uint32_t>();
     ZK_LAUNCH(zkdev::k_build_scalars, dim3((nv + 3 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
               (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), nv, n_in, (uint32_t)m, cstride,
-              mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u);
+              mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u, in_tail);
     // ---- multiexps (create_proof step 4).  The G2 job only needs the witness scalars: it is
     // enqueued first, on the side stream, and runs beside the H pipeline and the G1 multiexps (its
     // reduction tree is latency-bound with one job per proof; the G1 work fills the machine).
@@ -698,19 +743,19 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     if (host_norm) ZK_TRY(G2.export_to_host(G2.res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));
     else ZK_TRY(G2.normalize_to_host(G2.res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));   // B in affine form
     // ---- H pipeline (create_proof step 3)
-    ZK_TRY(P->abc.ensure(3 * np * m * 32));
+    ZK_TRY(P->abc.ensure((derived ? 2 : 3) * np * m * 32));
     uint32_t* A = P->abc.as<uint32_t>();
     uint32_t* B = A + np * m * 8;
     uint32_t* C = B + np * m * 8;
     const uint32_t* s1 = mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
     const uint32_t* srcs[3] = {(const uint32_t*)bt->d_a + first * (size_t)n_rows * 8,
                                (const uint32_t*)bt->d_b + first * (size_t)n_rows * 8,
-                               (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
+                               derived ? nullptr : (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
     uint32_t* dsts[3] = {A, B, C};
     // ifft (natural -> bit-reversed) of a and b, then * g^i / m (coset shift); c: * 1 / (m (g^m - 1)), plain - its
     // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7)
     const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
-    for (int k = 0; k < 3; k++)
+    for (int k = 0; k < (derived ? 2 : 3); k++)
         ZK_TRY(P->ntt.chain(dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
     // coset fft (bit-reversed -> natural) of a and b at once
     ZK_TRY(P->ntt.chain(A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
@@ -718,12 +763,16 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
         ProfScope ps("h_pointwise");
         size_t count = np * m;
         ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
-                  (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
+                  (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + (derived ? 16 : 8), cvec, (uint32_t)m,
+                  cstride, count);
     }
+    // Over the derived bases a(x_j) b(x_j) / (g^m - 1) is the scalar of G'_j as it stands (plain, natural order) and c went
+    // into the bases of the variables: four transforms per proof.  Otherwise:
     // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
     // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
-    ZK_TRY(P->ntt.chain(cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
-                        (const uint32_t*)C, (uint32_t)m));
+    if (!derived)
+        ZK_TRY(P->ntt.chain(cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
+                            (const uint32_t*)C, (uint32_t)m));
     // A batch runs the two G1 jobs of its proofs as two launch sets, each under the recoding width of its own size: the
     // C' jobs (65 k terms) here on the main stream behind the H pipeline, the A jobs (15.6 k terms, witness scalars only)
     // on the side stream behind the G2 set.  A few proofs made alone keep
@@ -731,15 +780,21 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     // i mod 8 and the sort is one workgroup per job, so alternating A, C' would put every large job on the odd XCDs.
     const size_t split_min = getenv("ZKAMD_SPLIT_MIN") ? (size_t)atoll(getenv("ZKAMD_SPLIT_MIN")) : 64;   // tests: 1
     const bool split = np >= split_min;
-    MsmG1& G1C = split ? P->g1 : P->g1_lone;
+    MsmG1& G1C = derived ? (split ? P->g1d : P->g1d_lone) : (split ? P->g1 : P->g1_lone);
+    const int32_t* map_c = derived ? (fold_in_msm ? P->map_cfd : P->map_cd).as<int32_t>() : (fold_in_msm ? P->map_cf : P->map_c).as<int32_t>();
+    const uint32_t npts1c = (uint32_t)G1C.n_points;
     for (size_t p = 0; p < np; p++) {
-        MsmJob jc = {cvec + p * (size_t)cstride * 8, (fold_in_msm ? P->map_cf : P->map_c).as<int32_t>(), cstride, 0, npts1, 0, 0, 0};
+        MsmJob jc = {cvec + p * (size_t)cstride * 8, map_c, cstride, 0, npts1c, 0, 0, 0};
         P->jobs1.push_back(jc);
     }
     P->jobs1a.clear();
     for (size_t p = 0; p < np; p++) {
         const uint32_t* w = wit + p * wstride * 8;
         MsmJob ja = {w, P->map_a.as<int32_t>(), nv + 3, P->off_a, npts1, 0, 0, 0};
+        if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
+            ja.table_base = P->drv.off_a;
+            ja.n_table = npts1c;
+        }
         (split ? P->jobs1a : P->jobs1).push_back(ja);
     }
     typedef zkdev::XYZZ<zkdev::Fq> DP1;
@@ -826,7 +881,7 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     return ZK_OK;
 }
 
-zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const uint8_t* rs, uint8_t* proofs_out) {
+zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const uint8_t* rs, uint8_t* proofs_out, bool derived = false) {
     if (!P || !bt || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
     ZK_TRY(use_device(P->device));
@@ -836,7 +891,7 @@ zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const 
     if (bt->n_rows > P->m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     if (bt->n_inputs != P->n_ic) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "number of inputs differs from vk.ic");
     if (bt->n_aux != P->n_l) return fail(ZK_ERR_IO, "number of aux variables differs from the l query");
-    if (!bt->d_a || !bt->d_b || !bt->d_c || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
+    if (!bt->d_a || !bt->d_b || (!bt->d_c && !derived) || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
         return fail(ZK_ERR_ASSIGNMENT_MISSING, "assignment pointer is null");
     ZK_TRY(ensure_maps(P, bt->n_inputs, bt->n_aux, bt->a_aux_density, bt->b_input_density, bt->b_aux_density));
     // proofs per launch set: large chunks amortise the latency-bound tails (reduction trees, sorts);
@@ -846,7 +901,7 @@ zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const 
     if (env && atoi(env) > 0) chunk = (size_t)atoi(env);
     for (size_t first = 0; first < n; first += chunk) {
         size_t np = std::min(chunk, n - first);
-        ZK_TRY(prove_chunk(P, np, bt, first, rs, proofs_out));
+        ZK_TRY(prove_chunk(P, np, bt, first, rs, proofs_out, derived));
     }
     return ZK_OK;
 }
@@ -953,6 +1008,8 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
         ~Guard() { delete p; }
     } guard{R};
     R->device = device;
+    static std::atomic<uint64_t> next_id{1};
+    R->id = next_id++;
     R->n_in = n_in;
     R->n_aux = n_aux;
     R->n_con = n_con;
@@ -1009,16 +1066,147 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
     return ZK_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// Derived bases of a (key, circuit) pair: four transforms per proof instead of six
+// ------------------------------------------------------------------------------------------
+// With x_j = g w^j, u_j = a(x_j) b(x_j) / (g^m - 1) and c_k the k-th row evaluation of C, the h of ntt.h k_h_pointwise is
+//     h_t = p_t - c_t / (g^m - 1),   p = the coset interpolation of u,   c_t = the coefficients of c,
+// for ANY a, b, c, and bellman drops h_(m-1).  Both parts are linear in the scalars, so their transforms can be applied to
+// the BASES once instead of to the scalars of every proof.  With H_(m-1) := the identity (the truncation),
+//     sum_t p_t H_t = sum_j u_j G'_j,         G'_j = (1/m) sum_t (g w^j)^-t H_t
+//     sum_t c_t H_t / (g^m - 1) = sum_k c_k L''_k,   L''_k = 1 / (m (g^m - 1)) sum_t w^-kt H_t
+// - two inverse transforms "in the exponent" over the points g^-t H_t / m and H_t / (m (g^m - 1)).  When c_k = sum_i C_ki z_i
+// are the library's own row evaluations (k_r1cs_eval), the second sum is sum_i z_i K_i with K_i = sum_k C_ki L''_k, and
+//     C' = sum_j u_j G'_j + sum_aux z_i (L_i - K_i) - sum_inputs z_i K_i + r (beta_1 + sum B1):
+// the terms of today's job plus one per input, no c, no transform after the pointwise product.  Exact for every assignment,
+// satisfying or not; nothing assumes that Z divides a b - c.
+//
+// Built on the GPU, one row of lanes per point (coop_tail.h basis_*): a scaling pass and log2 m butterfly stages per
+// transform, every butterfly one 255-bit scalar product; the K_i as one scalar product per entry of C summed per
+// column.  The set goes through into_affine and the same table of doublings as a key's bases (MsmGroup::build_with_tail);
+// a base that comes out as the identity - K_i of an input that C never mentions - is mapped out like an identity in a key
+// file.  Nothing happens when the pair cannot have one (a lane's clone, another circuit's shape): the caller then keeps the
+// six-transform form.
+zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
+    if (P->drv.ready && P->drv.circuit == R->id) return ZK_OK;
+    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, k = P->log_m;
+    const size_t m = P->m;
+    if (!P->g1.table.owned || R->h_row_ptr[2].size() != (size_t)n_con + 1 || n_in != P->n_ic || n_aux != P->n_l ||
+        (size_t)n_con + n_in > m || P->n_h + 1 != m)
+        return ZK_OK;
+    ZK_TRY(use_device(P->device));
+    const auto t0 = std::chrono::steady_clock::now();
+    typedef zkdev::XYZZ<zkdev::Fq> DP;
+    typedef zkdev::Affine<zkdev::Fq> DA;
+    P->drv.ready = false;
+    const DA* key = P->g1.table.as<DA>();
+    // C by columns, every coefficient negated (the variables carry - K_i) and in plain words
+    const std::vector<uint32_t>& rp = R->h_row_ptr[2];
+    const std::vector<uint32_t>& cl = R->h_col[2];
+    const uint32_t nnz = rp[n_con];
+    std::vector<uint32_t> ptr(nv + 1, 0), t_row(nnz ? nnz : 1);
+    std::vector<Fr> t_s(nnz ? nnz : 1);
+    for (uint32_t e = 0; e < nnz; e++) ptr[cl[e] + 1]++;
+    for (uint32_t i = 0; i < nv; i++) ptr[i + 1] += ptr[i];
+    {
+        std::vector<uint32_t> at(ptr.begin(), ptr.end() - 1);
+        for (uint32_t row = 0; row < n_con; row++)
+            for (uint32_t e = rp[row]; e < rp[row + 1]; e++) {
+                const uint32_t slot = at[cl[e]]++;
+                t_row[slot] = row;
+                t_s[slot] = (-R->h_coeff[2][e]).from_mont();
+            }
+    }
+    // H in bit-reversed order with the identity in the place of H_(m-1); the L query behind the (empty) inputs
+    std::vector<int32_t> idx(m + nv);
+    for (size_t pos = 0; pos < m; pos++) {
+        const uint32_t e = k ? (__builtin_bitreverse32((uint32_t)pos) >> (32 - k)) : 0;
+        idx[pos] = e < P->n_h ? (int32_t)(P->off_h + e) : -1;
+    }
+    for (uint32_t i = 0; i < nv; i++) idx[m + i] = i < n_in ? -1 : (int32_t)(P->off_l + (i - n_in));
+    const size_t rows = std::max<size_t>(m, nnz);
+    DevBuf d_idx, d_ptr, d_row, d_s, d_tw, d_w, src, ping, pong, lam, terms, tbl, all, stage;
+    for (DevBuf* b : {&d_idx, &d_ptr, &d_row, &d_s, &d_tw, &d_w, &src, &ping, &pong, &lam, &terms, &tbl, &all, &stage}) b->is_public = true;
+    ZK_TRY(d_idx.ensure(idx.size() * 4));
+    ZK_TRY(d_ptr.ensure(ptr.size() * 4));
+    ZK_TRY(d_row.ensure(t_row.size() * 4));
+    ZK_TRY(d_s.ensure(t_s.size() * 32));
+    ZK_TRY(d_tw.ensure(m * 32));
+    ZK_TRY(d_w.ensure(64));
+    ZK_TRY(src.ensure((m + nv) * sizeof(DP)));
+    ZK_TRY(ping.ensure(m * sizeof(DP)));
+    ZK_TRY(pong.ensure(m * sizeof(DP)));
+    ZK_TRY(lam.ensure(m * sizeof(DP)));
+    ZK_TRY(terms.ensure((nnz ? nnz : 1) * sizeof(DP)));
+    ZK_TRY(tbl.ensure(15 * rows * sizeof(DP)));
+    ZK_TRY(all.ensure((m + nv) * sizeof(DP)));
+    HIP_TRY(hipMemcpy(d_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_ptr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_row.p, t_row.data(), t_row.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_s.p, t_s.data(), t_s.size() * 32, hipMemcpyHostToDevice));
+    const Fr wv[2] = {P->ntt.w_inv, Fr::one()};
+    HIP_TRY(hipMemcpy(d_w.p, wv, 64, hipMemcpyHostToDevice));
+    // w^-e for e < m / 2 in plain words
+    ZK_LAUNCH(zkdev::k_fr_pow_table, dim3((unsigned)((m / 2 + 255) / 256)), dim3(256), 0, g_stream, d_tw.as<uint32_t>(),
+              (const uint32_t*)d_w.as<uint32_t>(), (const uint32_t*)d_w.as<uint32_t>() + 8, k, 0u, 1u, (uint32_t)(m / 2));
+    zkcoop::basis_gather(key, d_idx.as<int32_t>(), src.as<DP>(), (uint32_t)(m + nv), g_stream);
+    // in: the scaled points in bit-reversed order; out: the transform in natural order
+    auto transform = [&](const uint32_t* scale, DP* out) -> zk_status {
+        DP *a = ping.as<DP>(), *b = pong.as<DP>();
+        zkcoop::basis_scale(src.as<DP>(), nullptr, scale, tbl.as<DP>(), a, (uint32_t)m, g_stream);
+        for (uint32_t st = 0; st < k; st++) {
+            zkcoop::basis_dft_stage(a, st + 1 == k ? out : b, d_tw.as<uint32_t>(), tbl.as<DP>(), k, st, g_stream);
+            std::swap(a, b);
+        }
+        HIP_TRY(hipGetLastError());
+        return ZK_OK;
+    };
+    ZK_TRY(transform(P->ntt.s2.as<uint32_t>(), all.as<DP>()));        // g^-t / m
+    ZK_TRY(transform(P->ntt.sc_mont.as<uint32_t>(), lam.as<DP>()));   // 1 / (m (g^m - 1))
+    if (nnz) zkcoop::basis_scale(lam.as<DP>(), d_row.as<uint32_t>(), d_s.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), nnz, g_stream);
+    zkcoop::basis_segment_sums(src.as<DP>() + m, terms.as<DP>(), d_ptr.as<uint32_t>(), all.as<DP>() + m, nv, g_stream);
+    HIP_TRY(hipGetLastError());
+    std::vector<HG1> host(m + nv);
+    ZK_TRY(P->g1.normalize_to_host(all.as<DP>(), m + nv, host.data(), stage, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    std::vector<HG1A> pts(m + nv);
+    P->drv.pos.assign(m + nv, -1);
+    for (size_t i = 0; i < m + nv; i++) {
+        pts[i] = host[i].is_inf() ? HG1A::inf() : HG1A{host[i].x, host[i].y};
+        if (!host[i].is_inf()) P->drv.pos[i] = (int32_t)i;
+    }
+    ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, P->g1.c));
+    P->g1d_lone.alias(P->g1d, P->g1_lone.c);
+    P->drv.off_a = (uint32_t)(m + nv);
+    P->drv.off_b1 = P->drv.off_a + P->n_a + 2;
+    P->drv.circuit = R->id;
+    static std::atomic<uint32_t> serial{1};
+    P->drv.serial = serial++;
+    P->drv.bind_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    P->drv.ready = true;
+    if (getenv("ZKAMD_TRACE_HOST"))
+        fprintf(stderr, "[zkamd] derived bases: %zu + %u points, %u entries of C, %.1f ms, table %.2f GB\n", m, nv, nnz, P->drv.bind_ms,
+                (double)P->g1d.bytes / 1e9);
+    return ZK_OK;
+}
+
 // row evaluations + create_proof of the np assignments in R->z[slot] (Montgomery form)
-zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out) {
+// derived: the caller is one of the statement-to-proof entries, which take the four-transform form over the derived bases
+// of the pair (built here the first time); zk_prove_batch_witness keeps the key's own bases
+zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
     const uint32_t nv = R->n_in + R->n_aux, n_rows = R->n_con + R->n_in;
-    ZK_TRY(R->abc.ensure(3 * np * (size_t)n_rows * 32));
+    if (derived) {
+        ZK_TRY(ensure_derived(P, R));
+        derived = P->drv.ready && P->drv.circuit == R->id;
+    }
+    ZK_TRY(R->abc.ensure((derived ? 2 : 3) * np * (size_t)n_rows * 32));
     zkdev::R1csMat mm[3];
     for (int m = 0; m < 3; m++)
         mm[m] = zkdev::R1csMat{R->row_ptr[m].as<uint32_t>(), R->col[m].as<uint32_t>(), R->coeff[m].as<uint32_t>()};
     {
         ProfScope ps("r1cs_eval");
-        ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, 3, (unsigned)np), dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
+        ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, derived ? 2 : 3, (unsigned)np),   // (no rows of C over the derived bases)
+                  dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
                   (const uint32_t*)R->z[slot].as<uint32_t>(), R->abc.as<uint32_t>(), R->n_con, R->n_in, nv, n_rows,
                   np * (size_t)n_rows);
     }
@@ -1030,12 +1218,12 @@ zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint
     bt.flags = ZK_FR_MONTGOMERY;
     bt.d_a = R->abc.as<uint32_t>();
     bt.d_b = R->abc.as<uint32_t>() + np * (size_t)n_rows * 8;
-    bt.d_c = R->abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
+    bt.d_c = derived ? nullptr : R->abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
     bt.d_wit = R->z[slot].p;
     bt.a_aux_density = R->a_aux_density.data();
     bt.b_input_density = R->b_input_density.data();
     bt.b_aux_density = R->b_aux_density.data();
-    return prove_batch_dev(P, np, &bt, rs, proofs_out);
+    return prove_batch_dev(P, np, &bt, rs, proofs_out, derived);
 }
 
 size_t batch_chunk() {
@@ -1046,7 +1234,7 @@ size_t batch_chunk() {
 }
 
 zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t* witness, uint32_t flags, const uint8_t* rs,
-                              uint8_t* proofs_out) {
+                              uint8_t* proofs_out, bool derived) {
     if (!P || !R || !witness || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
     if (R->device != P->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
@@ -1065,7 +1253,7 @@ zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t*
             ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, R->z[0].as<uint32_t>(),
                       (const uint32_t*)R->z[0].as<uint32_t>(), 0u, cnt, P->bad.as<uint32_t>() + 1);
         }
-        ZK_TRY(prove_from_z(P, R, np, 0, rs + first * 64, proofs_out + first * 192));
+        ZK_TRY(prove_from_z(P, R, np, 0, rs + first * 64, proofs_out + first * 192, derived));
         if (P->pin_bad.as<uint32_t>()[1] & zkdev::ZK_BAD_SCALAR)
             return fail(ZK_ERR_INVALID_ARGUMENT, "a witness scalar is not a canonical field element (>= r)");
     }
@@ -1566,7 +1754,7 @@ zk_status ntt_run_dev(zk_ntt* T, void* d_data, uint32_t batch, uint32_t flags) {
 // what the wallet-level entries (wallet.cpp: gen_proof, the Jubjub host side) need of this translation unit
 namespace zkrt {
 zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out) {
-    return prove_from_z(P, R, np, slot, rs, proofs_out);
+    return prove_from_z(P, R, np, slot, rs, proofs_out, true);
 }
 size_t lib_batch_chunk() { return batch_chunk(); }
 bool lib_witness_on_host(size_t n) { return witness_on_host(n); }
@@ -1731,8 +1919,22 @@ zk_status zk_anonymous_r1cs_load(int device, zk_r1cs** out) try {
 } ZK_ABI_CATCH
 zk_status zk_prove_batch_witness(zk_params* p, zk_r1cs* circuit, size_t n, const uint8_t* witness, uint32_t flags,
                                  const uint8_t* rs, uint8_t* proofs_out) try {
-    return prove_batch_witness(p, circuit, n, witness, flags, rs, proofs_out);
+    return prove_batch_witness(p, circuit, n, witness, flags, rs, proofs_out, false);   // (a caller's witness: the key's own bases)
 } ZK_ABI_CATCH
+#ifdef ZK_TEST_HOOKS
+// Test hook, NOT part of the ABI (absent from libzkamd.so): zk_prove_batch_witness on the route of the statement-to-proof
+// entries - the four-transform form over the derived bases of (p, circuit) - for circuits that have no statement form.
+// info[0] = whether the pair has a derived set after the call, info[1] = how many of its bases are the identity (mapped out).
+zk_status zk_hook_prove_batch_witness_derived(zk_params* p, zk_r1cs* circuit, size_t n, const uint8_t* witness, uint32_t flags,
+                                              const uint8_t* rs, uint8_t* proofs_out, uint32_t info[2]) try {
+    const zk_status rc = prove_batch_witness(p, circuit, n, witness, flags, rs, proofs_out, true);
+    if (info && p && circuit) {
+        info[0] = p->drv.ready && p->drv.circuit == circuit->id ? 1u : 0u;
+        info[1] = (uint32_t)std::count(p->drv.pos.begin(), p->drv.pos.end(), -1);
+    }
+    return rc;
+} ZK_ABI_CATCH
+#endif
 
 zk_status zk_transfer_witness(const zk_transfer_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
     return transfer_witness(st, n, flags, witness_out);
@@ -1762,7 +1964,7 @@ zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, cons
             const size_t np = std::min(chunk, n - first), next = first + chunk;
             ZK_TRY(witness_gpu_finish(circuit, np, slot, first));
             if (next < n) ZK_TRY(witness_gpu_enqueue(circuit, st + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream));
-            ZK_TRY(prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192));
+            ZK_TRY(prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192, true));
             slot ^= 1;
         }
         return ZK_OK;
@@ -1787,7 +1989,7 @@ zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, cons
                 next_rc = transfer_witness(st + next, std::min(chunk, n - next), ZK_FR_MONTGOMERY, buf[cur ^ 1], next);
                 if (next_rc != ZK_OK) next_err = g_err;   // g_err is thread-local
             });
-        rc = prove_batch_witness(p, circuit, np, buf[cur], ZK_FR_MONTGOMERY, rs + first * 64, proofs_out + first * 192);
+        rc = prove_batch_witness(p, circuit, np, buf[cur], ZK_FR_MONTGOMERY, rs + first * 64, proofs_out + first * 192, true);
         producer.join();
         if (rc != ZK_OK) return rc;
         if (next_rc != ZK_OK) return fail(next_rc, next_err);
@@ -1821,7 +2023,7 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
             const size_t np = std::min(chunk, n - first), next = first + chunk;
             rc = witness_anon_gpu_finish(circuit, np, slot, first);
             if (rc == ZK_OK && next < n) rc = witness_anon_gpu_enqueue(circuit, st + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream, next);
-            if (rc == ZK_OK) rc = prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192);
+            if (rc == ZK_OK) rc = prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192, true);
             slot ^= 1;
         }
         if (rc != ZK_OK) {
@@ -1856,7 +2058,7 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
         zk_status rc = ZK_OK;
         for (size_t off = 0; off < np && rc == ZK_OK; off += chunk)
             rc = prove_batch_witness(p, circuit, std::min(chunk, np - off), buf[cur] + off * nv * 32, ZK_FR_MONTGOMERY,
-                                     rs + (first + off) * 64, proofs_out + (first + off) * 192);
+                                     rs + (first + off) * 64, proofs_out + (first + off) * 192, true);
         producer.join();
         if (rc != ZK_OK) return rc;
         if (next_rc != ZK_OK) return fail(next_rc, next_err);
@@ -2043,7 +2245,7 @@ struct zk_pipeline {
             zk_status rc_next = ZK_OK;
             if (have_nxt && !skip && rc == ZK_OK) rc_next = start(nxt, cur.slot ^ 1);
             if (!skip && rc == ZK_OK) rc = guarded([&] { return witness_gpu_finish(Rw, cur.n, cur.slot, cur.index_base); });
-            if (!skip && rc == ZK_OK) rc = guarded([&] { return prove_from_z(Pw, Rw, cur.n, cur.slot, cur.rs, cur.out); });
+            if (!skip && rc == ZK_OK) rc = guarded([&] { return prove_from_z(Pw, Rw, cur.n, cur.slot, cur.rs, cur.out, true); });
             // nothing of a failed job stays in flight when wait() returns: drain the device BEFORE the job is counted done
             if (rc != ZK_OK || rc_next != ZK_OK) (void)hipDeviceSynchronize();
             if (lane > 0 && (rc == ZK_ERR_OUT_OF_MEMORY || rc_next == ZK_ERR_OUT_OF_MEMORY)) {
@@ -2100,7 +2302,7 @@ struct zk_pipeline {
                 skip = err != ZK_OK;
             }
             zk_status rc = ZK_OK;
-            if (!skip) rc = guarded([&] { return prove_batch_witness(P, R, j.n, buf[j.slot].as<uint8_t>(), ZK_FR_MONTGOMERY, j.rs, j.out); });
+            if (!skip) rc = guarded([&] { return prove_batch_witness(P, R, j.n, buf[j.slot].as<uint8_t>(), ZK_FR_MONTGOMERY, j.rs, j.out, true); });
             std::lock_guard<std::mutex> lk(mu);
             if (rc != ZK_OK) fail_with(rc, g_err);
             slot_free[j.slot] = true;
@@ -2131,6 +2333,14 @@ zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) 
         return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     }
     (void)zkwit::tables();
+    {
+        // the derived bases of the pair before the lanes borrow the key's tables: every lane binds to the same set
+        const zk_status rc = ensure_derived(p, circuit);
+        if (rc != ZK_OK) {
+            delete L;
+            return rc;
+        }
+    }
     if (!witness_on_host()) {
         int lanes = 2;
         if (const char* env = getenv("ZKAMD_PIPELINE_LANES")) lanes = atoi(env);
