@@ -37,6 +37,7 @@
  * counterpart in the reference (why it exists is said at the declaration).
  *   zk_params_load, zk_params_free  Parameters::read(reader, checked)             core/proofs/src/confidential.rs:99
  *   zk_params_get_info, zk_params_get_windows   - (fields of Parameters: lengths of the queries; the recoding widths chosen here)
+ *   zk_params_get_merged            - (equal points inside the a, b_g1 and b_g2 queries: terms the multiexps do not add twice)
  *   zk_params_write_vk              Parameters.vk, the input of prepare_verifying_key   core/proofs/src/setup.rs:31, 62
  *   zk_prove / zk_prove_batch       create_random_proof -> create_proof           confidential.rs:149, anonymous.rs:165
  *   zk_prove_batch_dev              the same, assignments already in HBM          confidential.rs:149
@@ -155,6 +156,9 @@ zk_status zk_params_get_info(const zk_params* p, zk_params_info* info);
 /* The recoding widths in use: out[0] = the C' jobs (H + L + r B1) of a batch, out[1] = its A jobs, out[2] = both G1 jobs
  * of a few proofs made alone (one launch set), out[3] = the G2 job (B2).  zk_params_info.window_bits is out[0]. */
 zk_status zk_params_get_windows(const zk_params* p, uint32_t out[4]);
+/* Entries minus distinct points of the a, b_g1 and b_g2 queries (out[0..2]): variables with identical QAP columns have
+ * equal points, which a proof's multiexps take as one term under the sum of their scalars. */
+zk_status zk_params_get_merged(const zk_params* p, uint32_t out[3]);
 void zk_params_free(zk_params* p);
 
 /* ------------------------------------------------------------------------------------------

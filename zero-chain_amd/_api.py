@@ -192,6 +192,7 @@ class Parameters:
         info = _lib.ParamsInfo()
         lib.check(lib.zk_params_get_info(handle, C.byref(info)))
         self.info = {f[0]: getattr(info, f[0]) for f in info._fields_}
+        self.info.update(zip(("n_merged_a", "n_merged_b1", "n_merged_b2"), self.merged_bases))
 
     @classmethod
     def read(cls, reader, checked=True, device=0, lib=None):
@@ -214,6 +215,13 @@ class Parameters:
         w = (C.c_uint32 * 4)()
         self._lib.check(self._lib.zk_params_get_windows(self._h, w))
         return tuple(int(x) for x in w)
+
+    @property
+    def merged_bases(self):
+        """zk_params_get_merged: entries minus distinct points of the a, b_g1 and b_g2 queries."""
+        n = (C.c_uint32 * 3)()
+        self._lib.check(self._lib.zk_params_get_merged(self._h, n))
+        return tuple(int(x) for x in n)
 
     @property
     def vk(self):

@@ -1135,10 +1135,12 @@ k_msm_reduce1_redo(const XYZZ<Fq28>* __restrict__ tsums, const uint32_t* __restr
 }
 #endif
 // Second pass for the tasks the assembly loop flagged: the compiled addition with every special case.  A circuit's
-// CRS holds EQUAL points (variables with identical QAP polynomials: ~100-170 flagged tasks per 1024-proof launch of
-// the transfer circuit, each time a task starts with two of them), so this pass is on the hot path: one WAVE per
-// flagged task - lane l sums the points k = l (mod 64) of the task, an LDS tree adds the 64 partial sums - instead of
-// one thread walking up to 256 points behind everybody else (9.4 + 3.2 ms per chunk before, r03final trace).
+// CRS holds EQUAL points (variables with identical QAP polynomials); the jobs of a proof take each group of them as ONE
+// term under the sum of its scalars (zkamd.cpp ensure_maps), so two equal table entries meet in a task only by coincidence,
+// under ZKAMD_MERGE_BASES=0 (~100-170 flagged tasks per 1024-proof launch of the transfer circuit, each time a task
+// starts with two of them) or in a caller's own bases.  One WAVE per flagged task - lane l sums the points k = l (mod 64)
+// of the task, an LDS tree adds the 64 partial sums - instead of one thread walking up to 256 points behind everybody
+// else (9.4 + 3.2 ms per chunk before, r03final trace).
 template <class F>
 static __global__ void __launch_bounds__(64, 1)
 k_msm_accumulate_redo(const Affine<F>* __restrict__ table, const uint32_t* __restrict__ pairs, const uint4* __restrict__ sorted,

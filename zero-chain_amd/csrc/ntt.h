@@ -319,7 +319,7 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 }
 
 // Per-proof scalar vectors for the multiexps (plain form):
-//   wit_out[p] = [ wit[p][0..nv) | 1 | r | s ]                          (A and B2 multiexps)
+//   wit_out[p] = [ wit[p][0..nv) | 1 | r | s ]                          (A and B2 multiexps; the stride has the sums below)
 //   cvec[p]    = [ h (m, written later) | aux (n_aux) | r * z (nv) | r ]  (merged C multiexp:
 //                C' = H + L + r * (B1 + beta_1), one bucket set instead of three)
 //                fold != 0 appends [ s * z (nv) | s | r * s ] over the bases of the A query, alpha_1 and delta_1: the job is
@@ -327,19 +327,44 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 //                final fold would otherwise be a 255-bit double-and-add chain on the critical path (zkamd.cpp prove_chunk)
 //                in_tail != 0 appends [ inputs (n_in) ] at that position: the job over the derived bases of a (key, circuit)
 //                pair, whose input variables carry the c part of H (zkamd.cpp ensure_derived)
+// Equal points of a query are one term of its job (zkamd.cpp ensure_maps: the members' slots are mapped out): threads
+// i >= nv + 3 take one group each, groups = [ptr (ga + gb2 + gb1 + 1) | member variables], and sum the members' values mod r:
+//   wit_out[p] += [ sums of the A groups (ga) | sums of the B2 groups (gb2) ]
+//   cvec[p]    += [ r * sums of the B1 groups (gb1) ] and, with fold, [ s * sums of the A groups (ga) ], at its very end
+// (a member >= r counts as zero, as it does in its own slot; a sum that comes out zero has no digits and costs nothing)
 // tail[p] = (1, r, s).  Witness scalars are converted out of Montgomery form when `mont` is set.
 static __global__ void __launch_bounds__(256)
 k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ wit, const uint32_t* __restrict__ tail,
                 uint32_t nv, uint32_t n_in, uint32_t m, uint32_t cstride, uint32_t mont, uint32_t* bad, uint32_t fold,
-                uint32_t in_tail = 0) {
+                uint32_t in_tail = 0, const uint32_t* __restrict__ groups = nullptr, uint32_t ga = 0, uint32_t gb2 = 0,
+                uint32_t gb1 = 0) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= nv + 3) return;
+    const uint32_t wstride = nv + 3 + ga + gb2;
+    if (i >= wstride + gb1) return;
     const size_t p = blockIdx.y;
     uint32_t* cv = cvec + p * (size_t)cstride * 8;
     const uint32_t n_aux = nv - n_in;
     Fr r = ld_fr(tail + (p * 3 + 1) * 8);   // plain
     Fr sR = fold ? mul(ld_fr(tail + (p * 3 + 2) * 8), Fr::r2()) : Fr::zero();   // s in Montgomery form
     Fr v;
+    if (i >= nv + 3) {
+        const uint32_t g = i - (nv + 3);
+        const uint32_t* mem = groups + (ga + gb2 + gb1 + 1);
+        Fr sum = Fr::zero();   // in the form the witness came in: the sum of Montgomery forms is the form of the sum
+        for (uint32_t k = groups[g]; k < groups[g + 1]; k++) {
+            const Fr raw = ld_fr(wit + (p * nv + mem[k]) * 8);
+            if (!fr_geq_r(raw)) sum = add(sum, raw);   // (the member's own thread raises the flag)
+        }
+        if (g < ga + gb2) {
+            v = mont ? from_mont(sum) : sum;
+            if (fold && g < ga) st_fr(cv + (size_t)(cstride - ga + g) * 8, mul(v, sR));   // (sum)(s R) / R
+            st_fr(wit_out + (p * wstride + i) * 8, v);
+        } else {
+            const Fr rz = mont ? mul(sum, r) : mul(mul(sum, r), Fr::r2());
+            st_fr(cv + (size_t)(cstride - (fold ? ga : 0u) - (ga + gb2 + gb1 - g)) * 8, rz);
+        }
+        return;
+    }
     if (i < nv) {
         Fr raw = ld_fr(wit + (p * nv + i) * 8);
         if (fr_geq_r(raw)) {
@@ -366,7 +391,7 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
         if (fold && i == nv + 1) st_fr(cv + (size_t)(m + n_aux + 2 * nv + 2) * 8, mul(r, sR));   // r s for delta_1
         if (fold && i == nv + 2) st_fr(cv + (size_t)(m + n_aux + 2 * nv + 1) * 8, v);            // s for alpha_1
     }
-    st_fr(wit_out + (p * (nv + 3) + i) * 8, v);
+    st_fr(wit_out + (p * wstride + i) * 8, v);
 }
 
 }  // namespace zkdev

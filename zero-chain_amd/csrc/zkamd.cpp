@@ -325,6 +325,19 @@ struct zk_params {
     std::vector<uint8_t> dens_key;
     DevBuf map_a, map_b2, map_c, map_cf;   // (map_cf: the C job with the fold s * A inside, for a few proofs made alone)
     uint32_t map_nv = 0;
+    // Entries of a query whose affine points are EQUAL (variables with identical QAP columns), found once at load from the
+    // encodings: z_i P + z_j P = (z_i + z_j) P, so a job carries ONE term per distinct base and k_build_scalars sums the
+    // members' scalars.  CSR, group -> member positions in the query, groups in the order of their first members; a point
+    // that occurs once is in no group.  Each query on its own points: b_g1 and b_g2 need not agree.
+    struct Groups {
+        std::vector<uint32_t> ptr, mem;
+        uint32_t count() const { return ptr.empty() ? 0u : (uint32_t)ptr.size() - 1; }
+        uint32_t merged() const { return (uint32_t)mem.size() - count(); }   // entries - distinct points
+    } grp_a, grp_b1, grp_b2;
+    // what the maps in use were built with (ensure_maps; all 0 under ZKAMD_MERGE_BASES=0): the groups of the A, B2 and B1
+    // jobs and their CSR lists in VARIABLE indices, [ptr (ga + gb2 + gb1 + 1) | members], for k_build_scalars
+    uint32_t mg_a = 0, mg_b2 = 0, mg_b1 = 0;
+    DevBuf grp_dev;
     // workspaces
     DevBuf abc, wit, cvec, tail, stage_a, stage_b, stage_c, stage_w, fold_tbl, fold_c, fold_a1, fold_c1, fold_b2;
     PinBuf pin_g1, pin_g2, pin_tail;   // affine A, C / B of a chunk; [1 | r | s] per proof
@@ -343,6 +356,32 @@ struct zk_params {
 namespace {
 
 zk_status calibrate_kernel_forms(zk_params* P);
+
+// The groups of equal points of one query, from its uncompressed encodings (canonical: equal bytes are equal points, and an
+// encoding the decoder later refuses fails the load).  The point at infinity joins no group (in a query it fails the load as well).
+void group_equal_points(const uint8_t* enc, uint32_t n, size_t size, zk_params::Groups& G) {
+    std::vector<uint32_t> order;
+    order.reserve(n);
+    for (uint32_t i = 0; i < n; i++)
+        if (!(enc[i * size] & 0x40)) order.push_back(i);
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        const int c = memcmp(enc + x * size, enc + y * size, size);
+        return c ? c < 0 : x < y;
+    });
+    std::vector<std::pair<uint32_t, uint32_t>> runs;   // (first member, its place in `order`)
+    for (size_t i = 0, j; i < order.size(); i = j) {
+        for (j = i + 1; j < order.size() && !memcmp(enc + order[i] * size, enc + order[j] * size, size);) j++;
+        if (j - i > 1) runs.push_back({order[i], (uint32_t)i});
+    }
+    std::sort(runs.begin(), runs.end());
+    G.ptr.assign(1, 0u);
+    G.mem.clear();
+    for (const auto& run : runs) {
+        for (size_t j = run.second; j < order.size() && !memcmp(enc + run.first * size, enc + order[j] * size, size); j++)
+            G.mem.push_back(order[j]);
+        G.ptr.push_back((uint32_t)G.mem.size());
+    }
+}
 
 zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk_params** out) {
     ZK_TRY(use_device(device));
@@ -395,6 +434,9 @@ zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk
     ZK_TRY(locate(&P->n_a, 96, "a", &at_a));
     ZK_TRY(locate(&P->n_b1, 96, "b_g1", &at_b1));
     ZK_TRY(locate(&P->n_b2, 192, "b_g2", &at_b2));
+    group_equal_points(at_a, P->n_a, 96, P->grp_a);
+    group_equal_points(at_b1, P->n_b1, 96, P->grp_b1);
+    group_equal_points(at_b2, P->n_b2, 192, P->grp_b2);
     const Section sec1[7] = {{at_h, P->n_h, "h", false},       {at_l, P->n_l, "l", false},          {at_a, P->n_a, "a", false},
                              {pk, 1, "vk.alpha_g1", true},     {pk + 576, 1, "vk.delta_g1", true},  {at_b1, P->n_b1, "b_g1", false},
                              {pk + 96, 1, "vk.beta_g1", true}};
@@ -558,6 +600,7 @@ zk_params* params_clone_for_lane(const zk_params* P) {
     Q->alpha_g1_inf = P->alpha_g1_inf; Q->beta_g1_inf = P->beta_g1_inf; Q->beta_g2_inf = P->beta_g2_inf;
     Q->delta_g1_inf = P->delta_g1_inf; Q->delta_g2_inf = P->delta_g2_inf;
     Q->vk_bytes = P->vk_bytes;
+    Q->grp_a = P->grp_a; Q->grp_b1 = P->grp_b1; Q->grp_b2 = P->grp_b2;
     return Q;
 }
 zk_r1cs* r1cs_clone_for_lane(const zk_r1cs* R) {
@@ -578,24 +621,39 @@ zk_r1cs* r1cs_clone_for_lane(const zk_r1cs* R) {
 }
 
 // Build (or reuse) the per-circuit index maps from the density trackers.
+// Equal points of a query (zk_params::Groups) become ONE term of its job: every member's slot maps to -1 and a slot appended
+// for the group, whose scalar k_build_scalars makes the sum of the members', maps to the group's first point.
+// ZKAMD_MERGE_BASES=0 builds the maps without groups (a term per query entry), for measurements and parity.
 zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t* a_aux_d, const uint8_t* b_in_d,
                       const uint8_t* b_aux_d) {
+    const char* merge_env = getenv("ZKAMD_MERGE_BASES");
+    const bool merge = !(merge_env && atoi(merge_env) == 0);
     std::vector<uint8_t> key;
-    key.reserve(8 + n_in + 2 * (size_t)n_aux);
+    key.reserve(9 + n_in + 2 * (size_t)n_aux);
     for (int i = 0; i < 4; i++) key.push_back((uint8_t)(n_in >> (8 * i)));
     for (int i = 0; i < 4; i++) key.push_back((uint8_t)(n_aux >> (8 * i)));
     key.insert(key.end(), a_aux_d, a_aux_d + n_aux);
     key.insert(key.end(), b_in_d, b_in_d + n_in);
     key.insert(key.end(), b_aux_d, b_aux_d + n_aux);
     for (int i = 0; i < 4; i++) key.push_back((uint8_t)((P->drv.ready ? P->drv.serial : 0u) >> (8 * i)));
+    key.push_back(merge ? 1 : 0);
     if (key == P->dens_key) return ZK_OK;
     const uint32_t nv = n_in + n_aux;
-    // scalar layout per proof: [inputs | aux | 1 | r | s]
+    // scalar layout per proof: [inputs | aux | 1 | r | s | sums of the A groups | sums of the B2 groups]
     std::vector<int32_t> ma(nv + 3, -1), mb1(nv + 3, -1), mb2(nv + 3, -1);
+    std::vector<uint32_t> var_a, var_b;   // query position -> variable
+    var_a.reserve(P->n_a);
+    var_b.reserve(P->n_b1);
     uint32_t pa = n_in;
-    for (uint32_t i = 0; i < n_in; i++) ma[i] = (int32_t)i;   // A inputs: full density
+    for (uint32_t i = 0; i < n_in; i++) {   // A inputs: full density
+        ma[i] = (int32_t)i;
+        var_a.push_back(i);
+    }
     for (uint32_t j = 0; j < n_aux; j++)
-        if (a_aux_d[j]) ma[n_in + j] = (int32_t)pa++;
+        if (a_aux_d[j]) {
+            ma[n_in + j] = (int32_t)pa++;
+            var_a.push_back(n_in + j);
+        }
     // bellman's generator emits exactly one `a` entry per input and per dense aux variable (and the
     // b queries likewise): a different count means the assignment belongs to another circuit than the key
     if (pa != P->n_a)
@@ -605,15 +663,45 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     ma[nv + 1] = (int32_t)P->n_a + 1;                 // r * delta_g1 (never at infinity here: prove_* refuse)
     uint32_t pb = 0;
     for (uint32_t i = 0; i < n_in; i++)
-        if (b_in_d[i]) mb1[i] = mb2[i] = (int32_t)pb++;
+        if (b_in_d[i]) {
+            mb1[i] = mb2[i] = (int32_t)pb++;
+            var_b.push_back(i);
+        }
     for (uint32_t j = 0; j < n_aux; j++)
-        if (b_aux_d[j]) mb1[n_in + j] = mb2[n_in + j] = (int32_t)pb++;
+        if (b_aux_d[j]) {
+            mb1[n_in + j] = mb2[n_in + j] = (int32_t)pb++;
+            var_b.push_back(n_in + j);
+        }
     if (pb != P->n_b1 || pb != P->n_b2)
         return fail(ZK_ERR_IO, "the B density of the assignment (" + std::to_string(pb) + ") differs from the key's b queries (" +
                                    std::to_string(P->n_b1) + " in G1, " + std::to_string(P->n_b2) + " in G2)");
     if (!P->beta_g1_inf) mb1[nv] = (int32_t)P->n_b1;   // 1 * beta_g1
     if (!P->beta_g2_inf) mb2[nv] = (int32_t)P->n_b2;   // 1 * beta_g2
     mb2[nv + 2] = (int32_t)P->n_b2 + 1;                // s * delta_g2
+    // the groups of each query: members muted in that query's map; base[g] = the query position the group's sum goes to;
+    // the CSR lists in variable indices, A | B2 | B1, are what k_build_scalars sums over
+    static const zk_params::Groups none;
+    std::vector<uint32_t> gptr(1, 0u), gmem;
+    auto mute = [&](const zk_params::Groups& G, const std::vector<uint32_t>& var, std::vector<int32_t>& map, std::vector<int32_t>& base) {
+        for (uint32_t g = 0; g < G.count(); g++) {
+            base.push_back((int32_t)G.mem[G.ptr[g]]);
+            for (uint32_t k = G.ptr[g]; k < G.ptr[g + 1]; k++) {
+                map[var[G.mem[k]]] = -1;
+                gmem.push_back(var[G.mem[k]]);
+            }
+            gptr.push_back((uint32_t)gmem.size());
+        }
+    };
+    std::vector<int32_t> base_a, base_b2, base_b1;
+    mute(merge ? P->grp_a : none, var_a, ma, base_a);
+    mute(merge ? P->grp_b2 : none, var_b, mb2, base_b2);
+    mute(merge ? P->grp_b1 : none, var_b, mb1, base_b1);
+    const uint32_t ga = (uint32_t)base_a.size(), gb2 = (uint32_t)base_b2.size(), gb1 = (uint32_t)base_b1.size();
+    // (each of the two jobs over this vector selects its own sums; the other's stay -1)
+    ma.resize(nv + 3 + ga + gb2, -1);
+    mb2.resize(nv + 3 + ga + gb2, -1);
+    for (uint32_t g = 0; g < ga; g++) ma[nv + 3 + g] = base_a[g];
+    for (uint32_t g = 0; g < gb2; g++) mb2[nv + 3 + ga + g] = base_b2[g];
     // h coefficients leave the last transform in bit-reversed order; the top coefficient
     // (degree m - 1) is dropped exactly as bellman truncates it
     std::vector<int32_t> mh(P->m);
@@ -621,18 +709,25 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
         uint32_t e = P->log_m ? (__builtin_bitreverse32((uint32_t)pos) >> (32 - P->log_m)) : 0;
         mh[pos] = e < P->n_h ? (int32_t)e : -1;
     }
-    // merged C job: [h (m) | aux (n_aux) | r z (nv) | r], absolute positions in the G1 group table
+    // merged C job: [h (m) | aux (n_aux) | r z (nv) | r | r * sums of the B1 groups], absolute positions in the G1 group table
+    auto with_sums = [](std::vector<int32_t>& map, const std::vector<int32_t>& base, uint32_t off) {
+        for (int32_t b : base) map.push_back((int32_t)off + b);
+    };
     std::vector<int32_t> mc;
-    mc.reserve(P->m + n_aux + nv + 1);
+    mc.reserve(P->m + n_aux + 2 * (size_t)nv + 3 + gb1 + ga);
     for (size_t pos = 0; pos < P->m; pos++) mc.push_back(mh[pos] < 0 ? -1 : (int32_t)(P->off_h + mh[pos]));
     for (uint32_t j = 0; j < n_aux; j++) mc.push_back((int32_t)(P->off_l + j));
     for (uint32_t i = 0; i < nv; i++) mc.push_back(mb1[i] < 0 ? -1 : (int32_t)(P->off_b1 + mb1[i]));
     mc.push_back(P->beta_g1_inf ? -1 : (int32_t)(P->off_b1 + P->n_b1));   // r * beta_g1
     // the folded form of the job (ntt.h k_build_scalars, fold): + [s z (nv) | s | r s] over the A query, alpha_1, delta_1
+    // behind the r, and [s * sums of the A groups] at the end
     std::vector<int32_t> mcf(mc);
     for (uint32_t i = 0; i < nv + 2; i++) mcf.push_back(ma[i] < 0 ? -1 : (int32_t)(P->off_a + ma[i]));
+    with_sums(mc, base_b1, P->off_b1);
+    with_sums(mcf, base_b1, P->off_b1);
+    with_sums(mcf, base_a, P->off_a);
     if (P->drv.ready && P->drv.pos.size() == P->m + nv) {
-        // the same job over the derived bases: [u (m, natural order) | aux | r z | r | fold | inputs (n_in)]
+        // the same job over the derived bases: [u (m, natural order) | aux | r z | r | fold | inputs (n_in) | sums]
         const zk_params::Derived& D = P->drv;
         std::vector<int32_t> md;
         md.reserve(mcf.size() + n_in);
@@ -646,11 +741,17 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
             md.push_back(D.pos[P->m + i]);
             mdf.push_back(D.pos[P->m + i]);
         }
+        with_sums(md, base_b1, D.off_b1);
+        with_sums(mdf, base_b1, D.off_b1);
+        with_sums(mdf, base_a, D.off_a);
         ZK_TRY(P->map_cd.ensure(md.size() * 4));
         ZK_TRY(P->map_cfd.ensure(mdf.size() * 4));
         HIP_TRY(hipMemcpy(P->map_cd.p, md.data(), md.size() * 4, hipMemcpyHostToDevice));
         HIP_TRY(hipMemcpy(P->map_cfd.p, mdf.data(), mdf.size() * 4, hipMemcpyHostToDevice));
     }
+    gptr.insert(gptr.end(), gmem.begin(), gmem.end());
+    ZK_TRY(P->grp_dev.ensure(gptr.size() * 4));
+    HIP_TRY(hipMemcpy(P->grp_dev.p, gptr.data(), gptr.size() * 4, hipMemcpyHostToDevice));
     ZK_TRY(P->map_cf.ensure(mcf.size() * 4));
     HIP_TRY(hipMemcpy(P->map_cf.p, mcf.data(), mcf.size() * 4, hipMemcpyHostToDevice));
     ZK_TRY(P->map_a.ensure(ma.size() * 4));
@@ -661,6 +762,9 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     HIP_TRY(hipMemcpy(P->map_c.p, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
     P->dens_key.swap(key);
     P->map_nv = nv;
+    P->mg_a = ga;
+    P->mg_b2 = gb2;
+    P->mg_b1 = gb1;
     return ZK_OK;
 }
 
@@ -678,8 +782,9 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     const uint32_t n_in = bt->n_inputs, n_aux = bt->n_aux, nv = n_in + n_aux, n_rows = bt->n_rows;
     const size_t m = P->m;
     const bool mont = (bt->flags & ZK_FR_MONTGOMERY) != 0;
-    // ---- scalars [inputs | aux | 1 | r | s] per proof, plain
-    const size_t wstride = (size_t)(nv + 3);
+    // ---- scalars [inputs | aux | 1 | r | s | sums of the A groups | of the B2 groups] per proof, plain (ensure_maps)
+    const uint32_t ga = P->mg_a, gb2 = P->mg_b2, gb1 = P->mg_b1;
+    const size_t wstride = (size_t)(nv + 3 + ga + gb2);
     ZK_TRY(P->wit.ensure(np * wstride * 32));
     uint32_t* wit = P->wit.as<uint32_t>();
     ZK_TRY(P->pin_tail.ensure(np * 96));
@@ -712,12 +817,14 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
     const bool fold_in_msm = np <= fold_max;
     const uint32_t in_tail = derived ? (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0)) : 0u;   // (the inputs carry their K_i)
-    const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0));
+    // (the sums of the groups at the end: r * B1's, then s * A's with the fold)
+    const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0) + gb1 + (fold_in_msm ? ga : 0));
     ZK_TRY(P->cvec.ensure(np * (size_t)cstride * 32));
     uint32_t* cvec = P->cvec.as<uint32_t>();
-    ZK_LAUNCH(zkdev::k_build_scalars, dim3((nv + 3 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
+    // (the same launch: a thread per variable, three for the tail, one per group)
+    ZK_LAUNCH(zkdev::k_build_scalars, dim3((nv + 3 + ga + gb2 + gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
               (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), nv, n_in, (uint32_t)m, cstride,
-              mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u, in_tail);
+              mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u, in_tail, P->grp_dev.as<uint32_t>(), ga, gb2, gb1);
     // ---- multiexps (create_proof step 4).  The G2 job only needs the witness scalars: it is
     // enqueued first, on the side stream, and runs beside the H pipeline and the G1 multiexps (its
     // reduction tree is latency-bound with one job per proof; the G1 work fills the machine).
@@ -726,7 +833,7 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     const uint32_t npts1 = (uint32_t)P->g1.n_points, npts2 = (uint32_t)P->g2.n_points;
     for (size_t p = 0; p < np; p++) {
         const uint32_t* w = wit + p * wstride * 8;
-        MsmJob j2 = {w, P->map_b2.as<int32_t>(), nv + 3, 0, npts2, 0, 0, 0};
+        MsmJob j2 = {w, P->map_b2.as<int32_t>(), (uint32_t)wstride, 0, npts2, 0, 0, 0};
         P->jobs2.push_back(j2);
     }
     hipStream_t side = getenv("ZKAMD_NO_OVERLAP") ? g_stream : g_stream2;
@@ -790,7 +897,7 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     P->jobs1a.clear();
     for (size_t p = 0; p < np; p++) {
         const uint32_t* w = wit + p * wstride * 8;
-        MsmJob ja = {w, P->map_a.as<int32_t>(), nv + 3, P->off_a, npts1, 0, 0, 0};
+        MsmJob ja = {w, P->map_a.as<int32_t>(), (uint32_t)wstride, P->off_a, npts1, 0, 0, 0};
         if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
             ja.table_base = P->drv.off_a;
             ja.n_table = npts1c;
@@ -1822,6 +1929,13 @@ zk_status zk_params_get_windows(const zk_params* p, uint32_t out[4]) try {
     out[1] = p->g1a.c;
     out[2] = p->g1_lone.c;
     out[3] = p->g2.c;
+    return ZK_OK;
+} ZK_ABI_CATCH
+zk_status zk_params_get_merged(const zk_params* p, uint32_t out[3]) try {
+    if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    out[0] = p->grp_a.merged();
+    out[1] = p->grp_b1.merged();
+    out[2] = p->grp_b2.merged();
     return ZK_OK;
 } ZK_ABI_CATCH
 void zk_params_free(zk_params* p) { delete p; }
