@@ -73,6 +73,8 @@
  *   zk_jubjub_into_xy               IntoXY of the primitives (Point::read + as_prime_order + into_xy)   core/primitives/src/enc_key.rs:89, core/jubjub/src/curve/edwards.rs:92-165, :319-330
  *   zk_confidential_verify_batch    zk_system::verify_confidential_proof          modules/zk-system/src/lib.rs:56-115, input_builder.rs:15-27
  *   zk_anonymous_verify_batch       zk_system::verify_anonymous_proof             modules/zk-system/src/lib.rs:118-165
+ *   zk_redjubjub_sign               redjubjub::PrivateKey::sign                   core/jubjub/src/redjubjub.rs:73-103; callers confidential.rs:416-420, anonymous.rs:378-401
+ *   zk_redjubjub_verify_batch       redjubjub::PublicKey::verify, per signature   core/jubjub/src/redjubjub.rs:127-155; RedjubjubSignature::verify core/primitives/src/signature.rs:65-82
  *   zk_msm_create, zk_msm_create_variable, zk_msm_run, zk_msm_run_dev, zk_msm_free, zk_msm_g1, zk_msm_g2, zk_msm_cache_release
  *                                   bellman multiexp(FullDensity); group law core/pairing/src/bls12_381/ec.rs:296-526
  *   zk_ntt_fr, zk_ntt_create, zk_ntt_run_dev, zk_ntt_free
@@ -501,6 +503,34 @@ zk_status zk_confidential_verify_batch(zk_vk* vk, size_t n, const zk_confidentia
  * right, 49 right_ciphertext, 50 rvk, 51 g_epoch, 52 nonce; enc_balances: n x 12 x 64 bytes, required; 104 inputs. */
 zk_status zk_anonymous_verify_batch(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* enc_balances,
                                     const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out);
+
+/* ------------------------------------------------------------------------------------------
+ * RedJubjub (core/jubjub/src/redjubjub.rs): the signature an extrinsic carries.  The wallet signs with the rsk the derive
+ * and gen_proof entries return (confidential.rs:372-431); the runtime checks the signature against the account id, which
+ * is the rvk, on every extrinsic (core/primitives/src/signature.rs:65-82).  G = FixedGenerators::Diversifier, the generator
+ * of zk_jubjub_base_mul.  H*(a || b) = Fs::to_uniform(BLAKE2b-512 personalised "Zcash_RedJubjubH" over a then b).
+ * Message i is msgs[msg_offsets[i] .. msg_offsets[i + 1]) (msg_offsets: n + 1 values; empty messages are allowed, msgs may
+ * be NULL when all are; offsets that decrease are ZK_ERR_INVALID_ARGUMENT).
+ * ------------------------------------------------------------------------------------------ */
+/* PrivateKey::sign (redjubjub.rs:73-103) for n keys.  rsk: n x 32 bytes, canonical Fs (ZK_ERR_INVALID_ARGUMENT naming the
+ * index otherwise; the reference panics).  t: n x 80 bytes, the T the reference draws from its RNG - the library never draws
+ * randomness.  sigs_out: n x 64 bytes, Rbar | S with r = H*(T || M), Rbar = write(r G), S = r + H*(Rbar || M) rsk.
+ * Host only, on the zk_set_host_threads pool.  No branch or table address depends on rsk, T or r (masked selection in the
+ * fixed-base multiplication, masked reduction mod s); the final conditional subtraction inside the host Fr routines is
+ * variable-time, as in the reference's own Fr.  rsk, r and what is derived from them are wiped before the call returns. */
+zk_status zk_redjubjub_sign(size_t n, const uint8_t* rsk, const uint8_t* t, const uint8_t* msgs, const uint64_t* msg_offsets,
+                            uint8_t* sigs_out);
+/* PublicKey::read + PublicKey::verify (redjubjub.rs:118-155) for n signatures, one verdict each (not the reference's
+ * all-or-nothing batch_verify).  vks: n x 32 bytes; sigs: n x 64 bytes.  ok_out[i] = 1 or 0; reason_out (may be NULL), in the
+ * reference's order of tests: 0 accepted, 1 vk is not a point (Point::read fails: NotInField or NotOnCurve), 2 Rbar is not a
+ * point, 3 Sbar >= s, 4 the equation [8]([c]vk + R - [S]G) == O fails, c = H*(Rbar || M) over Rbar's bytes as given.  A
+ * refusal is a verdict, never an error.  As in the reference there is NO prime-order test: a key or an R with a torsion
+ * component, the identity, and x = 0 encoded with the sign bit set are all accepted.
+ * device < 0, or n <= ZKAMD_REDJUBJUB_HOST_MAX (default 320; read per call, 0 = always the kernels): on the host threads; else two kernels
+ * on `device` (csrc/redjubjub.h) while the host hashes the messages.  The bytes written do not depend on the form. */
+enum { ZK_REDJUBJUB_BAD_VK = 1, ZK_REDJUBJUB_BAD_R = 2, ZK_REDJUBJUB_BAD_S = 3, ZK_REDJUBJUB_BAD_EQUATION = 4 };
+zk_status zk_redjubjub_verify_batch(size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* msgs,
+                                    const uint64_t* msg_offsets, int device, uint8_t* ok_out, uint8_t* reason_out);
 
 /* ------------------------------------------------------------------------------------------
  * Stand-alone kernels (micro-benchmark / test entries)

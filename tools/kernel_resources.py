@@ -9,9 +9,11 @@ LLVM = os.path.join(os.environ.get("ROCM_PATH", "/opt/rocm"), "lib", "llvm", "bi
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def kernel_resources(so_path):
-    """{mangled kernel name: {"scratch": bytes per lane, "vgpr": n, "lds": bytes}} over every code object in the library"""
-    out = {}
+def kernel_resources_per_object(so_path):
+    """[{mangled kernel name: {"scratch": bytes per lane, "vgpr": n, "lds": bytes}}, ...]: one dict per code object of the library
+    (one per translation unit that holds device code).  Kernels with internal linkage that two units both compile carry the SAME
+    mangled name in both code objects: only this form can count them."""
+    out = []
     with tempfile.TemporaryDirectory() as tmp:
         fat = os.path.join(tmp, "fat.bin")
         subprocess.run([os.path.join(LLVM, "llvm-objcopy"), "--dump-section", ".hip_fatbin=" + fat, so_path], check=True)
@@ -23,11 +25,22 @@ def kernel_resources(so_path):
             subprocess.run([os.path.join(LLVM, "clang-offload-bundler"), "--unbundle", "--type=o",
                             "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", "--input=" + part, "--output=" + co], check=True)
             notes = subprocess.run([os.path.join(LLVM, "llvm-readelf"), "--notes", co], capture_output=True, text=True, check=True).stdout
+            obj = {}
             for blk in notes.split("- .agpr_count")[1:]:
                 name = re.search(r"\.name:\s+(\S+)", blk).group(1)
-                out[name] = {"scratch": int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)),
+                obj[name] = {"scratch": int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk).group(1)),
                              "vgpr": int(re.search(r"\.vgpr_count:\s+(\d+)", blk).group(1)),
                              "lds": int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", blk).group(1))}
+            out.append(obj)
+    return out
+
+
+def kernel_resources(so_path):
+    """{mangled kernel name: {"scratch": bytes per lane, "vgpr": n, "lds": bytes}} over every code object in the library (a name
+    that several code objects hold appears once: count with kernel_resources_per_object)"""
+    out = {}
+    for obj in kernel_resources_per_object(so_path):
+        out.update(obj)
     return out
 
 

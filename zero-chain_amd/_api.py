@@ -24,7 +24,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
                    ZK_NTT_OUT_BITREV)
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
-           "verify_transfer_batch", "jubjub_into_xy", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
+           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
@@ -444,6 +444,50 @@ def jubjub_into_xy(points, device=None, lib=None):
     vals = [None if st[i] else (int.from_bytes(raw[64 * i:64 * i + 32], "little"), int.from_bytes(raw[64 * i + 32:64 * i + 64], "little"))
             for i in range(n)]
     return vals, [int(v) for v in st[:n]]
+
+
+REDJUBJUB_REASONS = {1: "vk is not a point", 2: "Rbar is not a point", 3: "Sbar is not below the group order", 4: "the equation fails"}
+
+
+def _messages(msgs):
+    """(bytes of all messages, n + 1 offsets) as the two RedJubjub entries take them"""
+    msgs = [bytes(m) for m in msgs]
+    offs = np.zeros(len(msgs) + 1, dtype=np.uint64)
+    offs[1:] = np.cumsum([len(m) for m in msgs], dtype=np.uint64)
+    blob = b"".join(msgs)
+    return (_u8(blob) if blob else np.zeros(1, dtype=np.uint8)), offs
+
+
+def redjubjub_sign(rsks, ts, msgs, lib=None):
+    """zk_redjubjub_sign = redjubjub::PrivateKey::sign for a list of keys (32-byte strings as zk_transfer_derive returns them, or
+    Fs ints), the 80 random bytes T of each (the library draws none) and the messages.  Returns the 64-byte signatures."""
+    lib = lib or _lib.load()
+    n = len(msgs)
+    if len(rsks) != n or len(ts) != n:
+        raise ValueError("one key and one 80-byte T per message")
+    kb = _u8(b"".join(int(k).to_bytes(32, "little") if isinstance(k, int) else bytes(k) for k in rsks), 32 * n)
+    tb = _u8(b"".join(bytes(t) for t in ts), 80 * n)
+    blob, offs = _messages(msgs)
+    out = np.zeros(max(n, 1) * 64, dtype=np.uint8)
+    lib.check(lib.zk_redjubjub_sign(n, _ptr(kb) if n else None, _ptr(tb) if n else None, _ptr(blob), _ptr(offs), _ptr(out)))
+    ob = out.tobytes()
+    return [ob[64 * i:64 * i + 64] for i in range(n)]
+
+
+def redjubjub_verify(vks, sigs, msgs, device=None, lib=None):
+    """zk_redjubjub_verify_batch = redjubjub::PublicKey::verify for every (32-byte key, 64-byte signature, message), one verdict
+    each.  device None: the host form (device = -1); else the device whose kernels run once the batch is larger than
+    ZKAMD_REDJUBJUB_HOST_MAX.  Returns ([accepted], [reason]): reason 0, or a key of REDJUBJUB_REASONS."""
+    lib = lib or _lib.load()
+    n = len(msgs)
+    if len(vks) != n or len(sigs) != n:
+        raise ValueError("one key and one signature per message")
+    vb, sb = _u8(b"".join(bytes(v) for v in vks), 32 * n), _u8(b"".join(bytes(s) for s in sigs), 64 * n)
+    blob, offs = _messages(msgs)
+    ok, why = np.zeros(max(n, 1), dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    lib.check(lib.zk_redjubjub_verify_batch(n, _ptr(vb) if n else None, _ptr(sb) if n else None, _ptr(blob), _ptr(offs),
+                                            -1 if device is None else int(device), _ptr(ok), _ptr(why)))
+    return [bool(v) for v in ok[:n]], [int(v) for v in why[:n]]
 
 
 def _xt_array(xts, ctype, fill):

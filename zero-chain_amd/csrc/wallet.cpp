@@ -7,7 +7,9 @@
 //   elgamal::Ciphertext::decrypt     elgamal.rs:85-108 (the host half; the search is witness.cpp's, kernels elgamal_dlog.h)
 //   elgamal::Ciphertext::add / sub   elgamal.rs:139-158
 //   check_proof + ConfidentialXt / AnonymousXt packing   confidential.rs:208-361, anonymous.rs:200-352
-// Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; this unit holds no kernel.
+//   redjubjub PrivateKey::sign / PublicKey::verify       core/jubjub/src/redjubjub.rs:73-103, 127-155 (redjubjub.h)
+// Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
+// the signature check (redjubjub.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -239,7 +241,23 @@ zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_s
 
 }  // namespace
 
+#include "redjubjub.h"   // (here: it signs and hashes with the helpers above)
+
 extern "C" {
+
+zk_status zk_redjubjub_sign(size_t n, const uint8_t* rsk, const uint8_t* t, const uint8_t* msgs, const uint64_t* msg_offsets,
+                            uint8_t* sigs_out) try {
+    if (n && (!rsk || !t || !msg_offsets || !sigs_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    return zkrj::sign(n, rsk, t, msgs, msg_offsets, sigs_out);
+} ZK_ABI_CATCH
+
+zk_status zk_redjubjub_verify_batch(size_t n, const uint8_t* vks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+                                    int device, uint8_t* ok_out, uint8_t* reason_out) try {
+    if (n && (!vks || !sigs || !msg_offsets || !ok_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    return zkrj::verify_batch(n, vks, sigs, msgs, msg_offsets, device, ok_out, reason_out);
+} ZK_ABI_CATCH
 
 zk_status zk_spending_key_from_seed(const uint8_t* seed, size_t len, uint8_t spending_key_out[32]) try {
     if ((!seed && len) || !spending_key_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
