@@ -55,6 +55,9 @@
  *   zk_elgamal_table_create, zk_elgamal_decrypt, zk_elgamal_table_free
  *                                   elgamal::Ciphertext::decrypt (the brute-force walk) no_std_aliases/elgamal.rs:85-108
  *   zk_elgamal_add                  elgamal::Ciphertext::add / sub                no_std_aliases/elgamal.rs:139-158
+ *   zk_elgamal_ledger_apply         rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
+ *                                   modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350,
+ *                                   modules/anonymous-balances/src/lib.rs:169-225, core/primitives/src/ciphertext.rs:90-100
  *   zk_transfer_derive              the derivations at the head of gen_proof      confidential.rs:105-133
  *   zk_transfer_gen_proof_batch     ProofBuilder::gen_proof (Confidential)        confidential.rs:105-172, check_proof :208-278
  *   zk_anonymous_r1cs_load          structure half of AnonymousTransfer::synthesize      circuit/anonymous_transfer.rs:56-337
@@ -351,6 +354,38 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
 void zk_elgamal_table_free(zk_elgamal_table* t);
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
                          int subtract, uint8_t* left_out, uint8_t* right_out);
+/* zk_elgamal_ledger_apply: what the three balance modules do to storage around every proof of a block (rollover,
+ *   sub_enc_balance, add_pending_transfer: modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350;
+ *   twelve updates per extrinsic in modules/anonymous-balances/src/lib.rs:169-225) - Ciphertext::add / Ciphertext::sub
+ *   (core/primitives/src/ciphertext.rs:90-100) applied to n_slots stored ciphertexts one op after another, in index order.
+ *   INTEGRATION.md, "A block's balance updates", maps the modules' calls to slots and ops.
+ *   Reading: every ciphertext, of a slot or of an op, is read as elgamal::Ciphertext::read does - both points through Point::read
+ *     and as_prime_order, exactly what zk_jubjub_into_xy decides (x = 0 with the sign bit set is accepted, as there).
+ *   op_status_out[i]: 0, or (1 = left, 2 = right) | (IntoXY status << 6) of the first point of op i that is refused - the
+ *     refusal_out convention of zk_confidential_verify_batch; slot_status_out[s] the same for slot s.  A refusal is a status,
+ *     never an error.
+ *   before_out[i] (may be NULL): the value of slot ops[i].slot just before op i, also for a refused or skipped op.
+ *   An op that is neither refused nor skipped (flags bit 1) adds its ciphertext to its slot, or subtracts it (flags bit 0);
+ *     slots_out[s] is the value after the last op.  For a refused slot slots_out[s] and the before_out of all its ops are 64
+ *     zero bytes; those ops keep their own statuses.
+ *   Outputs are Point::write of the affine result (the identity is 01 00 .. 00): canonical, the same bytes in either form.
+ *   ops[i].slot >= n_slots, an unknown flag bit or a NULL required pointer with a non-zero count: ZK_ERR_INVALID_ARGUMENT naming
+ *     the index, nothing written.  n_ops == 0 copies the judged slots through; with both counts 0 no buffer is touched.
+ *   device < 0, or 2 (n_slots + n_ops) <= ZKAMD_INTO_XY_HOST_MAX points: on host threads; else on `device`.
+ *   The skip bit is for two passes over a block: the first, with before_out, yields the enc_balances of
+ *   zk_confidential_verify_batch; the second, with skip set on the extrinsics that were rejected, the state to store.
+ *   The data is public chain state: nothing here is constant-time, and no buffer is wiped. */
+#define ZK_LEDGER_SUBTRACT 1u
+#define ZK_LEDGER_SKIP 2u
+typedef struct {
+    uint32_t slot;    /* index into slots */
+    uint32_t flags;   /* bit 0: subtract (Ciphertext::sub); bit 1: skip - read and judged, not applied */
+    uint8_t left[32], right[32];
+} zk_ledger_op;
+zk_status zk_elgamal_ledger_apply(size_t n_slots, const uint8_t* slots /* n_slots x 64: left | right */,
+                                  size_t n_ops, const zk_ledger_op* ops, int device,
+                                  uint8_t* slots_out /* n_slots x 64 */, uint8_t* before_out /* n_ops x 64, may be NULL */,
+                                  uint8_t* slot_status_out /* n_slots */, uint8_t* op_status_out /* n_ops */);
 struct zk_vk;
 zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, struct zk_vk* vk, size_t n, const zk_transfer_request* req,
                                       const uint8_t* rs, zk_confidential_xt* out);

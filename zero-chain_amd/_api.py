@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -877,6 +877,48 @@ def elgamal_add(left_a, right_a, left_b, right_b, subtract=False, lib=None):
         lib.check(lib.zk_elgamal_add(*[_ptr(a) for a in ins], n, 1 if subtract else 0, _ptr(left), _ptr(right)))
     lb, rbb = left.tobytes(), right.tobytes()
     return [lb[i:i + 32] for i in range(0, 32 * n, 32)], [rbb[i:i + 32] for i in range(0, 32 * n, 32)]
+
+
+LEDGER_SUBTRACT, LEDGER_SKIP = 1, 2   # zk_ledger_op.flags
+LEDGER_SCAN_WIDTH = 256                # lanes of a workgroup of the device form's scan (csrc/ledger.h LEDGER_SCAN_W)
+
+
+def _ciphertext_refusal(v):
+    return None if not v else (("left", "right")[(int(v) & 63) - 1], INTO_XY_REASONS[int(v) >> 6])
+
+
+def ledger_apply(slots, ops, device=None, want_before=True, lib=None):
+    """zk_elgamal_ledger_apply: a block's rollover / sub_enc_balance / add_pending_transfer (the reference's three balance
+    modules) - Ciphertext::add / ::sub applied to stored ciphertexts one op after another.  slots: (left, right) pairs of
+    32-byte encodings, or 64-byte strings.  ops: (slot, flags, left, right) tuples - flags LEDGER_SUBTRACT | LEDGER_SKIP - or
+    an array of _lib.LedgerOp.  device None: the host form (device = -1); else the device whose kernels run once the call
+    holds more than ZKAMD_INTO_XY_HOST_MAX points.  Returns (slots_out, before, slot_refusals, op_refusals): 64-byte values
+    (bytes(64) for a refused slot and for the ops on it), `before` None without want_before, and a refusal None or (field,
+    reason) of the first point refused, field "left" or "right"."""
+    lib = lib or _lib.load()
+
+    def pair(c):
+        b = bytes(c) if isinstance(c, (bytes, bytearray)) else bytes(c[0]) + bytes(c[1])
+        if len(b) != 64:
+            raise ValueError("a ciphertext is 64 bytes (left || right)")
+        return b
+    ns = len(slots)
+    sb = _u8(b"".join(pair(c) for c in slots), 64 * ns)
+    if isinstance(ops, C.Array) and ops._type_ is _lib.LedgerOp:
+        arr = ops
+    else:
+        arr = (_lib.LedgerOp * len(ops))()
+        for dst, (slot, flags, left, right) in zip(arr, ops):
+            dst.slot, dst.flags = int(slot), int(flags)
+            dst.left[:], dst.right[:] = bytes(left), bytes(right)
+    no = len(arr)
+    so, bo = np.zeros(max(ns, 1) * 64, dtype=np.uint8), np.zeros(max(no, 1) * 64, dtype=np.uint8)
+    ss, os_ = np.zeros(max(ns, 1), dtype=np.uint8), np.zeros(max(no, 1), dtype=np.uint8)
+    lib.check(lib.zk_elgamal_ledger_apply(ns, _ptr(sb) if ns else None, no, arr if no else None, -1 if device is None else int(device), _ptr(so),
+                                          _ptr(bo) if want_before else None, _ptr(ss), _ptr(os_)))
+    sob, bob = so.tobytes(), bo.tobytes()
+    return ([sob[64 * i:64 * i + 64] for i in range(ns)], [bob[64 * i:64 * i + 64] for i in range(no)] if want_before else None,
+            [_ciphertext_refusal(v) for v in ss[:ns]], [_ciphertext_refusal(v) for v in os_[:no]])
 
 
 def balance_query(dec_key, encrypted_balance=None, pending_transfer=None, table=None, limit=ELGAMAL_DECRYPT_LIMIT):

@@ -86,6 +86,10 @@ class AnonymousXt(C.Structure):
                [(n, C.c_uint8 * 32) for n in ("right_ciphertext", "nonce", "rsk", "rvk")]
 
 
+class LedgerOp(C.Structure):
+    _fields_ = [("slot", C.c_uint32), ("flags", C.c_uint32), ("left", C.c_uint8 * 32), ("right", C.c_uint8 * 32)]
+
+
 class BatchDev(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("n_inputs", C.c_uint32), ("n_aux", C.c_uint32), ("flags", C.c_uint32),
                 ("d_a", C.c_void_p), ("d_b", C.c_void_p), ("d_c", C.c_void_p), ("d_wit", C.c_void_p),
@@ -134,6 +138,8 @@ _PROTOS = {
                                        C.c_void_p]),
     "zk_elgamal_table_free": (None, [C.c_void_p]),
     "zk_elgamal_add": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "zk_elgamal_ledger_apply": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LedgerOp), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p]),
     "zk_transfer_derive": (C.c_int32, [C.POINTER(TransferRequest), C.c_size_t, C.POINTER(TransferStatement), C.c_void_p]),
     "zk_transfer_gen_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(TransferRequest), C.c_void_p,
                                                 C.POINTER(ConfidentialXt)]),

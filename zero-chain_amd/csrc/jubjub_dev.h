@@ -1,10 +1,11 @@
-// Jubjub on the device, one lane per point: the pieces of xt_inputs.h's IntoXY chain that other kernels share (redjubjub.h).
+// Jubjub on the device, one lane per point: the pieces of xt_inputs.h's IntoXY chain that other kernels share (redjubjub.h, ledger.h).
 // Only ZK_DI functions and compile-time tables live here - no kernel, so a translation unit that includes this header
 // compiles none: k_into_xy stays in xt_inputs.h, which verify.cpp alone includes.
 //   Lds                      a lane's column of a block's LDS table, [slot][word][lane]
 //   pow_windows              a^e for a constant exponent in fixed 4-bit windows (~330 dependent products for r - 2)
 //   sqrt_one_pow             square root in Fr with ONE exponentiation, then Tonelli-Shanks (~290 + <= 500)
 //   ext_dbl, cache_put, ext_add_cached   extended twisted Edwards, a = -1: dbl-2008-hwcd, addends cached as (Y + X, Y - X, 2 d T, 2 Z)
+//   ext_add                  two extended points, add-2008-hwcd-3 (9 products): the operator of ledger.h's scan
 //   is_prime_order           [s]P == O over the width-4 NAF of s recoded at compile time (~2 200)
 //   read_point               edwards::Point::read: y, and x by 1 / (d y^2 + 1) and the square root (~620)
 #pragma once
@@ -176,6 +177,13 @@ ZK_DI EP ext_add_cached(const Lds& L, const EP& p, uint32_t i, bool negative, bo
     r.Z = mul(f, g);
     r.T = want_t ? mul(e, h) : Fr::zero();
     return r;
+}
+// p + q for two extended points (add-2008-hwcd-3 with k = 2 d: 9M; unified, and complete where both are of prime order)
+ZK_DI EP ext_add(const EP& p, const EP& q, const Fr& d2) {
+    const Fr a = mul(sub(p.Y, p.X), sub(q.Y, q.X)), b = mul(add(p.Y, p.X), add(q.Y, q.X));
+    const Fr c = mul(mul(p.T, d2), q.T), d = dbl(mul(p.Z, q.Z));
+    const Fr e = sub(b, a), f = sub(d, c), g = add(d, c), h = add(b, a);
+    return EP{mul(e, f), mul(g, h), mul(f, g), mul(e, h)};
 }
 // [s](x, y) == O ?
 ZK_DI bool is_prime_order(const Lds& L, const Fr& x, const Fr& y, const Fr& d2) {

@@ -8,6 +8,8 @@
 //   Proof::read                      core/bellman-verifier/src/lib.rs:67-110 (compressed points, into_affine)
 //   verify_confidential_proof / verify_anonymous_proof   modules/zk-system/src/lib.rs:56-165 (the public inputs from the
 //                                    extrinsic's bytes: PublicInputBuilder::push, IntoXY - xt_inputs.h)
+//   rollover / sub_enc_balance / add_pending_transfer    modules/encrypted-balances/src/lib.rs:133-222, encrypted-assets :266-350,
+//                                    anonymous-balances :169-225 (a block's Ciphertext::add / sub in order - ledger.h)
 // Device side: pairing.h.  Host side here: byte formats, the handle, the launch sequence.
 #include <algorithm>
 #include <new>
@@ -18,6 +20,7 @@
 #include "pairing.h"
 #include "coop_verify.h"
 #include "xt_inputs.h"
+#include "ledger.h"
 #include "verify_plan.h"
 
 using namespace zkrt;
@@ -1012,6 +1015,10 @@ zk_status zk_verify_proof(zk_vk* vk, const uint8_t proof[192], const uint8_t* pu
 zk_status zk_jubjub_into_xy(const uint8_t* points, size_t n, int device, uint8_t* xy_out, uint8_t* status_out) try {
     if (n && (!points || !xy_out || !status_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     return zkxt::into_xy(points, n, device, nullptr, xy_out, status_out);
+} ZK_ABI_CATCH
+zk_status zk_elgamal_ledger_apply(size_t n_slots, const uint8_t* slots, size_t n_ops, const zk_ledger_op* ops, int device, uint8_t* slots_out,
+                                  uint8_t* before_out, uint8_t* slot_status_out, uint8_t* op_status_out) try {
+    return zkledger::apply(n_slots, slots, n_ops, ops, device, slots_out, before_out, slot_status_out, op_status_out);
 } ZK_ABI_CATCH
 zk_status zk_confidential_verify_batch(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* enc_balances,
                                        const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out) try {

@@ -119,4 +119,22 @@ inline zk_status into_xy(const uint8_t* points, size_t n, int device, IntoXyBufs
     return ZK_OK;
 }
 
+// The device form alone, nothing copied back (ledger.h): the n encodings through k_into_xy in one launch on the library stream
+// of the device in use.  bufs->out then holds n x 16 coordinate words and, behind them, n status words; in_extra / out_extra
+// bytes are reserved behind the encodings and behind the statuses (from INTO_XY_OUT_ALIGN up) for what the caller keeps there.
+constexpr size_t INTO_XY_OUT_ALIGN = 16;
+inline size_t into_xy_out_bytes(size_t n) { return (n * 68 + INTO_XY_OUT_ALIGN - 1) / INTO_XY_OUT_ALIGN * INTO_XY_OUT_ALIGN; }
+inline zk_status into_xy_on_device(const uint8_t* points, size_t n, IntoXyBufs* bufs, size_t in_extra, size_t out_extra) {
+    if (n > (size_t)1 << 30) return fail(ZK_ERR_INVALID_ARGUMENT, "more than 2^30 points in one call");
+    ZK_TRY(bufs->in.ensure(n * 32 + in_extra));
+    ZK_TRY(bufs->out.ensure(into_xy_out_bytes(n) + out_extra));
+    if (!n) return ZK_OK;
+    HIP_TRY(hipMemcpyAsync(bufs->in.p, points, n * 32, hipMemcpyHostToDevice, zkrt::g_stream));
+    uint32_t* d_xy = bufs->out.as<uint32_t>();
+    zkrt::ProfScope ps("into_xy");
+    ZK_LAUNCH(k_into_xy, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, zkrt::g_stream, (const uint32_t*)bufs->in.as<uint32_t>(), d_xy, d_xy + n * 16,
+              (uint32_t)n);
+    return ZK_OK;
+}
+
 }  // namespace zkxt
