@@ -24,6 +24,13 @@ def field_kats(lib):
         rng = synth.SplitMix64(99 + field)
         a = [bls.from_limbs64(k[name + "_mul"]["a"]), bls.from_limbs64(k[name + "_sqr"]["a"]), 0, 1, mod - 1]
         b = [bls.from_limbs64(k[name + "_mul"]["b"]), bls.from_limbs64(k[name + "_sqr"]["a"]), 5, mod - 1, mod - 1]
+        # limb edges: words of all ones, 2^(32 k) +/- 1 and mod - 2^(32 k), all below the modulus
+        edge = [((1 << (64 * n)) - 1) % mod] + [((1 << (32 * j)) + d) % mod for j in range(1, 2 * n) for d in (-1, 1)]
+        edge += [mod - (1 << (32 * j)) for j in range(1, 2 * n)]
+        a += edge
+        b += edge[::-1]
+        a += edge
+        b += edge
         for _ in range(123):
             a.append(rng.field(mod) if field == 0 else (rng.field(1 << 255) * rng.field(1 << 255)) % mod)
             b.append(rng.field(mod) if field == 0 else (rng.field(1 << 255) * rng.field(1 << 255)) % mod)

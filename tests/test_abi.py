@@ -258,3 +258,5 @@ def test_shipped_library_carries_no_test_hook():
     for name in (b"ZKAMD_INJECT_THROW", b"ZKAMD_INJECT_LANE_OOM", b"ZKAMD_INJECT_SCRATCH_SLOW", b"ZKAMD_DEBUG_RLC", b"ZKAMD_DEBUG_TIMING"):
         assert name not in shipped, name
         assert name in hooks, name
+    assert b"zk_hook_field_op" not in shipped
+    assert b"zk_hook_field_op" in hooks

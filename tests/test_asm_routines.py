@@ -1,8 +1,11 @@
 """The hand-scheduled gfx950 product routines (zero-chain_amd/csrc/mul_asm.h) without a GPU: the committed header is
 exactly what tools/gen_mul_asm.py generates, and every routine, interpreted instruction by instruction for one lane
 by tools/sim_mul_asm.py (64-bit accumulators, SGPR constants, the register contract), gives the Montgomery products
-of core/pairing/src/bls12_381/fr.rs:438-571 and fq.rs:915-1127 on random and extreme operands.  The GPU suite then
-checks the same routines as the hardware executes them (field KATs, every parity test above them)."""
+of core/pairing/src/bls12_381/fr.rs:438-571 and fq.rs:915-1127 on random and extreme operands.  That proves the text against
+this project's own model of the instructions, not against the hardware.  On the hardware the saturated FR / FQ routines run
+under the field KATs (zk_debug_field_mul) and the five radix-2^28 routines (FQ28, FQ28SQR, FQ28MAC2, FQ2MUL28, FQ28MUL2) under
+tests/test_field_ops.py, one operation at a time against Python integers on operands at the edges of their bounds; the parity
+tests above them reach the same routines with random data only."""
 import importlib.util
 import os
 

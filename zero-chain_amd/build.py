@@ -1,8 +1,10 @@
 """Build the product library in-tree:
 
   libzkamd.so         gfx950 (hipcc --offload-arch=gfx950), the C ABI of include/zkamd.h.  Cross-compiles without a GPU.
-  libzkamd_hooks.so   the same sources with -DZK_TEST_HOOKS: fault injection and debug prints (host_common.h hook_env) for the
-                      three GPU tests that need them.  The shipped library reads none of those variables.
+  libzkamd_hooks.so   the same sources with -DZK_TEST_HOOKS: fault injection and debug prints (host_common.h hook_env) and the
+                      zk_hook_* entries (the plans, the inversion on rows, csrc/field_hooks.cpp: every field operation and the
+                      XYZZ group law on limbs the test chooses) for the tests that need them.  The shipped library reads none
+                      of those variables and exports none of those entries.
 """
 import os
 import subprocess
@@ -38,7 +40,7 @@ def _run(cmd):
     subprocess.check_call(cmd)
 
 
-TRANSLATION_UNITS = ("zkamd.cpp", "verify.cpp", "witness.cpp", "setup.cpp", "hostbind.cpp", "wallet.cpp", "coop_tail.cpp", "msm_g1.cpp", "msm_g2.cpp", "coop_verify.cpp", "coop_pairing.cpp")   # compiled in parallel, linked into one library
+TRANSLATION_UNITS = ("zkamd.cpp", "verify.cpp", "witness.cpp", "setup.cpp", "hostbind.cpp", "wallet.cpp", "coop_tail.cpp", "msm_g1.cpp", "msm_g2.cpp", "coop_verify.cpp", "coop_pairing.cpp", "field_hooks.cpp")   # compiled in parallel, linked into one library
 
 
 def _deps(path, seen=None):
