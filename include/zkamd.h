@@ -55,6 +55,9 @@
  *   zk_elgamal_table_create, zk_elgamal_decrypt, zk_elgamal_table_free
  *                                   elgamal::Ciphertext::decrypt (the brute-force walk) no_std_aliases/elgamal.rs:85-108
  *   zk_elgamal_add                  elgamal::Ciphertext::add / sub                no_std_aliases/elgamal.rs:139-158
+ *   zk_confidential_scan, zk_anonymous_scan   - (a block read with one decryption key: Ciphertext::decrypt per value,
+ *                                   no_std_aliases/elgamal.rs:85-108, and the signs of MultiCiphertexts::<Anonymous>::encrypt,
+ *                                   core/proofs/src/crypto_components.rs:168-220)
  *   zk_elgamal_ledger_apply         rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
  *                                   modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350,
  *                                   modules/anonymous-balances/src/lib.rs:169-225, core/primitives/src/ciphertext.rs:90-100
@@ -354,6 +357,50 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
 void zk_elgamal_table_free(zk_elgamal_table* t);
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
                          int subtract, uint8_t* left_out, uint8_t* right_out);
+/* Reading a block with ONE decryption key: which of n accepted extrinsics touch the wallet's key, and by how much.  The reference
+ * has no counterpart (zface reads one balance, getter.rs:135-174, and keeps no history); the parts are its own: the key is
+ * EncryptionKey::from_decryption_key(dec_key) (no_std_aliases/keys.rs:250-261, computed once per call), its 32 canonical bytes
+ * are compared with the keys an extrinsic carries, and every value is Ciphertext::decrypt (elgamal.rs:85-108) over [0, limit),
+ * limit 1 .. 2^32, with the search of zk_elgamal_decrypt on the table's device.  dec_key: a canonical Fs scalar, else
+ * ZK_ERR_INVALID_ARGUMENT; taking the decryption key alone, a caller cannot hand over a pair that does not belong together.
+ * zk_confidential_scan: role bit ZK_SCAN_SENDER when enc_key_sender is the wallet's, ZK_SCAN_RECIPIENT when enc_key_recipient
+ *   is (3: a transfer to oneself, 0: neither, and nothing else of that xt is looked at).  The sender decrypts
+ *   (left_amount_sender, right_randomness) into amount_sent and (left_fee, right_randomness) into fee, the recipient
+ *   (left_amount_recipient, right_randomness) into amount_received (confidential.rs:150-157: one right half for all three).
+ *   A value that is not below the limit - or was encrypted under another key - leaves its found bit clear and its field 0.
+ * zk_anonymous_scan: members has bit i set when enc_keys[i] is the wallet's (a key may appear more than once).  For each such
+ *   i the value of v = left_ciphertexts[i] - dec_key * right_ciphertext is x < limit with x G == v, or -x with x G == -v:
+ *   MultiCiphertexts::<Anonymous>::encrypt (crypto_components.rs:168-220) puts -amount under the sender's key, +amount under
+ *   the recipient's and 0 under every decoy's.  delta is the sum over the occurrences - what the ledger adds to this key's
+ *   balance (modules/anonymous-balances/src/lib.rs:169-225) - and found 1 only when every occurrence has a value; else delta is 0.
+ * Refusals are results, never errors.  Only the points the wallet's role uses are read, as Ciphertext::read reads them
+ *   (Point::read, then as_prime_order: what zk_jubjub_into_xy decides): refusal = (field number of zk_confidential_verify_batch /
+ *   zk_anonymous_verify_batch) | (ZK_INTO_XY_* status << 6) of the first of them, in push order, that is refused; found and the
+ *   values of that extrinsic are then 0.  A malformed point in an extrinsic that does not match is not looked at.
+ * NOT looked at: proofs, signatures, rvk, rsk, nonce and enc_balance.  The scan is for extrinsics the chain has ACCEPTED (verify
+ *   them with zk_confidential_verify_batch / zk_anonymous_verify_batch and zk_redjubjub_verify_batch first).
+ * Up to ZKAMD_SCAN_HOST_MAX values to decrypt (default 128, the measured crossover on 16 host threads; read per
+ *   call; 0 = always the kernels) the point work - decoding, dec_key * right once per extrinsic - runs on the host threads, above it in two
+ *   kernels on the table's device (csrc/elgamal_scan.h); the bytes written do not depend on the form.  dec_key and everything
+ *   derived from it are wiped on the host and zeroed on the device before the call returns.  The host form multiplies without
+ *   branching on dec_key; the device form is NOT constant-time: the recoded digits of dec_key decide where its chain adds.
+ * t == NULL, or a NULL xts / dec_key / out with n > 0: ZK_ERR_INVALID_ARGUMENT.  n == 0 touches nothing. */
+enum { ZK_SCAN_SENDER = 1, ZK_SCAN_RECIPIENT = 2 };                       /* role bits */
+enum { ZK_SCAN_FOUND_SENT = 1, ZK_SCAN_FOUND_FEE = 2, ZK_SCAN_FOUND_RECEIVED = 4 };
+typedef struct {            /* 16 bytes */
+    uint8_t role;           /* 0: neither key of the xt is the wallet's; 3: a transfer to oneself */
+    uint8_t found;          /* which of the three values below were found below the limit */
+    uint8_t refusal;        /* 0, or field | status << 6 */
+    uint8_t reserved;       /* 0 */
+    uint32_t amount_sent, fee, amount_received;
+} zk_confidential_scan_result;
+typedef struct {            /* 16 bytes */
+    uint16_t members;       /* bit i set: enc_keys[i] is the wallet's key; 0: absent */
+    uint8_t found;          /* 1: every occurrence decrypted to a value with |value| < limit */
+    uint8_t refusal;        /* 0, or field | status << 6 */
+    uint32_t reserved;      /* 0 */
+    int64_t delta;          /* sum over the occurrences: +a received, -a sent, 0 decoy */
+} zk_anonymous_scan_result;
 /* zk_elgamal_ledger_apply: what the three balance modules do to storage around every proof of a block (rollover,
  *   sub_enc_balance, add_pending_transfer: modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350;
  *   twelve updates per extrinsic in modules/anonymous-balances/src/lib.rs:169-225) - Ciphertext::add / Ciphertext::sub
@@ -443,6 +490,11 @@ typedef struct {   /* AnonymousXt, anonymous.rs:351-359 */
     uint8_t right_ciphertext[32], nonce[32], rsk[32], rvk[32];
 } zk_anonymous_xt;
 zk_status zk_anonymous_derive(const zk_anonymous_request* req, size_t n, zk_anonymous_statement* statements_out, uint8_t* rsk_out);
+/* the two scans (declared with zk_elgamal_decrypt above, where their results are) */
+zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
+                               zk_confidential_scan_result* out);
+zk_status zk_anonymous_scan(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
+                            zk_anonymous_scan_result* out);
 zk_status zk_anonymous_gen_proof_batch(zk_params* p, zk_r1cs* circuit, struct zk_vk* vk, size_t n, const zk_anonymous_request* req,
                                        const uint8_t* rs, zk_anonymous_xt* out);
 

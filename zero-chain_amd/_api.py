@@ -24,7 +24,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
                    ZK_NTT_OUT_BITREV)
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
-           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
+           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
@@ -810,6 +810,14 @@ ELGAMAL_DECRYPT_LIMIT = 1000000                                  # the reference
 ZERO_CIPHERTEXT = (b"\x01" + bytes(31), b"\x01" + bytes(31))     # Ciphertext::zero(): the identity twice
 
 
+SCAN_SENDER, SCAN_RECIPIENT = 1, 2                                # zk_confidential_scan_result.role
+SCAN_FOUND_SENT, SCAN_FOUND_FEE, SCAN_FOUND_RECEIVED = 1, 2, 4    # ... .found
+
+
+def _scan_refusal(v, names):
+    return None if not v else (names[(int(v) & 63) - 1], INTO_XY_REASONS[int(v) >> 6])
+
+
 def _points(encodings, n):
     return _u8(b"".join(bytes(e) for e in encodings), 32 * n)
 
@@ -844,6 +852,42 @@ class ElGamalTable:
         finally:
             kb[:] = 0   # (the caller's copy of the keys is the caller's)
         return [int(v) if f else None for v, f in zip(values, found)]
+
+    def _scan(self, fn, ctype, fill, result, xts, dec_key, limit):
+        if isinstance(xts, (bytes, bytearray, memoryview)):   # the packed extrinsics as they lie in memory
+            raw = bytes(xts)
+            if len(raw) % C.sizeof(ctype):
+                raise ValueError("%d bytes are no whole number of %s" % (len(raw), ctype.__name__))
+            arr = (ctype * (len(raw) // C.sizeof(ctype))).from_buffer_copy(raw)
+        else:
+            arr = _xt_array(xts, ctype, fill)
+        n = len(arr)
+        kb = scalars_to_bytes([int(dec_key)])
+        out = (result * max(n, 1))()
+        try:
+            self._lib.check(fn(self._h, n, arr if n else None, _ptr(kb), int(limit), out if n else None))
+        finally:
+            kb[:] = 0
+        return out[:n]
+
+    def scan_confidential(self, xts, dec_key, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_confidential_scan: which of the accepted ConfidentialXt `xts` - the array gen_proofs(..., raw=True) returns, a list
+        of such structures or of xt_fields dicts, or their raw bytes - carry the key of `dec_key` (an Fs integer), and the amounts
+        they move.  One dict per xt: role (0, SCAN_SENDER, SCAN_RECIPIENT or both), amount_sent, fee, amount_received (an int,
+        or None where no value below `limit` was found or the role does not use it) and refusal (None, or (field name, reason) of
+        the first used point that Ciphertext::read refuses; the values are then None).  Proofs and signatures are not looked at."""
+        res = self._scan(self._lib.zk_confidential_scan, _lib.ConfidentialXt, _fill_confidential_xt, _lib.ConfidentialScanResult, xts, dec_key, limit)
+        return [{"role": r.role, "refusal": _scan_refusal(r.refusal, CONFIDENTIAL_XT_POINTS),
+                 "amount_sent": r.amount_sent if r.found & SCAN_FOUND_SENT else None, "fee": r.fee if r.found & SCAN_FOUND_FEE else None,
+                 "amount_received": r.amount_received if r.found & SCAN_FOUND_RECEIVED else None} for r in res]
+
+    def scan_anonymous(self, xts, dec_key, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_anonymous_scan for accepted AnonymousXt (the dicts anonymous_gen_proofs returns, structures, or raw bytes).  One dict
+        per xt: members (the positions of the key among the twelve enc_keys; empty: absent), delta (the sum over them of +amount
+        received, -amount sent, 0 as a decoy; None unless every occurrence has a value with |value| < limit) and refusal."""
+        res = self._scan(self._lib.zk_anonymous_scan, _lib.AnonymousXt, _fill_anonymous_xt, _lib.AnonymousScanResult, xts, dec_key, limit)
+        return [{"members": [k for k in range(ANONYMOUS_SIZE) if r.members >> k & 1], "refusal": _scan_refusal(r.refusal, ANONYMOUS_XT_POINTS),
+                 "delta": r.delta if r.found else None} for r in res]
 
     def close(self):
         if self._h:

@@ -90,6 +90,15 @@ class LedgerOp(C.Structure):
     _fields_ = [("slot", C.c_uint32), ("flags", C.c_uint32), ("left", C.c_uint8 * 32), ("right", C.c_uint8 * 32)]
 
 
+class ConfidentialScanResult(C.Structure):
+    _fields_ = [("role", C.c_uint8), ("found", C.c_uint8), ("refusal", C.c_uint8), ("reserved", C.c_uint8),
+                ("amount_sent", C.c_uint32), ("fee", C.c_uint32), ("amount_received", C.c_uint32)]
+
+
+class AnonymousScanResult(C.Structure):
+    _fields_ = [("members", C.c_uint16), ("found", C.c_uint8), ("refusal", C.c_uint8), ("reserved", C.c_uint32), ("delta", C.c_int64)]
+
+
 class BatchDev(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("n_inputs", C.c_uint32), ("n_aux", C.c_uint32), ("flags", C.c_uint32),
                 ("d_a", C.c_void_p), ("d_b", C.c_void_p), ("d_c", C.c_void_p), ("d_wit", C.c_void_p),
@@ -138,6 +147,9 @@ _PROTOS = {
                                        C.c_void_p]),
     "zk_elgamal_table_free": (None, [C.c_void_p]),
     "zk_elgamal_add": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
+    "zk_confidential_scan": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_uint64,
+                                         C.POINTER(ConfidentialScanResult)]),
+    "zk_anonymous_scan": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_uint64, C.POINTER(AnonymousScanResult)]),
     "zk_elgamal_ledger_apply": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LedgerOp), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "zk_transfer_derive": (C.c_int32, [C.POINTER(TransferRequest), C.c_size_t, C.POINTER(TransferStatement), C.c_void_p]),

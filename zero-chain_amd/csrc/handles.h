@@ -78,12 +78,21 @@ struct zk_elgamal_table {
     zkrt::DevBuf consts, baby_xy, slots, giant_xy;
     // key-derived (left - dk right, the search's points, the logarithms): zeroed before release
     zkrt::DevBuf v, scratch, res;
-    zk_elgamal_table() { consts.is_public = baby_xy.is_public = slots.is_public = giant_xy.is_public = true; }
+    // the point stage of zk_confidential_scan / zk_anonymous_scan (elgamal_scan.h).  Public chain data: the encodings and the
+    // rows that pair them | their coordinates, statuses and the rows' flags.  Key-derived: the digits of dk and dk * right
+    zkrt::DevBuf scan_in, scan_out, scan_key;
+    zk_elgamal_table() {
+        consts.is_public = baby_xy.is_public = slots.is_public = giant_xy.is_public = scan_in.is_public = scan_out.is_public = true;
+    }
 };
 // witness.cpp: build the baby-step table of T (baby_bits, fp_bits and device set); the search for n points v (affine,
 // Montgomery x | y) over [0, limit): x_out[i] = the logarithm, or ~0 when there is none below the limit
 zk_status elgamal_table_build(zk_elgamal_table* T);
 zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v, uint64_t limit, uint64_t* x_out);
+// ... and its second half alone: the nb <= ELGAMAL_SEARCH_BLOCK points are already in T->v, written on the library stream (by
+// the copy of elgamal_dlog_search, or by k_scan_combine).  T->v is zeroed again on every way out.
+constexpr size_t ELGAMAL_SEARCH_BLOCK = (size_t)1 << 20;   // points per launch
+zk_status elgamal_dlog_search_resident(zk_elgamal_table* T, size_t nb, uint64_t limit, uint64_t* x_out);
 
 // Groth16 verification of a batch (verify.cpp; zk_verify_batch is this with own_proofs = false).  own_proofs: the
 // proofs are this library's own fresh results (gen_proof's self-check) - decoded without the r-torsion test.

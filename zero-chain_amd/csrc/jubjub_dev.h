@@ -6,7 +6,9 @@
 //   sqrt_one_pow             square root in Fr with ONE exponentiation, then Tonelli-Shanks (~290 + <= 500)
 //   ext_dbl, cache_put, ext_add_cached   extended twisted Edwards, a = -1: dbl-2008-hwcd, addends cached as (Y + X, Y - X, 2 d T, 2 Z)
 //   ext_add                  two extended points, add-2008-hwcd-3 (9 products): the operator of ledger.h's scan
+//   naf_chain                sum of signed odd digits times the cached P, 3P, 5P, 7P: 252 doublings, an addition per non-zero digit
 //   is_prime_order           [s]P == O over the width-4 NAF of s recoded at compile time (~2 200)
+//   mul_naf                  [k]P over a width-4 NAF recoded by the host at run time (elgamal_scan.h: ~2 400)
 //   read_point               edwards::Point::read: y, and x by 1 / (d y^2 + 1) and the square root (~620)
 #pragma once
 #include "dev_field.h"
@@ -185,10 +187,8 @@ ZK_DI EP ext_add(const EP& p, const EP& q, const Fr& d2) {
     const Fr e = sub(b, a), f = sub(d, c), g = add(d, c), h = add(b, a);
     return EP{mul(e, f), mul(g, h), mul(f, g), mul(e, h)};
 }
-// [s](x, y) == O ?
-ZK_DI bool is_prime_order(const Lds& L, const Fr& x, const Fr& y, const Fr& d2) {
-    constexpr NafDigits S = digits_order();
-    const EP p1{x, y, Fr::one(), mul(x, y)};
+// P, 3P, 5P, 7P as addends in slots 0 .. 15
+ZK_DI void cache_odd_multiples(const Lds& L, const EP& p1, const Fr& d2) {
     cache_put(L, 0, p1, d2);
     cache_put(L, 3, ext_dbl(p1, true), d2);   // 2P, in the place of 7P until 7P is written
     EP q = p1;
@@ -197,14 +197,32 @@ ZK_DI bool is_prime_order(const Lds& L, const Fr& x, const Fr& y, const Fr& d2) 
         q = ext_add_cached(L, q, 3, false, true);
         cache_put(L, i, q, d2);
     }
+}
+// sum_i digit(i) 2^i P over the cached multiples of P: digit(i) is 0 or odd in -7 .. 7 (a width-4 NAF), i = top .. 0, the same
+// in every lane of the wave.  T of the result only where want_t.
+template <class Digit>
+ZK_DI EP naf_chain(const Lds& L, int top, Digit digit, bool want_t) {
     EP acc{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()};
 #pragma unroll 1
-    for (int i = S.top; i >= 0; i--) {
-        const int v = S.d[i];
-        acc = ext_dbl(acc, v != 0);
-        if (v) acc = ext_add_cached(L, acc, (uint32_t)((v < 0 ? -v : v) >> 1), v < 0, false);
+    for (int i = top; i >= 0; i--) {
+        const int v = digit(i);
+        acc = ext_dbl(acc, v != 0 || (want_t && i == 0));
+        if (v) acc = ext_add_cached(L, acc, (uint32_t)((v < 0 ? -v : v) >> 1), v < 0, want_t && i == 0);
     }
+    return acc;
+}
+// [s](x, y) == O ?
+ZK_DI bool is_prime_order(const Lds& L, const Fr& x, const Fr& y, const Fr& d2) {
+    constexpr NafDigits S = digits_order();
+    cache_odd_multiples(L, EP{x, y, Fr::one(), mul(x, y)}, d2);
+    const EP acc = naf_chain(L, S.top, [&](int i) { return (int)S.d[i]; }, false);
     return acc.X.is_zero() && acc.Y == acc.Z;
+}
+// [k](x, y) in extended coordinates for a scalar the host recoded (d: its width-4 NAF, least significant first; top: the index
+// of its last non-zero digit, -1 for k = 0).  Every lane of the wave reads the same digits: one chain shape for all.
+ZK_DI EP mul_naf(const Lds& L, const Fr& x, const Fr& y, const Fr& d2, const int8_t* d, int top) {
+    cache_odd_multiples(L, EP{x, y, Fr::one(), mul(x, y)}, d2);
+    return naf_chain(L, top, [&](int i) { return (int)d[i]; }, true);
 }
 
 // edwards::Point::read (edwards.rs:92-165) of the encoding in the 8 words at enc: INTO_XY_OK, _NOT_IN_FIELD or _NOT_ON_CURVE.

@@ -8,8 +8,9 @@
 //   elgamal::Ciphertext::add / sub   elgamal.rs:139-158
 //   check_proof + ConfidentialXt / AnonymousXt packing   confidential.rs:208-361, anonymous.rs:200-352
 //   redjubjub PrivateKey::sign / PublicKey::verify       core/jubjub/src/redjubjub.rs:73-103, 127-155 (redjubjub.h)
+//   a block read with one decryption key                 - (elgamal.rs:85-108 per value, crypto_components.rs:168-220; elgamal_scan.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
-// the signature check (redjubjub.h).
+// the signature check (redjubjub.h) and the two of the scan's point stage (elgamal_scan.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -242,6 +243,7 @@ zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_s
 }  // namespace
 
 #include "redjubjub.h"   // (here: it signs and hashes with the helpers above)
+#include "elgamal_scan.h"   // (and the scan decodes, multiplies and wipes with them)
 
 extern "C" {
 
@@ -418,6 +420,16 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
         found_out[i] = found ? 1 : 0;
     }
     return ZK_OK;
+} ZK_ABI_CATCH
+
+zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
+                               zk_confidential_scan_result* out) try {
+    return zkscan::confidential(t, n, xts, dec_key, limit, out);
+} ZK_ABI_CATCH
+
+zk_status zk_anonymous_scan(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
+                            zk_anonymous_scan_result* out) try {
+    return zkscan::anonymous(t, n, xts, dec_key, limit, out);
 } ZK_ABI_CATCH
 
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,

@@ -218,9 +218,9 @@ zk_status elgamal_table_build(zk_elgamal_table* T) {
     HIP_TRY(hipStreamSynchronize(g_stream));
     return ZK_OK;
 }
-zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v, uint64_t limit, uint64_t* x_out) {
+// the search over the nb points resident in T->v
+static zk_status dlog_search_rows(zk_elgamal_table* T, size_t nb, uint64_t limit, uint64_t* x_out) {
     using namespace zkdlog;
-    static_assert(sizeof(zkhost::Fr) == 32 && sizeof(unsigned long long) == sizeof(uint64_t), "layouts");
     const uint32_t b = T->baby_bits, w = giant_stride_log(b);
     const uint64_t steps = (limit + (1ull << b) - 1) >> b;
     const uint32_t chunks = (uint32_t)((steps + (1ull << w) - 1) >> w);   // <= 2^16 (giant_stride_log)
@@ -232,48 +232,60 @@ zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v
         ZK_TRY(dlog_multiples(T, T->giant_xy.as<uint32_t>(), log, b + w));
         T->giant_count = 1u << log;
     }
-    constexpr size_t BLOCK = (size_t)1 << 20;   // ciphertexts per launch
-    for (size_t first = 0; first < n; first += BLOCK) {
-        const size_t nb = std::min(BLOCK, n - first);
-        ZK_TRY(T->v.ensure(nb * 64));
-        ZK_TRY(T->res.ensure(nb * 8));
-        Search s;
-        s.tab = dlog_table(T);
-        s.v = T->v.as<uint32_t>();
-        s.giant = T->giant_xy.as<uint32_t>();
-        s.consts = T->consts.as<uint32_t>();
-        s.scratch = nullptr;
-        s.res = T->res.as<unsigned long long>();
-        s.limit = limit;
-        s.steps = steps;
-        s.n = (uint32_t)nb;
-        s.baby_bits = b;
-        s.w_log = w;
-        s.chunks = chunks;
-        s.lanes = 0;
-        HIP_TRY(hipMemcpyAsync(T->v.p, v + first * 2, nb * 64, hipMemcpyHostToDevice, g_stream));
-        HIP_TRY(hipMemsetAsync(T->res.p, 0xff, nb * 8, g_stream));   // NOT_FOUND
-        size_t scratch_used = 0;
-        {
-            ProfScope ps("elgamal_dlog", g_stream);
-            if (steps == 1) {   // limit <= 2^b: the table holds the whole range
-                ZK_LAUNCH(k_dlog_probe, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, g_stream, s);
-            } else {
-                const uint64_t items = (uint64_t)nb * chunks;
-                s.lanes = (uint32_t)std::min<uint64_t>((items + 63) / 64 * 64, SEARCH_LANES);
-                scratch_used = (size_t)s.lanes * SEARCH_BATCH * 4 * 32;
-                ZK_TRY(T->scratch.ensure(scratch_used));
-                s.scratch = T->scratch.as<uint32_t>();
-                ZK_LAUNCH(k_dlog_search, dim3(s.lanes / 64), dim3(64), 0, g_stream, s);
-            }
+    ZK_TRY(T->res.ensure(nb * 8));
+    Search s;
+    s.tab = dlog_table(T);
+    s.v = T->v.as<uint32_t>();
+    s.giant = T->giant_xy.as<uint32_t>();
+    s.consts = T->consts.as<uint32_t>();
+    s.scratch = nullptr;
+    s.res = T->res.as<unsigned long long>();
+    s.limit = limit;
+    s.steps = steps;
+    s.n = (uint32_t)nb;
+    s.baby_bits = b;
+    s.w_log = w;
+    s.chunks = chunks;
+    s.lanes = 0;
+    HIP_TRY(hipMemsetAsync(T->res.p, 0xff, nb * 8, g_stream));   // NOT_FOUND
+    size_t scratch_used = 0;
+    {
+        ProfScope ps("elgamal_dlog", g_stream);
+        if (steps == 1) {   // limit <= 2^b: the table holds the whole range
+            ZK_LAUNCH(k_dlog_probe, dim3((unsigned)((nb + 63) / 64)), dim3(64), 0, g_stream, s);
+        } else {
+            const uint64_t items = (uint64_t)nb * chunks;
+            s.lanes = (uint32_t)std::min<uint64_t>((items + 63) / 64 * 64, SEARCH_LANES);
+            scratch_used = (size_t)s.lanes * SEARCH_BATCH * 4 * 32;
+            ZK_TRY(T->scratch.ensure(scratch_used));
+            s.scratch = T->scratch.as<uint32_t>();
+            ZK_LAUNCH(k_dlog_search, dim3(s.lanes / 64), dim3(64), 0, g_stream, s);
         }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(x_out + first, T->res.p, nb * 8, hipMemcpyDeviceToHost, g_stream));
-        // the key-derived points do not stay on the device between calls
-        HIP_TRY(hipMemsetAsync(T->v.p, 0, nb * 64, g_stream));
-        if (scratch_used) HIP_TRY(hipMemsetAsync(T->scratch.p, 0, scratch_used, g_stream));
-        HIP_TRY(hipMemsetAsync(T->res.p, 0, nb * 8, g_stream));
-        HIP_TRY(hipStreamSynchronize(g_stream));
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(x_out, T->res.p, nb * 8, hipMemcpyDeviceToHost, g_stream));
+    // the key-derived points do not stay on the device between calls
+    HIP_TRY(hipMemsetAsync(T->v.p, 0, nb * 64, g_stream));
+    if (scratch_used) HIP_TRY(hipMemsetAsync(T->scratch.p, 0, scratch_used, g_stream));
+    HIP_TRY(hipMemsetAsync(T->res.p, 0, nb * 8, g_stream));
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return ZK_OK;
+}
+zk_status elgamal_dlog_search_resident(zk_elgamal_table* T, size_t nb, uint64_t limit, uint64_t* x_out) {
+    static_assert(sizeof(zkhost::Fr) == 32 && sizeof(unsigned long long) == sizeof(uint64_t), "layouts");
+    const zk_status rc = dlog_search_rows(T, nb, limit, x_out);
+    if (rc != ZK_OK) {   // (a failure before the wipes above: the points are in T->v already)
+        (void)hipMemsetAsync(T->v.p, 0, nb * 64, g_stream);
+        (void)hipStreamSynchronize(g_stream);
+    }
+    return rc;
+}
+zk_status elgamal_dlog_search(zk_elgamal_table* T, size_t n, const zkhost::Fr* v, uint64_t limit, uint64_t* x_out) {
+    for (size_t first = 0; first < n; first += ELGAMAL_SEARCH_BLOCK) {
+        const size_t nb = std::min(ELGAMAL_SEARCH_BLOCK, n - first);
+        ZK_TRY(T->v.ensure(nb * 64));
+        HIP_TRY(hipMemcpyAsync(T->v.p, v + first * 2, nb * 64, hipMemcpyHostToDevice, g_stream));
+        ZK_TRY(elgamal_dlog_search_resident(T, nb, limit, x_out + first));
     }
     return ZK_OK;
 }
