@@ -79,7 +79,11 @@
  *   zk_jubjub_into_xy               IntoXY of the primitives (Point::read + as_prime_order + into_xy)   core/primitives/src/enc_key.rs:89, core/jubjub/src/curve/edwards.rs:92-165, :319-330
  *   zk_confidential_verify_batch    zk_system::verify_confidential_proof          modules/zk-system/src/lib.rs:56-115, input_builder.rs:15-27
  *   zk_anonymous_verify_batch       zk_system::verify_anonymous_proof             modules/zk-system/src/lib.rs:118-165
- *   zk_redjubjub_sign               redjubjub::PrivateKey::sign                   core/jubjub/src/redjubjub.rs:73-103; callers confidential.rs:416-420, anonymous.rs:378-401
+ *   zk_confidential_block_execute   encrypted_balances::confidential_transfer for every extrinsic of a block, in order
+ *                                   modules/encrypted-balances/src/lib.rs:25-96 (rollover :133-170, sub_enc_balance :173-196,
+ *                                   add_pending_transfer :199-222), modules/zk-system/src/lib.rs:56-115
+ *   zk_g_epoch                      GEpoch::group_hash                            core/primitives/src/g_epoch.rs:102-110, core/jubjub/src/group_hash.rs:17-46
+ *   zk_redjubjub_sign               redjubjub::PrivateKey::sign                 core/jubjub/src/redjubjub.rs:73-103; callers confidential.rs:416-420, anonymous.rs:378-401
  *   zk_redjubjub_verify_batch       redjubjub::PublicKey::verify, per signature   core/jubjub/src/redjubjub.rs:127-155; RedjubjubSignature::verify core/primitives/src/signature.rs:65-82
  *   zk_msm_create, zk_msm_create_variable, zk_msm_run, zk_msm_run_dev, zk_msm_free, zk_msm_g1, zk_msm_g2, zk_msm_cache_release
  *                                   bellman multiexp(FullDensity); group law core/pairing/src/bls12_381/ec.rs:296-526
@@ -590,6 +594,71 @@ zk_status zk_confidential_verify_batch(zk_vk* vk, size_t n, const zk_confidentia
  * right, 49 right_ciphertext, 50 rvk, 51 g_epoch, 52 nonce; enc_balances: n x 12 x 64 bytes, required; 104 inputs. */
 zk_status zk_anonymous_verify_batch(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* enc_balances,
                                     const uint8_t* g_epochs, size_t g_epoch_stride, uint8_t* ok_out, uint8_t* refusal_out);
+
+/* ------------------------------------------------------------------------------------------
+ * A block of confidential transfers executed in one call: encrypted_balances::confidential_transfer
+ * (modules/encrypted-balances/src/lib.rs:25-96) for n extrinsics IN ORDER, over the stored state of the accounts they name, the
+ * nonce pool and g_epoch.  The result - a verdict per extrinsic and the accounts to store - equals that of this loop over the
+ * extrinsics; acc(k) is the account whose enc_key has the bytes k, the pool starts as nonce_pool:
+ *   1. Signature.  sigs given and signature i (message i of msgs / msg_offsets as zk_redjubjub_verify_batch, key xts[i].rvk)
+ *      does not verify: BAD_SIGNATURE, detail = the reason of zk_redjubjub_verify_batch.  Nothing else happens: the call is
+ *      never dispatched (ensure_signed, lib.rs:36).  sigs == NULL: signatures are not this call's business.
+ *   2. Stored account unreadable.  acc(sender) or acc(recipient) holds a balance or pending ciphertext that Ciphertext::read
+ *      refuses (what zk_jubjub_into_xy decides): BAD_ACCOUNT, nothing else happens.  The outputs of an unreadable account that a
+ *      dispatched extrinsic names are 64 zero bytes twice, as for the ledger's refused slot.  (So the balance - fields 7 and 8 of
+ *      zk_confidential_verify_batch - is never the refused point of step 5.)
+ *   3. Rollover (lib.rs:41-46, 133-170).  rollover(sender), then rollover(recipient): an account with ZK_BLOCK_ROLLOVER_DUE
+ *      that has not rolled over in this block gets balance += pending, pending = Ciphertext::zero(), and ZK_BLOCK_ROLLED in its
+ *      output flags.  This stays whatever happens to the extrinsic below.
+ *   4. Nonce.  nonce is in the pool (equal bytes, as Vec<Nonce>::contains): NONCE_USED.  The reference assert!s here (lib.rs:49)
+ *      and pushes an accepted nonce onto a COPY of the pool (lib.rs:69: nonce_pool() returns the vector by value); this entry does
+ *      what those lines mean to do - a rejection, and a pool that grows with every accepted extrinsic of the block.
+ *   5. Public inputs.  Those of verify_confidential_proof (the eleven fields of zk_confidential_verify_batch), balance_sender =
+ *      acc(sender).balance as it stands at this moment.  A refused point: REFUSED_POINT, detail = field | status << 6.
+ *   6. Proof.  verify_proof fails: INVALID_PROOF.
+ *   7. ACCEPTED: the nonce joins the pool; acc(sender).balance -= (left_amount_sender, right_randomness) + (left_fee,
+ *      right_randomness); acc(recipient).pending += (left_amount_recipient, right_randomness).
+ * accounts_out[a] is account a after the loop, its ciphertexts as Point::write gives them (canonical); an account that no
+ * dispatched extrinsic names is copied through, flags and all.  The caller stores the accounts, sets LastRollOver where ROLLED is
+ * set, appends the nonces of the accepted extrinsics to its pool and pays the fees: storage, epochs and fees stay the runtime's.
+ * A bad extrinsic is a verdict, never an error.  ZK_ERR_INVALID_ARGUMENT (the index in zk_last_error(), nothing written): an
+ * extrinsic whose sender or recipient key is not among the accounts, two accounts with equal keys, a NULL buffer with a non-zero
+ * count, offsets that decrease.  ZK_ERR_MALFORMED_VERIFYING_KEY unless the key has 22 inputs.  n == 0 copies the accounts through.
+ * Exactness does not rest on the proof system's soundness: the call proceeds in rounds.  A round verifies, in one batch, every
+ * extrinsic whose verdict is open, each against the balance it meets if every still-open predecessor is rejected; a sweep in
+ * order settles those whose hypothesis held (the first open one always does).  A block in which no sender has two extrinsics
+ * that pass steps 1-5 takes ONE round and verifies each proof at most once; an extrinsic settled at steps 1, 2, 4 or 5 is not
+ * verified at all.  stats_out (may be NULL): rounds (0 when steps 1 and 2 settle everything), the proofs verified over all
+ * rounds, and the distinct 32-byte encodings decoded - eight per extrinsic, four per account, g_epoch, each once.
+ * Up to ZKAMD_INTO_XY_HOST_MAX distinct encodings (read per call) the point work runs on the host threads, above it on the key's
+ * device (csrc/block_exec.h); the verification always runs on the key's device.  The bytes written do not depend on the form.
+ * ------------------------------------------------------------------------------------------ */
+#define ZK_BLOCK_ROLLOVER_DUE 1u   /* in:  last_rollover < current epoch (lib.rs:145) */
+#define ZK_BLOCK_ROLLED       2u   /* out: rolled over by this block: the caller sets LastRollOver */
+typedef struct {
+    uint8_t enc_key[32];
+    uint8_t balance[64], pending[64];  /* EncryptedBalance / PendingTransfer, left | right; None = Ciphertext::zero() */
+    uint32_t flags;
+} zk_block_account;
+enum { ZK_BLOCK_ACCEPTED = 0, ZK_BLOCK_BAD_SIGNATURE = 1, ZK_BLOCK_NONCE_USED = 2, ZK_BLOCK_BAD_ACCOUNT = 3,
+       ZK_BLOCK_REFUSED_POINT = 4, ZK_BLOCK_INVALID_PROOF = 5 };
+typedef struct {
+    uint8_t verdict;    /* ZK_BLOCK_* */
+    uint8_t detail;     /* BAD_SIGNATURE: reason of zk_redjubjub_verify_batch; REFUSED_POINT: the refusal byte of
+                           zk_confidential_verify_batch (field | status << 6); else 0 */
+    uint16_t reserved;
+} zk_block_verdict;
+typedef struct { uint32_t rounds, proofs_verified, points_decoded, reserved; } zk_block_stats;
+zk_status zk_confidential_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts,
+    const uint8_t* sigs /* n x 64 or NULL: signatures are not this call's business */,
+    const uint8_t* msgs, const uint64_t* msg_offsets /* as zk_redjubjub_verify_batch; vk of xt i = xts[i].rvk */,
+    size_t n_accounts, const zk_block_account* accounts, size_t n_pool, const uint8_t* nonce_pool /* n_pool x 32 */,
+    const uint8_t g_epoch[32], zk_block_account* accounts_out, zk_block_verdict* verdicts_out,
+    zk_block_stats* stats_out /* may be NULL */);
+/* GEpoch::group_hash (core/primitives/src/g_epoch.rs:102-110): the Jubjub group hash (core/jubjub/src/group_hash.rs:17-46,
+ * find_group_hash curve/mod.rs:223-247) personalised "zcgepoch" over the four little-endian bytes of `epoch` and a counter byte
+ * from 0 - the g_epoch every wallet and verifier entry takes.  Host only.  out: Point::write of the point. */
+zk_status zk_g_epoch(uint32_t epoch, uint8_t out[32]);
 
 /* ------------------------------------------------------------------------------------------
  * RedJubjub (core/jubjub/src/redjubjub.rs): the signature an extrinsic carries.  The wallet signs with the rsk the derive

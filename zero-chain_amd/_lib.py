@@ -90,6 +90,18 @@ class LedgerOp(C.Structure):
     _fields_ = [("slot", C.c_uint32), ("flags", C.c_uint32), ("left", C.c_uint8 * 32), ("right", C.c_uint8 * 32)]
 
 
+class BlockAccount(C.Structure):
+    _fields_ = [("enc_key", C.c_uint8 * 32), ("balance", C.c_uint8 * 64), ("pending", C.c_uint8 * 64), ("flags", C.c_uint32)]
+
+
+class BlockVerdict(C.Structure):
+    _fields_ = [("verdict", C.c_uint8), ("detail", C.c_uint8), ("reserved", C.c_uint16)]
+
+
+class BlockStats(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("rounds", "proofs_verified", "points_decoded", "reserved")]
+
+
 class ConfidentialScanResult(C.Structure):
     _fields_ = [("role", C.c_uint8), ("found", C.c_uint8), ("refusal", C.c_uint8), ("reserved", C.c_uint8),
                 ("amount_sent", C.c_uint32), ("fee", C.c_uint32), ("amount_received", C.c_uint32)]
@@ -173,6 +185,10 @@ _PROTOS = {
                                                  C.c_void_p, C.c_void_p]),
     "zk_anonymous_verify_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_void_p, C.c_size_t,
                                               C.c_void_p, C.c_void_p]),
+    "zk_confidential_block_execute": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.POINTER(BlockAccount), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BlockAccount),
+                                                  C.POINTER(BlockVerdict), C.POINTER(BlockStats)]),
+    "zk_g_epoch": (C.c_int32, [C.c_uint32, C.c_void_p]),
     "zk_redjubjub_sign": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zk_redjubjub_verify_batch": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "zk_anonymous_prove_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousStatement), C.c_void_p,

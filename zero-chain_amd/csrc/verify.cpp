@@ -21,6 +21,7 @@
 #include "coop_verify.h"
 #include "xt_inputs.h"
 #include "ledger.h"
+#include "block_exec.h"
 #include "verify_plan.h"
 
 using namespace zkrt;
@@ -136,6 +137,8 @@ struct zk_vk {
     DevBuf rlc_rho, rlc_s, rlc_pts, rlc_c, rlc_csum, rlc_acc, rlc_inf, rlc_all, rlc_exp, rlc_want, rlc_prod, rlc_fe;
     DevBuf rlc_ab_lambda;   // e(alpha, beta)^lambda, lambda = -x^2 (the coefficients are a_i + b_i lambda: pairing.h k_rlc_scale)
     zkxt::IntoXyBufs xt;    // IntoXY of the extrinsics' points (xt_inputs.h)
+    DevBuf block;           // the block executor's ledger layout, scan results and public inputs (block_exec.h; public chain state)
+    PinBuf block_rows;      // ... and the rows of public inputs of a round on their way into verify_batch
     // the G1 decoder and the input accumulator run beside the G2 decoder on the lane's side streams
     hipEvent_t ev_join[2] = {nullptr, nullptr};
     // Blake2s over e(alpha, beta), the prepared -gamma / -delta coefficients and ic: the domain separation of the combined
@@ -1059,6 +1062,23 @@ zk_status zk_anonymous_verify_batch(zk_vk* vk, size_t n, const zk_anonymous_xt* 
         }
     };
     return xt_verify_batch(vk, n, xts, g_epochs, g_epoch_stride, ok_out, refusal_out, 4 * ZK_ANONYMOUS_SIZE + 4, 4 * ZK_ANONYMOUS_SIZE + 3, field);
+} ZK_ABI_CATCH
+zk_status zk_confidential_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* sigs, const uint8_t* msgs,
+                                        const uint64_t* msg_offsets, size_t n_accounts, const zk_block_account* accounts, size_t n_pool,
+                                        const uint8_t* nonce_pool, const uint8_t g_epoch[32], zk_block_account* accounts_out,
+                                        zk_block_verdict* verdicts_out, zk_block_stats* stats_out) try {
+    if (!vk) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (vk->ic.size() != 2 * zkblock::XT_FIELDS + 1) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "the key does not have 22 public inputs");
+    vk->block.is_public = true;
+    auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
+        return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::XT_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
+    };
+    return zkblock::execute(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool, nonce_pool,
+                            g_epoch, accounts_out, verdicts_out, stats_out);
+} ZK_ABI_CATCH
+zk_status zk_g_epoch(uint32_t epoch, uint8_t out[32]) try {
+    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    return zkblock::g_epoch(epoch, out);
 } ZK_ABI_CATCH
 
 #ifdef ZK_TEST_HOOKS
