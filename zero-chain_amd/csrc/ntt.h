@@ -192,8 +192,6 @@ k_ntt_pass(uint32_t* data, const uint32_t* __restrict__ src, const uint32_t* __r
 // coefficient by coefficient - for ANY a, b, c, satisfied constraints or not: the same vector as bellman's, one
 // transform of size m less (6 instead of 7).  The coefficients of c come out of its inverse transform scaled by
 // 1 / (m (g^m - 1)) (NttPlan sc_*) and are subtracted in the store of the last pass (k_ntt_pass `minus`).
-// Over the derived bases of a (key, circuit) pair the product IS the scalar: `zinv` then points at the plain words of
-// 1 / (g^m - 1), the result leaves Montgomery form in the same multiplication and no transform follows (prove_chunk).
 static __global__ void __launch_bounds__(256)
 k_h_pointwise(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, const uint32_t* __restrict__ c,
               const uint32_t* __restrict__ zinv, uint32_t* out, uint32_t m, uint32_t out_stride, size_t count) {
@@ -204,6 +202,29 @@ k_h_pointwise(const uint32_t* __restrict__ a, const uint32_t* __restrict__ b, co
     if (c) x = sub(x, ld_fr(c + i * 8));
     size_t proof = i / m, e = i % m;
     st_fr(out + (proof * out_stride + e) * 8, mul(x, z));
+}
+
+// The H scalars over the derived bases of a (key, circuit) pair (zkamd.cpp ensure_derived), on the DOMAIN, for the live rows
+// only: with da_j = sum_t t a_t w^(jt) (the forward transform of the coefficients times their index, = w^j a'(w^j)) and db
+// likewise,
+//     s_j = da_j b_j + a_j db_j      (m times the quotient's value at w^j, up to the part that is linear in the row products)
+//     e_k = a_k b_k - c_k            (the residual of row k: zero for a satisfied constraint, and then no digits, no pairs)
+// for j, k < n_rows, written as plain words to out[proof * out_stride + j] and out[proof * out_stride + n_rows + k].  Rows
+// >= n_rows are zero padding - a_j = b_j = c_j = 0 for every assignment - so their s_j and e_j vanish and have no term.
+// da, db: `m` elements per proof (natural order); a, b, c: the row evaluations, n_rows per proof.  All Montgomery.
+static __global__ void __launch_bounds__(256)
+k_h_live_rows(const uint32_t* __restrict__ da, const uint32_t* __restrict__ db, const uint32_t* __restrict__ a,
+              const uint32_t* __restrict__ b, const uint32_t* __restrict__ c, uint32_t* out, uint32_t m, uint32_t n_rows,
+              uint32_t out_stride, size_t count) {
+    size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const size_t proof = i / n_rows, j = i % n_rows;
+    const Fr x = ld_fr(a + i * 8), y = ld_fr(b + i * 8);
+    const Fr s = add(mul(ld_fr(da + (proof * m + j) * 8), y), mul(x, ld_fr(db + (proof * m + j) * 8)));
+    const Fr e = sub(mul(x, y), ld_fr(c + i * 8));
+    uint32_t* o = out + (proof * out_stride + j) * 8;
+    st_fr(o, from_mont(s));
+    st_fr(o + (size_t)n_rows * 8, from_mont(e));
 }
 
 // out[i] = in[i] * tab[i]  (optional table) ; used by the stand-alone zk_ntt_fr entry
@@ -239,6 +260,7 @@ ZK_DI Fr fr_pow_u32(Fr base, uint32_t e) {
 // Table generation.  mode 0: out[i] = base^i                     (twiddles, i < count)
 //                    mode 1: out[pos] = base^bitrev(pos) * scale   (coset tables, bit-reversed)
 //                    mode 2: out[i] = base^i * scale
+//                    mode 3: out[pos] = bitrev(pos) * scale        (the index of a coefficient, bit-reversed; base unused)
 // `base`, `scale` are Montgomery; if raw_out the Montgomery factor is stripped from the result
 // (so that multiplying a Montgomery value by the table entry yields a PLAIN value).
 static __global__ void __launch_bounds__(256)
@@ -248,7 +270,14 @@ k_fr_pow_table(uint32_t* out, const uint32_t* __restrict__ base, const uint32_t*
     if (i >= count) return;
     uint32_t e = i;
     if (mode == 1) e = log_n ? (__builtin_bitreverse32(i) >> (32 - log_n)) : 0;
-    Fr v = fr_pow_u32(ld_fr(base), e);
+    Fr v;
+    if (mode == 3) {
+        v = Fr::zero();
+        v.l[0] = log_n ? (__builtin_bitreverse32(i) >> (32 - log_n)) : 0;
+        v = to_mont(v);
+    } else {
+        v = fr_pow_u32(ld_fr(base), e);
+    }
     if (mode) v = mul(v, ld_fr(scale));
     if (raw_out) v = from_mont(v);
     st_fr(out + (size_t)i * 8, v);
@@ -320,7 +349,8 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 
 // Per-proof scalar vectors for the multiexps (plain form):
 //   wit_out[p] = [ wit[p][0..nv) | 1 | r | s ]                          (A and B2 multiexps; the stride has the sums below)
-//   cvec[p]    = [ h (m, written later) | aux (n_aux) | r * z (nv) | r ]  (merged C multiexp:
+//   cvec[p]    = [ h (m, written later) | aux (n_aux) | r * z (nv) | r ]  (merged C multiexp; `m` = the length of the H block:
+//                the domain's size, or 2 n_rows over the derived bases - k_h_live_rows;
 //                C' = H + L + r * (B1 + beta_1), one bucket set instead of three)
 //                fold != 0 appends [ s * z (nv) | s | r * s ] over the bases of the A query, alpha_1 and delta_1: the job is
 //                then C = s * A + C' itself (A = alpha_1 + sum z_i A_i + r delta_1) - for a few proofs made alone, whose

@@ -65,8 +65,9 @@ struct NttPlan {
     DevBuf s1_plain, s1_mont, s2;    // prover tables, bit-reversed order (see prove_chunk)
     DevBuf sc_plain, sc_mont;        // constant 1 / (n (g^n - 1)): the scaling of c's coefficients (k_h_pointwise)
     DevBuf coset_fwd, coset_inv;     // g^i and g^-i / n, natural order (Montgomery)
-    DevBuf consts;                   // [0] = 1/n, [1] = 1/(g^n - 1)   (Montgomery), [2] = 1/(g^n - 1) in plain words
-    Fr w_inv;                        // w^-1 (Montgomery): the transforms of the derived bases make their own table of it
+    DevBuf dt;                       // t / n at the bit-reversed position of t (Montgomery): a's coefficients -> those of x a'(x)
+    DevBuf consts;                   // [0] = 1/n, [1] = 1/(g^n - 1)   (Montgomery)
+    Fr w_inv, n_inv, z_inv;          // w^-1, 1/n, 1/(g^n - 1) (Montgomery): the transforms of the derived bases make their own tables
     DevBuf scratch;                  // permutation scratch for the stand-alone entry
     size_t bytes = 0;
 
@@ -175,9 +176,11 @@ struct NttPlan {
         Fr gn = g;
         for (uint32_t i = 0; i < k; i++) gn = gn.sqr();
         Fr zinv = zkhost::fr_inv(gn - Fr::one());   // divide_by_z_on_coset
-        Fr cs[3] = {ninv, zinv, zinv.from_mont()};
-        ZK_TRY(upload_fr(consts, cs, 3));
+        Fr cs[2] = {ninv, zinv};
+        ZK_TRY(upload_fr(consts, cs, 2));
         w_inv = winv;
+        n_inv = ninv;
+        z_inv = zinv;
         ZK_TRY(pow_table(tw_fwd, w, Fr::one(), 0, 0, n / 2));
         ZK_TRY(pow_table(tw_inv, winv, Fr::one(), 0, 0, n / 2));
         // after the first inverse transform: * g^i / n, and lift the (plain or Montgomery) input
@@ -186,6 +189,8 @@ struct NttPlan {
         ZK_TRY(pow_table(s1_mont, g, ninv, 1, 0, n));
         // after the last inverse transform: * g^-i / n and drop the Montgomery factor
         ZK_TRY(pow_table(s2, ginv, ninv, 1, 1, n));
+        // after the inverse transform of a or b over the derived bases: * t / n, coefficient t of x a'(x) (prove_chunk)
+        ZK_TRY(pow_table(dt, Fr::one(), ninv, 3, 0, n));
         // c's inverse transform: * 1 / (n (g^n - 1)), result plain (from a plain or a Montgomery input)
         ZK_TRY(pow_table(sc_plain, Fr::one(), ninv * zinv, 2, 0, n));
         ZK_TRY(pow_table(sc_mont, Fr::one(), ninv * zinv, 2, 1, n));
@@ -308,15 +313,17 @@ struct zk_params {
     // instead of 2048 (c = 10 against the throughput optimum 13) cut a lone proof from 3.54 to 3.16 ms
     MsmG2 g2_lone;
     NttPlan ntt;
-    // The derived bases of this key and ONE circuit (ensure_derived): the H query on the coset-Lagrange basis with the c part
-    // of H folded into the bases of the variables.  g1d = [G' (m) | D (inputs, aux) | a | alpha_1 | delta_1 | b_g1 | beta_1]
+    // The derived bases of this key and ONE circuit (ensure_derived): the H query on the Lagrange basis of the domain for the
+    // circuit's live rows, with the part of H that is linear in the row products folded into the bases of the variables and
+    // of the rows' residuals.  g1d = [Lambda (n_rows) | E (n_rows) | D (inputs, aux) | a | alpha_1 | delta_1 | b_g1 | beta_1]
     // with its own table of doublings; g1d_lone = the same table under the width of a few proofs made alone.
     struct Derived {
         bool ready = false;
         uint64_t circuit = 0;       // zk_r1cs::id it was built for
         uint32_t serial = 0;        // changes with every build: part of the key of the cached maps
+        uint32_t n_rows = 0;        // live rows of the circuit: constraints + inputs
         uint32_t off_a = 0, off_b1 = 0;
-        std::vector<int32_t> pos;   // [G' | D]: position in slice 0, or -1 for a base that came out as the identity
+        std::vector<int32_t> pos;   // [Lambda | E | D]: position in slice 0, or -1 for a base that came out as the identity
         double bind_ms = 0;
     } drv;
     MsmG1 g1d, g1d_lone;
@@ -592,6 +599,7 @@ zk_params* params_clone_for_lane(const zk_params* P) {
     Q->ntt.s1_plain.borrow(P->ntt.s1_plain);
     Q->ntt.s1_mont.borrow(P->ntt.s1_mont);
     Q->ntt.s2.borrow(P->ntt.s2);
+    Q->ntt.dt.borrow(P->ntt.dt);
     Q->ntt.sc_plain.borrow(P->ntt.sc_plain);
     Q->ntt.sc_mont.borrow(P->ntt.sc_mont);
     Q->ntt.coset_fwd.borrow(P->ntt.coset_fwd);
@@ -726,20 +734,21 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     with_sums(mc, base_b1, P->off_b1);
     with_sums(mcf, base_b1, P->off_b1);
     with_sums(mcf, base_a, P->off_a);
-    if (P->drv.ready && P->drv.pos.size() == P->m + nv) {
-        // the same job over the derived bases: [u (m, natural order) | aux | r z | r | fold | inputs (n_in) | sums]
+    if (P->drv.ready && P->drv.pos.size() == 2 * (size_t)P->drv.n_rows + nv) {
+        // the same job over the derived bases: [s (n_rows) | e (n_rows) | aux | r z | r | fold | inputs (n_in) | sums]
         const zk_params::Derived& D = P->drv;
+        const size_t head = 2 * (size_t)D.n_rows;
         std::vector<int32_t> md;
         md.reserve(mcf.size() + n_in);
-        for (size_t j = 0; j < P->m; j++) md.push_back(D.pos[j]);
-        for (uint32_t j = 0; j < n_aux; j++) md.push_back(D.pos[P->m + n_in + j]);
+        for (size_t j = 0; j < head; j++) md.push_back(D.pos[j]);
+        for (uint32_t j = 0; j < n_aux; j++) md.push_back(D.pos[head + n_in + j]);
         for (uint32_t i = 0; i < nv; i++) md.push_back(mb1[i] < 0 ? -1 : (int32_t)(D.off_b1 + mb1[i]));
         md.push_back(P->beta_g1_inf ? -1 : (int32_t)(D.off_b1 + P->n_b1));
         std::vector<int32_t> mdf(md);
         for (uint32_t i = 0; i < nv + 2; i++) mdf.push_back(ma[i] < 0 ? -1 : (int32_t)(D.off_a + ma[i]));
         for (uint32_t i = 0; i < n_in; i++) {
-            md.push_back(D.pos[P->m + i]);
-            mdf.push_back(D.pos[P->m + i]);
+            md.push_back(D.pos[head + i]);
+            mdf.push_back(D.pos[head + i]);
         }
         with_sums(md, base_b1, D.off_b1);
         with_sums(mdf, base_b1, D.off_b1);
@@ -775,8 +784,8 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // (prove_chunk: the fold and the three into_affine run on the GPU, k_ct_scale_add /
 // k_xyzz_normalize_export; the host encodes the 192 bytes.)
 
-// derived: a, b are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over the
-// derived bases (ensure_derived); c is not read.
+// derived: a, b, c are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over
+// the derived bases (ensure_derived), whose H scalars are those of the live rows.
 zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
     const auto t_begin = std::chrono::steady_clock::now();
     const uint32_t n_in = bt->n_inputs, n_aux = bt->n_aux, nv = n_in + n_aux, n_rows = bt->n_rows;
@@ -816,14 +825,17 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     // (read at every chunk: the emulation suite sends small batches through the chunk form of the fold)
     const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
     const bool fold_in_msm = np <= fold_max;
-    const uint32_t in_tail = derived ? (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0)) : 0u;   // (the inputs carry their K_i)
+    if (derived && (!mont || P->drv.n_rows != n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
+    // the H block at the head of the C' job: bellman's m coefficients, or [s | e] of the live rows over the derived bases
+    const uint32_t head = derived ? 2 * n_rows : (uint32_t)m;
+    const uint32_t in_tail = derived ? (uint32_t)(head + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0)) : 0u;   // (the inputs carry their part of c)
     // (the sums of the groups at the end: r * B1's, then s * A's with the fold)
-    const uint32_t cstride = (uint32_t)(m + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0) + gb1 + (fold_in_msm ? ga : 0));
+    const uint32_t cstride = (uint32_t)(head + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0) + gb1 + (fold_in_msm ? ga : 0));
     ZK_TRY(P->cvec.ensure(np * (size_t)cstride * 32));
     uint32_t* cvec = P->cvec.as<uint32_t>();
     // (the same launch: a thread per variable, three for the tail, one per group)
     ZK_LAUNCH(zkdev::k_build_scalars, dim3((nv + 3 + ga + gb2 + gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
-              (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), nv, n_in, (uint32_t)m, cstride,
+              (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), nv, n_in, head, cstride,
               mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u, in_tail, P->grp_dev.as<uint32_t>(), ga, gb2, gb1);
     // ---- multiexps (create_proof step 4).  The G2 job only needs the witness scalars: it is
     // enqueued first, on the side stream, and runs beside the H pipeline and the G1 multiexps (its
@@ -854,27 +866,33 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     uint32_t* A = P->abc.as<uint32_t>();
     uint32_t* B = A + np * m * 8;
     uint32_t* C = B + np * m * 8;
-    const uint32_t* s1 = mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
     const uint32_t* srcs[3] = {(const uint32_t*)bt->d_a + first * (size_t)n_rows * 8,
                                (const uint32_t*)bt->d_b + first * (size_t)n_rows * 8,
-                               derived ? nullptr : (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
+                               (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
     uint32_t* dsts[3] = {A, B, C};
     // ifft (natural -> bit-reversed) of a and b, then * g^i / m (coset shift); c: * 1 / (m (g^m - 1)), plain - its
-    // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7)
+    // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7).
+    // Over the derived bases: a and b only, * t / m - the coefficients of x a'(x) - and the forward chain below is a plain
+    // transform back onto the domain; the row evaluations themselves stay where they are (the chains load out of place).
+    const uint32_t* s1 = derived ? P->ntt.dt.as<uint32_t>() : mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
     const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
     for (int k = 0; k < (derived ? 2 : 3); k++)
         ZK_TRY(P->ntt.chain(dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
-    // coset fft (bit-reversed -> natural) of a and b at once
+    // (coset) fft (bit-reversed -> natural) of a and b at once
     ZK_TRY(P->ntt.chain(A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
     {
         ProfScope ps("h_pointwise");
-        size_t count = np * m;
-        ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
-                  (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + (derived ? 16 : 8), cvec, (uint32_t)m,
-                  cstride, count);
+        if (derived) {
+            // s_j and e_k of the live rows ARE the scalars (plain, natural order): four transforms per proof, none after this
+            const size_t count = np * (size_t)n_rows;
+            ZK_LAUNCH(zkdev::k_h_live_rows, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
+                      (const uint32_t*)B, srcs[0], srcs[1], srcs[2], cvec, (uint32_t)m, n_rows, cstride, count);
+        } else {
+            const size_t count = np * m;
+            ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
+                      (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
+        }
     }
-    // Over the derived bases a(x_j) b(x_j) / (g^m - 1) is the scalar of G'_j as it stands (plain, natural order) and c went
-    // into the bases of the variables: four transforms per proof.  Otherwise:
     // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
     // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
     if (!derived)
@@ -998,7 +1016,7 @@ zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const 
     if (bt->n_rows > P->m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     if (bt->n_inputs != P->n_ic) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "number of inputs differs from vk.ic");
     if (bt->n_aux != P->n_l) return fail(ZK_ERR_IO, "number of aux variables differs from the l query");
-    if (!bt->d_a || !bt->d_b || (!bt->d_c && !derived) || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
+    if (!bt->d_a || !bt->d_b || !bt->d_c || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
         return fail(ZK_ERR_ASSIGNMENT_MISSING, "assignment pointer is null");
     ZK_TRY(ensure_maps(P, bt->n_inputs, bt->n_aux, bt->a_aux_density, bt->b_input_density, bt->b_aux_density));
     // proofs per launch set: large chunks amortise the latency-bound tails (reduction trees, sorts);
@@ -1174,29 +1192,32 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
 }
 
 // ------------------------------------------------------------------------------------------
-// Derived bases of a (key, circuit) pair: four transforms per proof instead of six
+// Derived bases of a (key, circuit) pair: four transforms per proof instead of six, H scalars on the live rows only
 // ------------------------------------------------------------------------------------------
-// With x_j = g w^j, u_j = a(x_j) b(x_j) / (g^m - 1) and c_k the k-th row evaluation of C, the h of ntt.h k_h_pointwise is
-//     h_t = p_t - c_t / (g^m - 1),   p = the coset interpolation of u,   c_t = the coefficients of c,
-// for ANY a, b, c, and bellman drops h_(m-1).  Both parts are linear in the scalars, so their transforms can be applied to
-// the BASES once instead of to the scalars of every proof.  With H_(m-1) := the identity (the truncation),
-//     sum_t p_t H_t = sum_j u_j G'_j,         G'_j = (1/m) sum_t (g w^j)^-t H_t
-//     sum_t c_t H_t / (g^m - 1) = sum_k c_k L''_k,   L''_k = 1 / (m (g^m - 1)) sum_t w^-kt H_t
-// - two inverse transforms "in the exponent" over the points g^-t H_t / m and H_t / (m (g^m - 1)).  When c_k = sum_i C_ki z_i
-// are the library's own row evaluations (k_r1cs_eval), the second sum is sum_i z_i K_i with K_i = sum_k C_ki L''_k, and
-//     C' = sum_j u_j G'_j + sum_aux z_i (L_i - K_i) - sum_inputs z_i K_i + r (beta_1 + sum B1):
-// the terms of today's job plus one per input, no c, no transform after the pointwise product.  Exact for every assignment,
-// satisfying or not; nothing assumes that Z divides a b - c.
+// With p = a b - c = q Z + R (Z = x^m - 1, deg R < m), bellman's h is q + R / (g^m - 1): q is the quotient and R = sum_k e_k L_k
+// interpolates the residuals e_k = a_k b_k - c_k of the rows, for ANY a, b, c; bellman drops h_(m-1).  On the DOMAIN
+//     q(w^j) = (a b - W)'(w^j) w^j / m,        W = the interpolant of the row products w_k = c_k + e_k
+// (differentiate p - R = q Z at a root of Z).  Its a b part is s_j / m with s_j = da_j b_j + a_j db_j, da_j = w^j a'(w^j) =
+// sum_t t a_t w^(jt): one plain forward transform of the coefficients times their index.  Its W part is LINEAR in w, and so
+// is R: both transpose onto the bases once.  With H'_t = H_t, H'_(m-1) := the identity (the truncation),
+//     Lambda_k = (1/m) sum_t w^-kt H'_t,      M_k = -(1/m^2) sum_t t w^-kt H'_t
+// - two inverse transforms "in the exponent" - and c_k = sum_i C_ki z_i the library's own row evaluations (k_r1cs_eval),
+//     sum_t h_t H_t = sum_j s_j (Lambda_j / m) + sum_i z_i (sum_k C_ki M_k) + sum_k e_k (M_k + Lambda_k / (g^m - 1)).
+// A padding row j >= n_rows = n_con + n_in has a_j = b_j = c_j = 0 for every assignment, so s_j = e_j = 0: the job has
+// n_rows H scalars of full width (of m), n_rows residuals that are zero - no digits, no pairs - unless a constraint fails,
+// and the variables' terms it had anyway:
+//     C' = sum_j s_j Lambda_j / m + sum_k e_k E_k + sum_aux z_i (L_i + D_i) + sum_inputs z_i D_i + r (beta_1 + sum B1).
+// Exact for every assignment, satisfying or not; nothing assumes that Z divides a b - c.
 //
 // Built on the GPU, one row of lanes per point (coop_tail.h basis_*): a scaling pass and log2 m butterfly stages per
-// transform, every butterfly one 255-bit scalar product; the K_i as one scalar product per entry of C summed per
-// column.  The set goes through into_affine and the same table of doublings as a key's bases (MsmGroup::build_with_tail);
-// a base that comes out as the identity - K_i of an input that C never mentions - is mapped out like an identity in a key
-// file.  Nothing happens when the pair cannot have one (a lane's clone, another circuit's shape): the caller then keeps the
-// six-transform form.
+// transform, every butterfly one 255-bit scalar product; D_i as one scalar product per entry of C summed per column, E_k
+// as one per live row.  The set goes through into_affine and its own table of doublings, under the recoding width of its
+// own term count; a base that comes out as the identity - D_i of an input that C never mentions - is mapped out like an
+// identity in a key file.  Nothing happens when the pair cannot have one (a lane's clone, another circuit's shape): the
+// caller then keeps the six-transform form.
 zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     if (P->drv.ready && P->drv.circuit == R->id) return ZK_OK;
-    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, k = P->log_m;
+    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, n_rows = n_con + n_in, k = P->log_m;
     const size_t m = P->m;
     if (!P->g1.table.owned || R->h_row_ptr[2].size() != (size_t)n_con + 1 || n_in != P->n_ic || n_aux != P->n_l ||
         (size_t)n_con + n_in > m || P->n_h + 1 != m)
@@ -1207,11 +1228,11 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     typedef zkdev::Affine<zkdev::Fq> DA;
     P->drv.ready = false;
     const DA* key = P->g1.table.as<DA>();
-    // C by columns, every coefficient negated (the variables carry - K_i) and in plain words
+    // C by columns, the coefficients in plain words
     const std::vector<uint32_t>& rp = R->h_row_ptr[2];
     const std::vector<uint32_t>& cl = R->h_col[2];
     const uint32_t nnz = rp[n_con];
-    std::vector<uint32_t> ptr(nv + 1, 0), t_row(nnz ? nnz : 1);
+    std::vector<uint32_t> ptr(nv + 1, 0), t_row(nnz ? nnz : 1), each(n_rows + 1);
     std::vector<Fr> t_s(nnz ? nnz : 1);
     for (uint32_t e = 0; e < nnz; e++) ptr[cl[e] + 1]++;
     for (uint32_t i = 0; i < nv; i++) ptr[i + 1] += ptr[i];
@@ -1221,9 +1242,10 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
             for (uint32_t e = rp[row]; e < rp[row + 1]; e++) {
                 const uint32_t slot = at[cl[e]]++;
                 t_row[slot] = row;
-                t_s[slot] = (-R->h_coeff[2][e]).from_mont();
+                t_s[slot] = R->h_coeff[2][e].from_mont();
             }
     }
+    for (uint32_t i = 0; i <= n_rows; i++) each[i] = i;   // (segments of one term: E_k = M_k + one point)
     // H in bit-reversed order with the identity in the place of H_(m-1); the L query behind the (empty) inputs
     std::vector<int32_t> idx(m + nv);
     for (size_t pos = 0; pos < m; pos++) {
@@ -1231,36 +1253,51 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
         idx[pos] = e < P->n_h ? (int32_t)(P->off_h + e) : -1;
     }
     for (uint32_t i = 0; i < nv; i++) idx[m + i] = i < n_in ? -1 : (int32_t)(P->off_l + (i - n_in));
-    const size_t rows = std::max<size_t>(m, nnz);
-    DevBuf d_idx, d_ptr, d_row, d_s, d_tw, d_w, src, ping, pong, lam, terms, tbl, all, stage;
-    for (DevBuf* b : {&d_idx, &d_ptr, &d_row, &d_s, &d_tw, &d_w, &src, &ping, &pong, &lam, &terms, &tbl, &all, &stage}) b->is_public = true;
+    const size_t rows = std::max<size_t>(m, nnz), n_set = 2 * (size_t)n_rows + nv;
+    DevBuf d_idx, d_ptr, d_each, d_row, d_s, d_tw, d_w, d_sl, d_sm, d_se, src, ping, pong, lam, mk, terms, tbl, all, stage;
+    for (DevBuf* b : {&d_idx, &d_ptr, &d_each, &d_row, &d_s, &d_tw, &d_w, &d_sl, &d_sm, &d_se, &src, &ping, &pong, &lam, &mk, &terms, &tbl, &all, &stage})
+        b->is_public = true;
     ZK_TRY(d_idx.ensure(idx.size() * 4));
     ZK_TRY(d_ptr.ensure(ptr.size() * 4));
+    ZK_TRY(d_each.ensure(each.size() * 4));
     ZK_TRY(d_row.ensure(t_row.size() * 4));
     ZK_TRY(d_s.ensure(t_s.size() * 32));
     ZK_TRY(d_tw.ensure(m * 32));
-    ZK_TRY(d_w.ensure(64));
+    ZK_TRY(d_w.ensure(5 * 32));
+    ZK_TRY(d_sl.ensure(m * 32));
+    ZK_TRY(d_sm.ensure(m * 32));
+    ZK_TRY(d_se.ensure((size_t)n_rows * 32));
     ZK_TRY(src.ensure((m + nv) * sizeof(DP)));
     ZK_TRY(ping.ensure(m * sizeof(DP)));
     ZK_TRY(pong.ensure(m * sizeof(DP)));
     ZK_TRY(lam.ensure(m * sizeof(DP)));
-    ZK_TRY(terms.ensure((nnz ? nnz : 1) * sizeof(DP)));
+    ZK_TRY(mk.ensure(m * sizeof(DP)));
+    ZK_TRY(terms.ensure(std::max<size_t>(nnz ? nnz : 1, n_rows) * sizeof(DP)));
     ZK_TRY(tbl.ensure(15 * rows * sizeof(DP)));
-    ZK_TRY(all.ensure((m + nv) * sizeof(DP)));
+    ZK_TRY(all.ensure(n_set * sizeof(DP)));
     HIP_TRY(hipMemcpy(d_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_ptr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_each.p, each.data(), each.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_row.p, t_row.data(), t_row.size() * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d_s.p, t_s.data(), t_s.size() * 32, hipMemcpyHostToDevice));
-    const Fr wv[2] = {P->ntt.w_inv, Fr::one()};
-    HIP_TRY(hipMemcpy(d_w.p, wv, 64, hipMemcpyHostToDevice));
-    // w^-e for e < m / 2 in plain words
-    ZK_LAUNCH(zkdev::k_fr_pow_table, dim3((unsigned)((m / 2 + 255) / 256)), dim3(256), 0, g_stream, d_tw.as<uint32_t>(),
-              (const uint32_t*)d_w.as<uint32_t>(), (const uint32_t*)d_w.as<uint32_t>() + 8, k, 0u, 1u, (uint32_t)(m / 2));
+    const Fr ninv2 = P->ntt.n_inv * P->ntt.n_inv;
+    const Fr wv[5] = {P->ntt.w_inv, Fr::one(), ninv2, -ninv2, fr_from_u64((uint64_t)m) * P->ntt.z_inv};
+    HIP_TRY(hipMemcpy(d_w.p, wv, sizeof(wv), hipMemcpyHostToDevice));
+    const uint32_t* cw = d_w.as<uint32_t>();
+    auto table = [&](DevBuf& out, const uint32_t* base, const uint32_t* scale, uint32_t mode, size_t count) {
+        ZK_LAUNCH(zkdev::k_fr_pow_table, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, out.as<uint32_t>(), base, scale,
+                  k, mode, 1u, (uint32_t)count);
+    };
+    // plain words: w^-e for e < m / 2; 1 / m^2 and - t / m^2 at the bit-reversed position of t; m / (g^m - 1) per live row
+    if (m > 1) table(d_tw, cw, cw + 8, 0, m / 2);
+    table(d_sl, cw + 8, cw + 16, 2, m);
+    table(d_sm, cw + 8, cw + 24, 3, m);
+    table(d_se, cw + 8, cw + 32, 2, n_rows);
     zkcoop::basis_gather(key, d_idx.as<int32_t>(), src.as<DP>(), (uint32_t)(m + nv), g_stream);
     // in: the scaled points in bit-reversed order; out: the transform in natural order
     auto transform = [&](const uint32_t* scale, DP* out) -> zk_status {
         DP *a = ping.as<DP>(), *b = pong.as<DP>();
-        zkcoop::basis_scale(src.as<DP>(), nullptr, scale, tbl.as<DP>(), a, (uint32_t)m, g_stream);
+        zkcoop::basis_scale(src.as<DP>(), nullptr, scale, tbl.as<DP>(), k ? a : out, (uint32_t)m, g_stream);
         for (uint32_t st = 0; st < k; st++) {
             zkcoop::basis_dft_stage(a, st + 1 == k ? out : b, d_tw.as<uint32_t>(), tbl.as<DP>(), k, st, g_stream);
             std::swap(a, b);
@@ -1268,23 +1305,36 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
         HIP_TRY(hipGetLastError());
         return ZK_OK;
     };
-    ZK_TRY(transform(P->ntt.s2.as<uint32_t>(), all.as<DP>()));        // g^-t / m
-    ZK_TRY(transform(P->ntt.sc_mont.as<uint32_t>(), lam.as<DP>()));   // 1 / (m (g^m - 1))
-    if (nnz) zkcoop::basis_scale(lam.as<DP>(), d_row.as<uint32_t>(), d_s.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), nnz, g_stream);
-    zkcoop::basis_segment_sums(src.as<DP>() + m, terms.as<DP>(), d_ptr.as<uint32_t>(), all.as<DP>() + m, nv, g_stream);
+    ZK_TRY(transform(d_sl.as<uint32_t>(), lam.as<DP>()));   // Lambda_j / m: the 1 / m of s_j rides in the base
+    ZK_TRY(transform(d_sm.as<uint32_t>(), mk.as<DP>()));    // M_k
+    DP* set = all.as<DP>();
+    HIP_TRY(hipMemcpyAsync(set, lam.p, (size_t)n_rows * sizeof(DP), hipMemcpyDeviceToDevice, g_stream));
+    // E_k = M_k + (m / (g^m - 1)) (Lambda_k / m)
+    zkcoop::basis_scale(lam.as<DP>(), nullptr, d_se.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), n_rows, g_stream);
+    zkcoop::basis_segment_sums(mk.as<DP>(), terms.as<DP>(), d_each.as<uint32_t>(), set + n_rows, n_rows, g_stream);
+    // D_i = sum_k C_ki M_k, behind L_i for an aux variable
+    if (nnz) zkcoop::basis_scale(mk.as<DP>(), d_row.as<uint32_t>(), d_s.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), nnz, g_stream);
+    zkcoop::basis_segment_sums(src.as<DP>() + m, terms.as<DP>(), d_ptr.as<uint32_t>(), set + 2 * (size_t)n_rows, nv, g_stream);
     HIP_TRY(hipGetLastError());
-    std::vector<HG1> host(m + nv);
-    ZK_TRY(P->g1.normalize_to_host(all.as<DP>(), m + nv, host.data(), stage, g_stream));
+    std::vector<HG1> host(n_set);
+    ZK_TRY(P->g1.normalize_to_host(set, n_set, host.data(), stage, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
-    std::vector<HG1A> pts(m + nv);
-    P->drv.pos.assign(m + nv, -1);
-    for (size_t i = 0; i < m + nv; i++) {
+    std::vector<HG1A> pts(n_set);
+    P->drv.pos.assign(n_set, -1);
+    size_t live = 0;
+    for (size_t i = 0; i < n_set; i++) {
         pts[i] = host[i].is_inf() ? HG1A::inf() : HG1A{host[i].x, host[i].y};
-        if (!host[i].is_inf()) P->drv.pos[i] = (int32_t)i;
+        if (!host[i].is_inf()) {
+            P->drv.pos[i] = (int32_t)i;
+            if (i < n_rows || i >= 2 * (size_t)n_rows) live++;
+        }
     }
-    ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, P->g1.c));
+    // (the width of the set's own terms: the residuals are zero scalars unless a constraint fails)
+    const uint32_t c_set = pick_window(live + P->n_b1, 1);
+    ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, c_set));
     P->g1d_lone.alias(P->g1d, P->g1_lone.c);
-    P->drv.off_a = (uint32_t)(m + nv);
+    P->drv.n_rows = n_rows;
+    P->drv.off_a = (uint32_t)n_set;
     P->drv.off_b1 = P->drv.off_a + P->n_a + 2;
     P->drv.circuit = R->id;
     static std::atomic<uint32_t> serial{1};
@@ -1292,8 +1342,8 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     P->drv.bind_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     P->drv.ready = true;
     if (getenv("ZKAMD_TRACE_HOST"))
-        fprintf(stderr, "[zkamd] derived bases: %zu + %u points, %u entries of C, %.1f ms, table %.2f GB\n", m, nv, nnz, P->drv.bind_ms,
-                (double)P->g1d.bytes / 1e9);
+        fprintf(stderr, "[zkamd] derived bases: 2 x %u + %u points, %u entries of C, width %u, %.1f ms, table %.2f GB\n", n_rows, nv, nnz,
+                c_set, P->drv.bind_ms, (double)P->g1d.bytes / 1e9);
     return ZK_OK;
 }
 
@@ -1306,14 +1356,13 @@ zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint
         ZK_TRY(ensure_derived(P, R));
         derived = P->drv.ready && P->drv.circuit == R->id;
     }
-    ZK_TRY(R->abc.ensure((derived ? 2 : 3) * np * (size_t)n_rows * 32));
+    ZK_TRY(R->abc.ensure(3 * np * (size_t)n_rows * 32));
     zkdev::R1csMat mm[3];
     for (int m = 0; m < 3; m++)
         mm[m] = zkdev::R1csMat{R->row_ptr[m].as<uint32_t>(), R->col[m].as<uint32_t>(), R->coeff[m].as<uint32_t>()};
     {
         ProfScope ps("r1cs_eval");
-        ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, derived ? 2 : 3, (unsigned)np),   // (no rows of C over the derived bases)
-                  dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
+        ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, 3, (unsigned)np), dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
                   (const uint32_t*)R->z[slot].as<uint32_t>(), R->abc.as<uint32_t>(), R->n_con, R->n_in, nv, n_rows,
                   np * (size_t)n_rows);
     }
@@ -1325,7 +1374,7 @@ zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint
     bt.flags = ZK_FR_MONTGOMERY;
     bt.d_a = R->abc.as<uint32_t>();
     bt.d_b = R->abc.as<uint32_t>() + np * (size_t)n_rows * 8;
-    bt.d_c = derived ? nullptr : R->abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
+    bt.d_c = R->abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
     bt.d_wit = R->z[slot].p;
     bt.a_aux_density = R->a_aux_density.data();
     bt.b_input_density = R->b_input_density.data();
@@ -2047,6 +2096,22 @@ zk_status zk_hook_prove_batch_witness_derived(zk_params* p, zk_r1cs* circuit, si
         info[1] = (uint32_t)std::count(p->drv.pos.begin(), p->drv.pos.end(), -1);
     }
     return rc;
+} ZK_ABI_CATCH
+// Test hook: the layout of the derived set (p, circuit) carries, [Lambda | E | D | a | alpha_1 | delta_1 | b_g1 | beta_1].
+// info = [has a set, terms of the H block, of the residual block, of the variables, offset of the A query's copy, of the
+// b_g1 query's, recoding width of the set], zeros behind info[0] without one.
+zk_status zk_hook_derived_layout(zk_params* p, zk_r1cs* circuit, uint32_t info[7]) try {
+    if (!p || !circuit || !info) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    std::fill(info, info + 7, 0u);
+    const zk_params::Derived& D = p->drv;
+    if (!D.ready || D.circuit != circuit->id) return ZK_OK;
+    info[0] = 1;
+    info[1] = info[2] = D.n_rows;
+    info[3] = (uint32_t)D.pos.size() - 2 * D.n_rows;
+    info[4] = D.off_a;
+    info[5] = D.off_b1;
+    info[6] = p->g1d.c;
+    return ZK_OK;
 } ZK_ABI_CATCH
 #endif
 
