@@ -61,24 +61,25 @@ OP_NAMES = [n for n, _, _ in OPS]
 OP_CODE = {n: i for i, n in enumerate(OP_NAMES)}
 
 
-def ops_of_the_c_source():
-    """The names of enum FieldOp as the preprocessor would list them, read from csrc/field_hooks.cpp."""
+def ops_of_the_c_source(table="ZK_HK_OPS"):
+    """The names of enum FieldOp (table ZK_HK_OPS) or of the row ops that continue its codes (ZK_HK_COOP_OPS) as the
+    preprocessor would list them, read from csrc/field_hooks.cpp."""
     src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "zero-chain_amd", "csrc", "field_hooks.cpp")).read()
     src = src.replace("\\\n", " ")
     macros = {m.group(1): m.group(2) for m in re.finditer(r"^#define (ZK_HK_\w+)\(X[^)]*\)\s+(.*)$", src, flags=re.M)}
 
     def expand(body, args):
         names = []
-        for m in re.finditer(r"\b(X|ZK_HK_B|ZK_HK_FP|ZK_HK_GROUP)\(X?,?\s*([^,)]+)", body):
+        for m in re.finditer(r"\b(X|ZK_HK_B|ZK_HK_FP|ZK_HK_GROUP|ZK_HK_CB|ZK_HK_CGROUP)\(X?,?\s*([^,)]+)", body):
             kind, first = m.group(1), m.group(2).strip()
             if kind == "X":
                 for k, v in args.items():
                     first = first.replace(k + "##", v).replace("##" + k, v)
                 names.append(first.replace("##", ""))
             else:
-                names += expand(macros[kind], {"B": first} if kind == "ZK_HK_B" else {"P": first})
+                names += expand(macros[kind], {"B": first} if kind in ("ZK_HK_B", "ZK_HK_CB") else {"P": first})
         return names
-    return expand(macros["ZK_HK_OPS"], {})
+    return expand(macros[table], {})
 
 
 # ------------------------------------------------------------------------------------------------ limbs
@@ -171,13 +172,18 @@ def run(lib, name, rows):
     """rows: one list of input slots per row, a slot a list of up to 16 words.  Returns one list of output slots (14 limbs)
     per row.  The launch always ends in a partial wave."""
     code, (_, ni, no) = OP_CODE[name], OPS[OP_CODE[name]]
+    return launch(lib, name, code, ni, no, rows, 64)
+
+
+def launch(lib, name, code, ni, no, rows, wave):
+    """One call of the hook for op `code` (ni -> no slots), `wave` rows to a GPU wave."""
     assert rows and all(len(r) == ni for r in rows), name
     rows = list(rows)
     first = len(rows)
-    while len(rows) < 65 or len(rows) % 64 == 0:      # one full wave and a partial one at the least: repeat rows
+    while len(rows) < wave + 1 or len(rows) % wave == 0:      # one full wave and a partial one at the least: repeat rows
         rows.append(rows[len(rows) % first])
     n = len(rows)
-    assert n % 64 != 0 and n <= 6000, (name, n)
+    assert n % wave != 0 and n <= 6000, (name, n)
     a = np.zeros((n, ni, 16), dtype=np.uint32)
     for i, r in enumerate(rows):
         for s, slot in enumerate(r):
@@ -240,7 +246,7 @@ def rows_sub(b_bound, lift):
     return rows
 
 
-def check_fq28_linear(lib, name):
+def check_fq28_linear(lib, name, run=run):
     if name == "FQ28_ADD":
         rows = rows_add()
         want = lambda r: val(r[0]) + val(r[1])
@@ -339,7 +345,7 @@ def rows_mul():
     return rows
 
 
-def check_fq28_mul(lib, name):
+def check_fq28_mul(lib, name, run=run, assert_product=assert_product):
     if name == "FQ28_MUL":
         rows = rows_mul()
         want = lambda r: mont(val(r[0]) * val(r[1]))
@@ -405,7 +411,7 @@ def rows_mul_sub2(b):
     return rows
 
 
-def check_fq28_mul_sub2(lib, name):
+def check_fq28_mul_sub2(lib, name, run=run, assert_product=assert_product):
     b = int(name.rsplit("_", 1)[1])
     out, rows = run(lib, name, rows_mul_sub2(b))
     for r, o in zip(rows, out):
@@ -436,7 +442,7 @@ def rows_zero():
     return rows
 
 
-def check_fq28_unary(lib, name):
+def check_fq28_unary(lib, name, run=run):
     if name == "FQ28_CANON":
         out, rows = run(lib, name, [[a] for a in operands(64)])
         for r, o in zip(rows, out):
@@ -468,7 +474,7 @@ def words32(v, n=12):
     return [(v >> (32 * i)) & 0xffffffff for i in range(n)]
 
 
-def check_fq28_host(lib, name):
+def check_fq28_host(lib, name, run=run, assert_product=assert_product):
     if name == "FQ28_UNPACK":
         vs = host_values() + [(1 << 384) - 1, (1 << 384) - (1 << 32), 1 << 383]
         out, rows = run(lib, name, [[words32(v)] for v in vs])
@@ -502,7 +508,7 @@ def pair_rows(rows):
     return out
 
 
-def check_fq2x_linear(lib, name):
+def check_fq2x_linear(lib, name, run=run):
     if name == "FQ2X_ADD":
         base = rows_add()
         want = lambda r: val(r[0]) + val(r[1])
@@ -575,7 +581,7 @@ def rows_fq2x_sqr(a_bound):
     return rows
 
 
-def check_fq2x_products(lib, name):
+def check_fq2x_products(lib, name, run=run, assert_product=assert_product):
     if name == "FQ2X_MUL":
         out, rows = run(lib, name, rows_fq2x_mul())
         for r, o in zip(rows, out):
@@ -914,14 +920,17 @@ def check_op(lib, name):
 
 def op_table_and_the_first_code_past_it(lib):
     """The C enum lists the names of OPS in their order (so the two tables have the same length; check_op reaches every code
-    of it), and the first code past the table is refused without touching the output."""
+    of it), and the first code past the table - past the row ops, which continue it - is refused without touching the
+    output."""
     assert ops_of_the_c_source() == OP_NAMES
+    past = len(OPS) + len(ops_of_the_c_source("ZK_HK_COOP_OPS"))     # the row ops (tests/coop_cases.py) continue the codes
     fn = lib.dll.zk_hook_field_op
     fn.restype = C.c_int
     fn.argtypes = [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t]
     a = np.zeros((1, 16, 16), dtype=np.uint32)
     out = np.full((1, 16, 16), 7, dtype=np.uint32)
     assert fn(len(OPS) - 1, a.ctypes.data, out.ctypes.data, 0) == 0
-    assert fn(len(OPS), a.ctypes.data, out.ctypes.data, 1) == ZK_ERR_INVALID_ARGUMENT
+    assert fn(past - 1, a.ctypes.data, out.ctypes.data, 0) == 0
+    assert fn(past, a.ctypes.data, out.ctypes.data, 1) == ZK_ERR_INVALID_ARGUMENT
     assert fn(0xffffffff, a.ctypes.data, out.ctypes.data, 1) == ZK_ERR_INVALID_ARGUMENT
     assert (out == 7).all()

@@ -1035,6 +1035,16 @@ def verifier_small_circuit(lib, seed=5, n_in=3, n_aux=12, n_con=14):
         params.close()
 
 
+def fq_inverse_edge_values():
+    """Plain values below q at the edges of an inversion (the list of fq_inverse_on_rows; tests/coop_cases.py stores them
+    at other magnitudes)."""
+    Q = bls.Q_MOD
+    xs = [0, 1, Q - 1, 2, Q - 2, 3, (Q + 1) // 2, (Q - 1) // 2, 1 << 30, (1 << 30) - 1, (1 << 60) + 1, 1 << 380, Q >> 1, Q - (1 << 200)]
+    xs += [pow(k, Q - 2, Q) for k in (2, 3, 5, 7, 1 << 29, (1 << 31) - 1, 1 << 62)]
+    xs += [(1 << (30 * k)) % Q for k in range(1, 13)] + [((1 << (30 * k)) - 1) % Q for k in range(1, 13)]
+    return xs
+
+
 def fq_inverse_on_rows(lib, n=600, seed=77):
     """The inversion in Fq of the verification kernels on rows - a half-GCD on 30-bit limbs (csrc/coop_inv.h) - against
     pow(x, q - 2, q) on edge values (0, 1, q - 1, 2, small and large powers of two, values around 2^30 k limb boundaries,
@@ -1042,9 +1052,7 @@ def fq_inverse_on_rows(lib, n=600, seed=77):
     import ctypes as C2
     Q = bls.Q_MOD
     rng = synth.SplitMix64(seed)
-    xs = [0, 1, Q - 1, 2, Q - 2, 3, (Q + 1) // 2, (Q - 1) // 2, 1 << 30, (1 << 30) - 1, (1 << 60) + 1, 1 << 380, Q >> 1, Q - (1 << 200)]
-    xs += [pow(k, Q - 2, Q) for k in (2, 3, 5, 7, 1 << 29, (1 << 31) - 1, 1 << 62)]
-    xs += [(1 << (30 * k)) % Q for k in range(1, 13)] + [((1 << (30 * k)) - 1) % Q for k in range(1, 13)]
+    xs = fq_inverse_edge_values()
     while len(xs) < n:
         xs.append(rng.field(Q))
     R = pow(2, 384, Q)
