@@ -276,6 +276,37 @@ def test_gpu_merged_proofs_are_the_unmerged_ones(gpu_hooks_lib, monkeypatch, n):
         params.close()
 
 
+def chain_fold_in_one_launch_set(lib, monkeypatch, route):
+    """The fold as its own kernel behind ONE G1 launch set (all C' jobs, then all A jobs): the combination no default reaches
+    - the fold leaves the multiexp beyond 128 proofs, where the G1 jobs are two sets since 64.  The smallest circuit with equal
+    points in both queries, a proof alone and three in chunks of two: groups, two chunks, a last chunk of one proof."""
+    monkeypatch.setenv("ZKAMD_FOLD_IN_MSM_MAX", "0")
+    monkeypatch.setenv("ZKAMD_SPLIT_MIN", "100000")
+    monkeypatch.setenv("ZKAMD_BATCH_CHUNK", "2")
+    r1, pk, zs, rs, want = case("booleans")
+    params = zk.Parameters.read(pk, checked=False, lib=lib)
+    mats = zk.ConstraintMatrices(r1.n_in, r1.n_aux, r1.constraints, lib=lib)
+    try:
+        assert params.merged_bases == (1, 1, 1)
+        assert route(lib, mats, params, zs[:1], rs[:1]) == want[:1]
+        assert route(lib, mats, params, zs, rs) == want
+    finally:
+        mats.close()
+        params.close()
+
+
+@pytest.mark.parametrize("route", [_own, _derived], ids=["key", "derived"])
+def test_emulated_chain_fold_in_one_launch_set(emu_lib, monkeypatch, route):
+    monkeypatch.setenv("ZKAMD_WINDOW_BITS", "5")
+    chain_fold_in_one_launch_set(emu_lib, monkeypatch, route)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("route", [_own, _derived], ids=["key", "derived"])
+def test_gpu_chain_fold_in_one_launch_set(gpu_hooks_lib, monkeypatch, route):
+    chain_fold_in_one_launch_set(gpu_hooks_lib, monkeypatch, route)
+
+
 @pytest.mark.gpu
 def test_gpu_transfer_key_groups_and_a_chunk_of_64(gpu_lib):
     """The transfer key merges at least the identical columns of the circuit's matrices, and a chunk of 64 statements proves

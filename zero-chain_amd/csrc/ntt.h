@@ -17,6 +17,7 @@
 // and for s = 0 the whole tile is contiguous.  Twiddles are read from a table in HBM.
 #pragma once
 #include "dev_field.h"
+#include "prove_plan.h"
 
 namespace zkdev {
 
@@ -347,15 +348,15 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
     st_fr(out + (size_t)mat * out_mat_stride * 8 + (p * n_rows + row) * 8, acc);
 }
 
-// Per-proof scalar vectors for the multiexps (plain form):
+// Per-proof scalar vectors for the multiexps (plain form), every section where the layout L has it (prove_plan.h CJobLayout):
 //   wit_out[p] = [ wit[p][0..nv) | 1 | r | s ]                          (A and B2 multiexps; the stride has the sums below)
-//   cvec[p]    = [ h (m, written later) | aux (n_aux) | r * z (nv) | r ]  (merged C multiexp; `m` = the length of the H block:
-//                the domain's size, or 2 n_rows over the derived bases - k_h_live_rows;
-//                C' = H + L + r * (B1 + beta_1), one bucket set instead of three)
-//                fold != 0 appends [ s * z (nv) | s | r * s ] over the bases of the A query, alpha_1 and delta_1: the job is
+//   cvec[p]    = [ H block (written later) | aux (n_aux) | r * z (nv) | r ]  (merged C multiexp: C' = H + L + r * (B1 + beta_1),
+//                one bucket set instead of three; the H block is the domain's size, or 2 n_rows over the derived bases -
+//                k_h_live_rows)
+//                L.fold appends [ s * z (nv) | s | r * s ] over the bases of the A query, alpha_1 and delta_1: the job is
 //                then C = s * A + C' itself (A = alpha_1 + sum z_i A_i + r delta_1) - for a few proofs made alone, whose
-//                final fold would otherwise be a 255-bit double-and-add chain on the critical path (zkamd.cpp prove_chunk)
-//                in_tail != 0 appends [ inputs (n_in) ] at that position: the job over the derived bases of a (key, circuit)
+//                final fold would otherwise be a 255-bit double-and-add chain on the critical path (prove_plan.h prove_plan)
+//                L.in_tail != 0 appends [ inputs (n_in) ] at that position: the job over the derived bases of a (key, circuit)
 //                pair, whose input variables carry the c part of H (zkamd.cpp ensure_derived)
 // Equal points of a query are one term of its job (zkamd.cpp ensure_maps: the members' slots are mapped out): threads
 // i >= nv + 3 take one group each, groups = [ptr (ga + gb2 + gb1 + 1) | member variables], and sum the members' values mod r:
@@ -365,33 +366,30 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 // tail[p] = (1, r, s).  Witness scalars are converted out of Montgomery form when `mont` is set.
 static __global__ void __launch_bounds__(256)
 k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ wit, const uint32_t* __restrict__ tail,
-                uint32_t nv, uint32_t n_in, uint32_t m, uint32_t cstride, uint32_t mont, uint32_t* bad, uint32_t fold,
-                uint32_t in_tail = 0, const uint32_t* __restrict__ groups = nullptr, uint32_t ga = 0, uint32_t gb2 = 0,
-                uint32_t gb1 = 0) {
+                const zkrt::CJobLayout L, uint32_t mont, uint32_t* bad, const uint32_t* __restrict__ groups) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    const uint32_t wstride = nv + 3 + ga + gb2;
-    if (i >= wstride + gb1) return;
+    if (i >= L.wstride + L.gb1) return;
     const size_t p = blockIdx.y;
-    uint32_t* cv = cvec + p * (size_t)cstride * 8;
-    const uint32_t n_aux = nv - n_in;
+    uint32_t* cv = cvec + p * (size_t)L.cstride * 8;
+    const uint32_t nv = L.w_one, fold = L.fold;
     Fr r = ld_fr(tail + (p * 3 + 1) * 8);   // plain
     Fr sR = fold ? mul(ld_fr(tail + (p * 3 + 2) * 8), Fr::r2()) : Fr::zero();   // s in Montgomery form
     Fr v;
-    if (i >= nv + 3) {
-        const uint32_t g = i - (nv + 3);
-        const uint32_t* mem = groups + (ga + gb2 + gb1 + 1);
+    if (i >= L.w_sum_a) {
+        const uint32_t g = i - L.w_sum_a;
+        const uint32_t* mem = groups + (L.ga + L.gb2 + L.gb1 + 1);
         Fr sum = Fr::zero();   // in the form the witness came in: the sum of Montgomery forms is the form of the sum
         for (uint32_t k = groups[g]; k < groups[g + 1]; k++) {
             const Fr raw = ld_fr(wit + (p * nv + mem[k]) * 8);
             if (!fr_geq_r(raw)) sum = add(sum, raw);   // (the member's own thread raises the flag)
         }
-        if (g < ga + gb2) {
+        if (i < L.wstride) {
             v = mont ? from_mont(sum) : sum;
-            if (fold && g < ga) st_fr(cv + (size_t)(cstride - ga + g) * 8, mul(v, sR));   // (sum)(s R) / R
-            st_fr(wit_out + (p * wstride + i) * 8, v);
+            if (fold && g < L.ga) st_fr(cv + (size_t)(L.sum_a + g) * 8, mul(v, sR));   // (sum)(s R) / R
+            st_fr(wit_out + (p * L.wstride + i) * 8, v);
         } else {
             const Fr rz = mont ? mul(sum, r) : mul(mul(sum, r), Fr::r2());
-            st_fr(cv + (size_t)(cstride - (fold ? ga : 0u) - (ga + gb2 + gb1 - g)) * 8, rz);
+            st_fr(cv + (size_t)(L.sum_b1 + (i - L.wstride)) * 8, rz);
         }
         return;
     }
@@ -411,17 +409,17 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
             v = raw;
             rz = mul(mul(raw, r), Fr::r2());      // (z r / R)(R^2) / R = z r
         }
-        if (i >= n_in) st_fr(cv + (size_t)(m + (i - n_in)) * 8, v);
-        st_fr(cv + (size_t)(m + n_aux + i) * 8, rz);
-        if (fold) st_fr(cv + (size_t)(m + n_aux + nv + 1 + i) * 8, mul(v, sR));   // (z)(s R) / R = z s
-        if (in_tail && i < n_in) st_fr(cv + (size_t)(in_tail + i) * 8, v);
+        if (i >= L.n_in) st_fr(cv + (size_t)(L.aux + (i - L.n_in)) * 8, v);
+        st_fr(cv + (size_t)(L.rz + i) * 8, rz);
+        if (fold) st_fr(cv + (size_t)(L.sz + i) * 8, mul(v, sR));   // (z)(s R) / R = z s
+        if (L.in_tail && i < L.n_in) st_fr(cv + (size_t)(L.in_tail + i) * 8, v);
     } else {
         v = ld_fr(tail + (p * 3 + (i - nv)) * 8);
-        if (i == nv) st_fr(cv + (size_t)(m + n_aux + nv) * 8, r);   // r * 1 for beta_1
-        if (fold && i == nv + 1) st_fr(cv + (size_t)(m + n_aux + 2 * nv + 2) * 8, mul(r, sR));   // r s for delta_1
-        if (fold && i == nv + 2) st_fr(cv + (size_t)(m + n_aux + 2 * nv + 1) * 8, v);            // s for alpha_1
+        if (i == nv) st_fr(cv + (size_t)L.r * 8, r);   // r * 1 for beta_1
+        if (fold && i == nv + 1) st_fr(cv + (size_t)L.rs * 8, mul(r, sR));   // r s for delta_1
+        if (fold && i == nv + 2) st_fr(cv + (size_t)L.s * 8, v);            // s for alpha_1
     }
-    st_fr(wit_out + (p * wstride + i) * 8, v);
+    st_fr(wit_out + (p * L.wstride + i) * 8, v);
 }
 
 }  // namespace zkdev

@@ -30,6 +30,7 @@
 #include "host_math.h"
 #include "ntt.h"
 #include "msm_group.h"
+#include "prove_plan.h"
 #include "transfer_witness.h"
 #include "handles.h"
 #include "transfer_r1cs.h"
@@ -647,7 +648,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     key.push_back(merge ? 1 : 0);
     if (key == P->dens_key) return ZK_OK;
     const uint32_t nv = n_in + n_aux;
-    // scalar layout per proof: [inputs | aux | 1 | r | s | sums of the A groups | sums of the B2 groups]
+    // scalar layout per proof: [inputs | aux | 1 | r | s | sums of the A groups | sums of the B2 groups] (prove_plan.h CJobLayout)
     std::vector<int32_t> ma(nv + 3, -1), mb1(nv + 3, -1), mb2(nv + 3, -1);
     std::vector<uint32_t> var_a, var_b;   // query position -> variable
     var_a.reserve(P->n_a);
@@ -706,10 +707,11 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     mute(merge ? P->grp_b1 : none, var_b, mb1, base_b1);
     const uint32_t ga = (uint32_t)base_a.size(), gb2 = (uint32_t)base_b2.size(), gb1 = (uint32_t)base_b1.size();
     // (each of the two jobs over this vector selects its own sums; the other's stay -1)
-    ma.resize(nv + 3 + ga + gb2, -1);
-    mb2.resize(nv + 3 + ga + gb2, -1);
-    for (uint32_t g = 0; g < ga; g++) ma[nv + 3 + g] = base_a[g];
-    for (uint32_t g = 0; g < gb2; g++) mb2[nv + 3 + ga + g] = base_b2[g];
+    const CJobLayout W = cjob_layout(n_in, n_aux, (uint32_t)P->m, ga, gb2, gb1, false, false);
+    ma.resize(W.wstride, -1);
+    mb2.resize(W.wstride, -1);
+    for (uint32_t g = 0; g < ga; g++) ma[W.w_sum_a + g] = base_a[g];
+    for (uint32_t g = 0; g < gb2; g++) mb2[W.w_sum_b2 + g] = base_b2[g];
     // h coefficients leave the last transform in bit-reversed order; the top coefficient
     // (degree m - 1) is dropped exactly as bellman truncates it
     std::vector<int32_t> mh(P->m);
@@ -717,58 +719,70 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
         uint32_t e = P->log_m ? (__builtin_bitreverse32((uint32_t)pos) >> (32 - P->log_m)) : 0;
         mh[pos] = e < P->n_h ? (int32_t)e : -1;
     }
-    // merged C job: [h (m) | aux (n_aux) | r z (nv) | r | r * sums of the B1 groups], absolute positions in the G1 group table
-    auto with_sums = [](std::vector<int32_t>& map, const std::vector<int32_t>& base, uint32_t off) {
-        for (int32_t b : base) map.push_back((int32_t)off + b);
+    auto upload = [](DevBuf& dst, const auto& v) -> zk_status {
+        ZK_TRY(dst.ensure(v.size() * 4));
+        HIP_TRY(hipMemcpy(dst.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
+        return ZK_OK;
     };
-    std::vector<int32_t> mc;
-    mc.reserve(P->m + n_aux + 2 * (size_t)nv + 3 + gb1 + ga);
-    for (size_t pos = 0; pos < P->m; pos++) mc.push_back(mh[pos] < 0 ? -1 : (int32_t)(P->off_h + mh[pos]));
-    for (uint32_t j = 0; j < n_aux; j++) mc.push_back((int32_t)(P->off_l + j));
-    for (uint32_t i = 0; i < nv; i++) mc.push_back(mb1[i] < 0 ? -1 : (int32_t)(P->off_b1 + mb1[i]));
-    mc.push_back(P->beta_g1_inf ? -1 : (int32_t)(P->off_b1 + P->n_b1));   // r * beta_g1
-    // the folded form of the job (ntt.h k_build_scalars, fold): + [s z (nv) | s | r s] over the A query, alpha_1, delta_1
-    // behind the r, and [s * sums of the A groups] at the end
-    std::vector<int32_t> mcf(mc);
-    for (uint32_t i = 0; i < nv + 2; i++) mcf.push_back(ma[i] < 0 ? -1 : (int32_t)(P->off_a + ma[i]));
-    with_sums(mc, base_b1, P->off_b1);
-    with_sums(mcf, base_b1, P->off_b1);
-    with_sums(mcf, base_a, P->off_a);
-    if (P->drv.ready && P->drv.pos.size() == 2 * (size_t)P->drv.n_rows + nv) {
-        // the same job over the derived bases: [s (n_rows) | e (n_rows) | aux | r z | r | fold | inputs (n_in) | sums]
-        const zk_params::Derived& D = P->drv;
-        const size_t head = 2 * (size_t)D.n_rows;
-        std::vector<int32_t> md;
-        md.reserve(mcf.size() + n_in);
-        for (size_t j = 0; j < head; j++) md.push_back(D.pos[j]);
-        for (uint32_t j = 0; j < n_aux; j++) md.push_back(D.pos[head + n_in + j]);
-        for (uint32_t i = 0; i < nv; i++) md.push_back(mb1[i] < 0 ? -1 : (int32_t)(D.off_b1 + mb1[i]));
-        md.push_back(P->beta_g1_inf ? -1 : (int32_t)(D.off_b1 + P->n_b1));
-        std::vector<int32_t> mdf(md);
-        for (uint32_t i = 0; i < nv + 2; i++) mdf.push_back(ma[i] < 0 ? -1 : (int32_t)(D.off_a + ma[i]));
-        for (uint32_t i = 0; i < n_in; i++) {
-            md.push_back(D.pos[head + i]);
-            mdf.push_back(D.pos[head + i]);
+    // The index map of the merged C job, absolute positions in the G1 group table, section by section where the layout has
+    // them (prove_plan.h CJobLayout: what k_build_scalars stores by): the H block, the aux and - derived - the input variables
+    // on the bases given, the r and fold sections and the sums of the groups on the copies of the b_g1 and A queries.
+    auto upload_c_map = [&](DevBuf& dst, const CJobLayout& L, const int32_t* head, const int32_t* aux, const int32_t* inputs,
+                            uint32_t off_a, uint32_t off_b1) -> zk_status {
+        std::vector<int32_t> map(head, head + L.head);
+        map.reserve(L.cstride);
+        bool fits = true;
+        auto section = [&](uint32_t off) { fits = fits && map.size() == off; };
+        auto query = [&](const std::vector<int32_t>& q, uint32_t from, uint32_t n, uint32_t off) {
+            for (uint32_t i = from; i < from + n; i++) map.push_back(q[i] < 0 ? -1 : (int32_t)(off + q[i]));
+        };
+        section(L.aux);
+        map.insert(map.end(), aux, aux + n_aux);
+        section(L.rz);
+        query(mb1, 0, nv, off_b1);
+        section(L.r);
+        query(mb1, nv, 1, off_b1);   // r * beta_1
+        if (L.fold) {   // [s z (nv) | s | r s] over the A query, alpha_1, delta_1
+            section(L.sz);
+            query(ma, 0, nv, off_a);
+            section(L.s);
+            query(ma, nv, 1, off_a);
+            section(L.rs);
+            query(ma, nv + 1, 1, off_a);
         }
-        with_sums(md, base_b1, D.off_b1);
-        with_sums(mdf, base_b1, D.off_b1);
-        with_sums(mdf, base_a, D.off_a);
-        ZK_TRY(P->map_cd.ensure(md.size() * 4));
-        ZK_TRY(P->map_cfd.ensure(mdf.size() * 4));
-        HIP_TRY(hipMemcpy(P->map_cd.p, md.data(), md.size() * 4, hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(P->map_cfd.p, mdf.data(), mdf.size() * 4, hipMemcpyHostToDevice));
+        if (L.derived) {
+            section(L.in_tail);
+            map.insert(map.end(), inputs, inputs + n_in);
+        }
+        section(L.sum_b1);
+        query(base_b1, 0, gb1, off_b1);
+        if (L.fold) {
+            section(L.sum_a);
+            query(base_a, 0, ga, off_a);
+        }
+        section(L.cstride);
+        if (!fits) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the C map does not follow its layout");
+        return upload(dst, map);
+    };
+    std::vector<int32_t> hk;   // the key's own bases: [h (m) | l (n_aux)]
+    hk.reserve(P->m + n_aux);
+    for (size_t pos = 0; pos < P->m; pos++) hk.push_back(mh[pos] < 0 ? -1 : (int32_t)(P->off_h + mh[pos]));
+    for (uint32_t j = 0; j < n_aux; j++) hk.push_back((int32_t)(P->off_l + j));
+    for (bool fold : {false, true})
+        ZK_TRY(upload_c_map(fold ? P->map_cf : P->map_c, cjob_layout(n_in, n_aux, (uint32_t)P->m, ga, gb2, gb1, fold, false), hk.data(),
+                            hk.data() + P->m, nullptr, P->off_a, P->off_b1));
+    if (P->drv.ready && P->drv.pos.size() == 2 * (size_t)P->drv.n_rows + nv) {
+        // the same job over the derived bases, pos = [s (n_rows) | e (n_rows) | inputs | aux]
+        const zk_params::Derived& D = P->drv;
+        const uint32_t head = 2 * D.n_rows;
+        for (bool fold : {false, true})
+            ZK_TRY(upload_c_map(fold ? P->map_cfd : P->map_cd, cjob_layout(n_in, n_aux, head, ga, gb2, gb1, fold, true), D.pos.data(),
+                                D.pos.data() + head + n_in, D.pos.data() + head, D.off_a, D.off_b1));
     }
     gptr.insert(gptr.end(), gmem.begin(), gmem.end());
-    ZK_TRY(P->grp_dev.ensure(gptr.size() * 4));
-    HIP_TRY(hipMemcpy(P->grp_dev.p, gptr.data(), gptr.size() * 4, hipMemcpyHostToDevice));
-    ZK_TRY(P->map_cf.ensure(mcf.size() * 4));
-    HIP_TRY(hipMemcpy(P->map_cf.p, mcf.data(), mcf.size() * 4, hipMemcpyHostToDevice));
-    ZK_TRY(P->map_a.ensure(ma.size() * 4));
-    ZK_TRY(P->map_b2.ensure(mb2.size() * 4));
-    ZK_TRY(P->map_c.ensure(mc.size() * 4));
-    HIP_TRY(hipMemcpy(P->map_a.p, ma.data(), ma.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P->map_b2.p, mb2.data(), mb2.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(P->map_c.p, mc.data(), mc.size() * 4, hipMemcpyHostToDevice));
+    ZK_TRY(upload(P->grp_dev, gptr));
+    ZK_TRY(upload(P->map_a, ma));
+    ZK_TRY(upload(P->map_b2, mb2));
     P->dens_key.swap(key);
     P->map_nv = nv;
     P->mg_a = ga;
@@ -784,219 +798,247 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // (prove_chunk: the fold and the three into_affine run on the GPU, k_ct_scale_add /
 // k_xyzz_normalize_export; the host encodes the 192 bytes.)
 
+// One chunk of proofs: the plan (prove_plan.h), what its stages hand to each other, and the stages in the order they run.
 // derived: a, b, c are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over
 // the derived bases (ensure_derived), whose H scalars are those of the live rows.
-zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
-    const auto t_begin = std::chrono::steady_clock::now();
-    const uint32_t n_in = bt->n_inputs, n_aux = bt->n_aux, nv = n_in + n_aux, n_rows = bt->n_rows;
-    const size_t m = P->m;
-    const bool mont = (bt->flags & ZK_FR_MONTGOMERY) != 0;
-    // ---- scalars [inputs | aux | 1 | r | s | sums of the A groups | of the B2 groups] per proof, plain (ensure_maps)
-    const uint32_t ga = P->mg_a, gb2 = P->mg_b2, gb1 = P->mg_b1;
-    const size_t wstride = (size_t)(nv + 3 + ga + gb2);
-    ZK_TRY(P->wit.ensure(np * wstride * 32));
-    uint32_t* wit = P->wit.as<uint32_t>();
-    ZK_TRY(P->pin_tail.ensure(np * 96));
-    uint8_t* tail = P->pin_tail.as<uint8_t>();
-    memset(tail, 0, np * 96);
-    std::vector<uint64_t> rsv(np * 8);
-    for (size_t p = 0; p < np; p++) {
-        const uint8_t* rr = rs + (first + p) * 64;
-        load_scalar_le(rr, &rsv[p * 8]);
-        load_scalar_le(rr + 32, &rsv[p * 8 + 4]);
-        if (!scalar_lt_r(&rsv[p * 8]) || !scalar_lt_r(&rsv[p * 8 + 4]))
-            return fail(ZK_ERR_INVALID_ARGUMENT, "r or s is not a canonical scalar (>= field modulus)");
-        tail[p * 96] = 1;
-        memcpy(&tail[p * 96 + 32], rr, 64);
+static_assert(PROVE_FOLD_IN_MSM_MAX == MSM_FEW_JOBS, "the fold rides in the multiexp up to the few-jobs limit of a launch set");
+typedef zkdev::XYZZ<zkdev::Fq> DP1;
+struct ChunkRun {
+    zk_params* P;
+    size_t np;
+    const zk_batch_dev* bt;
+    size_t first;            // the chunk's first proof in the batch
+    bool derived, mont;
+    ProvePlan plan;
+    hipStream_t side;        // the G2 set and the A jobs of a split chunk run here, beside the H pipeline
+    MsmG2* G2;
+    MsmG1* G1C;              // the group of the C' jobs
+    const int32_t* map_c;
+    uint32_t *wit, *cvec, *bad;
+    const DP1* a_dev = nullptr;   // A of every proof, where the G1 launch sets left it
+
+    // ---- scalars [inputs | aux | 1 | r | s | sums of the A groups | of the B2 groups] per proof, plain, and the merged C job's
+    // but for its H block (prove_plan.h CJobLayout)
+    zk_status scalars(const uint8_t* rs) {
+        const CJobLayout& L = plan.layout;
+        const uint32_t nv = L.n_in + L.n_aux;
+        ZK_TRY(P->wit.ensure(np * (size_t)L.wstride * 32));
+        wit = P->wit.as<uint32_t>();
+        ZK_TRY(P->pin_tail.ensure(np * 96));
+        uint8_t* tail = P->pin_tail.as<uint8_t>();
+        memset(tail, 0, np * 96);
+        std::vector<uint64_t> rsv(np * 8);
+        for (size_t p = 0; p < np; p++) {
+            const uint8_t* rr = rs + (first + p) * 64;
+            load_scalar_le(rr, &rsv[p * 8]);
+            load_scalar_le(rr + 32, &rsv[p * 8 + 4]);
+            if (!scalar_lt_r(&rsv[p * 8]) || !scalar_lt_r(&rsv[p * 8 + 4]))
+                return fail(ZK_ERR_INVALID_ARGUMENT, "r or s is not a canonical scalar (>= field modulus)");
+            tail[p * 96] = 1;
+            memcpy(&tail[p * 96 + 32], rr, 64);
+        }
+        ZK_TRY(P->tail.ensure(np * 96));
+        HIP_TRY(hipMemcpyAsync(P->tail.p, tail, np * 96, hipMemcpyHostToDevice, g_stream));
+        ZK_TRY(P->bad.ensure(8));
+        ZK_TRY(P->pin_bad.ensure(8));
+        bad = P->bad.as<uint32_t>();
+        HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
+        ZK_TRY(P->cvec.ensure(np * (size_t)L.cstride * 32));
+        cvec = P->cvec.as<uint32_t>();
+        // (the same launch: a thread per variable, three for the tail, one per group)
+        ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.wstride + L.gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
+                  (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), L, mont ? 1u : 0u, bad,
+                  P->grp_dev.as<uint32_t>());
+        return ZK_OK;
     }
-    ZK_TRY(P->tail.ensure(np * 96));
-    HIP_TRY(hipMemcpyAsync(P->tail.p, tail, np * 96, hipMemcpyHostToDevice, g_stream));
-    ZK_TRY(P->bad.ensure(8));
-    ZK_TRY(P->pin_bad.ensure(8));
-    uint32_t* bad = P->bad.as<uint32_t>();
-    HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
-    // A few proofs made alone carry the final fold C = s * A + C' INSIDE the C multiexp: s * A = s alpha_1 + sum (s z_i) A_i +
-    // (r s) delta_1 is 15.6 k more terms over bases whose doublings are in the table (+19 % pairs in a launch whose duration is
-    // the length of its longest task, not their number), where the fold's kernel (k_ct_scale_add) is a chain of 252 doublings and ~75 additions
-    // of ONE point: 4.7 ms of a 7.4 ms proof under a 255-bit s (profiles/r06c_lone_baseline_random_rs_launch_list.txt).
-    // A batch keeps the chain: one row per proof, hidden behind the other pipeline lane, no extra pairs.
-    // Up to the few-jobs limit of a launch set (128 proofs): there the chain is exposed at the end of the call - 4.7 ms on
-    // a call of 17.6 ms for 32 proofs - and 19 % more G1 pairs cost less.  ZKAMD_FOLD_IN_MSM_MAX overrides (measurements).
-    // (read at every chunk: the emulation suite sends small batches through the chunk form of the fold)
-    const size_t fold_max = getenv("ZKAMD_FOLD_IN_MSM_MAX") ? (size_t)atoll(getenv("ZKAMD_FOLD_IN_MSM_MAX")) : MSM_FEW_JOBS;
-    const bool fold_in_msm = np <= fold_max;
-    if (derived && (!mont || P->drv.n_rows != n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
-    // the H block at the head of the C' job: bellman's m coefficients, or [s | e] of the live rows over the derived bases
-    const uint32_t head = derived ? 2 * n_rows : (uint32_t)m;
-    const uint32_t in_tail = derived ? (uint32_t)(head + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0)) : 0u;   // (the inputs carry their part of c)
-    // (the sums of the groups at the end: r * B1's, then s * A's with the fold)
-    const uint32_t cstride = (uint32_t)(head + n_aux + nv + 1 + (fold_in_msm ? nv + 2 : 0) + (derived ? n_in : 0) + gb1 + (fold_in_msm ? ga : 0));
-    ZK_TRY(P->cvec.ensure(np * (size_t)cstride * 32));
-    uint32_t* cvec = P->cvec.as<uint32_t>();
-    // (the same launch: a thread per variable, three for the tail, one per group)
-    ZK_LAUNCH(zkdev::k_build_scalars, dim3((nv + 3 + ga + gb2 + gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
-              (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), nv, n_in, head, cstride,
-              mont ? 1u : 0u, bad, fold_in_msm ? 1u : 0u, in_tail, P->grp_dev.as<uint32_t>(), ga, gb2, gb1);
+
     // ---- multiexps (create_proof step 4).  The G2 job only needs the witness scalars: it is
     // enqueued first, on the side stream, and runs beside the H pipeline and the G1 multiexps (its
     // reduction tree is latency-bound with one job per proof; the G1 work fills the machine).
-    P->jobs1.clear();
-    P->jobs2.clear();
-    const uint32_t npts1 = (uint32_t)P->g1.n_points, npts2 = (uint32_t)P->g2.n_points;
-    for (size_t p = 0; p < np; p++) {
-        const uint32_t* w = wit + p * wstride * 8;
-        MsmJob j2 = {w, P->map_b2.as<int32_t>(), (uint32_t)wstride, 0, npts2, 0, 0, 0};
-        P->jobs2.push_back(j2);
+    zk_status g2_set() {
+        const uint32_t wstride = plan.layout.wstride;
+        P->jobs2.clear();
+        for (size_t p = 0; p < np; p++) {
+            MsmJob j2 = {wit + p * (size_t)wstride * 8, P->map_b2.as<int32_t>(), wstride, 0, (uint32_t)P->g2.n_points, 0, 0, 0};
+            P->jobs2.push_back(j2);
+        }
+        HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
+        HIP_TRY(hipStreamWaitEvent(side, g_ev_fork, 0));
+        ZK_TRY(G2->enqueue(P->jobs2, P->res2, side, false));
+        ZK_TRY(P->pin_g2.ensure(np * sizeof(HG2)));
+        if (plan.host_norm) ZK_TRY(G2->export_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));
+        else ZK_TRY(G2->normalize_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));   // B in affine form
+        return ZK_OK;
     }
-    hipStream_t side = getenv("ZKAMD_NO_OVERLAP") ? g_stream : g_stream2;
-    HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
-    HIP_TRY(hipStreamWaitEvent(side, g_ev_fork, 0));
-    static const size_t g2_lone_max = getenv("ZKAMD_G2_LONE_MAX") ? (size_t)atoll(getenv("ZKAMD_G2_LONE_MAX")) : 2;   // (measurement override)
-    MsmG2& G2 = np <= g2_lone_max ? P->g2_lone : P->g2;
-    ZK_TRY(G2.enqueue(P->jobs2, P->res2, side, false));
-    ZK_TRY(P->pin_g2.ensure(np * sizeof(HG2)));
-    ZK_TRY(P->pin_g1.ensure(2 * np * sizeof(HG1)));
-    // into_affine of a handful of proofs: on the host (the encoder's to_affine), the kernels only export
-    static const size_t host_norm_max = getenv("ZKAMD_HOST_NORMALIZE_MAX") ? (size_t)atoll(getenv("ZKAMD_HOST_NORMALIZE_MAX")) : 16;
-    const bool host_norm = np <= host_norm_max;
-    if (host_norm) ZK_TRY(G2.export_to_host(G2.res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));
-    else ZK_TRY(G2.normalize_to_host(G2.res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));   // B in affine form
-    // ---- H pipeline (create_proof step 3)
-    ZK_TRY(P->abc.ensure((derived ? 2 : 3) * np * m * 32));
-    uint32_t* A = P->abc.as<uint32_t>();
-    uint32_t* B = A + np * m * 8;
-    uint32_t* C = B + np * m * 8;
-    const uint32_t* srcs[3] = {(const uint32_t*)bt->d_a + first * (size_t)n_rows * 8,
-                               (const uint32_t*)bt->d_b + first * (size_t)n_rows * 8,
-                               (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
-    uint32_t* dsts[3] = {A, B, C};
-    // ifft (natural -> bit-reversed) of a and b, then * g^i / m (coset shift); c: * 1 / (m (g^m - 1)), plain - its
-    // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7).
-    // Over the derived bases: a and b only, * t / m - the coefficients of x a'(x) - and the forward chain below is a plain
-    // transform back onto the domain; the row evaluations themselves stay where they are (the chains load out of place).
-    const uint32_t* s1 = derived ? P->ntt.dt.as<uint32_t>() : mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
-    const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
-    for (int k = 0; k < (derived ? 2 : 3); k++)
-        ZK_TRY(P->ntt.chain(dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
-    // (coset) fft (bit-reversed -> natural) of a and b at once
-    ZK_TRY(P->ntt.chain(A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
-    {
-        ProfScope ps("h_pointwise");
-        if (derived) {
-            // s_j and e_k of the live rows ARE the scalars (plain, natural order): four transforms per proof, none after this
-            const size_t count = np * (size_t)n_rows;
-            ZK_LAUNCH(zkdev::k_h_live_rows, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
-                      (const uint32_t*)B, srcs[0], srcs[1], srcs[2], cvec, (uint32_t)m, n_rows, cstride, count);
+
+    // ---- H pipeline (create_proof step 3): the H block of every C job
+    zk_status h_pipeline() {
+        const size_t m = P->m;
+        const uint32_t n_rows = bt->n_rows, cstride = plan.layout.cstride;
+        ZK_TRY(P->abc.ensure((derived ? 2 : 3) * np * m * 32));
+        uint32_t* A = P->abc.as<uint32_t>();
+        uint32_t* B = A + np * m * 8;
+        uint32_t* C = B + np * m * 8;
+        const uint32_t* srcs[3] = {(const uint32_t*)bt->d_a + first * (size_t)n_rows * 8,
+                                   (const uint32_t*)bt->d_b + first * (size_t)n_rows * 8,
+                                   (const uint32_t*)bt->d_c + first * (size_t)n_rows * 8};
+        uint32_t* dsts[3] = {A, B, C};
+        // ifft (natural -> bit-reversed) of a and b, then * g^i / m (coset shift); c: * 1 / (m (g^m - 1)), plain - its
+        // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7).
+        // Over the derived bases: a and b only, * t / m - the coefficients of x a'(x) - and the forward chain below is a plain
+        // transform back onto the domain; the row evaluations themselves stay where they are (the chains load out of place).
+        const uint32_t* s1 = derived ? P->ntt.dt.as<uint32_t>() : mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
+        const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
+        for (int k = 0; k < (derived ? 2 : 3); k++)
+            ZK_TRY(P->ntt.chain(dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
+        // (coset) fft (bit-reversed -> natural) of a and b at once
+        ZK_TRY(P->ntt.chain(A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
+        {
+            ProfScope ps("h_pointwise");
+            if (derived) {
+                // s_j and e_k of the live rows ARE the scalars (plain, natural order): four transforms per proof, none after this
+                const size_t count = np * (size_t)n_rows;
+                ZK_LAUNCH(zkdev::k_h_live_rows, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
+                          (const uint32_t*)B, srcs[0], srcs[1], srcs[2], cvec, (uint32_t)m, n_rows, cstride, count);
+            } else {
+                const size_t count = np * m;
+                ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
+                          (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
+            }
+        }
+        // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
+        // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
+        if (!derived)
+            ZK_TRY(P->ntt.chain(cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
+                                (const uint32_t*)C, (uint32_t)m));
+        return ZK_OK;
+    }
+
+    // ---- the G1 launch sets (prove_plan.h, split): the C' jobs on the main stream behind the H pipeline and the A jobs on the
+    // side stream behind the G2 set, or one set on the main stream - all C' jobs, then all A jobs
+    zk_status g1_sets() {
+        const bool split = plan.split;
+        const uint32_t wstride = plan.layout.wstride, cstride = plan.layout.cstride;
+        const uint32_t npts1 = (uint32_t)P->g1.n_points, npts1c = (uint32_t)G1C->n_points;
+        P->jobs1.clear();
+        P->jobs1a.clear();
+        for (size_t p = 0; p < np; p++) {
+            MsmJob jc = {cvec + p * (size_t)cstride * 8, map_c, cstride, 0, npts1c, 0, 0, 0};
+            P->jobs1.push_back(jc);
+        }
+        for (size_t p = 0; p < np; p++) {
+            MsmJob ja = {wit + p * (size_t)wstride * 8, P->map_a.as<int32_t>(), wstride, P->off_a, npts1, 0, 0, 0};
+            if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
+                ja.table_base = P->drv.off_a;
+                ja.n_table = npts1c;
+            }
+            (split ? P->jobs1a : P->jobs1).push_back(ja);
+        }
+        if (split) {
+            ZK_TRY(P->g1a.enqueue(P->jobs1a, P->res1a, side, false));
+            a_dev = P->g1a.res_dev;
+            HIP_TRY(hipEventRecord(g_ev_join, side));
+            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false));
+            HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when the side stream is the main one)
         } else {
-            const size_t count = np * m;
-            ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
-                      (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
+            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false));
+            a_dev = G1C->res_dev + np;
         }
+        return ZK_OK;
     }
-    // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
-    // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
-    if (!derived)
-        ZK_TRY(P->ntt.chain(cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
-                            (const uint32_t*)C, (uint32_t)m));
-    // A batch runs the two G1 jobs of its proofs as two launch sets, each under the recoding width of its own size: the
-    // C' jobs (65 k terms) here on the main stream behind the H pipeline, the A jobs (15.6 k terms, witness scalars only)
-    // on the side stream behind the G2 set.  A few proofs made alone keep
-    // ONE set (fewer launches on their critical path): all C' jobs, then all A jobs - workgroup i of a launch runs on XCD
-    // i mod 8 and the sort is one workgroup per job, so alternating A, C' would put every large job on the odd XCDs.
-    const size_t split_min = getenv("ZKAMD_SPLIT_MIN") ? (size_t)atoll(getenv("ZKAMD_SPLIT_MIN")) : 64;   // tests: 1
-    const bool split = np >= split_min;
-    MsmG1& G1C = derived ? (split ? P->g1d : P->g1d_lone) : (split ? P->g1 : P->g1_lone);
-    const int32_t* map_c = derived ? (fold_in_msm ? P->map_cfd : P->map_cd).as<int32_t>() : (fold_in_msm ? P->map_cf : P->map_c).as<int32_t>();
-    const uint32_t npts1c = (uint32_t)G1C.n_points;
-    for (size_t p = 0; p < np; p++) {
-        MsmJob jc = {cvec + p * (size_t)cstride * 8, map_c, cstride, 0, npts1c, 0, 0, 0};
-        P->jobs1.push_back(jc);
-    }
-    P->jobs1a.clear();
-    for (size_t p = 0; p < np; p++) {
-        const uint32_t* w = wit + p * wstride * 8;
-        MsmJob ja = {w, P->map_a.as<int32_t>(), (uint32_t)wstride, P->off_a, npts1, 0, 0, 0};
-        if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
-            ja.table_base = P->drv.off_a;
-            ja.n_table = npts1c;
-        }
-        (split ? P->jobs1a : P->jobs1).push_back(ja);
-    }
-    typedef zkdev::XYZZ<zkdev::Fq> DP1;
-    const DP1* a_dev = nullptr;
-    if (split) {
-        ZK_TRY(P->g1a.enqueue(P->jobs1a, P->res1a, side, false));
-        a_dev = P->g1a.res_dev;
-        HIP_TRY(hipEventRecord(g_ev_join, side));
-        ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
-        HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when ZKAMD_NO_OVERLAP made the side stream the main one)
-    } else {
-        ZK_TRY(G1C.enqueue(P->jobs1, P->res1, g_stream, false));
-        a_dev = G1C.res_dev + np;
-    }
+
     // ---- final fold on the GPU: C = s * A + C' (coop_tail.h scale_add), A and C to affine form; the host
     // only encodes.  (On the host the fold was 0.47 ms per proof with the GPU idle: 8 % of the step.)
-    {
+    zk_status fold_export() {
         ProfScope ps("proof_fold", g_stream);
-        const DP1* cprime = G1C.res_dev;
-        const DP1* a = a_dev;
+        const DP1* cprime = G1C->res_dev;
         const DP1* cfin = cprime;   // the C job was s * A + C' already
-        if (!fold_in_msm) {
+        if (!plan.fold_in_msm) {
             ZK_TRY(P->fold_tbl.ensure(np * 15 * sizeof(DP1)));
             ZK_TRY(P->fold_c.ensure(np * sizeof(DP1)));
             // one row of 16 lanes per proof (coop_tail.cpp): 256 waves, each chain 4 - 5 x shorter than a lane's
-            zkcoop::scale_add(a, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
+            zkcoop::scale_add(a_dev, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
                               P->fold_c.as<DP1>(), (uint32_t)np, g_stream);
             cfin = P->fold_c.as<DP1>();
         }
-        if (host_norm) {
-            ZK_TRY(G1C.export_to_host(a, np, P->pin_g1.as<HG1>() + np, P->fold_a1, g_stream));
-            ZK_TRY(G1C.export_to_host(cfin, np, P->pin_g1.as<HG1>(), P->fold_c1, g_stream));
+        ZK_TRY(P->pin_g1.ensure(2 * np * sizeof(HG1)));
+        if (plan.host_norm) {
+            ZK_TRY(G1C->export_to_host(a_dev, np, P->pin_g1.as<HG1>() + np, P->fold_a1, g_stream));
+            ZK_TRY(G1C->export_to_host(cfin, np, P->pin_g1.as<HG1>(), P->fold_c1, g_stream));
         } else {
-            ZK_TRY(G1C.normalize2_to_host(a, cfin, np, P->pin_g1.as<HG1>() + np, P->pin_g1.as<HG1>(), P->fold_a1, P->fold_c1, g_stream));
+            ZK_TRY(G1C->normalize2_to_host(a_dev, cfin, np, P->pin_g1.as<HG1>() + np, P->pin_g1.as<HG1>(), P->fold_a1, P->fold_c1, g_stream));
         }
+        return ZK_OK;
     }
-    HIP_TRY(hipMemcpyAsync(P->pin_bad.p, bad, 8, hipMemcpyDeviceToHost, g_stream));
-    const bool trace_host = getenv("ZKAMD_TRACE_HOST") != nullptr;
-    const auto t_wait = std::chrono::steady_clock::now();
-    ZK_TRY(G1C.collect(g_stream));
-    ZK_TRY(G2.collect(side));
-    {
+
+    // ---- wait for the GPU; the flags the kernels raised over the caller's scalars
+    zk_status collect(std::chrono::steady_clock::time_point& t_wait) {
+        HIP_TRY(hipMemcpyAsync(P->pin_bad.p, bad, 8, hipMemcpyDeviceToHost, g_stream));
+        t_wait = std::chrono::steady_clock::now();
+        ZK_TRY(G1C->collect(g_stream));
+        ZK_TRY(G2->collect(side));
         // the reference cannot even represent these assignments (FrRepr -> Fr fails for values >= r,
         // fr.rs:276-289; ProvingAssignment starts with alloc_input(ONE = 1))
         const uint32_t flags = P->pin_bad.as<uint32_t>()[0];
         if (flags & zkdev::ZK_BAD_SCALAR)
             return fail(ZK_ERR_INVALID_ARGUMENT, "an assignment scalar (a, b, c, input or aux) is not a canonical field element (>= r)");
         if (flags & zkdev::ZK_BAD_ONE) return fail(ZK_ERR_INVALID_ARGUMENT, "input 0 of an assignment is not ONE = 1");
+        return ZK_OK;
     }
-    const auto t_enc = std::chrono::steady_clock::now();
+
     // ---- encoding (host, one thread per slice of the chunk): pin_g1[p] = C, pin_g1[np + p] = A, pin_g2[p] = B
-    const unsigned nthreads = host_threads(np, 32);
-    uint8_t* const own_affine = g_own_affine_sink;   // (read on the calling thread: the workers below are other threads)
-    auto work = [&](size_t lo, size_t hi) {
-        for (size_t p = lo; p < hi; p++)
-        {
-            uint8_t* out = proofs_out + (first + p) * 192;
-            const HG1A pa = zkhost::to_affine(P->pin_g1.as<HG1>()[np + p]), pc = zkhost::to_affine(P->pin_g1.as<HG1>()[p]);
-            const HG2A pb = zkhost::to_affine(P->pin_g2.as<HG2>()[p]);
-            zkhost::g1_to_compressed(pa, out);
-            zkhost::g2_to_compressed(pb, out + 48);
-            zkhost::g1_to_compressed(pc, out + 144);
-            if (own_affine) {   // for the self-check of gen_proof (host_common.h g_own_affine_sink)
-                uint8_t* o = own_affine + p * OWN_AFFINE_BYTES;   // (a cursor: the chunks of a call arrive in order)
-                memcpy(o, &pa.x, 48);
-                memcpy(o + 48, &pa.y, 48);
-                memcpy(o + 96, &pb.x, 96);
-                memcpy(o + 192, &pb.y, 96);
-                memcpy(o + 288, &pc.x, 48);
-                memcpy(o + 336, &pc.y, 48);
+    void encode(uint8_t* proofs_out) {
+        const unsigned nthreads = host_threads(np, 32);
+        uint8_t* const own_affine = g_own_affine_sink;   // (read on the calling thread: the workers below are other threads)
+        auto work = [&](size_t lo, size_t hi) {
+            for (size_t p = lo; p < hi; p++)
+            {
+                uint8_t* out = proofs_out + (first + p) * 192;
+                const HG1A pa = zkhost::to_affine(P->pin_g1.as<HG1>()[np + p]), pc = zkhost::to_affine(P->pin_g1.as<HG1>()[p]);
+                const HG2A pb = zkhost::to_affine(P->pin_g2.as<HG2>()[p]);
+                zkhost::g1_to_compressed(pa, out);
+                zkhost::g2_to_compressed(pb, out + 48);
+                zkhost::g1_to_compressed(pc, out + 144);
+                if (own_affine) {   // for the self-check of gen_proof (host_common.h g_own_affine_sink)
+                    uint8_t* o = own_affine + p * OWN_AFFINE_BYTES;   // (a cursor: the chunks of a call arrive in order)
+                    memcpy(o, &pa.x, 48);
+                    memcpy(o + 48, &pa.y, 48);
+                    memcpy(o + 96, &pb.x, 96);
+                    memcpy(o + 192, &pb.y, 96);
+                    memcpy(o + 288, &pc.x, 48);
+                    memcpy(o + 336, &pc.y, 48);
+                }
             }
-        }
-    };
-    auto part = [&](unsigned t) { work(np * t / nthreads, np * (t + 1) / nthreads); };
-    run_threads(nthreads, part);
-    if (g_own_affine_sink) g_own_affine_sink += np * OWN_AFFINE_BYTES;
-    if (trace_host) {
+        };
+        auto part = [&](unsigned t) { work(np * t / nthreads, np * (t + 1) / nthreads); };
+        run_threads(nthreads, part);
+        if (g_own_affine_sink) g_own_affine_sink += np * OWN_AFFINE_BYTES;
+    }
+};
+
+zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t first, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
+    const auto t_begin = std::chrono::steady_clock::now();
+    const ProveTunables tun = ProveTunables::read();
+    const bool mont = (bt->flags & ZK_FR_MONTGOMERY) != 0;
+    if (derived && (!mont || P->drv.n_rows != bt->n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
+    ChunkRun c = {P, np, bt, first, derived, mont,
+                  prove_plan(np, bt->n_inputs, bt->n_aux, bt->n_rows, P->m, P->mg_a, P->mg_b2, P->mg_b1, derived, tun)};
+    c.side = c.plan.one_stream ? g_stream : g_stream2;
+    c.G2 = c.plan.g2_lone ? &P->g2_lone : &P->g2;
+    MsmG1* const g1s[] = {&P->g1, &P->g1_lone, &P->g1d, &P->g1d_lone};   // in the order of PG1 and PMap
+    DevBuf* const maps[] = {&P->map_c, &P->map_cf, &P->map_cd, &P->map_cfd};
+    c.G1C = g1s[(int)c.plan.g1];
+    c.map_c = maps[(int)c.plan.map]->as<int32_t>();
+    ZK_TRY(c.scalars(rs));
+    ZK_TRY(c.g2_set());
+    ZK_TRY(c.h_pipeline());
+    ZK_TRY(c.g1_sets());
+    ZK_TRY(c.fold_export());
+    std::chrono::steady_clock::time_point t_wait;
+    ZK_TRY(c.collect(t_wait));
+    const auto t_enc = std::chrono::steady_clock::now();
+    c.encode(proofs_out);
+    if (tun.trace_host) {
         const auto t_end = std::chrono::steady_clock::now();
         fprintf(stderr, "[zkamd] chunk of %zu: enqueue %.2f ms, wait for the GPU %.2f ms, host encoding %.2f ms\n", np,
                 std::chrono::duration<double, std::milli>(t_wait - t_begin).count(),
@@ -1019,11 +1061,7 @@ zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const 
     if (!bt->d_a || !bt->d_b || !bt->d_c || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
         return fail(ZK_ERR_ASSIGNMENT_MISSING, "assignment pointer is null");
     ZK_TRY(ensure_maps(P, bt->n_inputs, bt->n_aux, bt->a_aux_density, bt->b_input_density, bt->b_aux_density));
-    // proofs per launch set: large chunks amortise the latency-bound tails (reduction trees, sorts);
-    // the workspaces of a 1024-proof chunk of the Transfer circuit take ~35 GB of the 288 GB
-    size_t chunk = 1024;
-    const char* env = getenv("ZKAMD_BATCH_CHUNK");
-    if (env && atoi(env) > 0) chunk = (size_t)atoi(env);
+    const size_t chunk = ProveTunables::read().batch_chunk;
     for (size_t first = 0; first < n; first += chunk) {
         size_t np = std::min(chunk, n - first);
         ZK_TRY(prove_chunk(P, np, bt, first, rs, proofs_out, derived));
@@ -1055,12 +1093,10 @@ zk_status prove_batch_host(zk_params* P, size_t n, const zk_assignment* asgs, co
     // staging buffers.  A batch that fits one device chunk is cut in two halves so that only the first
     // half's copy is exposed (measured on 1024 Transfer proofs: whole 2101, halves 2240, quarters 2119
     // proofs/s - smaller launch sets lose more in the kernels than the hidden copy gains).
-    size_t chunk = 1024;
-    if (const char* env = getenv("ZKAMD_BATCH_CHUNK"))
-        if (atoi(env) > 0) chunk = (size_t)atoi(env);
+    const ProveTunables tun = ProveTunables::read();
+    const size_t chunk = tun.batch_chunk;
     size_t hc = n > chunk ? chunk : (n >= 512 ? (n + 1) / 2 : n);
-    if (const char* env = getenv("ZKAMD_HOST_CHUNK"))
-        if (atoi(env) > 0) hc = std::min(chunk, (size_t)atoi(env));
+    if (tun.host_chunk) hc = std::min(chunk, tun.host_chunk);
     hc = std::min(hc, n);
     const size_t slots = n > hc ? 2 : 1;
     ZK_TRY(P->stage_a.ensure(slots * hc * rb));
@@ -1382,13 +1418,6 @@ zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint
     return prove_batch_dev(P, np, &bt, rs, proofs_out, derived);
 }
 
-size_t batch_chunk() {
-    size_t chunk = 1024;
-    const char* env = getenv("ZKAMD_BATCH_CHUNK");
-    if (env && atoi(env) > 0) chunk = (size_t)atoi(env);
-    return chunk;
-}
-
 zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t* witness, uint32_t flags, const uint8_t* rs,
                               uint8_t* proofs_out, bool derived) {
     if (!P || !R || !witness || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
@@ -1397,7 +1426,7 @@ zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t*
     ZK_TRY(use_device(P->device));
     const uint32_t nv = R->n_in + R->n_aux, n_rows = R->n_con + R->n_in;
     if (n_rows > P->m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
-    const size_t chunk = batch_chunk();
+    const size_t chunk = ProveTunables::read().batch_chunk;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
         ZK_TRY(R->z[0].ensure(np * (size_t)nv * 32));
@@ -1912,7 +1941,7 @@ namespace zkrt {
 zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out) {
     return prove_from_z(P, R, np, slot, rs, proofs_out, true);
 }
-size_t lib_batch_chunk() { return batch_chunk(); }
+size_t lib_batch_chunk() { return ProveTunables::read().batch_chunk; }
 bool lib_witness_on_host(size_t n) { return witness_on_host(n); }
 int lib_params_device(const zk_params* P) { return P->device; }
 size_t lib_params_domain(const zk_params* P) { return P->m; }
@@ -2113,6 +2142,22 @@ zk_status zk_hook_derived_layout(zk_params* p, zk_r1cs* circuit, uint32_t info[7
     info[6] = p->g1d.c;
     return ZK_OK;
 } ZK_ABI_CATCH
+// Test hook: the plan of a chunk of np proofs (prove_plan.h) under the environment of the call, no GPU involved: out[0 .. 32) =
+// the fields of ProvePlan up to the map, the enumerators as numbers; the batch chunk, the host chunk and the trace switch of
+// ProveTunables; the fields of CJobLayout in their order
+zk_status zk_hook_prove_plan(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t n_rows, size_t m, uint32_t ga, uint32_t gb2, uint32_t gb1,
+                             int derived, uint64_t* out, size_t out_words) try {
+    if (!out || out_words < 32) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    const ProveTunables tun = ProveTunables::read();
+    const ProvePlan p = prove_plan(np, n_in, n_aux, n_rows, m, ga, gb2, gb1, derived != 0, tun);
+    const CJobLayout& L = p.layout;
+    const uint64_t f[32] = {p.fold_in_msm, p.host_norm, p.g2_lone, p.split, p.one_stream, (uint64_t)p.g1, (uint64_t)p.map,
+                            tun.batch_chunk, tun.host_chunk, tun.trace_host,
+                            L.n_in, L.n_aux, L.head, L.ga, L.gb2, L.gb1, L.fold, L.derived, L.w_one, L.w_sum_a, L.w_sum_b2, L.wstride,
+                            L.aux, L.rz, L.r, L.sz, L.s, L.rs, L.in_tail, L.sum_b1, L.sum_a, L.cstride};
+    std::copy(f, f + 32, out);
+    return ZK_OK;
+} ZK_ABI_CATCH
 #endif
 
 zk_status zk_transfer_witness(const zk_transfer_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
@@ -2129,7 +2174,7 @@ zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, cons
     if (circuit->device != p->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
     if (n == 0) return ZK_OK;
     const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
-    const size_t chunk = batch_chunk();
+    const size_t chunk = ProveTunables::read().batch_chunk;
     zk_status rc = use_device(p->device);
     if (rc != ZK_OK) return rc;
     if ((size_t)circuit->n_con + circuit->n_in > p->m)
@@ -2190,7 +2235,7 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
     if (n == 0) return ZK_OK;
     ZK_TRY(use_device(p->device));
     const size_t nv = ZK_ANONYMOUS_N_INPUTS + ZK_ANONYMOUS_N_AUX;
-    size_t chunk = batch_chunk();
+    size_t chunk = ProveTunables::read().batch_chunk;
     if (chunk > 512) chunk = 512;   // domain 2^16: half the proofs of a transfer chunk fill the same workspaces
     if (!witness_on_host(n)) {
         // witness generation on the GPU (witness_anon_gpu.h), statement in: 1.7 KB instead of 1.6 MB of witness vector; the
@@ -2277,7 +2322,7 @@ zk_status zk_transfer_witness_gpu(zk_r1cs* circuit, const zk_transfer_statement*
     if (circuit->n_in != ZK_TRANSFER_N_INPUTS || circuit->n_aux != ZK_TRANSFER_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
     ZK_TRY(use_device(circuit->device));
-    const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, chunk = batch_chunk();
+    const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, chunk = ProveTunables::read().batch_chunk;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
         ZK_TRY(witness_gpu_enqueue(circuit, st + first, np, 0, g_stream));
@@ -2322,7 +2367,7 @@ struct zk_pipeline {
     std::thread t_lane[MAX_LANES];
     int n_lanes = 1;      // lanes started at create
     int live_lanes = 1;   // ... minus the ones that retired when their workspaces did not fit (mu held)
-    size_t chunk = 1024, nv = 0;
+    size_t chunk = 0, nv = 0;   // (proofs per launch set: ProveTunables, at zk_pipeline_create)
     PinBuf buf[2];
     std::mutex mu;
     std::condition_variable cv;
@@ -2505,8 +2550,7 @@ zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) 
     L->P = p;
     L->R = circuit;
     L->nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
-    if (const char* env = getenv("ZKAMD_BATCH_CHUNK"))
-        if (atoi(env) > 0) L->chunk = (size_t)atoi(env);
+    L->chunk = ProveTunables::read().batch_chunk;
     if ((size_t)circuit->n_con + circuit->n_in > p->m) {
         delete L;
         return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
