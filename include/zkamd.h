@@ -38,6 +38,7 @@
  *   zk_params_load, zk_params_free  Parameters::read(reader, checked)             core/proofs/src/confidential.rs:99
  *   zk_params_get_info, zk_params_get_windows   - (fields of Parameters: lengths of the queries; the recoding widths chosen here)
  *   zk_params_get_merged            - (equal points inside the a, b_g1 and b_g2 queries: terms the multiexps do not add twice)
+ *   zk_params_get_pairs             - (sums of two bases whose variables tend to hold one value: two terms of a proof as one)
  *   zk_params_write_vk              Parameters.vk, the input of prepare_verifying_key   core/proofs/src/setup.rs:31, 62
  *   zk_prove / zk_prove_batch       create_random_proof -> create_proof           confidential.rs:149, anonymous.rs:165
  *   zk_prove_batch_dev              the same, assignments already in HBM          confidential.rs:149
@@ -171,6 +172,12 @@ zk_status zk_params_get_windows(const zk_params* p, uint32_t out[4]);
 /* Entries minus distinct points of the a, b_g1 and b_g2 queries (out[0..2]): variables with identical QAP columns have
  * equal points, which a proof's multiexps take as one term under the sum of their scalars. */
 zk_status zk_params_get_merged(const zk_params* p, uint32_t out[3]);
+/* Value pairs of the key and the circuit it was last bound to by a statement-to-proof entry (all zero before that, and for a
+ * circuit the library has no probe statements for): out[0..3] = the bases P_j + P_p kept for the a, b_g1, b_g2 and l
+ * queries, one per linked pair of variables that has both terms in the query; out[4..7] = the terms a proof is expected to
+ * merge in each of them (the mean over the library's probe statements).  Two linked variables that hold the same value in
+ * a proof are one term of its multiexps over the sum of their bases; ZKAMD_MERGE_VALUES=0 keeps a term per variable. */
+zk_status zk_params_get_pairs(const zk_params* p, uint32_t out[8]);
 void zk_params_free(zk_params* p);
 
 /* ------------------------------------------------------------------------------------------

@@ -224,6 +224,15 @@ class Parameters:
         return tuple(int(x) for x in n)
 
     @property
+    def value_pairs(self):
+        """zk_params_get_pairs: {"bases": ..., "expected_merges": ...} per query (a, b_g1, b_g2, l) for the circuit the key
+        was last bound to by a statement-to-proof entry; zeros before that."""
+        n = (C.c_uint32 * 8)()
+        self._lib.check(self._lib.zk_params_get_pairs(self._h, n))
+        names = ("a", "b_g1", "b_g2", "l")
+        return {"bases": dict(zip(names, (int(x) for x in n[:4]))), "expected_merges": dict(zip(names, (int(x) for x in n[4:])))}
+
+    @property
     def vk(self):
         """The VerifyingKey section of the parameter file (uncompressed points)."""
         n_ic = self.info["n_ic"]

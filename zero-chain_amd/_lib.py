@@ -126,6 +126,7 @@ _PROTOS = {
     "zk_params_get_info": (C.c_int32, [C.c_void_p, C.POINTER(ParamsInfo)]),
     "zk_params_get_windows": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "zk_params_get_merged": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "zk_params_get_pairs": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "zk_bind_host_to_device": (C.c_int32, [C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "zk_params_free": (None, [C.c_void_p]),
     "zk_prove": (C.c_int32, [C.c_void_p, C.POINTER(Assignment), C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -224,6 +224,16 @@ struct MsmGroup {
         return ZK_OK;
     }
     zk_status run(std::vector<MsmJob>& jobs, std::vector<HPoint>& out);
+    // The (digit, point) pairs of the last launch set, nj jobs, counted from its buckets; after collect() and before the next
+    // enqueue on this group.  For measurements (ZKAMD_TRACE_HOST): it reads nj * nb words back.
+    zk_status count_pairs(size_t nj, uint64_t* total) {
+        std::vector<uint32_t> h(nj * (size_t)nb);
+        *total = 0;
+        if (h.empty() || !cnt.p) return ZK_OK;
+        HIP_TRY(hipMemcpy(h.data(), cnt.p, h.size() * 4, hipMemcpyDeviceToHost));
+        for (uint32_t x : h) *total += x;
+        return ZK_OK;
+    }
 
 private:
     // the table of doublings over slice 0, enqueued on st

@@ -364,11 +364,62 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 //   cvec[p]    += [ r * sums of the B1 groups (gb1) ] and, with fold, [ s * sums of the A groups (ga) ], at its very end
 // (a member >= r counts as zero, as it does in its own slot; a sum that comes out zero has no digits and costs nothing)
 // tail[p] = (1, r, s).  Witness scalars are converted out of Montgomery form when `mont` is set.
+//
+// Value pairs (`pairs` given and the layout has their sections): pairs = [pred A | succ A | pred B | succ B | pred L | succ L |
+// qa | qb2 | ql | qb1], nv entries each.  pred / succ link the variables of a query into static chains (value_pairs.h: at
+// most one of each per variable, -1 for none, chains no longer than PAIR_WALK_MAX variables; the B chains serve b_g1 and
+// b_g2); q*[j] = the slot of the base P_j + P_pred[j] in that query's pair section, -1 where the query has no such base.  A
+// RUN is a stretch of a chain whose members hold the same non-zero value in this proof; the thread of variable j walks back
+// to the start of its run and so knows its position t in it.  Members 2k and 2k + 1 of a run are one term z (P_2k + P_2k+1)
+// of the query where it has the base:
+//   t odd                             the slot of j gets 0 and the pair's slot z_j, where the query has the pair of (pred, j)
+//   t even, the successor is equal    the slot of j gets 0 where the query has the pair of (j, succ): the successor emits it
+//   otherwise                         the slot of j gets z_j, as without pairs
+// and a pair's slot is written by the thread of its second variable in every case (0 when it is not emitted).  z_p P_p +
+// z_j P_j = z_j (P_p + P_j) whenever z_p = z_j: an identity in the group, for every assignment.
+// A member of a group of equal bases takes part with its own point (the group's): the group's sum leaves out the members whose
+// term went into a pair.
+constexpr uint32_t PAIR_WALK_MAX = 32;
+// Which queries keep the term of variable i of the witness zp, whose value is raw (canonical) - bits: A, B2, L, B1 - and in
+// *emit the queries in which it is the second variable of a merged pair (its pair's slot gets the value where there is one).
+// Only the chains that serve a query of `mask` are walked: the bits of the others stay set in the answer.
+ZK_DI uint32_t pair_decide(const int32_t* __restrict__ pairs, uint32_t nv, const uint32_t* __restrict__ zp, uint32_t i, const Fr& raw,
+                           uint32_t* emit, uint32_t mask = 15u) {
+    uint32_t own = 15u;
+    *emit = 0u;
+    if (raw == Fr::zero()) return own;
+    const int32_t* q = pairs + 6 * (size_t)nv;
+#pragma unroll 1
+    for (uint32_t c = 0; c < 3; c++) {   // the chains of A, B, L; the queries each serves as bits
+        if (!(mask & (c == 0 ? 1u : c == 1 ? 10u : 4u))) continue;
+        const int32_t* pred = pairs + 2 * c * (size_t)nv;
+        const int32_t* succ = pred + nv;
+        uint32_t t = 0;
+        for (int32_t k = pred[i]; k >= 0 && t < PAIR_WALK_MAX && ld_fr(zp + (size_t)k * 8) == raw; k = pred[k]) t++;
+        // the link whose pair takes the variable's term, where the query has that pair
+        int32_t e = -1;
+        if (t & 1u) {
+            e = (int32_t)i;
+            *emit |= c == 0 ? 1u : c == 1 ? 10u : 4u;
+        } else {
+            const int32_t sc = succ[i];
+            if (sc >= 0 && ld_fr(zp + (size_t)sc * 8) == raw) e = sc;
+        }
+        if (e >= 0) {
+            if (c == 0 && q[e] >= 0) own &= ~1u;
+            if (c == 1 && q[nv + e] >= 0) own &= ~2u;
+            if (c == 2 && q[2 * (size_t)nv + e] >= 0) own &= ~4u;
+            if (c == 1 && q[3 * (size_t)nv + e] >= 0) own &= ~8u;
+        }
+    }
+    return own;
+}
 static __global__ void __launch_bounds__(256)
 k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ wit, const uint32_t* __restrict__ tail,
-                const zkrt::CJobLayout L, uint32_t mont, uint32_t* bad, const uint32_t* __restrict__ groups) {
+                const zkrt::CJobLayout L, uint32_t mont, uint32_t* bad, const uint32_t* __restrict__ groups,
+                const int32_t* __restrict__ pairs = nullptr) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= L.wstride + L.gb1) return;
+    if (i >= L.w_end + L.gb1) return;
     const size_t p = blockIdx.y;
     uint32_t* cv = cvec + p * (size_t)L.cstride * 8;
     const uint32_t nv = L.w_one, fold = L.fold;
@@ -379,17 +430,22 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
         const uint32_t g = i - L.w_sum_a;
         const uint32_t* mem = groups + (L.ga + L.gb2 + L.gb1 + 1);
         Fr sum = Fr::zero();   // in the form the witness came in: the sum of Montgomery forms is the form of the sum
+        const bool with_pairs = pairs && L.w_b2v;
+        const uint32_t bit = g < L.ga ? 1u : g < L.ga + L.gb2 ? 2u : 8u;   // the query of the group
         for (uint32_t k = groups[g]; k < groups[g + 1]; k++) {
             const Fr raw = ld_fr(wit + (p * nv + mem[k]) * 8);
-            if (!fr_geq_r(raw)) sum = add(sum, raw);   // (the member's own thread raises the flag)
+            if (fr_geq_r(raw)) continue;   // (the member's own thread raises the flag)
+            uint32_t emit;
+            if (with_pairs && !(pair_decide(pairs, nv, wit + p * (size_t)nv * 8, mem[k], raw, &emit, bit) & bit)) continue;   // (in a pair)
+            sum = add(sum, raw);
         }
-        if (i < L.wstride) {
+        if (i < L.w_end) {
             v = mont ? from_mont(sum) : sum;
             if (fold && g < L.ga) st_fr(cv + (size_t)(L.sum_a + g) * 8, mul(v, sR));   // (sum)(s R) / R
             st_fr(wit_out + (p * L.wstride + i) * 8, v);
         } else {
             const Fr rz = mont ? mul(sum, r) : mul(mul(sum, r), Fr::r2());
-            st_fr(cv + (size_t)(L.sum_b1 + (i - L.wstride)) * 8, rz);
+            st_fr(cv + (size_t)(L.sum_b1 + (i - L.w_end)) * 8, rz);
         }
         return;
     }
@@ -409,10 +465,27 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
             v = raw;
             rz = mul(mul(raw, r), Fr::r2());      // (z r / R)(R^2) / R = z r
         }
-        if (i >= L.n_in) st_fr(cv + (size_t)(L.aux + (i - L.n_in)) * 8, v);
-        st_fr(cv + (size_t)(L.rz + i) * 8, rz);
-        if (fold) st_fr(cv + (size_t)(L.sz + i) * 8, mul(v, sR));   // (z)(s R) / R = z s
+        const Fr sz = fold ? mul(v, sR) : Fr::zero();   // (z)(s R) / R = z s
+        // value pairs: which queries keep the variable's own term (bits: A, B2, L, B1), and where it emits its pair
+        uint32_t own = 15u, emit = 0u;
+        int32_t qa = -1, qb2 = -1, ql = -1, qb1 = -1;
+        if (pairs && L.w_b2v) {
+            const int32_t* q = pairs + 6 * (size_t)nv;
+            qa = q[i]; qb2 = q[nv + i]; ql = q[2 * (size_t)nv + i]; qb1 = q[3 * (size_t)nv + i];
+            own = pair_decide(pairs, nv, wit + p * (size_t)nv * 8, i, raw, &emit);
+            const Fr zero = Fr::zero();
+            st_fr(wit_out + (p * L.wstride + L.w_b2v + i) * 8, own & 2u ? v : zero);
+            if (qa >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_a + qa) * 8, emit & 1u ? v : zero);
+            if (qb2 >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_b2 + qb2) * 8, emit & 2u ? v : zero);
+            if (ql >= 0) st_fr(cv + (size_t)(L.pair_l + ql) * 8, emit & 4u ? v : zero);
+            if (qb1 >= 0) st_fr(cv + (size_t)(L.pair_b1 + qb1) * 8, emit & 8u ? rz : zero);
+            if (fold && qa >= 0) st_fr(cv + (size_t)(L.pair_a + qa) * 8, emit & 1u ? sz : zero);
+        }
+        if (i >= L.n_in) st_fr(cv + (size_t)(L.aux + (i - L.n_in)) * 8, own & 4u ? v : Fr::zero());
+        st_fr(cv + (size_t)(L.rz + i) * 8, own & 8u ? rz : Fr::zero());
+        if (fold) st_fr(cv + (size_t)(L.sz + i) * 8, own & 1u ? sz : Fr::zero());
         if (L.in_tail && i < L.n_in) st_fr(cv + (size_t)(L.in_tail + i) * 8, v);
+        if (!(own & 1u)) v = Fr::zero();   // (the slot of the A job, below)
     } else {
         v = ld_fr(tail + (p * 3 + (i - nv)) * 8);
         if (i == nv) st_fr(cv + (size_t)L.r * 8, r);   // r * 1 for beta_1

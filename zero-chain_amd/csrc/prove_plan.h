@@ -59,6 +59,12 @@ struct ProveTunables {
 // head: bellman's m coefficients, or [s | e] of the live rows (2 n_rows) over the derived bases, whose input variables carry
 // the c part of H (zkamd.cpp ensure_derived).  fold: the job is C = s * A + C' itself, over the bases of the A query, alpha_1
 // and delta_1 behind the r.  A section the form does not have is at offset 0 (k_build_scalars tests in_tail for that).
+// Value pairs (zkamd.cpp derived_pairs, value_pairs.h; all lengths 0 without them): two linked variables that hold the same
+// value in a proof are one term over the sum of their two bases, whose slots lie behind everything above -
+//   witness vector:  ... | the variables again, for the B2 job (nv) | pairs of the A query (pa) | of the B2 query (pb2) ]
+//   C job:           ... | pairs of the L section (pl) | r * pairs of the B1 query (pb1) | (fold: s * pairs of the A query (pa)) ]
+// (the A and B2 jobs read one vector and a pair may exist in one query only: with pairs the B2 job has its own copy of the
+// variables' slots, so that each query zeroes what it merged and nothing else.)
 struct CJobLayout {
     uint32_t n_in, n_aux, head, ga, gb2, gb1, fold, derived;   // what it was computed from
     uint32_t w_one, w_sum_a, w_sum_b2, wstride;                // witness vector: 1 (r, s behind it), the two blocks of sums
@@ -67,17 +73,34 @@ struct CJobLayout {
     uint32_t in_tail;                                          // ... over the derived bases
     uint32_t sum_b1, sum_a;                                    // (the sums of the groups at the end: r * B1's, then s * A's with fold)
     uint32_t cstride;
+    uint32_t pa, pb2, pl, pb1;                                 // value pairs per query (0: none)
+    uint32_t w_end;                                            // witness vector: the end of the sums (its stride without pairs)
+    uint32_t w_b2v, w_pair_a, w_pair_b2;                       // ... with pairs
+    uint32_t pair_l, pair_b1, pair_a;                          // C job, with pairs (pair_a: with fold)
+};
+
+// The counts of value pairs per query, in the order the layout takes them
+struct PairCounts {
+    uint32_t a = 0, b2 = 0, l = 0, b1 = 0;
+    bool any() const { return (a | b2 | l | b1) != 0; }
 };
 
 inline CJobLayout cjob_layout(uint32_t n_in, uint32_t n_aux, uint32_t head, uint32_t ga, uint32_t gb2, uint32_t gb1, bool fold,
-                              bool derived) {
+                              bool derived, const PairCounts& pc = PairCounts()) {
     const uint32_t nv = n_in + n_aux;
     CJobLayout L = {};
     L.n_in = n_in; L.n_aux = n_aux; L.head = head; L.ga = ga; L.gb2 = gb2; L.gb1 = gb1; L.fold = fold; L.derived = derived;
     L.w_one = nv;
     L.w_sum_a = nv + 3;
     L.w_sum_b2 = L.w_sum_a + ga;
-    L.wstride = L.w_sum_b2 + gb2;
+    L.w_end = L.wstride = L.w_sum_b2 + gb2;
+    L.pa = pc.a; L.pb2 = pc.b2; L.pl = pc.l; L.pb1 = pc.b1;
+    if (pc.any()) {
+        L.w_b2v = L.wstride;
+        L.w_pair_a = L.w_b2v + nv;
+        L.w_pair_b2 = L.w_pair_a + pc.a;
+        L.wstride = L.w_pair_b2 + pc.b2;
+    }
     uint32_t at = head;
     auto section = [&at](uint32_t len) { const uint32_t off = at; at += len; return off; };
     L.aux = section(n_aux);
@@ -91,6 +114,11 @@ inline CJobLayout cjob_layout(uint32_t n_in, uint32_t n_aux, uint32_t head, uint
     if (derived) L.in_tail = section(n_in);
     L.sum_b1 = section(gb1);
     if (fold) L.sum_a = section(ga);
+    if (pc.any()) {
+        L.pair_l = section(pc.l);
+        L.pair_b1 = section(pc.b1);
+        if (fold) L.pair_a = section(pc.a);
+    }
     L.cstride = at;
     return L;
 }
@@ -110,9 +138,10 @@ struct ProvePlan {
 };
 
 // np proofs of a circuit of n_in + n_aux variables and n_rows live rows under a key of domain m; ga, gb2, gb1: the groups of
-// equal bases the maps in use were built with; derived: the four-transform form over the derived bases
+// equal bases the maps in use were built with; derived: the four-transform form over the derived bases; pc: the value pairs
+// that set carries (over the derived set only: the key's own tables are built before any circuit is known)
 inline ProvePlan prove_plan(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t n_rows, size_t m, uint32_t ga, uint32_t gb2,
-                            uint32_t gb1, bool derived, const ProveTunables& tun) {
+                            uint32_t gb1, bool derived, const ProveTunables& tun, const PairCounts& pc = PairCounts()) {
     ProvePlan p;
     // A few proofs made alone carry the final fold C = s * A + C' INSIDE the C multiexp: s * A = s alpha_1 + sum (s z_i) A_i +
     // (r s) delta_1 is 15.6 k more terms over bases whose doublings are in the table (+19 % pairs in a launch whose duration is
@@ -136,7 +165,8 @@ inline ProvePlan prove_plan(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t n
     p.g1 = derived ? (p.split ? PG1::G1D : PG1::G1D_LONE) : (p.split ? PG1::G1 : PG1::G1_LONE);
     p.map = derived ? (p.fold_in_msm ? PMap::MAP_CFD : PMap::MAP_CD) : (p.fold_in_msm ? PMap::MAP_CF : PMap::MAP_C);
     // the H block at the head of the C' job: bellman's m coefficients, or [s | e] of the live rows over the derived bases
-    p.layout = cjob_layout(n_in, n_aux, derived ? 2 * n_rows : (uint32_t)m, ga, gb2, gb1, p.fold_in_msm, derived);
+    p.layout = cjob_layout(n_in, n_aux, derived ? 2 * n_rows : (uint32_t)m, ga, gb2, gb1, p.fold_in_msm, derived,
+                           derived ? pc : PairCounts());
     return p;
 }
 

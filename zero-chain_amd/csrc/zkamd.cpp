@@ -32,6 +32,7 @@
 #include "msm_group.h"
 #include "prove_plan.h"
 #include "transfer_witness.h"
+#include "value_pairs.h"
 #include "handles.h"
 #include "transfer_r1cs.h"
 
@@ -316,8 +317,8 @@ struct zk_params {
     NttPlan ntt;
     // The derived bases of this key and ONE circuit (ensure_derived): the H query on the Lagrange basis of the domain for the
     // circuit's live rows, with the part of H that is linear in the row products folded into the bases of the variables and
-    // of the rows' residuals.  g1d = [Lambda (n_rows) | E (n_rows) | D (inputs, aux) | a | alpha_1 | delta_1 | b_g1 | beta_1]
-    // with its own table of doublings; g1d_lone = the same table under the width of a few proofs made alone.
+    // of the rows' residuals.  g1d = [Lambda (n_rows) | E (n_rows) | D (inputs, aux) | (the value pairs' bases: prs below) | a | alpha_1 |
+    // delta_1 | b_g1 | beta_1] with its own table of doublings; g1d_lone = the same table under the width of a few proofs made alone.
     struct Derived {
         bool ready = false;
         uint64_t circuit = 0;       // zk_r1cs::id it was built for
@@ -329,6 +330,23 @@ struct zk_params {
     } drv;
     MsmG1 g1d, g1d_lone;
     DevBuf map_cd, map_cfd;         // map_c / map_cf over the derived bases
+    // Value pairs of the (key, circuit) pair the derived set was built for (value_pairs.h; derived_pairs below): one more
+    // base P_j + P_pred[j] per link of the circuit's chains and query that has both ends, behind the derived set in g1d (L, B1
+    // and A queries) and behind the B2 query in a table of its own, g2p.  links = [chains of A, B, L | qa | qb2 | ql | qb1] as
+    // k_build_scalars reads it; base_* = where the pair bases lie (absolute in g1d; in g2p); exp_* = the terms a proof is
+    // expected to merge per query (the mean over the probe statements), for the recoding widths.
+    struct Pairs {
+        bool ready = false;
+        std::vector<int32_t> links;
+        uint32_t base_l = 0, base_b1 = 0, base_a = 0, base_b2 = 0;
+        PairCounts n;
+        uint32_t exp_a = 0, exp_b2 = 0, exp_l = 0, exp_b1 = 0;
+    } prs;
+    MsmG1 g1da;                     // the A jobs of a split chunk over g1d's table (its copy of the A query + the pairs)
+    MsmG2 g2p, g2p_lone;            // [b_g2 | beta_2 | delta_2 | pairs]
+    DevBuf map_ad, map_b2d, pairs_dev;
+    PairCounts mpairs;              // the pairs the maps in use were built with (ensure_maps; none under ZKAMD_MERGE_VALUES=0)
+    std::vector<uint8_t> enc_a, enc_b1, enc_b2;   // the encodings of the three queries (the sums of two bases are made from them)
     // cached per-circuit index maps (keyed by the density bytes)
     std::vector<uint8_t> dens_key;
     DevBuf map_a, map_b2, map_c, map_cf;   // (map_cf: the C job with the fold s * A inside, for a few proofs made alone)
@@ -445,6 +463,13 @@ zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk
     group_equal_points(at_a, P->n_a, 96, P->grp_a);
     group_equal_points(at_b1, P->n_b1, 96, P->grp_b1);
     group_equal_points(at_b2, P->n_b2, 192, P->grp_b2);
+    // (kept for the keys that can have value pairs alone - those of the two built-in circuits, by their counts: 6 MB for the
+    //  transfer key; the points the pairs need are decoded from them a second time, on the host, when the key is bound)
+    if ((P->n_ic == ZK_TRANSFER_N_INPUTS && P->n_l == ZK_TRANSFER_N_AUX) || (P->n_ic == ZK_ANONYMOUS_N_INPUTS && P->n_l == ZK_ANONYMOUS_N_AUX)) {
+        P->enc_a.assign(at_a, at_a + (size_t)P->n_a * 96);
+        P->enc_b1.assign(at_b1, at_b1 + (size_t)P->n_b1 * 96);
+        P->enc_b2.assign(at_b2, at_b2 + (size_t)P->n_b2 * 192);
+    }
     const Section sec1[7] = {{at_h, P->n_h, "h", false},       {at_l, P->n_l, "l", false},          {at_a, P->n_a, "a", false},
                              {pk, 1, "vk.alpha_g1", true},     {pk + 576, 1, "vk.delta_g1", true},  {at_b1, P->n_b1, "b_g1", false},
                              {pk + 96, 1, "vk.beta_g1", true}};
@@ -592,6 +617,13 @@ zk_params* params_clone_for_lane(const zk_params* P) {
         Q->drv = P->drv;
         Q->g1d.alias(P->g1d, P->g1d.c);
         Q->g1d_lone.alias(P->g1d, P->g1d_lone.c);
+        if (P->prs.ready) {
+            Q->prs = P->prs;
+            Q->g1da.alias(P->g1d, P->g1da.c);
+            Q->g2p.c = P->g2p.c; Q->g2p.maxd = P->g2p.maxd; Q->g2p.nb = P->g2p.nb; Q->g2p.n_points = P->g2p.n_points;
+            Q->g2p.table.borrow(P->g2p.table);
+            Q->g2p_lone.alias(P->g2p, P->g2p_lone.c);
+        }
     }
     Q->ntt.log_n = P->ntt.log_n;
     Q->ntt.n = P->ntt.n;
@@ -629,6 +661,12 @@ zk_r1cs* r1cs_clone_for_lane(const zk_r1cs* R) {
     return Q;
 }
 
+// ZKAMD_MERGE_VALUES=0: the maps are built without value pairs (a term per variable), for measurements and parity
+bool merge_values_on() {
+    const char* e = getenv("ZKAMD_MERGE_VALUES");
+    return !(e && atoi(e) == 0);
+}
+
 // Build (or reuse) the per-circuit index maps from the density trackers.
 // Equal points of a query (zk_params::Groups) become ONE term of its job: every member's slot maps to -1 and a slot appended
 // for the group, whose scalar k_build_scalars makes the sum of the members', maps to the group's first point.
@@ -646,8 +684,12 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     key.insert(key.end(), b_aux_d, b_aux_d + n_aux);
     for (int i = 0; i < 4; i++) key.push_back((uint8_t)((P->drv.ready ? P->drv.serial : 0u) >> (8 * i)));
     key.push_back(merge ? 1 : 0);
-    if (key == P->dens_key) return ZK_OK;
     const uint32_t nv = n_in + n_aux;
+    // value pairs: over the derived set that carries them (its serial is in the key), unless ZKAMD_MERGE_VALUES=0
+    const bool pairs = merge_values_on() && P->drv.ready && P->prs.ready && P->prs.links.size() == 10 * (size_t)nv;
+    key.push_back(pairs ? 1 : 0);
+    if (key == P->dens_key) return ZK_OK;
+    const PairCounts pc = pairs ? P->prs.n : PairCounts();
     // scalar layout per proof: [inputs | aux | 1 | r | s | sums of the A groups | sums of the B2 groups] (prove_plan.h CJobLayout)
     std::vector<int32_t> ma(nv + 3, -1), mb1(nv + 3, -1), mb2(nv + 3, -1);
     std::vector<uint32_t> var_a, var_b;   // query position -> variable
@@ -760,6 +802,16 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
             section(L.sum_a);
             query(base_a, 0, ga, off_a);
         }
+        if (L.w_b2v) {   // the pair bases lie in the table as the layout orders them (ensure_derived)
+            section(L.pair_l);
+            for (uint32_t k = 0; k < L.pl; k++) map.push_back((int32_t)(P->prs.base_l + k));
+            section(L.pair_b1);
+            for (uint32_t k = 0; k < L.pb1; k++) map.push_back((int32_t)(P->prs.base_b1 + k));
+            if (L.fold) {
+                section(L.pair_a);
+                for (uint32_t k = 0; k < L.pa; k++) map.push_back((int32_t)(P->prs.base_a + k));
+            }
+        }
         section(L.cstride);
         if (!fits) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the C map does not follow its layout");
         return upload(dst, map);
@@ -776,8 +828,24 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
         const zk_params::Derived& D = P->drv;
         const uint32_t head = 2 * D.n_rows;
         for (bool fold : {false, true})
-            ZK_TRY(upload_c_map(fold ? P->map_cfd : P->map_cd, cjob_layout(n_in, n_aux, head, ga, gb2, gb1, fold, true), D.pos.data(),
+            ZK_TRY(upload_c_map(fold ? P->map_cfd : P->map_cd, cjob_layout(n_in, n_aux, head, ga, gb2, gb1, fold, true, pc), D.pos.data(),
                                 D.pos.data() + head + n_in, D.pos.data() + head, D.off_a, D.off_b1));
+    }
+    if (pairs) {
+        // The A and B2 jobs of a chunk with pairs: the A map in absolute positions of the derived table (its copy of the A query,
+        // the pair bases in front of it), the B2 map over its own copy of the variables' slots and the table with its pairs
+        const CJobLayout Wp = cjob_layout(n_in, n_aux, 0, ga, gb2, gb1, false, true, pc);
+        std::vector<int32_t> mad(Wp.wstride, -1), mbd(Wp.wstride, -1);
+        for (uint32_t i = 0; i < W.wstride; i++) {
+            if (ma[i] >= 0) mad[i] = (int32_t)(P->drv.off_a + ma[i]);
+            if (i >= nv) mbd[i] = mb2[i];
+        }
+        for (uint32_t i = 0; i < nv; i++) mbd[Wp.w_b2v + i] = mb2[i];
+        for (uint32_t k = 0; k < pc.a; k++) mad[Wp.w_pair_a + k] = (int32_t)(P->prs.base_a + k);
+        for (uint32_t k = 0; k < pc.b2; k++) mbd[Wp.w_pair_b2 + k] = (int32_t)(P->prs.base_b2 + k);
+        ZK_TRY(upload(P->map_ad, mad));
+        ZK_TRY(upload(P->map_b2d, mbd));
+        ZK_TRY(upload(P->pairs_dev, P->prs.links));
     }
     gptr.insert(gptr.end(), gmem.begin(), gmem.end());
     ZK_TRY(upload(P->grp_dev, gptr));
@@ -788,6 +856,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     P->mg_a = ga;
     P->mg_b2 = gb2;
     P->mg_b1 = gb1;
+    P->mpairs = pc;
     return ZK_OK;
 }
 
@@ -816,6 +885,7 @@ struct ChunkRun {
     const int32_t* map_c;
     uint32_t *wit, *cvec, *bad;
     const DP1* a_dev = nullptr;   // A of every proof, where the G1 launch sets left it
+    bool pairs = false;      // the layout has the sections of the value pairs: the A and B2 jobs over their tables and maps
 
     // ---- scalars [inputs | aux | 1 | r | s | sums of the A groups | of the B2 groups] per proof, plain, and the merged C job's
     // but for its H block (prove_plan.h CJobLayout)
@@ -846,9 +916,9 @@ struct ChunkRun {
         ZK_TRY(P->cvec.ensure(np * (size_t)L.cstride * 32));
         cvec = P->cvec.as<uint32_t>();
         // (the same launch: a thread per variable, three for the tail, one per group)
-        ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.wstride + L.gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
+        ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.w_end + L.gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
                   (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), L, mont ? 1u : 0u, bad,
-                  P->grp_dev.as<uint32_t>());
+                  P->grp_dev.as<uint32_t>(), pairs ? (const int32_t*)P->pairs_dev.as<int32_t>() : (const int32_t*)nullptr);
         return ZK_OK;
     }
 
@@ -859,7 +929,7 @@ struct ChunkRun {
         const uint32_t wstride = plan.layout.wstride;
         P->jobs2.clear();
         for (size_t p = 0; p < np; p++) {
-            MsmJob j2 = {wit + p * (size_t)wstride * 8, P->map_b2.as<int32_t>(), wstride, 0, (uint32_t)P->g2.n_points, 0, 0, 0};
+            MsmJob j2 = {wit + p * (size_t)wstride * 8, (pairs ? P->map_b2d : P->map_b2).as<int32_t>(), wstride, 0, (uint32_t)G2->n_points, 0, 0, 0};
             P->jobs2.push_back(j2);
         }
         HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
@@ -928,15 +998,20 @@ struct ChunkRun {
         }
         for (size_t p = 0; p < np; p++) {
             MsmJob ja = {wit + p * (size_t)wstride * 8, P->map_a.as<int32_t>(), wstride, P->off_a, npts1, 0, 0, 0};
-            if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
+            if (pairs) {   // (absolute positions in the derived table: the pair bases lie in front of its copy of the A query)
+                ja.map = P->map_ad.as<int32_t>();
+                ja.table_base = 0;
+                ja.n_table = (uint32_t)P->g1d.n_points;
+            } else if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
                 ja.table_base = P->drv.off_a;
                 ja.n_table = npts1c;
             }
             (split ? P->jobs1a : P->jobs1).push_back(ja);
         }
         if (split) {
-            ZK_TRY(P->g1a.enqueue(P->jobs1a, P->res1a, side, false));
-            a_dev = P->g1a.res_dev;
+            MsmG1& G1A = pairs ? P->g1da : P->g1a;
+            ZK_TRY(G1A.enqueue(P->jobs1a, P->res1a, side, false));
+            a_dev = G1A.res_dev;
             HIP_TRY(hipEventRecord(g_ev_join, side));
             ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false));
             HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when the side stream is the main one)
@@ -1022,9 +1097,10 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     const bool mont = (bt->flags & ZK_FR_MONTGOMERY) != 0;
     if (derived && (!mont || P->drv.n_rows != bt->n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
     ChunkRun c = {P, np, bt, first, derived, mont,
-                  prove_plan(np, bt->n_inputs, bt->n_aux, bt->n_rows, P->m, P->mg_a, P->mg_b2, P->mg_b1, derived, tun)};
+                  prove_plan(np, bt->n_inputs, bt->n_aux, bt->n_rows, P->m, P->mg_a, P->mg_b2, P->mg_b1, derived, tun, P->mpairs)};
+    c.pairs = c.plan.layout.w_b2v != 0;
     c.side = c.plan.one_stream ? g_stream : g_stream2;
-    c.G2 = c.plan.g2_lone ? &P->g2_lone : &P->g2;
+    c.G2 = c.pairs ? (c.plan.g2_lone ? &P->g2p_lone : &P->g2p) : (c.plan.g2_lone ? &P->g2_lone : &P->g2);
     MsmG1* const g1s[] = {&P->g1, &P->g1_lone, &P->g1d, &P->g1d_lone};   // in the order of PG1 and PMap
     DevBuf* const maps[] = {&P->map_c, &P->map_cf, &P->map_cd, &P->map_cfd};
     c.G1C = g1s[(int)c.plan.g1];
@@ -1044,6 +1120,13 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
                 std::chrono::duration<double, std::milli>(t_wait - t_begin).count(),
                 std::chrono::duration<double, std::milli>(t_enc - t_wait).count(),
                 std::chrono::duration<double, std::milli>(t_end - t_enc).count());
+        // the (digit, point) pairs of the chunk's launch sets, counted from their buckets
+        uint64_t pc1 = 0, pa1 = 0, p2 = 0;
+        ZK_TRY(c.G1C->count_pairs(c.plan.split ? np : 2 * np, &pc1));
+        if (c.plan.split) ZK_TRY((c.pairs ? P->g1da : P->g1a).count_pairs(np, &pa1));
+        ZK_TRY(c.G2->count_pairs(np, &p2));
+        fprintf(stderr, "[zkamd] chunk of %zu: pairs per proof: %s %.0f, A set %.0f, G2 set %.0f\n", np, c.plan.split ? "C' set" : "C' and A set",
+                (double)pc1 / (double)np, (double)pa1 / (double)np, (double)p2 / (double)np);
     }
     return ZK_OK;
 }
@@ -1251,6 +1334,143 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
 // own term count; a base that comes out as the identity - D_i of an input that C never mentions - is mapped out like an
 // identity in a key file.  Nothing happens when the pair cannot have one (a lane's clone, another circuit's shape): the
 // caller then keeps the six-transform form.
+// The value pairs of a (key, circuit) pair (value_pairs.h): for every link (p, j) of the circuit's chains and every query in
+// which both variables have a term - dense there, the base not the identity - one more base P_j + P_p.  A member of a group
+// of equal bases takes part with its own point, which is the group's: k_build_scalars leaves it out of the group's sum when
+// its term goes into a pair.  set = the derived set [Lambda | E | D] in host form (the L terms of the job are its D block).  The
+// sums are made on the host cores from the key's encodings; a sum that comes out as the identity has no base (both keep
+// their terms).  Fills P->prs but for where the bases lie; a circuit without built-in probes has no pairs.
+// the natively emitted constraint systems of the two built-in circuits (transfer_r1cs.h), each built once per process
+const zkr1cs::System& builtin_system(zkpairs::Circuit c) {
+    if (c == zkpairs::TRANSFER) {
+        static const zkr1cs::System sys = zkr1cs::transfer_system();
+        return sys;
+    }
+    static const zkr1cs::System sys = zkr1cs::anonymous_system();
+    return sys;
+}
+struct PairBases {
+    std::vector<HG1A> l, b1, a;
+    std::vector<HG2A> b2;
+};
+template <class A>
+A sum_of_two(const A& x, const A& y) {
+    typedef decltype(x.x) F;
+    return zkhost::to_affine(zkhost::padd(zkhost::Point<F>::from_affine(x), zkhost::Point<F>::from_affine(y)));
+}
+void derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>& set, uint32_t n_rows, PairBases& out) {
+    zk_params::Pairs& X = P->prs;
+    X = zk_params::Pairs();
+    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux;
+    zkpairs::Circuit kind;
+    if (n_in == ZK_TRANSFER_N_INPUTS && n_aux == ZK_TRANSFER_N_AUX) kind = zkpairs::TRANSFER;
+    else if (n_in == ZK_ANONYMOUS_N_INPUTS && n_aux == ZK_ANONYMOUS_N_AUX) kind = zkpairs::ANONYMOUS;
+    else return;
+    if (P->enc_a.size() != (size_t)P->n_a * 96 || P->enc_b1.size() != (size_t)P->n_b1 * 96 || P->enc_b2.size() != (size_t)P->n_b2 * 192) return;
+    std::vector<uint8_t> a_dense(nv, 1), b_dense(nv, 0);
+    for (uint32_t i = 0; i < nv; i++) {
+        if (i >= n_in) a_dense[i] = R->a_aux_density[i - n_in];
+        b_dense[i] = i < n_in ? R->b_input_density[i] : R->b_aux_density[i - n_in];
+    }
+    {
+        // The probes are witnesses of the BUILT-IN circuit: another circuit with its counts would get chains that merge nothing
+        // and pay for their bases and tables.  The caller's matrices must have the built-in system's constraint count and
+        // densities (which variables occur in A and in B) - what the chains are made from.
+        const zkr1cs::System& sys = builtin_system(kind);
+        if (sys.n_inputs != n_in || sys.n_aux != n_aux || sys.n_constraints != R->n_con) return;
+        std::vector<uint8_t> sa(nv, 0), sb(nv, 0);
+        for (uint32_t i = 0; i < n_in; i++) sa[i] = 1;
+        for (uint32_t v : sys.m[0].col) sa[v] = 1;
+        for (uint32_t v : sys.m[1].col) sb[v] = 1;
+        if (sa != a_dense || sb != b_dense) return;
+    }
+    const std::vector<std::vector<Fr>>& probes = zkpairs::circuit_probes(kind);
+    if (probes.empty() || probes[0].size() != nv || set.size() != 2 * (size_t)n_rows + nv) return;
+    // [pred A | succ A | pred B | succ B | pred L | succ L]
+    const std::vector<int32_t> chains = zkpairs::chains_of(probes, n_in, a_dense, b_dense);
+    const int32_t *pred_a = chains.data(), *pred_b = pred_a + 2 * (size_t)nv, *pred_l = pred_a + 4 * (size_t)nv;
+    // variable -> position in the A query / the B queries / the set, -1 where it has no term
+    std::vector<int32_t> pa(nv, -1), pb1(nv, -1), pb2(nv, -1), pl(nv, -1);
+    uint32_t at = 0;
+    for (uint32_t i = 0; i < nv; i++)
+        if (i < n_in || R->a_aux_density[i - n_in]) pa[i] = (int32_t)at++;
+    if (at != P->n_a) return;
+    at = 0;
+    for (uint32_t i = 0; i < nv; i++)
+        if (i < n_in ? R->b_input_density[i] : R->b_aux_density[i - n_in]) pb1[i] = pb2[i] = (int32_t)at++;
+    if (at != P->n_b1 || at != P->n_b2) return;
+    for (uint32_t i = n_in; i < nv; i++)
+        if (!set[2 * (size_t)n_rows + i].is_inf()) pl[i] = (int32_t)(2 * n_rows + i);
+    struct Cand {
+        uint32_t j;
+        int32_t p, q;   // positions of the two bases
+    };
+    std::vector<Cand> ca, cb1, cb2, cl;
+    for (uint32_t j = 0; j < nv; j++) {
+        int32_t p = pred_a[j];
+        if (p >= 0 && pa[j] >= 0 && pa[p] >= 0) ca.push_back({j, pa[p], pa[j]});
+        p = pred_b[j];
+        if (p >= 0 && pb1[j] >= 0 && pb1[p] >= 0) cb1.push_back({j, pb1[p], pb1[j]});
+        if (p >= 0 && pb2[j] >= 0 && pb2[p] >= 0) cb2.push_back({j, pb2[p], pb2[j]});
+        p = pred_l[j];
+        if (p >= 0 && pl[j] >= 0 && pl[p] >= 0) cl.push_back({j, pl[p], pl[j]});
+    }
+    std::vector<HG1A> sa(ca.size()), sb1(cb1.size()), sl(cl.size());
+    std::vector<HG2A> sb2(cb2.size());
+    auto g1_at = [](const std::vector<uint8_t>& enc, int32_t pos) {
+        HG1A pt = HG1A::inf();
+        if (zkhost::g1_from_uncompressed(enc.data() + (size_t)pos * 96, &pt) != zkhost::DEC_OK) pt = HG1A::inf();
+        return pt;
+    };
+    auto g2_at = [](const std::vector<uint8_t>& enc, int32_t pos) {
+        HG2A pt = HG2A::inf();
+        if (zkhost::g2_from_uncompressed(enc.data() + (size_t)pos * 192, &pt) != zkhost::DEC_OK) pt = HG2A::inf();
+        return pt;
+    };
+    const size_t total = ca.size() + cb1.size() + cb2.size() + cl.size();
+    const unsigned nthreads = host_threads(total / 64 + 1, 32);
+    auto part = [&](unsigned t) {
+        auto range = [&](size_t n, auto&& fn) {
+            for (size_t k = n * t / nthreads; k < n * (t + 1) / nthreads; k++) fn(k);
+        };
+        range(ca.size(), [&](size_t k) { sa[k] = sum_of_two(g1_at(P->enc_a, ca[k].p), g1_at(P->enc_a, ca[k].q)); });
+        range(cb1.size(), [&](size_t k) { sb1[k] = sum_of_two(g1_at(P->enc_b1, cb1[k].p), g1_at(P->enc_b1, cb1[k].q)); });
+        range(cb2.size(), [&](size_t k) { sb2[k] = sum_of_two(g2_at(P->enc_b2, cb2[k].p), g2_at(P->enc_b2, cb2[k].q)); });
+        range(cl.size(), [&](size_t k) { sl[k] = sum_of_two(set[cl[k].p], set[cl[k].q]); });
+    };
+    run_threads(nthreads, part);
+    // links = [the chains | qa | qb2 | ql | qb1]
+    X.links.assign(10 * (size_t)nv, -1);
+    std::copy(chains.begin(), chains.end(), X.links.begin());
+    auto keep = [&](const std::vector<Cand>& c, const auto& sums, auto& bases, int32_t* q) {
+        for (size_t k = 0; k < c.size(); k++)
+            if (!sums[k].is_inf()) {
+                q[c[k].j] = (int32_t)bases.size();
+                bases.push_back(sums[k]);
+            }
+        return (uint32_t)bases.size();
+    };
+    int32_t* q = &X.links[6 * (size_t)nv];
+    X.n.a = keep(ca, sa, out.a, q);
+    X.n.b2 = keep(cb2, sb2, out.b2, q + nv);
+    X.n.l = keep(cl, sl, out.l, q + 2 * (size_t)nv);
+    X.n.b1 = keep(cb1, sb1, out.b1, q + 3 * (size_t)nv);
+    // what a proof is expected to merge, from the probes
+    uint64_t merged[4] = {0, 0, 0, 0};
+    for (const std::vector<Fr>& z : probes) {
+        merged[0] += zkpairs::count_merges(pred_a, q, z);
+        merged[1] += zkpairs::count_merges(pred_b, q + nv, z);
+        merged[2] += zkpairs::count_merges(pred_l, q + 2 * (size_t)nv, z);
+        merged[3] += zkpairs::count_merges(pred_b, q + 3 * (size_t)nv, z);
+    }
+    const uint64_t np = probes.size();
+    X.exp_a = (uint32_t)(merged[0] / np);
+    X.exp_b2 = (uint32_t)(merged[1] / np);
+    X.exp_l = (uint32_t)(merged[2] / np);
+    X.exp_b1 = (uint32_t)(merged[3] / np);
+    X.ready = X.n.any();
+}
+
 zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     if (P->drv.ready && P->drv.circuit == R->id) return ZK_OK;
     const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, n_rows = n_con + n_in, k = P->log_m;
@@ -1366,11 +1586,37 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
         }
     }
     // (the width of the set's own terms: the residuals are zero scalars unless a constraint fails)
-    const uint32_t c_set = pick_window(live + P->n_b1, 1);
+    // value pairs: [pairs of the L terms | of the B1 query | of the A query] behind the set, the B2 query's in a table of its own.
+    // A set expects fewer terms per proof with them (the mean over the probes), and its width follows that.
+    PairBases pb;
+    derived_pairs(P, R, pts, n_rows, pb);
+    zk_params::Pairs& X = P->prs;
+    X.base_l = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.l.begin(), pb.l.end());
+    X.base_b1 = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.b1.begin(), pb.b1.end());
+    X.base_a = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.a.begin(), pb.a.end());
+    X.base_b2 = P->n_b2 + 2;
+    const bool values = merge_values_on();   // (the widths of a run with the switch off stay those of a set without pairs)
+    const uint32_t c_set = pick_window(live + P->n_b1 - (values ? std::min<size_t>(X.exp_l + X.exp_b1, live) : 0), 1);
     ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, c_set));
     P->g1d_lone.alias(P->g1d, P->g1_lone.c);
+    if (X.ready) {
+        P->g1da.alias(P->g1d, values ? pick_window(P->n_a - std::min(X.exp_a, P->n_a), 3) : P->g1a.c);
+        std::vector<HG2A> pts2(P->n_b2 + 2, HG2A::inf());
+        bool ok = P->vk_bytes.size() >= 864;
+        for (uint32_t i = 0; ok && i < P->n_b2; i++) ok = zkhost::g2_from_uncompressed(P->enc_b2.data() + (size_t)i * 192, &pts2[i]) == zkhost::DEC_OK;
+        ok = ok && zkhost::g2_from_uncompressed(P->vk_bytes.data() + 192, &pts2[P->n_b2]) == zkhost::DEC_OK &&
+             zkhost::g2_from_uncompressed(P->vk_bytes.data() + 672, &pts2[P->n_b2 + 1]) == zkhost::DEC_OK;
+        if (!ok) return fail(ZK_ERR_IO, "internal: the b_g2 query does not decode a second time");
+        pts2.insert(pts2.end(), pb.b2.begin(), pb.b2.end());
+        const uint32_t c2 = values ? pick_window(P->n_b2 - std::min(X.exp_b2, P->n_b2), 2) : P->g2.c;
+        ZK_TRY(P->g2p.build(pts2, c2, false, "pair bases (G2)"));
+        P->g2p_lone.alias(P->g2p, getenv("ZKAMD_WINDOW_BITS_G2") || c2 <= 10 ? c2 : 10u);
+    }
     P->drv.n_rows = n_rows;
-    P->drv.off_a = (uint32_t)n_set;
+    P->drv.off_a = (uint32_t)pts.size();
     P->drv.off_b1 = P->drv.off_a + P->n_a + 2;
     P->drv.circuit = R->id;
     static std::atomic<uint32_t> serial{1};
@@ -1380,6 +1626,10 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     if (getenv("ZKAMD_TRACE_HOST"))
         fprintf(stderr, "[zkamd] derived bases: 2 x %u + %u points, %u entries of C, width %u, %.1f ms, table %.2f GB\n", n_rows, nv, nnz,
                 c_set, P->drv.bind_ms, (double)P->g1d.bytes / 1e9);
+    if (getenv("ZKAMD_TRACE_HOST") && X.ready)
+        fprintf(stderr, "[zkamd] value pairs: bases a %u, b_g2 %u, l %u, b_g1 %u; merges expected per proof %u, %u, %u, %u; widths "
+                        "C' %u, A %u, G2 %u; G2 table %.2f GB\n", X.n.a, X.n.b2, X.n.l, X.n.b1, X.exp_a, X.exp_b2, X.exp_l, X.exp_b1,
+                c_set, P->g1da.c, P->g2p.c, (double)P->g2p.bytes / 1e9);
     return ZK_OK;
 }
 
@@ -2016,6 +2266,13 @@ zk_status zk_params_get_merged(const zk_params* p, uint32_t out[3]) try {
     out[2] = p->grp_b2.merged();
     return ZK_OK;
 } ZK_ABI_CATCH
+zk_status zk_params_get_pairs(const zk_params* p, uint32_t out[8]) try {
+    if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    const zk_params::Pairs& X = p->prs;
+    const uint32_t v[8] = {X.n.a, X.n.b1, X.n.b2, X.n.l, X.exp_a, X.exp_b1, X.exp_b2, X.exp_l};
+    for (int i = 0; i < 8; i++) out[i] = p->drv.ready && X.ready ? v[i] : 0u;
+    return ZK_OK;
+} ZK_ABI_CATCH
 void zk_params_free(zk_params* p) { delete p; }
 zk_status zk_params_write_vk(const zk_params* p, uint8_t* out, size_t cap, size_t* len) try {
     if (!p || !len) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
@@ -2051,10 +2308,7 @@ zk_status zk_r1cs_load(uint32_t n_inputs, uint32_t n_aux, uint32_t n_constraints
 void zk_r1cs_free(zk_r1cs* r) { delete r; }
 
 // the natively emitted constraint system of the transfer circuit (transfer_r1cs.h), built once per process
-static const zkr1cs::System& transfer_system_cached() {
-    static const zkr1cs::System sys = zkr1cs::transfer_system();
-    return sys;
-}
+static const zkr1cs::System& transfer_system_cached() { return builtin_system(zkpairs::TRANSFER); }
 zk_status zk_transfer_r1cs_fingerprint(uint8_t hash_out[32], uint32_t* n_inputs, uint32_t* n_aux, uint32_t* n_constraints) try {
     const zkr1cs::System& sys = transfer_system_cached();
     if (hash_out) sys.fingerprint(hash_out);
@@ -2089,10 +2343,7 @@ zk_status zk_transfer_r1cs_load(int device, zk_r1cs** out) try {
     return system_load(sys, device, out);
 } ZK_ABI_CATCH
 // the anonymous-transfer circuit, emitted the same way
-static const zkr1cs::System& anonymous_system_cached() {
-    static const zkr1cs::System sys = zkr1cs::anonymous_system();
-    return sys;
-}
+static const zkr1cs::System& anonymous_system_cached() { return builtin_system(zkpairs::ANONYMOUS); }
 zk_status zk_anonymous_r1cs_fingerprint(uint8_t hash_out[32], uint32_t* n_inputs, uint32_t* n_aux, uint32_t* n_constraints) try {
     const zkr1cs::System& sys = anonymous_system_cached();
     if (hash_out) sys.fingerprint(hash_out);
@@ -2156,6 +2407,112 @@ zk_status zk_hook_prove_plan(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t 
                             L.n_in, L.n_aux, L.head, L.ga, L.gb2, L.gb1, L.fold, L.derived, L.w_one, L.w_sum_a, L.w_sum_b2, L.wstride,
                             L.aux, L.rz, L.r, L.sz, L.s, L.rs, L.in_tail, L.sum_b1, L.sum_a, L.cstride};
     std::copy(f, f + 32, out);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: zk_hook_prove_plan for a set with value pairs, counts = pairs of the [a, b_g2, l, b_g1] queries: the same 32 words,
+// then the pair fields of CJobLayout in their order (11 words and a zero)
+zk_status zk_hook_prove_plan_pairs(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t n_rows, size_t m, uint32_t ga, uint32_t gb2,
+                                   uint32_t gb1, int derived, const uint32_t counts[4], uint64_t* out, size_t out_words) try {
+    if (!out || !counts || out_words < 44) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    PairCounts pc;
+    pc.a = counts[0]; pc.b2 = counts[1]; pc.l = counts[2]; pc.b1 = counts[3];
+    const ProveTunables tun = ProveTunables::read();
+    const ProvePlan p = prove_plan(np, n_in, n_aux, n_rows, m, ga, gb2, gb1, derived != 0, tun, pc);
+    const CJobLayout& L = p.layout;
+    const uint64_t f[44] = {p.fold_in_msm, p.host_norm, p.g2_lone, p.split, p.one_stream, (uint64_t)p.g1, (uint64_t)p.map,
+                            tun.batch_chunk, tun.host_chunk, tun.trace_host,
+                            L.n_in, L.n_aux, L.head, L.ga, L.gb2, L.gb1, L.fold, L.derived, L.w_one, L.w_sum_a, L.w_sum_b2, L.wstride,
+                            L.aux, L.rz, L.r, L.sz, L.s, L.rs, L.in_tail, L.sum_b1, L.sum_a, L.cstride,
+                            L.pa, L.pb2, L.pl, L.pb1, L.w_end, L.w_b2v, L.w_pair_a, L.w_pair_b2, L.pair_l, L.pair_b1, L.pair_a, 0};
+    std::copy(f, f + 44, out);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: the chains of a built-in circuit (value_pairs.h; 0 = transfer, 1 = anonymous) under the densities of its natively
+// emitted system, out = [pred A | succ A | pred B | succ B | pred L | succ L | A-dense | B-dense], 8 nv words
+zk_status zk_hook_pair_chains(int circuit, int32_t* out, size_t cap, uint32_t* nv_out) try {
+    if (circuit != 0 && circuit != 1) return fail(ZK_ERR_INVALID_ARGUMENT, "no such circuit");
+    const zkr1cs::System& sys = circuit ? anonymous_system_cached() : transfer_system_cached();
+    const uint32_t nv = sys.n_inputs + sys.n_aux;
+    if (nv_out) *nv_out = nv;
+    if (!out) return ZK_OK;
+    if (cap < 8 * (size_t)nv) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    std::vector<uint8_t> a_dense(nv, 0), b_dense(nv, 0);
+    for (uint32_t i = 0; i < sys.n_inputs; i++) a_dense[i] = 1;
+    for (uint32_t v : sys.m[0].col) a_dense[v] = 1;
+    for (uint32_t v : sys.m[1].col) b_dense[v] = 1;
+    const std::vector<int32_t> c = zkpairs::chains_of(zkpairs::circuit_probes((zkpairs::Circuit)circuit), sys.n_inputs, a_dense, b_dense);
+    std::copy(c.begin(), c.end(), out);
+    std::copy(a_dense.begin(), a_dense.end(), out + 6 * (size_t)nv);
+    std::copy(b_dense.begin(), b_dense.end(), out + 7 * (size_t)nv);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: links -> chains as the library finalizes them (value_pairs.h chains_finalize), pred in place, succ out
+zk_status zk_hook_chains_finalize(int32_t* pred, int32_t* succ, uint32_t nv) try {
+    if (!pred || !succ) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    std::vector<int32_t> p(pred, pred + nv);
+    for (int32_t& x : p)
+        if (x >= (int32_t)nv) x = -1;
+    const std::vector<int32_t> s = zkpairs::chains_finalize(p);
+    std::copy(p.begin(), p.end(), pred);
+    std::copy(s.begin(), s.end(), succ);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: k_build_scalars itself on ONE witness (plain words, n_in + n_aux scalars) under the layout of a derived chunk with
+// the given value pairs and groups of equal bases (ngroups = groups of the [a, b_g2, b_g1] queries, groups = [ptr | member
+// variables] as k_build_scalars reads them): links = [pred A | succ A | pred B | succ B | pred L | succ L | qa | qb2 |
+// ql | qb1] as the kernel reads them (chains as zk_hook_chains_finalize leaves them), counts = the pairs per query [a, b_g2,
+// l, b_g1].  wit_out / cvec_out: the two scalar vectors (layout[0] and layout[1] scalars of 32 bytes; the H block has length 0); layout = [wstride, cstride, w_b2v,
+// w_pair_a, w_pair_b2, aux, rz, r, sz, s, rs, in_tail, pair_l, pair_b1, pair_a, w_one, w_sum_a, w_sum_b2, sum_b1, sum_a].
+zk_status zk_hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t counts[4], const int32_t* links, const uint32_t ngroups[3],
+                                const uint32_t* groups, int fold, const uint8_t* wit, const uint8_t r[32], const uint8_t s[32],
+                                uint8_t* wit_out, size_t wit_cap, uint8_t* cvec_out, size_t cvec_cap, uint32_t layout[20]) try {
+    if (!counts || !links || !ngroups || !groups || !wit || !r || !s || !layout || !n_in) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    ZK_TRY(use_device(0));
+    const uint32_t nv = n_in + n_aux;
+    PairCounts pc;
+    pc.a = counts[0]; pc.b2 = counts[1]; pc.l = counts[2]; pc.b1 = counts[3];
+    for (size_t k = 0; k < 10 * (size_t)nv; k++) {
+        const uint32_t bound = k < 6 * (size_t)nv ? nv : counts[k / nv - 6];
+        if (links[k] < -1 || links[k] >= (int32_t)bound) return fail(ZK_ERR_INVALID_ARGUMENT, "link out of range");
+    }
+    const uint32_t ng = ngroups[0] + ngroups[1] + ngroups[2];
+    for (uint32_t g = 0; g < ng; g++)
+        if (groups[g] > groups[g + 1]) return fail(ZK_ERR_INVALID_ARGUMENT, "groups are not monotone");
+    if (groups[0] != 0) return fail(ZK_ERR_INVALID_ARGUMENT, "groups do not start at 0");
+    for (uint32_t k = 0; k < groups[ng]; k++)
+        if (groups[ng + 1 + k] >= nv) return fail(ZK_ERR_INVALID_ARGUMENT, "group member out of range");
+    const CJobLayout L = cjob_layout(n_in, n_aux, 0, ngroups[0], ngroups[1], ngroups[2], fold != 0, true, pc);
+    const uint32_t f[20] = {L.wstride, L.cstride, L.w_b2v, L.w_pair_a, L.w_pair_b2, L.aux, L.rz, L.r, L.sz, L.s, L.rs, L.in_tail,
+                            L.pair_l, L.pair_b1, L.pair_a, L.w_one, L.w_sum_a, L.w_sum_b2, L.sum_b1, L.sum_a};
+    std::copy(f, f + 20, layout);
+    if (!wit_out || !cvec_out) return ZK_OK;
+    if (wit_cap < (size_t)L.wstride * 32 || cvec_cap < (size_t)L.cstride * 32) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    DevBuf d_wit, d_tail, d_links, d_grp, d_out, d_cv, d_bad;
+    ZK_TRY(d_wit.ensure((size_t)nv * 32));
+    ZK_TRY(d_tail.ensure(96));
+    ZK_TRY(d_links.ensure(10 * (size_t)nv * 4));
+    const size_t grp_words = (size_t)ng + 1 + groups[ng];
+    ZK_TRY(d_grp.ensure(grp_words * 4));
+    ZK_TRY(d_out.ensure((size_t)L.wstride * 32));
+    ZK_TRY(d_cv.ensure((size_t)L.cstride * 32));
+    ZK_TRY(d_bad.ensure(8));
+    uint8_t tail[96] = {1};
+    memcpy(tail + 32, r, 32);
+    memcpy(tail + 64, s, 32);
+    HIP_TRY(hipMemcpy(d_wit.p, wit, (size_t)nv * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_tail.p, tail, 96, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_links.p, links, 10 * (size_t)nv * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_grp.p, groups, grp_words * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(d_out.p, 0xff, (size_t)L.wstride * 32));   // (a slot nobody writes shows)
+    HIP_TRY(hipMemset(d_cv.p, 0xff, (size_t)L.cstride * 32));
+    HIP_TRY(hipMemset(d_bad.p, 0, 8));
+    ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.w_end + L.gb1 + 255) / 256, 1u), dim3(256), 0, g_stream, d_out.as<uint32_t>(),
+              d_cv.as<uint32_t>(), (const uint32_t*)d_wit.as<uint32_t>(), (const uint32_t*)d_tail.as<uint32_t>(), L, 0u, d_bad.as<uint32_t>(),
+              (const uint32_t*)d_grp.as<uint32_t>(), (const int32_t*)d_links.as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(hipMemcpy(wit_out, d_out.p, (size_t)L.wstride * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(cvec_out, d_cv.p, (size_t)L.cstride * 32, hipMemcpyDeviceToHost));
     return ZK_OK;
 } ZK_ABI_CATCH
 #endif
