@@ -17,6 +17,7 @@
 #include <chrono>
 #include <algorithm>
 #include <new>
+#include <memory>
 #include <mutex>
 #include <condition_variable>
 #include <deque>
@@ -29,6 +30,7 @@
 #include "host_common.h"
 #include "host_math.h"
 #include "ntt.h"
+#include "ntt_plan.h"
 #include "msm_group.h"
 #include "prove_plan.h"
 #include "transfer_witness.h"
@@ -73,74 +75,13 @@ struct NttPlan {
     DevBuf scratch;                  // permutation scratch for the stand-alone entry
     size_t bytes = 0;
 
-    // Tile form of the transforms of 2^17 and more (ZKAMD_NTT_TILES = mid | big | small; A/B):
-    //   mid (default, round 6)   2^11-element tiles (64 KiB of LDS, 512 threads), two workgroups per CU; the pass whose tile is
-    //                            contiguous takes 11 stages, the strided ones up to 9 (four columns = 128-byte segments): 2^20 in
-    //                            two passes.  Pair of transforms, ms: 2^17 0.228 -> 0.140, 2^18 0.245 -> 0.155, 2^20 0.288 -> 0.279,
-    //                            2^22 1.349 -> 1.166 against `big` (profiles/r06q_ntt_tiles.txt; VERDICT r5 item 4 asked <= 0.27)
-    //   big (rounds 2-5)         2^12-element tiles (128 KiB, 1024 threads), one workgroup per CU, 10 stages per pass
-    //   small                    the 2^10-element tiles of the in-step transforms at every size
-    static int tile_form() {
-        static const int f = [] {
-            const char* e = getenv("ZKAMD_NTT_TILES");
-            return !e ? 1 : !strcmp(e, "big") ? 2 : !strcmp(e, "small") ? 0 : 1;
-        }();
+    // The tile choice of the transforms of 2^17 and more, read once per process (ZKAMD_NTT_TILES, ntt_plan.h ntt_tiles), and the
+    // form of a chain of `batch` transforms of this size under it: the product's one place that decides a form.
+    static NttForm tiles() {
+        static const NttForm f = ntt_tiles(getenv("ZKAMD_NTT_TILES"));
         return f;
     }
-    static bool big(uint32_t k) { return tile_form() == 2 && k >= (uint32_t)zkdev::NTT_BIG_LOG; }
-    static bool mid(uint32_t k) { return tile_form() == 1 && k >= (uint32_t)zkdev::NTT_BIG_LOG; }
-    static uint32_t threads_for(uint32_t k) { return mid(k) ? 512u : big(k) ? (uint32_t)zkdev::NTT_BIG_THREADS : (uint32_t)zkdev::NTT_THREADS; }
-    // A handful of small transforms (the H pipeline of a proof made alone: 2^15 elements, 32 workgroups of 2^10-element tiles,
-    // every thread four butterflies per stage one after the other - 25 us per pass on a machine that is otherwise idle):
-    // the latency form cuts the tiles to 2^8 elements, one butterfly per thread and stage, four times the workgroups
-    // (~10 us per pass; the 32-byte segments of its strided pass come out of L2).  Chosen per chain by the batch's size.
-    static bool latency_form(uint32_t k, uint32_t batch) { return k >= 9 && k < (uint32_t)zkdev::NTT_BIG_LOG && ((uint64_t)batch << k) <= (1u << 17); }
-    static std::vector<NttPass> passes(uint32_t k, bool dif, uint32_t stride, bool latency = false) {
-        std::vector<NttPass> out;
-        if (k == 0) return out;
-        std::vector<uint32_t> gs;   // stages per pass, in the order of the global stages t0 = 0, g0, g0 + g1 ...
-        uint32_t tile_log;
-        if (latency) {
-            tile_log = 8;
-            const uint32_t np = (k + 7) / 8;
-            for (uint32_t i = 0; i < np; i++) gs.push_back(k / np + (i < k % np ? 1 : 0));
-        } else if (mid(k)) {
-            tile_log = 11;
-            const uint32_t g0 = 11, rest = k - g0, np = (rest + 8) / 9;
-            std::vector<uint32_t> strided;
-            for (uint32_t i = 0; i < np; i++) strided.push_back(rest / np + (i < rest % np ? 1 : 0));
-            // DIF: stage t0 = 0 has the LARGEST distance, the contiguous pass comes last; DIT: first
-            if (dif) {
-                gs = strided;
-                gs.push_back(g0);
-            } else {
-                gs.push_back(g0);
-                gs.insert(gs.end(), strided.begin(), strided.end());
-            }
-        } else {
-            const uint32_t max_g = big(k) ? zkdev::NTT_BIG_MAX_G : zkdev::NTT_MAX_G;
-            tile_log = big(k) ? zkdev::NTT_BIG_TILE_LOG : zkdev::NTT_TILE_LOG;
-            const uint32_t np = (k + max_g - 1) / max_g;
-            for (uint32_t i = 0; i < np; i++) gs.push_back(k / np + (i < k % np ? 1 : 0));
-        }
-        uint32_t t0 = 0;
-        for (uint32_t g : gs) {
-            NttPass p;
-            p.log_n = k;
-            p.t0 = t0;
-            p.g = g;
-            uint32_t lcw = tile_log - p.g;
-            if (lcw > k - p.g) lcw = k - p.g;
-            p.log_cw = lcw;
-            p.dif = dif ? 1 : 0;
-            p.stride = stride;
-            p.src_stride = 0;
-            p.src_valid = 0;
-            out.push_back(p);
-            t0 += p.g;
-        }
-        return out;
-    }
+    NttForm form(uint32_t batch) const { return ntt_form(tiles(), log_n, batch); }
 
     zk_status upload_fr(DevBuf& buf, const Fr* v, size_t count) {
         ZK_TRY(buf.ensure(count * 32));
@@ -201,25 +142,26 @@ struct NttPlan {
         return ZK_OK;
     }
 
-    // Run one chain of passes over `batch` polynomials laid out with `stride` elements.
-    zk_status chain(uint32_t* data, uint32_t batch, uint32_t stride, bool dif, bool inverse,
+    // Run one chain of passes, in the tile form `form` (ntt_plan.h), over `batch` polynomials laid out with `stride` elements.
+    // [first, first + count) cuts the launches out of the chain's pass list (the test hooks run one pass on a state of their
+    // own); pre, src and bad go with the chain's first pass, post and sub with its last.
+    zk_status chain(NttForm form, uint32_t* data, uint32_t batch, uint32_t stride, bool dif, bool inverse,
                     const uint32_t* pre, const uint32_t* post, const uint32_t* src = nullptr,
                     uint32_t src_stride = 0, uint32_t src_valid = 0, uint32_t* bad = nullptr,
-                    const uint32_t* sub = nullptr, uint32_t sub_stride = 0) {
-        const bool latency = latency_form(log_n, batch);
-        std::vector<NttPass> ps = passes(log_n, dif, stride, latency);
+                    const uint32_t* sub = nullptr, uint32_t sub_stride = 0, size_t first = 0, size_t count = SIZE_MAX) {
+        std::vector<NttLaunch> ps;
+        if (!ntt_passes(log_n, dif, stride, form, &ps)) return fail(ZK_ERR_INVALID_ARGUMENT, "no such tile form for this size");
         const uint32_t* tw = inverse ? tw_inv.as<uint32_t>() : tw_fwd.as<uint32_t>();
-        for (size_t i = 0; i < ps.size(); i++) {
-            NttPass p = ps[i];
+        for (size_t i = first; i < ps.size() && i - first < count; i++) {
+            NttPass p = ps[i].pass;
             const uint32_t* s = nullptr;
             if (i == 0 && src) {
                 s = src;
                 p.src_stride = src_stride;
                 p.src_valid = src_valid;
             }
-            unsigned cols = (unsigned)(n >> p.g);
-            dim3 grid(cols >> p.log_cw, batch);
-            size_t shmem = ((size_t)1 << (p.g + p.log_cw)) * 32;
+            dim3 grid(ps[i].grid_x, batch);
+            size_t shmem = ps[i].lds_bytes;
             ProfScope ps_(dif ? "ntt_pass_dif" : "ntt_pass_dit");
 #ifndef ZK_EMU
             if (shmem > 65536) {
@@ -229,12 +171,12 @@ struct NttPlan {
                 std::lock_guard<std::mutex> lock(mu);
                 const uint64_t bit = 1ull << (g_device & 63);
                 if (!(raised & bit)) {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(zkdev::k_ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(zkdev::k_ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_MAX));
                     raised |= bit;
                 }
             }
 #endif
-            ZK_LAUNCH_SYNC(zkdev::k_ntt_pass, grid, dim3(latency ? (1u << (p.g + p.log_cw - 1)) : threads_for(log_n)), shmem, g_stream, data, s, tw,
+            ZK_LAUNCH_SYNC(zkdev::k_ntt_pass, grid, dim3(ps[i].threads), shmem, g_stream, data, s, tw,
                            i == 0 ? pre : (const uint32_t*)nullptr,
                            i + 1 == ps.size() ? post : (const uint32_t*)nullptr, p, i == 0 && s ? bad : (uint32_t*)nullptr,
                            i + 1 == ps.size() ? sub : (const uint32_t*)nullptr, sub_stride);
@@ -960,9 +902,9 @@ struct ChunkRun {
         const uint32_t* s1 = derived ? P->ntt.dt.as<uint32_t>() : mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
         const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
         for (int k = 0; k < (derived ? 2 : 3); k++)
-            ZK_TRY(P->ntt.chain(dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
+            ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)np), dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
         // (coset) fft (bit-reversed -> natural) of a and b at once
-        ZK_TRY(P->ntt.chain(A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
+        ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)(2 * np)), A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
         {
             ProfScope ps("h_pointwise");
             if (derived) {
@@ -979,7 +921,7 @@ struct ChunkRun {
         // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
         // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
         if (!derived)
-            ZK_TRY(P->ntt.chain(cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
+            ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)np), cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
                                 (const uint32_t*)C, (uint32_t)m));
         return ZK_OK;
     }
@@ -2166,7 +2108,7 @@ zk_status ntt_run_dev(zk_ntt* T, void* d_data, uint32_t batch, uint32_t flags) {
     const bool dif = !in_br;
     bool post_fused = false;
     if (post && !dif) post_fused = true;   // DIT ends in natural order: fuse the scaling
-    ZK_TRY(pl.chain(d, batch, (uint32_t)n, dif, inverse, pre, post_fused ? post : nullptr));
+    ZK_TRY(pl.chain(pl.form(batch), d, batch, (uint32_t)n, dif, inverse, pre, post_fused ? post : nullptr));
     const bool have_br = dif;   // order after the chain
     if (have_br != out_br) {
         ZK_TRY(pl.scratch.ensure(count * 32));
@@ -3095,6 +3037,98 @@ zk_status zk_ntt_create(uint32_t log_n, int device, zk_ntt** out) try {
 } ZK_ABI_CATCH
 zk_status zk_ntt_run_dev(zk_ntt* t, void* d_data, uint32_t batch, uint32_t flags) try { return ntt_run_dev(t, d_data, batch, flags); } ZK_ABI_CATCH
 void zk_ntt_free(zk_ntt* t) { delete t; }
+#ifdef ZK_TEST_HOOKS
+// Test hook, no GPU involved: the launches of one chain of 2^log_n-point transforms (ntt_plan.h).  form = an NttForm, or
+// -1: the form the product takes for `batch` transforms under the tile choice of this process, or 0x10 | tiles: the same under
+// the tile choice given.  words = [form | per pass: t0, g, log_cw, dif, threads, grid_x, lds_bytes], *n_words of them.
+zk_status zk_hook_ntt_plan(uint32_t log_n, uint32_t batch, int dif, int form, uint32_t* words, size_t cap, size_t* n_words) try {
+    if (!words || !n_words) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (form == -1) form = ntt_form(NttPlan::tiles(), log_n, batch);
+    else if (form >= 0x11 && form <= 0x13) form = ntt_form((NttForm)(form & 3), log_n, batch);
+    std::vector<NttLaunch> ps;
+    if (!ntt_passes(log_n, dif != 0, 1u << (log_n <= NTT_MAX_LOG ? log_n : 0), form, &ps))
+        return fail(ZK_ERR_INVALID_ARGUMENT, "no such tile form for this size");
+    *n_words = 1 + 7 * ps.size();
+    if (cap < *n_words) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    words[0] = (uint32_t)form;
+    for (size_t i = 0; i < ps.size(); i++) {
+        const NttLaunch& l = ps[i];
+        const uint32_t f[7] = {l.pass.t0, l.pass.g, l.pass.log_cw, l.pass.dif, l.threads, l.grid_x, l.lds_bytes};
+        std::copy(f, f + 7, words + 1 + 7 * i);
+    }
+    return ZK_OK;
+} ZK_ABI_CATCH
+// (the plan of the size the two hooks below were asked for last: its ten tables are built once for a run of calls)
+static zk_status hook_ntt_plan_of(uint32_t log_n, NttPlan** out) {
+    static std::unique_ptr<NttPlan> plan;
+    ZK_TRY(use_device(0));
+    if (!plan || plan->log_n != log_n) {
+        plan.reset(new NttPlan());
+        const zk_status st = plan->init(log_n);
+        if (st != ZK_OK) {
+            plan.reset();
+            return st;
+        }
+    }
+    *out = plan.get();
+    return ZK_OK;
+}
+// Test hook: NttPlan::chain - the product's, not a copy - on host arrays that the hook uploads and downloads.  data = batch *
+// stride elements (stride >= n; back in place), pre / post = n elements, src = batch * src_stride (src_stride >= src_valid),
+// minus = batch * minus_stride (minus_stride >= n), each optional; *bad = the flag word after the chain (0 going in).  Only the
+// passes [first, first + count) of the chain's list are launched, on whatever state `data` holds.
+zk_status zk_hook_ntt_chain(uint32_t log_n, int form, int dif, int inverse, uint32_t batch, uint32_t stride, uint32_t* data,
+                            const uint32_t* pre, const uint32_t* post, const uint32_t* src, uint32_t src_stride, uint32_t src_valid,
+                            const uint32_t* minus, uint32_t minus_stride, uint32_t first, uint32_t count, uint32_t* bad) try {
+    if (!data || !bad) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (log_n > 21 || !batch || batch > 64) return fail(ZK_ERR_INVALID_ARGUMENT, "hook sizes: log_n <= 21, 1 <= batch <= 64");
+    const size_t n = (size_t)1 << log_n;
+    if (stride < n || ((uint64_t)batch * stride >> 24) || (src && src_stride < src_valid) || (minus && minus_stride < n))
+        return fail(ZK_ERR_INVALID_ARGUMENT, "stride shorter than what it holds");
+    if (!ntt_form_allowed(form, log_n)) return fail(ZK_ERR_INVALID_ARGUMENT, "no such tile form for this size");
+    NttPlan* pl = nullptr;
+    ZK_TRY(hook_ntt_plan_of(log_n, &pl));
+    DevBuf d_data, d_pre, d_post, d_src, d_minus, d_bad;
+    const auto up = [](DevBuf& b, const uint32_t* host, size_t elems) -> zk_status {
+        b.is_public = true;
+        ZK_TRY(b.ensure(elems * 32 + 32));
+        if (host && elems) HIP_TRY(hipMemcpy(b.p, host, elems * 32, hipMemcpyHostToDevice));
+        return ZK_OK;
+    };
+    ZK_TRY(up(d_data, data, (size_t)batch * stride));
+    if (pre) ZK_TRY(up(d_pre, pre, n));
+    if (post) ZK_TRY(up(d_post, post, n));
+    if (src) ZK_TRY(up(d_src, src, (size_t)batch * src_stride));
+    if (minus) ZK_TRY(up(d_minus, minus, (size_t)batch * minus_stride));
+    ZK_TRY(up(d_bad, nullptr, 0));
+    HIP_TRY(hipMemset(d_bad.p, 0, 32));
+    const zk_status st = pl->chain((NttForm)form, d_data.as<uint32_t>(), batch, stride, dif != 0, inverse != 0,
+                                   pre ? d_pre.as<uint32_t>() : nullptr, post ? d_post.as<uint32_t>() : nullptr,
+                                   src ? d_src.as<uint32_t>() : nullptr, src_stride, src_valid, d_bad.as<uint32_t>(),
+                                   minus ? d_minus.as<uint32_t>() : nullptr, minus_stride, first, count);
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    ZK_TRY(st);
+    HIP_TRY(hipMemcpy(data, d_data.p, (size_t)batch * stride * 32, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(bad, d_bad.p, 4, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: the bytes of one table of NttPlan::init for the domain 2^log_n, which = 0 .. 10: tw_fwd, tw_inv, s1_plain, s1_mont,
+// s2, dt, sc_plain, sc_mont, coset_fwd, coset_inv, consts.  *bytes = its length; out == nullptr asks for the length alone.
+zk_status zk_hook_ntt_table(uint32_t log_n, uint32_t which, uint8_t* out, size_t cap, size_t* bytes) try {
+    if (!bytes || which > 10) return fail(ZK_ERR_INVALID_ARGUMENT, "no such table");
+    if (log_n > 21) return fail(ZK_ERR_INVALID_ARGUMENT, "hook sizes: log_n <= 21");
+    NttPlan* pl = nullptr;
+    ZK_TRY(hook_ntt_plan_of(log_n, &pl));
+    const DevBuf* tabs[11] = {&pl->tw_fwd, &pl->tw_inv, &pl->s1_plain, &pl->s1_mont, &pl->s2, &pl->dt,
+                              &pl->sc_plain, &pl->sc_mont, &pl->coset_fwd, &pl->coset_inv, &pl->consts};
+    *bytes = tabs[which]->cap;   // (what init asked for: a DevBuf holds exactly that)
+    if (!out) return ZK_OK;
+    if (cap < *bytes) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    if (*bytes) HIP_TRY(hipMemcpy(out, tabs[which]->p, *bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_ABI_CATCH
+#endif
 
 zk_status zk_ntt_fr(uint8_t* data, uint32_t log_n, int inverse, int coset) try {
     if (!data) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
