@@ -83,6 +83,9 @@
  *   zk_confidential_block_execute   encrypted_balances::confidential_transfer for every extrinsic of a block, in order
  *                                   modules/encrypted-balances/src/lib.rs:25-96 (rollover :133-170, sub_enc_balance :173-196,
  *                                   add_pending_transfer :199-222), modules/zk-system/src/lib.rs:56-115
+ *   zk_anonymous_block_execute      anonymous_balances::anonymous_transfer for every extrinsic of a block, in order
+ *                                   modules/anonymous-balances/src/lib.rs:23-82 (rollover :169-206, add_pending_transfer :209-229),
+ *                                   modules/zk-system/src/lib.rs:118-165
  *   zk_g_epoch                      GEpoch::group_hash                            core/primitives/src/g_epoch.rs:102-110, core/jubjub/src/group_hash.rs:17-46
  *   zk_redjubjub_sign               redjubjub::PrivateKey::sign                 core/jubjub/src/redjubjub.rs:73-103; callers confidential.rs:416-420, anonymous.rs:378-401
  *   zk_redjubjub_verify_batch       redjubjub::PublicKey::verify, per signature   core/jubjub/src/redjubjub.rs:127-155; RedjubjubSignature::verify core/primitives/src/signature.rs:65-82
@@ -659,6 +662,50 @@ typedef struct { uint32_t rounds, proofs_verified, points_decoded, reserved; } z
 zk_status zk_confidential_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts,
     const uint8_t* sigs /* n x 64 or NULL: signatures are not this call's business */,
     const uint8_t* msgs, const uint64_t* msg_offsets /* as zk_redjubjub_verify_batch; vk of xt i = xts[i].rvk */,
+    size_t n_accounts, const zk_block_account* accounts, size_t n_pool, const uint8_t* nonce_pool /* n_pool x 32 */,
+    const uint8_t g_epoch[32], zk_block_account* accounts_out, zk_block_verdict* verdicts_out,
+    zk_block_stats* stats_out /* may be NULL */);
+/* ------------------------------------------------------------------------------------------
+ * A block of anonymous transfers executed in one call: anonymous_balances::anonymous_transfer
+ * (modules/anonymous-balances/src/lib.rs:23-82) for n extrinsics IN ORDER.  The arguments, zk_block_account, zk_block_verdict,
+ * zk_block_stats, the ZK_BLOCK_* verdicts and the two flag bits are those of zk_confidential_block_execute.  The result equals
+ * that of this loop over the extrinsics; acc(k) is the account whose enc_key has the bytes k, the pool starts as nonce_pool:
+ *   1. Signature.  Exactly as step 1 above: sigs == NULL means signatures are not this call's business; a bad signature is
+ *      BAD_SIGNATURE with the reason of zk_redjubjub_verify_batch, and nothing else happens.
+ *   2. Stored account unreadable.  Any of the twelve acc(enc_keys[k]) holds a balance or pending ciphertext that Ciphertext::read
+ *      refuses: BAD_ACCOUNT, nothing else happens - NO member of the ring is rolled over by this extrinsic.  (The convention of
+ *      the confidential entry.  The reference's `for e in &enc_keys { rollover(e)? }` loop, lib.rs:37-39, would have rolled the
+ *      members before the unreadable one.)  The outputs of an unreadable account that a dispatched extrinsic names are 64 zero
+ *      bytes twice.
+ *   3. Rollover (lib.rs:37-39, 169-206), for each of the twelve keys in order: an account with ZK_BLOCK_ROLLOVER_DUE that has not
+ *      rolled over in this block gets balance += pending, pending = Ciphertext::zero(), and ZK_BLOCK_ROLLED.  A key that appears
+ *      twice in a ring rolls once.  This stays whatever happens to the extrinsic below.
+ *   4. Nonce.  nonce is in the pool: NONCE_USED (the reference assert!s, lib.rs:42; a rejection here, as above).  The pool grows
+ *      with every accepted extrinsic.
+ *   5. Public inputs.  The 52 fields of zk_anonymous_verify_batch; member k's balance is acc(enc_keys[k]).balance as it stands
+ *      after step 3.  A refused point: REFUSED_POINT, detail = field | status << 6 of the first refused point in push order.
+ *      Fields 25..48 are never the refused one: step 2 judged them.
+ *   6. Proof.  verify_proof fails: INVALID_PROOF.
+ *   7. ACCEPTED: the nonce joins the pool; for k = 0..11, acc(enc_keys[k]).pending += (left_ciphertexts[k], right_ciphertext).
+ * accounts_out, the accounts no dispatched extrinsic names (copied through, flags and all), what stays the runtime's (storage,
+ * epochs, LastRollOver) and the argument mistakes (ZK_ERR_INVALID_ARGUMENT with the index in zk_last_error(), nothing written: a
+ * ring key that is not among the accounts, two accounts with equal keys, a NULL buffer with a non-zero count, offsets that
+ * decrease) are as for the confidential entry.  ZK_ERR_MALFORMED_VERIFYING_KEY unless the key has 104 inputs.  n == 0 copies
+ * the accounts through.
+ * ONE verification batch is exact here.  Transfers only ever add to pending slots; a balance changes only by rollover, and
+ * whether an account rolls over is known from signatures and stored bytes alone: rolled[a] = due[a] && (some extrinsic that
+ * passes steps 1 and 2 names a).  An extrinsic that reaches step 5 has itself rolled every due member of its ring, so the balance
+ * it meets for member a is rolled[a] ? balance + pending : balance - independent of its position and of every verdict.  The call
+ * verifies, in one batch, every extrinsic that passes steps 1 and 2, whose nonce is not in the CALLER's pool and that has no
+ * refused point; one sweep in order then applies steps 4 to 7 (a later twin of an accepted nonce is NONCE_USED although its
+ * proof was checked).  stats_out (may be NULL): rounds = 1 if any extrinsic passes steps 1 and 2, else 0; proofs_verified = the
+ * size of that batch; points_decoded = the distinct 32-byte encodings, each decoded once - 27 per extrinsic, four per account,
+ * g_epoch.
+ * Up to ZKAMD_INTO_XY_HOST_MAX distinct encodings (read per call) the point work runs on the host threads, above it on the key's
+ * device (csrc/anon_block_exec.h); the verification always runs on the key's device.  The bytes written do not depend on the form.
+ * ------------------------------------------------------------------------------------------ */
+zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt* xts,
+    const uint8_t* sigs /* n x 64 or NULL */, const uint8_t* msgs, const uint64_t* msg_offsets,
     size_t n_accounts, const zk_block_account* accounts, size_t n_pool, const uint8_t* nonce_pool /* n_pool x 32 */,
     const uint8_t g_epoch[32], zk_block_account* accounts_out, zk_block_verdict* verdicts_out,
     zk_block_stats* stats_out /* may be NULL */);

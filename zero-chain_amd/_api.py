@@ -24,7 +24,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
                    ZK_NTT_OUT_BITREV)
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
-           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
+           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
@@ -564,17 +564,8 @@ BLOCK_ROLLOVER_DUE, BLOCK_ROLLED = 1, 2          # flags of an account: in (last
 BLOCK_VERDICTS = ("accepted", "bad signature", "nonce used", "bad account", "refused point", "invalid proof")   # ZK_BLOCK_*
 
 
-def execute_confidential_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=None, msgs=None):
-    """zk_confidential_block_execute = encrypted_balances::confidential_transfer (modules/encrypted-balances/src/lib.rs:25-96)
-    for a block of ConfidentialXt in order (include/zkamd.h states the seven steps).  xts: as verify_confidential_xts.
-    accounts: dicts with enc_key, balance and pending ((left, right) encodings; None = Ciphertext::zero()) and flags
-    (BLOCK_ROLLOVER_DUE).  nonce_pool: the 32-byte nonces already used in this epoch.  sigs / msgs: the 64-byte signature and
-    the signed message of every xt (the key is its rvk), or None - signatures are then not this call's business.
-    Returns (verdicts, accounts_out, stats): a verdict is (name of BLOCK_VERDICTS, detail) with detail None, the reason of
-    REDJUBJUB_REASONS for a bad signature, or (field name, reason) for a refused point; accounts_out are dicts like the input
-    with the flags as written (BLOCK_ROLLED); stats has rounds, proofs_verified, points_decoded."""
+def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msgs):
     lib = pvk._lib
-    arr = _xt_array(xts, _lib.ConfidentialXt, _fill_confidential_xt)
     n, na = len(arr), len(accounts)
     acc, out = (_lib.BlockAccount * max(na, 1))(), (_lib.BlockAccount * max(na, 1))()
     for dst, a in zip(acc, accounts):
@@ -591,21 +582,43 @@ def execute_confidential_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=Non
         sb = _u8(b"".join(bytes(s) for s in sigs), 64 * n) if n else None
         blob, offs = _messages(msgs)
     verdicts, stats, ge = (_lib.BlockVerdict * max(n, 1))(), _lib.BlockStats(), _u8(bytes(g_epoch), 32)
-    lib.check(lib.zk_confidential_block_execute(pvk._h, n, arr if n else None, None if sb is None else _ptr(sb), None if blob is None else _ptr(blob),
-                                                None if offs is None else _ptr(offs), na, acc if na else None, len(nonce_pool),
-                                                None if pool is None else _ptr(pool), _ptr(ge), out if na else None,
-                                                verdicts if n else None, C.byref(stats)))
+    lib.check(fn(pvk._h, n, arr if n else None, None if sb is None else _ptr(sb), None if blob is None else _ptr(blob),
+                 None if offs is None else _ptr(offs), na, acc if na else None, len(nonce_pool),
+                 None if pool is None else _ptr(pool), _ptr(ge), out if na else None,
+                 verdicts if n else None, C.byref(stats)))
 
     def detail(v):
         if v.verdict == 1:
             return REDJUBJUB_REASONS[v.detail]
         if v.verdict == 4:
-            return (CONFIDENTIAL_XT_POINTS[(v.detail & 63) - 1], INTO_XY_REASONS[v.detail >> 6])
+            return (names[(v.detail & 63) - 1], INTO_XY_REASONS[v.detail >> 6])
         return None
     ct = lambda b: (bytes(b[:32]), bytes(b[32:]))
     return ([(BLOCK_VERDICTS[v.verdict], detail(v)) for v in verdicts[:n]],
             [dict(enc_key=bytes(o.enc_key), balance=ct(o.balance), pending=ct(o.pending), flags=int(o.flags)) for o in out[:na]],
             dict(rounds=stats.rounds, proofs_verified=stats.proofs_verified, points_decoded=stats.points_decoded))
+
+
+def execute_confidential_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=None, msgs=None):
+    """zk_confidential_block_execute = encrypted_balances::confidential_transfer (modules/encrypted-balances/src/lib.rs:25-96)
+    for a block of ConfidentialXt in order (include/zkamd.h states the seven steps).  xts: as verify_confidential_xts.
+    accounts: dicts with enc_key, balance and pending ((left, right) encodings; None = Ciphertext::zero()) and flags
+    (BLOCK_ROLLOVER_DUE).  nonce_pool: the 32-byte nonces already used in this epoch.  sigs / msgs: the 64-byte signature and
+    the signed message of every xt (the key is its rvk), or None - signatures are then not this call's business.
+    Returns (verdicts, accounts_out, stats): a verdict is (name of BLOCK_VERDICTS, detail) with detail None, the reason of
+    REDJUBJUB_REASONS for a bad signature, or (field name, reason) for a refused point; accounts_out are dicts like the input
+    with the flags as written (BLOCK_ROLLED); stats has rounds, proofs_verified, points_decoded."""
+    arr = _xt_array(xts, _lib.ConfidentialXt, _fill_confidential_xt)
+    return _execute_block(pvk, pvk._lib.zk_confidential_block_execute, arr, CONFIDENTIAL_XT_POINTS, accounts, nonce_pool, g_epoch, sigs, msgs)
+
+
+def execute_anonymous_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=None, msgs=None):
+    """zk_anonymous_block_execute = anonymous_balances::anonymous_transfer (modules/anonymous-balances/src/lib.rs:23-82) for a
+    block of AnonymousXt in order (include/zkamd.h states the seven steps).  xts: as verify_anonymous_xts; every key of a ring
+    names one of `accounts`.  Arguments and result as execute_confidential_block; a refused field is named from
+    ANONYMOUS_XT_POINTS, and stats["rounds"] is never more than 1: the whole block verifies in one batch."""
+    arr = _xt_array(xts, _lib.AnonymousXt, _fill_anonymous_xt)
+    return _execute_block(pvk, pvk._lib.zk_anonymous_block_execute, arr, ANONYMOUS_XT_POINTS, accounts, nonce_pool, g_epoch, sigs, msgs)
 
 
 def g_epoch(epoch, lib=None):

@@ -189,6 +189,9 @@ _PROTOS = {
     "zk_confidential_block_execute": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                   C.POINTER(BlockAccount), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BlockAccount),
                                                   C.POINTER(BlockVerdict), C.POINTER(BlockStats)]),
+    "zk_anonymous_block_execute": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                               C.POINTER(BlockAccount), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BlockAccount),
+                                               C.POINTER(BlockVerdict), C.POINTER(BlockStats)]),
     "zk_g_epoch": (C.c_int32, [C.c_uint32, C.c_void_p]),
     "zk_redjubjub_sign": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zk_redjubjub_verify_batch": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

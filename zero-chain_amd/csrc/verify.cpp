@@ -22,6 +22,7 @@
 #include "xt_inputs.h"
 #include "ledger.h"
 #include "block_exec.h"
+#include "anon_block_exec.h"
 #include "verify_plan.h"
 
 using namespace zkrt;
@@ -1075,6 +1076,19 @@ zk_status zk_confidential_block_execute(zk_vk* vk, size_t n, const zk_confidenti
     };
     return zkblock::execute(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool, nonce_pool,
                             g_epoch, accounts_out, verdicts_out, stats_out);
+} ZK_ABI_CATCH
+zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* sigs, const uint8_t* msgs,
+                                     const uint64_t* msg_offsets, size_t n_accounts, const zk_block_account* accounts, size_t n_pool,
+                                     const uint8_t* nonce_pool, const uint8_t g_epoch[32], zk_block_account* accounts_out,
+                                     zk_block_verdict* verdicts_out, zk_block_stats* stats_out) try {
+    if (!vk) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (vk->ic.size() != 2 * zkblock::AX_FIELDS + 1) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "the key does not have 104 public inputs");
+    vk->block.is_public = true;
+    auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
+        return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::AX_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
+    };
+    return zkblock::execute_anonymous(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool,
+                                      nonce_pool, g_epoch, accounts_out, verdicts_out, stats_out);
 } ZK_ABI_CATCH
 zk_status zk_g_epoch(uint32_t epoch, uint8_t out[32]) try {
     if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
