@@ -86,7 +86,10 @@
  *   zk_anonymous_block_execute      anonymous_balances::anonymous_transfer for every extrinsic of a block, in order
  *                                   modules/anonymous-balances/src/lib.rs:23-82 (rollover :169-206, add_pending_transfer :209-229),
  *                                   modules/zk-system/src/lib.rs:118-165
- *   zk_g_epoch                      GEpoch::group_hash                            core/primitives/src/g_epoch.rs:102-110, core/jubjub/src/group_hash.rs:17-46
+ *   zk_asset_block_execute          encrypted_assets::issue, confidential_transfer and destroy for every extrinsic of a block, in order
+ *                                   modules/encrypted-assets/src/lib.rs:32-83, :86-164, :167-215 (rollover :266-304, sub_enc_balance
+ *                                   :307-331, add_pending_transfer :334-358), modules/zk-system/src/lib.rs:56-115
+ *   zk_g_epoch                      GEpoch::group_hash                       core/primitives/src/g_epoch.rs:102-110, core/jubjub/src/group_hash.rs:17-46
  *   zk_redjubjub_sign               redjubjub::PrivateKey::sign                 core/jubjub/src/redjubjub.rs:73-103; callers confidential.rs:416-420, anonymous.rs:378-401
  *   zk_redjubjub_verify_batch       redjubjub::PublicKey::verify, per signature   core/jubjub/src/redjubjub.rs:127-155; RedjubjubSignature::verify core/primitives/src/signature.rs:65-82
  *   zk_msm_create, zk_msm_create_variable, zk_msm_run, zk_msm_run_dev, zk_msm_free, zk_msm_g1, zk_msm_g2, zk_msm_cache_release
@@ -709,6 +712,85 @@ zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt*
     size_t n_accounts, const zk_block_account* accounts, size_t n_pool, const uint8_t* nonce_pool /* n_pool x 32 */,
     const uint8_t g_epoch[32], zk_block_account* accounts_out, zk_block_verdict* verdicts_out,
     zk_block_stats* stats_out /* may be NULL */);
+/* ------------------------------------------------------------------------------------------
+ * A block of encrypted-asset extrinsics executed in one call: the three dispatch functions of modules/encrypted-assets/src/lib.rs
+ * - issue (:32-83), confidential_transfer (:86-164), destroy (:167-215) - for n extrinsics IN ORDER.  zk_confidential_xt,
+ * zk_block_account, zk_block_verdict, zk_block_stats, the ZK_BLOCK_* verdicts, the two flag bits and the signature arguments
+ * are those of zk_confidential_block_execute; the verifying key is the confidential one.  kinds[i] says which call extrinsic i
+ * is, asset_ids[i] the id a transfer or destroy names.  An account of this module is keyed by (asset id, enc_key):
+ * account_asset_ids[a] is the id of accounts[a], acc(c, k) the account with asset id c whose enc_key has the bytes k.  The
+ * result equals that of this loop over the extrinsics; the pool starts as nonce_pool, the id counter as next_asset_id:
+ *  TRANSFER (lib.rs:86-164): steps 1-7 of zk_confidential_block_execute with acc(asset_ids[i], .) in place of acc(.) - signature,
+ *   an unreadable acc(id, sender) or acc(id, recipient) (BAD_ACCOUNT), rollover of both (:104-110, :266-304), nonce (:113),
+ *   the public inputs against acc(id, sender).balance as it stands (:116-127), the proof, and sub_enc_balance /
+ *   add_pending_transfer (:137-154, :307-358).
+ *  ISSUE (lib.rs:32-83) reads enc_key_sender (the issuer), left_amount_sender (total), left_fee, enc_balance, right_randomness,
+ *   rvk, nonce and proof; the recipient fields are not looked at.  It names no account and rolls nothing over.
+ *   1. Signature, as step 1 of the confidential entry (ensure_signed, :42).
+ *   2. Nonce in the pool (:49): NONCE_USED.
+ *   3. Public inputs of verify_confidential_proof(issuer, issuer, total, total, enc_balance, rvk, fee, randomness, nonce) (:55-66)
+ *      with the field numbers of zk_confidential_verify_batch: 1 = 2 = the issuer, 3 = 4 = total, 7 and 8 the halves of the
+ *      extrinsic's OWN enc_balance - which CAN be the refused point here.  A refused point: REFUSED_POINT, detail =
+ *      field | status << 6 of the first in push order.
+ *   4. Proof: INVALID_PROOF.
+ *   5. ACCEPTED (:72-82): the nonce joins the pool; the extrinsic gets the counter's value as its id and the counter goes up by
+ *      one; effects_out[i].first = Ciphertext::from_left_right(total, randomness) as Point::write gives it - what
+ *      EncryptedBalance((id, issuer)) and TotalSupply(id) get.  Storing them stays the caller's.
+ *  DESTROY (lib.rs:167-215) reads the same fields, enc_key_sender as the owner, asset_ids[i] as the id.
+ *   1. Signature (:178).
+ *   2. acc(id, owner) unreadable: BAD_ACCOUNT.  (A convention, the one step 2 of the sibling entries chose: the reference
+ *      would `take` without reading.)
+ *   3. Nonce (:185): NONCE_USED.
+ *   4. Public inputs (owner, owner, dummy_amount, dummy_amount, enc_balance, rvk, dummy_fee, randomness, nonce) (:189-200),
+ *      dummy_amount = left_amount_sender, dummy_fee = left_fee; fields 7 and 8 as for an issue.
+ *   5. Proof: INVALID_PROOF.
+ *   6. ACCEPTED (:206-214): the nonce joins the pool; effects_out[i].first and .second are the account's balance and pending
+ *      transfer as they stand (canonical); both then become Ciphertext::zero(), and ZK_BLOCK_TAKEN is set in the account's
+ *      output flags.  A destroy does NOT roll its account over (:178-186), but it names it: the account's outputs are
+ *      re-encoded canonically whatever the verdict past step 1.
+ * What follows from the loop:
+ *   - An account named first by a destroy and later by a transfer rolls over at the transfer, over the pending transfer as it
+ *     stands then - zero after an accepted destroy, so the rollover moves nothing.  ZK_BLOCK_ROLLED is set whenever step 3 of a
+ *     dispatched transfer reaches a due account.
+ *   - None = Ciphertext::zero() throughout, exactly as in the confidential entry: after an accepted destroy a later subtraction
+ *     subtracts from zero, where the reference's `and_then` (:321-328) would keep None.
+ * accounts_out as for the confidential entry (an account no dispatched transfer or destroy names is copied through, flags and
+ * all).  effects_out[i] of a rejected extrinsic: zeros, with the id it named (0 for an issue).  *next_asset_id_out: the counter
+ * after the loop.  The caller stores accounts and issued balances, TotalSupply and NextAssetId, removes the entries of accounts
+ * with ZK_BLOCK_TAKEN, deposits the events and pays the fees.
+ * ZK_ERR_INVALID_ARGUMENT (the index in zk_last_error(), nothing written): a kind above 2; a transfer or destroy whose (id, key)
+ * is not among the accounts; two accounts with equal (id, key); a NULL buffer with a non-zero count; offsets that decrease;
+ * next_asset_id plus the number of issue extrinsics above UINT32_MAX; and ANY account, transfer or destroy whose asset id lies in
+ * [next_asset_id, next_asset_id + the number of issue extrinsics of the call) - the ids this very call may assign, which keeps
+ * the identity of every slot independent of the verdicts.  The caller's recourse: split the block in front of the named
+ * extrinsic and hand each call the accounts its own extrinsics name; a call without an issue accepts every id, so splitting
+ * ends.  ZK_ERR_MALFORMED_VERIFYING_KEY unless the key has 22 inputs.  n == 0 copies the accounts through and returns next_asset_id.
+ * Rounds as in the confidential entry, the hypothesis of each being that every still-open predecessor is rejected.  Issues and
+ * destroys take no balance from the ledger: only a still-open earlier extrinsic with the same nonce holds them, and each is
+ * verified once.  A transfer waits for the next round when an earlier transfer from its account, or an earlier destroy of its
+ * sender's account, is held or was accepted in this sweep, or an earlier extrinsic with its nonce is open.  ONE round for a
+ * block in which no account sends twice and no destroy precedes a transfer from its account.  stats_out (may be NULL):
+ * points_decoded = the distinct 32-byte encodings, each decoded once - eight per extrinsic, two more (enc_balance) for an issue
+ * or destroy, four per account, g_epoch.
+ * Up to ZKAMD_INTO_XY_HOST_MAX distinct encodings (read per call) the point work runs on the host, above it on the key's device,
+ * where a scan that can forget (csrc/asset_block_exec.h) takes the place of the ledger's; the bytes do not depend on the form.
+ * ------------------------------------------------------------------------------------------ */
+#define ZK_BLOCK_TAKEN 4u      /* out: an accepted destroy took this account in this block */
+enum { ZK_ASSET_TRANSFER = 0, ZK_ASSET_ISSUE = 1, ZK_ASSET_DESTROY = 2 };
+typedef struct {               /* 136 bytes */
+    uint32_t asset_id;         /* issue accepted: the id assigned; transfer, destroy: the id named; else 0 */
+    uint32_t reserved;         /* 0 */
+    uint8_t first[64];         /* issue accepted: Ciphertext::from_left_right(total, randomness), what EncryptedBalance
+                                  and TotalSupply get; destroy accepted: the balance taken; else 64 zero bytes */
+    uint8_t second[64];        /* destroy accepted: the pending transfer taken; else 64 zero bytes */
+} zk_asset_effect;
+zk_status zk_asset_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts,
+    const uint8_t* kinds /* n: ZK_ASSET_* */, const uint32_t* asset_ids /* n: ignored for an issue */,
+    const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets,
+    size_t n_accounts, const zk_block_account* accounts, const uint32_t* account_asset_ids /* n_accounts */,
+    size_t n_pool, const uint8_t* nonce_pool, const uint8_t g_epoch[32], uint32_t next_asset_id,
+    zk_block_account* accounts_out, zk_block_verdict* verdicts_out, zk_asset_effect* effects_out,
+    uint32_t* next_asset_id_out, zk_block_stats* stats_out /* may be NULL */);
 /* GEpoch::group_hash (core/primitives/src/g_epoch.rs:102-110): the Jubjub group hash (core/jubjub/src/group_hash.rs:17-46,
  * find_group_hash curve/mod.rs:223-247) personalised "zcgepoch" over the four little-endian bytes of `epoch` and a counter byte
  * from 0 - the g_epoch every wallet and verifier entry takes.  Host only.  out: Point::write of the point. */

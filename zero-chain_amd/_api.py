@@ -24,7 +24,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
                    ZK_NTT_OUT_BITREV)
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
-           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
+           "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
@@ -564,7 +564,9 @@ BLOCK_ROLLOVER_DUE, BLOCK_ROLLED = 1, 2          # flags of an account: in (last
 BLOCK_VERDICTS = ("accepted", "bad signature", "nonce used", "bad account", "refused point", "invalid proof")   # ZK_BLOCK_*
 
 
-def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msgs):
+def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msgs, asset=None):
+    """asset: None, or (kinds, asset_ids, next_asset_id) for zk_asset_block_execute - the same marshalling with the asset ids
+    of extrinsics and accounts beside it, and (effects, next_asset_id) between accounts_out and stats in the result"""
     lib = pvk._lib
     n, na = len(arr), len(accounts)
     acc, out = (_lib.BlockAccount * max(na, 1))(), (_lib.BlockAccount * max(na, 1))()
@@ -582,10 +584,22 @@ def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msg
         sb = _u8(b"".join(bytes(s) for s in sigs), 64 * n) if n else None
         blob, offs = _messages(msgs)
     verdicts, stats, ge = (_lib.BlockVerdict * max(n, 1))(), _lib.BlockStats(), _u8(bytes(g_epoch), 32)
-    lib.check(fn(pvk._h, n, arr if n else None, None if sb is None else _ptr(sb), None if blob is None else _ptr(blob),
-                 None if offs is None else _ptr(offs), na, acc if na else None, len(nonce_pool),
-                 None if pool is None else _ptr(pool), _ptr(ge), out if na else None,
-                 verdicts if n else None, C.byref(stats)))
+    head = (pvk._h, n, arr if n else None)
+    signed = (None if sb is None else _ptr(sb), None if blob is None else _ptr(blob), None if offs is None else _ptr(offs))
+    pooled = (len(nonce_pool), None if pool is None else _ptr(pool), _ptr(ge))
+    if asset is None:
+        lib.check(fn(*head, *signed, na, acc if na else None, *pooled, out if na else None, verdicts if n else None, C.byref(stats)))
+    else:
+        kinds, asset_ids, next_asset_id = asset
+        if len(kinds) != n or len(asset_ids) != n:
+            raise ValueError("one kind and one asset id per xt")
+        kb = _u8(bytes(ASSET_KINDS.index(k) if isinstance(k, str) else int(k) for k in kinds), n) if n else None
+        ib = np.array([int(v) for v in asset_ids], dtype=np.uint32) if n else None
+        ab = np.array([int(a["asset_id"]) for a in accounts], dtype=np.uint32) if na else None
+        effects, next_out = (_lib.AssetEffect * max(n, 1))(), C.c_uint32(0)
+        lib.check(fn(*head, None if kb is None else _ptr(kb), None if ib is None else _ptr(ib), *signed, na, acc if na else None,
+                     None if ab is None else _ptr(ab), *pooled, int(next_asset_id), out if na else None, verdicts if n else None,
+                     effects if n else None, C.byref(next_out), C.byref(stats)))
 
     def detail(v):
         if v.verdict == 1:
@@ -594,9 +608,14 @@ def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msg
             return (names[(v.detail & 63) - 1], INTO_XY_REASONS[v.detail >> 6])
         return None
     ct = lambda b: (bytes(b[:32]), bytes(b[32:]))
-    return ([(BLOCK_VERDICTS[v.verdict], detail(v)) for v in verdicts[:n]],
-            [dict(enc_key=bytes(o.enc_key), balance=ct(o.balance), pending=ct(o.pending), flags=int(o.flags)) for o in out[:na]],
-            dict(rounds=stats.rounds, proofs_verified=stats.proofs_verified, points_decoded=stats.points_decoded))
+    res = ([(BLOCK_VERDICTS[v.verdict], detail(v)) for v in verdicts[:n]],
+           [dict(enc_key=bytes(o.enc_key), balance=ct(o.balance), pending=ct(o.pending), flags=int(o.flags)) for o in out[:na]],
+           dict(rounds=stats.rounds, proofs_verified=stats.proofs_verified, points_decoded=stats.points_decoded))
+    if asset is None:
+        return res
+    for o, a in zip(res[1], accounts):
+        o["asset_id"] = int(a["asset_id"])
+    return res[:2] + ([dict(asset_id=int(fx.asset_id), first=ct(fx.first), second=ct(fx.second)) for fx in effects[:n]], int(next_out.value)) + res[2:]
 
 
 def execute_confidential_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=None, msgs=None):
@@ -619,6 +638,24 @@ def execute_anonymous_block(pvk, xts, accounts, nonce_pool, g_epoch, sigs=None, 
     ANONYMOUS_XT_POINTS, and stats["rounds"] is never more than 1: the whole block verifies in one batch."""
     arr = _xt_array(xts, _lib.AnonymousXt, _fill_anonymous_xt)
     return _execute_block(pvk, pvk._lib.zk_anonymous_block_execute, arr, ANONYMOUS_XT_POINTS, accounts, nonce_pool, g_epoch, sigs, msgs)
+
+
+ASSET_KINDS = ("transfer", "issue", "destroy")   # ZK_ASSET_*
+BLOCK_TAKEN = 4                                  # flag of an account, out: an accepted destroy took it in this block
+
+
+def execute_asset_block(pvk, xts, kinds, asset_ids, accounts, nonce_pool, g_epoch, next_asset_id, sigs=None, msgs=None):
+    """zk_asset_block_execute = encrypted_assets::issue, confidential_transfer and destroy (modules/encrypted-assets/src/lib.rs:32-83,
+    :86-164, :167-215) for a block of ConfidentialXt in order (include/zkamd.h states the steps of each).  kinds: a name of
+    ASSET_KINDS (or its number) per xt; asset_ids: the id a transfer or destroy names (ignored for an issue); accounts: as
+    execute_confidential_block with an asset_id key - an account is keyed by (asset_id, enc_key); next_asset_id: the id the first
+    accepted issue gets.  Returns (verdicts, accounts_out, effects, next_asset_id, stats): an effect is a dict with asset_id (the
+    id assigned to an accepted issue, the id named by a transfer or destroy), first and second ((left, right): the ciphertext an
+    accepted issue creates; the balance and the pending transfer an accepted destroy took; else zero bytes); accounts_out carry
+    BLOCK_TAKEN where a destroy was accepted."""
+    arr = _xt_array(xts, _lib.ConfidentialXt, _fill_confidential_xt)
+    return _execute_block(pvk, pvk._lib.zk_asset_block_execute, arr, CONFIDENTIAL_XT_POINTS, accounts, nonce_pool, g_epoch, sigs, msgs,
+                          asset=(kinds, asset_ids, next_asset_id))
 
 
 def g_epoch(epoch, lib=None):

@@ -102,6 +102,10 @@ class BlockStats(C.Structure):
     _fields_ = [(n, C.c_uint32) for n in ("rounds", "proofs_verified", "points_decoded", "reserved")]
 
 
+class AssetEffect(C.Structure):
+    _fields_ = [("asset_id", C.c_uint32), ("reserved", C.c_uint32), ("first", C.c_uint8 * 64), ("second", C.c_uint8 * 64)]
+
+
 class ConfidentialScanResult(C.Structure):
     _fields_ = [("role", C.c_uint8), ("found", C.c_uint8), ("refusal", C.c_uint8), ("reserved", C.c_uint8),
                 ("amount_sent", C.c_uint32), ("fee", C.c_uint32), ("amount_received", C.c_uint32)]
@@ -192,6 +196,10 @@ _PROTOS = {
     "zk_anonymous_block_execute": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
                                                C.POINTER(BlockAccount), C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(BlockAccount),
                                                C.POINTER(BlockVerdict), C.POINTER(BlockStats)]),
+    "zk_asset_block_execute": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_size_t, C.POINTER(BlockAccount), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_uint32,
+                                           C.POINTER(BlockAccount), C.POINTER(BlockVerdict), C.POINTER(AssetEffect), C.POINTER(C.c_uint32),
+                                           C.POINTER(BlockStats)]),
     "zk_g_epoch": (C.c_int32, [C.c_uint32, C.c_void_p]),
     "zk_redjubjub_sign": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zk_redjubjub_verify_batch": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),

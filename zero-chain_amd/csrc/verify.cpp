@@ -23,6 +23,7 @@
 #include "ledger.h"
 #include "block_exec.h"
 #include "anon_block_exec.h"
+#include "asset_block_exec.h"
 #include "verify_plan.h"
 
 using namespace zkrt;
@@ -1090,6 +1091,21 @@ zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt*
     return zkblock::execute_anonymous(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool,
                                       nonce_pool, g_epoch, accounts_out, verdicts_out, stats_out);
 } ZK_ABI_CATCH
+zk_status zk_asset_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* kinds, const uint32_t* asset_ids, const uint8_t* sigs,
+                                 const uint8_t* msgs, const uint64_t* msg_offsets, size_t n_accounts, const zk_block_account* accounts,
+                                 const uint32_t* account_asset_ids, size_t n_pool, const uint8_t* nonce_pool, const uint8_t g_epoch[32],
+                                 uint32_t next_asset_id, zk_block_account* accounts_out, zk_block_verdict* verdicts_out, zk_asset_effect* effects_out,
+                                 uint32_t* next_asset_id_out, zk_block_stats* stats_out) try {
+    if (!vk) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (vk->ic.size() != 2 * zkblock::XT_FIELDS + 1) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "the key does not have 22 public inputs");
+    vk->block.is_public = true;
+    auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
+        return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::XT_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
+    };
+    return zkblock::execute_asset(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, kinds, asset_ids, sigs, msgs, msg_offsets, n_accounts,
+                                  accounts, account_asset_ids, n_pool, nonce_pool, g_epoch, next_asset_id, accounts_out, verdicts_out, effects_out,
+                                  next_asset_id_out, stats_out);
+} ZK_ABI_CATCH
 zk_status zk_g_epoch(uint32_t epoch, uint8_t out[32]) try {
     if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     return zkblock::g_epoch(epoch, out);
@@ -1121,6 +1137,12 @@ zk_status zk_hook_verify_plan(size_t n, size_t n_inputs, int own_proofs, int hav
                            p.inputs_mul, (uint64_t)p.pairing, verify_takes_combined(form, n, tun)};
     std::copy(f, f + 9, out);
     return ZK_OK;
+} ZK_ABI_CATCH
+// ... and zk_elgamal_ledger_apply's arguments through the scan that can forget (asset_block_exec.h): flag bit 2 is LEDGER_CLEAR,
+// the four k_asset_* kernels always run
+zk_status zk_hook_ledger_apply_clear(size_t n_slots, const uint8_t* slots, size_t n_ops, const zk_ledger_op* ops, int device, uint8_t* slots_out,
+                                     uint8_t* before_out, uint8_t* slot_status_out, uint8_t* op_status_out) try {
+    return zkblock::apply_clear(n_slots, slots, n_ops, ops, device, slots_out, before_out, slot_status_out, op_status_out);
 } ZK_ABI_CATCH
 #endif
 
