@@ -59,7 +59,11 @@
  *   zk_confidential_scan, zk_anonymous_scan   - (a block read with one decryption key: Ciphertext::decrypt per value,
  *                                   no_std_aliases/elgamal.rs:85-108, and the signs of MultiCiphertexts::<Anonymous>::encrypt,
  *                                   core/proofs/src/crypto_components.rs:168-220)
- *   zk_elgamal_ledger_apply         rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
+ *   zk_scan_keys_create, zk_scan_keys_get, zk_scan_keys_free   - (a set of decryption keys and the encryption key of each:
+ *                                   EncryptionKey::from_decryption_key, no_std_aliases/keys.rs:250-261, once per key)
+ *   zk_confidential_scan_keys, zk_anonymous_scan_keys   - (a block read with every key of such a set in one call: the parts of the
+ *                                   two scans above, keys.rs:250-261, elgamal.rs:85-108, crypto_components.rs:168-220)
+ *   zk_elgamal_ledger_apply        rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
  *                                   modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350,
  *                                   modules/anonymous-balances/src/lib.rs:169-225, core/primitives/src/ciphertext.rs:90-100
  *   zk_transfer_derive              the derivations at the head of gen_proof      confidential.rs:105-133
@@ -512,6 +516,44 @@ zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confident
                                zk_confidential_scan_result* out);
 zk_status zk_anonymous_scan(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                             zk_anonymous_scan_result* out);
+/* The two scans for a SET of decryption keys - an exchange's, a custodian's, an auditor's - in one call.  The reference has no
+ * counterpart; the parts are those of the two scans (keys.rs:250-261, elgamal.rs:85-108, crypto_components.rs:168-220).
+ * zk_scan_keys_create: dec_keys is n_keys x 32 bytes, little-endian, n_keys >= 1.  Every key must be a canonical Fs scalar (else
+ *   ZK_ERR_INVALID_ARGUMENT naming its index) and no two may be equal (else ZK_ERR_INVALID_ARGUMENT naming both indices: a key set
+ *   is a set).  The handle holds the scalars, the 32 canonical bytes of EncryptionKey::from_decryption_key for each - derived
+ *   once, here, on the zk_set_host_threads pool, not per block - and an index from those bytes to the key's number.  Like the
+ *   single-key entries it takes decryption keys alone, so a caller cannot hand over a pair that does not belong together.  It is
+ *   host-only and binds no device.  zk_scan_keys_free wipes the scalars before releasing them (NULL: nothing).
+ * zk_scan_keys_get: the derived encryption keys of keys first .. first + count - 1 (count x 32 bytes); a range outside the set is
+ *   ZK_ERR_INVALID_ARGUMENT.
+ * zk_confidential_scan_keys / zk_anonymous_scan_keys: a hit is a pair (extrinsic i, key k) in which key k's 32 bytes equal
+ *   enc_key_sender or enc_key_recipient of xts[i] (one of the twelve enc_keys for the anonymous scan).  hits_out[h] names the
+ *   pair (xt, key) and r is, byte for byte, what zk_confidential_scan / zk_anonymous_scan writes into out[i] for dec_key k: role
+ *   or members, the found bits, the values or delta, and the refusal byte with its push order.  An extrinsic can be hit by
+ *   several keys: a transfer between two keys of the set gives two hits, a transfer to oneself ONE hit with role 3, a ring up to
+ *   twelve.  Hits are ordered by xt ascending, then key ascending.  Pairs that do not match produce nothing, and nothing of an
+ *   extrinsic without a hit is looked at.
+ *   Matching happens on the host first: with more hits than hits_cap the call fails with ZK_ERR_INVALID_ARGUMENT, *n_hits_out
+ *   holds the number needed, hits_out is untouched and no other work is started.  2 n (confidential) / 12 n (anonymous) always
+ *   suffices.  On success *n_hits_out is the number of hits written; on any other failure it is 0.
+ *   limit and ZKAMD_SCAN_HOST_MAX are those of the single-key entries: up to that many values to decrypt the point work - once
+ *   per HIT: dec_key k * right - runs on the host threads, above it in two kernels on the table's device (csrc/scan_keys.h), whose
+ *   lanes each carry the scalar of their own hit; the bytes written do not depend on the form.  The scalars of the hits, and
+ *   everything derived from them, travel per call: they are wiped on the host and zeroed on the device before the call returns,
+ *   and nothing of the key set stays on the device between calls.  The host form multiplies without branching on a key; the
+ *   device form is NOT constant-time: a zero digit of a lane's scalar skips that lane's addition.
+ *   t == NULL, keys == NULL, n_hits_out == NULL, a NULL xts with n > 0, or a NULL hits_out with hits to write:
+ *   ZK_ERR_INVALID_ARGUMENT ("null argument").  n == 0 sets *n_hits_out = 0 and touches nothing else. */
+typedef struct zk_scan_keys zk_scan_keys;
+zk_status zk_scan_keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_keys** out);
+zk_status zk_scan_keys_get(const zk_scan_keys* k, size_t first, size_t count, uint8_t* enc_keys_out);  /* count x 32 bytes */
+void zk_scan_keys_free(zk_scan_keys* k);
+typedef struct { uint32_t xt, key; zk_confidential_scan_result r; } zk_confidential_scan_hit;  /* 24 bytes */
+typedef struct { uint32_t xt, key; zk_anonymous_scan_result r; } zk_anonymous_scan_hit;        /* 24 bytes */
+zk_status zk_confidential_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n, const zk_confidential_xt* xts,
+                                    uint64_t limit, zk_confidential_scan_hit* hits_out, size_t hits_cap, size_t* n_hits_out);
+zk_status zk_anonymous_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n, const zk_anonymous_xt* xts,
+                                 uint64_t limit, zk_anonymous_scan_hit* hits_out, size_t hits_cap, size_t* n_hits_out);
 zk_status zk_anonymous_gen_proof_batch(zk_params* p, zk_r1cs* circuit, struct zk_vk* vk, size_t n, const zk_anonymous_request* req,
                                        const uint8_t* rs, zk_anonymous_xt* out);
 

@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -933,8 +933,65 @@ def _scan_refusal(v, names):
     return None if not v else (names[(int(v) & 63) - 1], INTO_XY_REASONS[int(v) >> 6])
 
 
+def _confidential_scan_dict(r):
+    return {"role": r.role, "refusal": _scan_refusal(r.refusal, CONFIDENTIAL_XT_POINTS),
+            "amount_sent": r.amount_sent if r.found & SCAN_FOUND_SENT else None, "fee": r.fee if r.found & SCAN_FOUND_FEE else None,
+            "amount_received": r.amount_received if r.found & SCAN_FOUND_RECEIVED else None}
+
+
+def _anonymous_scan_dict(r):
+    return {"members": [k for k in range(ANONYMOUS_SIZE) if r.members >> k & 1], "refusal": _scan_refusal(r.refusal, ANONYMOUS_XT_POINTS),
+            "delta": r.delta if r.found else None}
+
+
 def _points(encodings, n):
     return _u8(b"".join(bytes(e) for e in encodings), 32 * n)
+
+
+class ScanKeys:
+    """zk_scan_keys: a set of decryption keys (Fs integers, no two equal) for ElGamalTable.scan_confidential_keys /
+    scan_anonymous_keys.  The encryption key of each is derived once, here; the handle lives on the host and binds no device."""
+
+    def __init__(self, dec_keys, lib=None):
+        self._lib = lib or _lib.load()
+        self._h = None
+        self._n = len(dec_keys)
+        kb = scalars_to_bytes([int(k) for k in dec_keys])
+        h = C.c_void_p()
+        try:
+            self._lib.check(self._lib.zk_scan_keys_create(_ptr(kb) if kb.size else None, self._n, C.byref(h)))
+        finally:
+            kb[:] = 0   # (the caller's copy of the keys is the caller's)
+        self._h = h
+
+    def __len__(self):
+        return self._n
+
+    def enc_keys(self, first=0, count=None):
+        """zk_scan_keys_get: the 32-byte encryption keys of keys first .. first + count - 1 (all from `first` by default)"""
+        count = max(self._n - first, 0) if count is None else count
+        out = np.zeros(32 * max(count, 1), dtype=np.uint8)
+        self._lib.check(self._lib.zk_scan_keys_get(self._h, int(first), int(count), _ptr(out)))
+        ob = out.tobytes()
+        return [ob[i:i + 32] for i in range(0, 32 * count, 32)]
+
+    def close(self):
+        if self._h:
+            self._lib.zk_scan_keys_free(self._h)
+            self._h = None
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class ElGamalTable:
@@ -992,17 +1049,50 @@ class ElGamalTable:
         or None where no value below `limit` was found or the role does not use it) and refusal (None, or (field name, reason) of
         the first used point that Ciphertext::read refuses; the values are then None).  Proofs and signatures are not looked at."""
         res = self._scan(self._lib.zk_confidential_scan, _lib.ConfidentialXt, _fill_confidential_xt, _lib.ConfidentialScanResult, xts, dec_key, limit)
-        return [{"role": r.role, "refusal": _scan_refusal(r.refusal, CONFIDENTIAL_XT_POINTS),
-                 "amount_sent": r.amount_sent if r.found & SCAN_FOUND_SENT else None, "fee": r.fee if r.found & SCAN_FOUND_FEE else None,
-                 "amount_received": r.amount_received if r.found & SCAN_FOUND_RECEIVED else None} for r in res]
+        return [_confidential_scan_dict(r) for r in res]
 
     def scan_anonymous(self, xts, dec_key, limit=ELGAMAL_DECRYPT_LIMIT):
         """zk_anonymous_scan for accepted AnonymousXt (the dicts anonymous_gen_proofs returns, structures, or raw bytes).  One dict
         per xt: members (the positions of the key among the twelve enc_keys; empty: absent), delta (the sum over them of +amount
         received, -amount sent, 0 as a decoy; None unless every occurrence has a value with |value| < limit) and refusal."""
         res = self._scan(self._lib.zk_anonymous_scan, _lib.AnonymousXt, _fill_anonymous_xt, _lib.AnonymousScanResult, xts, dec_key, limit)
-        return [{"members": [k for k in range(ANONYMOUS_SIZE) if r.members >> k & 1], "refusal": _scan_refusal(r.refusal, ANONYMOUS_XT_POINTS),
-                 "delta": r.delta if r.found else None} for r in res]
+        return [_anonymous_scan_dict(r) for r in res]
+
+    def _scan_keys(self, fn, ctype, fill, hit, per_xt, xts, keys, limit):
+        """the hit array of zk_confidential_scan_keys / zk_anonymous_scan_keys, sized by the entry's own count"""
+        if keys._lib is not self._lib:
+            raise ValueError("the key set and the table belong to different libraries")
+        if isinstance(xts, (bytes, bytearray, memoryview)):
+            raw = bytes(xts)
+            if len(raw) % C.sizeof(ctype):
+                raise ValueError("%d bytes are no whole number of %s" % (len(raw), ctype.__name__))
+            arr = (ctype * (len(raw) // C.sizeof(ctype))).from_buffer_copy(raw)
+        else:
+            arr = _xt_array(xts, ctype, fill)
+        n = len(arr)
+        cap = min(per_xt * n, 4096)   # a guess; the entry says what a fuller block needs before it starts any work
+        while True:
+            out, count = (hit * max(cap, 1))(), C.c_size_t(0)
+            rc = fn(self._h, keys._h, n, arr if n else None, int(limit), out, cap, C.byref(count))
+            if rc != 0 and count.value > cap:
+                cap = count.value
+                continue
+            self._lib.check(rc)
+            return out[:count.value]
+
+    def scan_confidential_keys(self, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_confidential_scan_keys: `xts` as scan_confidential takes them, read with every key of the ScanKeys `keys` in one
+        call.  Returns [(xt, key, dict)] in (xt, key) order: one entry per extrinsic and key of the set that it carries, the dict
+        being scan_confidential's for that key (a transfer between two keys of the set appears twice, one to oneself once with
+        role 3)."""
+        res = self._scan_keys(self._lib.zk_confidential_scan_keys, _lib.ConfidentialXt, _fill_confidential_xt, _lib.ConfidentialScanHit, 2, xts, keys, limit)
+        return [(h.xt, h.key, _confidential_scan_dict(h.r)) for h in res]
+
+    def scan_anonymous_keys(self, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_anonymous_scan_keys: [(xt, key, dict)] in (xt, key) order, the dict being scan_anonymous's for that key; a ring can
+        appear up to twelve times."""
+        res = self._scan_keys(self._lib.zk_anonymous_scan_keys, _lib.AnonymousXt, _fill_anonymous_xt, _lib.AnonymousScanHit, ANONYMOUS_SIZE, xts, keys, limit)
+        return [(h.xt, h.key, _anonymous_scan_dict(h.r)) for h in res]
 
     def close(self):
         if self._h:
@@ -1021,6 +1111,16 @@ class ElGamalTable:
             self.close()
         except Exception:
             pass
+
+
+def scan_confidential_keys(table, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+    """ElGamalTable.scan_confidential_keys of `table`"""
+    return table.scan_confidential_keys(xts, keys, limit)
+
+
+def scan_anonymous_keys(table, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+    """ElGamalTable.scan_anonymous_keys of `table`"""
+    return table.scan_anonymous_keys(xts, keys, limit)
 
 
 def elgamal_add(left_a, right_a, left_b, right_b, subtract=False, lib=None):

@@ -115,6 +115,14 @@ class AnonymousScanResult(C.Structure):
     _fields_ = [("members", C.c_uint16), ("found", C.c_uint8), ("refusal", C.c_uint8), ("reserved", C.c_uint32), ("delta", C.c_int64)]
 
 
+class ConfidentialScanHit(C.Structure):
+    _fields_ = [("xt", C.c_uint32), ("key", C.c_uint32), ("r", ConfidentialScanResult)]
+
+
+class AnonymousScanHit(C.Structure):
+    _fields_ = [("xt", C.c_uint32), ("key", C.c_uint32), ("r", AnonymousScanResult)]
+
+
 class BatchDev(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("n_inputs", C.c_uint32), ("n_aux", C.c_uint32), ("flags", C.c_uint32),
                 ("d_a", C.c_void_p), ("d_b", C.c_void_p), ("d_c", C.c_void_p), ("d_wit", C.c_void_p),
@@ -167,6 +175,13 @@ _PROTOS = {
     "zk_confidential_scan": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_void_p, C.c_uint64,
                                          C.POINTER(ConfidentialScanResult)]),
     "zk_anonymous_scan": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_void_p, C.c_uint64, C.POINTER(AnonymousScanResult)]),
+    "zk_scan_keys_create": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)]),
+    "zk_scan_keys_get": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p]),
+    "zk_scan_keys_free": (None, [C.c_void_p]),
+    "zk_confidential_scan_keys": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(ConfidentialXt), C.c_uint64,
+                                              C.POINTER(ConfidentialScanHit), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "zk_anonymous_scan_keys": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_uint64,
+                                           C.POINTER(AnonymousScanHit), C.c_size_t, C.POINTER(C.c_size_t)]),
     "zk_elgamal_ledger_apply": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LedgerOp), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "zk_transfer_derive": (C.c_int32, [C.POINTER(TransferRequest), C.c_size_t, C.POINTER(TransferStatement), C.c_void_p]),

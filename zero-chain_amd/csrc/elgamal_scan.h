@@ -3,6 +3,8 @@
 // the match, Ciphertext::read (elgamal.rs:116-133) for the points the wallet's role uses, Ciphertext::decrypt (elgamal.rs:85-108)
 // for every value, and the signs of MultiCiphertexts::<Anonymous>::encrypt (crypto_components.rs:168-220).
 // Included by wallet.cpp below redjubjub.h (fs_lt_mod, jubjub_fixed_mul, jubjub_var_mul, jubjub_encode, WipeOnExit, zkrj::ld_fr).
+// The host side below serves a SET of keys as well (scan_keys.h): a match carries the number of its key (always 0 here), the plan,
+// the host form and the slicing are shared, and only the kernel that multiplies differs.
 //
 // The host matches the 32 bytes of the wallet's key against the keys of every extrinsic and gathers, for the matching ones only,
 //   points   every used left half and the right half, in the push order of the verifiers' field numbers
@@ -129,7 +131,34 @@ struct Row {
 struct Match {
     size_t xt;             // index of the extrinsic in the caller's array
     uint32_t pt0, row0;    // its points and rows start here and end where the next match's start
+    uint32_t key;          // the number of the key it matched (0 where the call has one key)
 };
+// The decryption keys of a call: ONE (zk_confidential_scan, zk_anonymous_scan) or a set (scan_keys.h).  A match carries the number
+// of its key, and the point stage multiplies its right half by that key's scalar.
+struct Keys {
+    size_t n;
+    const uint64_t* dk;      // n x 4 words, plain
+    const uint8_t* enc;      // n x 32 bytes: EncryptionKey::from_decryption_key of each
+    const uint32_t* order;   // the key numbers sorted by those bytes (memcmp order); NULL where n == 1
+    const uint64_t* scalar(uint32_t k) const { return dk + 4 * (size_t)k; }
+    // the number of the key whose 32 bytes are b, or -1
+    int64_t find(const uint8_t b[32]) const {
+        if (!order) return memcmp(b, enc, 32) ? -1 : 0;
+        size_t lo = 0, hi = n;
+        while (lo < hi) {
+            const size_t mid = (lo + hi) / 2;
+            const int c = memcmp(enc + 32 * (size_t)order[mid], b, 32);
+            if (c == 0) return order[mid];
+            (c < 0 ? lo : hi) = c < 0 ? mid + 1 : mid;
+        }
+        return -1;
+    }
+};
+// one (key, mask) per key of the call that an extrinsic carries, by key number: mask = role bits (confidential), members (anonymous)
+struct Hit {
+    uint32_t key, mask;
+};
+constexpr size_t MAX_HITS_PER_XT = 12;   // ZK_ANONYMOUS_SIZE keys in a ring, all of the set
 // what one slice of a call decrypts: at most ELGAMAL_SEARCH_BLOCK search rows
 struct Plan {
     std::vector<Match> matches;
@@ -148,7 +177,7 @@ struct Plan {
         what.push_back(w);
         n_search += anon ? 2 : 1;
     }
-    void close() { matches.push_back(Match{(size_t)-1, (uint32_t)points(), (uint32_t)rows.size()}); }   // the end marker
+    void close() { matches.push_back(Match{(size_t)-1, (uint32_t)points(), (uint32_t)rows.size(), 0}); }   // the end marker
 };
 // what the point stage and the search leave: a status per point, a flag per row, a logarithm (or ~0) per search row
 struct Found {
@@ -199,7 +228,7 @@ inline uint8_t read_prime_order(const uint8_t b[32], zkwit::JPoint* out) {
 }
 
 // the host form: the statuses, the flags, and v of every search row into T->v
-inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const uint64_t dk[4], Found* f) {
+inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const Keys& keys, Found* f) {
     const size_t nm = pl.matches.size() - 1;
     std::vector<zkwit::JPoint> v(pl.n_search);
     WipeOnExit wipe_v{v.data(), v.size() * sizeof(zkwit::JPoint)};
@@ -218,7 +247,7 @@ inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const uint6
             for (uint32_t r = a.row0; r < b.row0; r++)
                 f->flags[r] = f->status[pl.rows[r].left] != zkxt::INTO_XY_OK || f->status[pl.rows[r].right_pt] != zkxt::INTO_XY_OK;
             if (!ok) continue;   // a refused extrinsic: its rows stay the neutral element
-            const zkwit::EPoint s = jubjub_var_mul(pts[pl.rows[a.row0].right_pt - a.pt0], dk);
+            const zkwit::EPoint s = jubjub_var_mul(pts[pl.rows[a.row0].right_pt - a.pt0], keys.scalar(a.key));
             const zkwit::EPoint minus_s{zkhost::Fr::zero() - s.X, s.Y, s.Z, zkhost::Fr::zero() - s.T};
             for (uint32_t r = a.row0; r < b.row0; r++) proj[r - r0] = zkwit::ext_add(zkwit::to_ext(pts[pl.rows[r].left - a.pt0]), minus_s);
         }
@@ -236,18 +265,18 @@ inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const uint6
     return ZK_OK;
 }
 
-// the device form: the same three, by the two kernels
-inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const uint64_t dk[4], Found* f) {
+// the device form: the same three, by two kernels.  head: the key-derived bytes the point kernel reads, at the start of scan_key
+// (a multiple of 16; D follows them); launch_points starts that kernel.
+template <class LaunchPoints>
+inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const std::vector<uint8_t>& head, Found* f, LaunchPoints launch_points) {
     const size_t np = pl.points(), p64 = (np + 63) / 64 * 64, nm = pl.matches.size() - 1, nr = pl.rows.size();
-    // scan_in: encodings (padded) | rights | rows.  scan_out: coordinates | statuses | flags.  scan_key: digits | D
-    std::vector<uint8_t> in(p64 * 32 + nm * 32 + nr * 16, 0), digits(DIGITS_BYTES);
-    WipeOnExit wipe_digits{digits.data(), digits.size()};
+    // scan_in: encodings (padded) | rights | rows.  scan_out: coordinates | statuses | flags.  scan_key: head | D
+    std::vector<uint8_t> in(p64 * 32 + nm * 32 + nr * 16, 0);
     memcpy(in.data(), pl.enc.data(), np * 32);
     for (size_t m = 0; m < nm; m++) memcpy(&in[p64 * 32 + m * 32], &pl.enc[(size_t)pl.rows[pl.matches[m].row0].right_pt * 32], 32);
     static_assert(sizeof(Row) == 16, "four words");
     memcpy(&in[p64 * 32 + nm * 32], pl.rows.data(), nr * 16);
-    naf_recode(dk, digits.data());
-    const size_t key_bytes = DIGITS_BYTES + nm * 128;
+    const size_t key_bytes = head.size() + nm * 128;
     ZK_TRY(T->scan_in.ensure(in.size()));
     ZK_TRY(T->scan_out.ensure(np * 68 + nr * 4));
     ZK_TRY(T->scan_key.ensure(key_bytes));
@@ -256,16 +285,11 @@ inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const uin
     const uint32_t *d_right = d_enc + p64 * 8, *d_rows = d_right + nm * 8;
     uint32_t* d_xy = T->scan_out.as<uint32_t>();
     uint32_t *d_status = d_xy + np * 16, *d_flags = d_status + np;
-    const int8_t* d_digits = T->scan_key.as<int8_t>();
-    uint32_t* d_d = T->scan_key.as<uint32_t>() + DIGITS_BYTES / 4;
+    uint32_t* d_d = T->scan_key.as<uint32_t>() + head.size() / 4;
     auto run = [&]() -> zk_status {
         HIP_TRY(hipMemcpyAsync(T->scan_in.p, in.data(), in.size(), hipMemcpyHostToDevice, zkrt::g_stream));
-        HIP_TRY(hipMemcpyAsync(T->scan_key.p, digits.data(), DIGITS_BYTES, hipMemcpyHostToDevice, zkrt::g_stream));
-        {
-            zkrt::ProfScope ps("scan_points");
-            ZK_LAUNCH(k_scan_points, dim3((unsigned)(p64 / 64 + (nm + 63) / 64)), dim3(64), 0, zkrt::g_stream, d_enc, (uint32_t)np, (uint32_t)p64,
-                      d_right, (uint32_t)nm, d_digits, d_xy, d_status, d_d);
-        }
+        HIP_TRY(hipMemcpyAsync(T->scan_key.p, head.data(), head.size(), hipMemcpyHostToDevice, zkrt::g_stream));
+        launch_points(dim3((unsigned)(p64 / 64 + (nm + 63) / 64)), d_enc, (uint32_t)np, (uint32_t)p64, d_right, (uint32_t)nm, T->scan_key.p, d_xy, d_status, d_d);
         HIP_TRY(hipGetLastError());
         {
             zkrt::ProfScope ps("scan_combine");
@@ -282,16 +306,28 @@ inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const uin
         return ZK_OK;
     };
     const zk_status rc = run();
-    if (rc != ZK_OK) {   // the digits, D and v do not stay behind a failure either
+    if (rc != ZK_OK) {   // the head, D and v do not stay behind a failure either
         (void)hipMemsetAsync(T->scan_key.p, 0, key_bytes, zkrt::g_stream);
         (void)hipMemsetAsync(T->v.p, 0, (size_t)pl.n_search * 64, zkrt::g_stream);
         (void)hipStreamSynchronize(zkrt::g_stream);
     }
     return rc;
 }
+// one key: its width-4 NAF, recoded here once per call, and k_scan_points
+inline zk_status points_one_key(zk_elgamal_table* T, const Plan& pl, const Keys& keys, Found* f) {
+    std::vector<uint8_t> digits(DIGITS_BYTES);
+    WipeOnExit wipe_digits{digits.data(), digits.size()};
+    naf_recode(keys.scalar(0), digits.data());
+    return points_on_device(T, pl, digits, f, [](dim3 grid, const uint32_t* enc, uint32_t np, uint32_t p64, const uint32_t* right, uint32_t nm, void* head,
+                                                 uint32_t* xy, uint32_t* status, uint32_t* d) {
+        zkrt::ProfScope ps("scan_points");
+        ZK_LAUNCH(k_scan_points, grid, dim3(64), 0, zkrt::g_stream, enc, np, p64, right, nm, (const int8_t*)head, xy, status, d);
+    });
+}
 
 // one slice: the point stage in the form the row count asks for, then the search over the rows resident in T->v
-inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const uint64_t dk[4], uint64_t limit, Found* f) {
+template <class Device>
+inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const Keys& keys, uint64_t limit, Found* f, Device device) {
     pl.close();
     f->status.assign(pl.points(), 0);
     f->flags.assign(pl.rows.size(), 0);
@@ -299,7 +335,7 @@ inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const uint64_t dk[4
     if (pl.rows.empty()) return ZK_OK;
     const char* e = getenv("ZKAMD_SCAN_HOST_MAX");
     const size_t host_max = e && *e ? (size_t)strtoull(e, nullptr, 10) : HOST_MAX;
-    ZK_TRY(pl.rows.size() <= host_max ? points_on_host(T, pl, dk, f) : points_on_device(T, pl, dk, f));
+    ZK_TRY(pl.rows.size() <= host_max ? points_on_host(T, pl, keys, f) : device(T, pl, keys, f));
     return elgamal_dlog_search_resident(T, pl.n_search, limit, f->x.data());
 }
 // field | status << 6 of the first refused point of match m in push order, or 0
@@ -309,12 +345,121 @@ inline uint8_t refusal_of(const Plan& pl, const Found& f, size_t m) {
     return 0;
 }
 
-// The two entries share everything but how an extrinsic is matched and how its rows are read back:
-//   add(plan, xt, key, index)       pushes the match, its points and its rows when the wallet's key is in xt
-//   finish(plan, found, m, out)     writes the result of match m
-template <class Xt, class Result, class Add, class Finish>
-inline zk_status scan(zk_elgamal_table* t, size_t n, const Xt* xts, const uint8_t dec_key[32], uint64_t limit, Result* out, size_t rows_per_xt,
-                      Add add, Finish finish) {
+// The two kinds of extrinsic share everything but how one is matched and how its rows are read back:
+//   match(xt, keys, hits)            the keys of the call that xt carries, by key number, each with its mask; returns their count
+//   add(plan, xt, index, hit)        pushes the match of one of them, its points and its rows
+//   finish(plan, found, m, limit, out)   writes the result of match m
+struct Confidential {
+    typedef zk_confidential_xt Xt;
+    typedef zk_confidential_scan_result Result;
+    static constexpr size_t ROWS_PER_XT = 3;   // search rows of one extrinsic, over all its matches
+    static size_t match(const Xt& x, const Keys& keys, Hit hits[MAX_HITS_PER_XT]) {
+        const int64_t s = keys.find(x.enc_key_sender), r = keys.find(x.enc_key_recipient);
+        size_t n = 0;
+        if (s >= 0 && s == r) {
+            hits[n++] = Hit{(uint32_t)s, ZK_SCAN_SENDER | ZK_SCAN_RECIPIENT};   // a transfer to oneself
+        } else {
+            if (s >= 0) hits[n++] = Hit{(uint32_t)s, ZK_SCAN_SENDER};
+            if (r >= 0) hits[n++] = Hit{(uint32_t)r, ZK_SCAN_RECIPIENT};
+            if (n == 2 && hits[0].key > hits[1].key) std::swap(hits[0], hits[1]);
+        }
+        return n;
+    }
+    static void add(Plan& pl, const Xt& x, size_t i, const Hit& h) {
+        const bool s = h.mask & ZK_SCAN_SENDER, r = h.mask & ZK_SCAN_RECIPIENT;
+        pl.matches.push_back(Match{i, (uint32_t)pl.points(), (uint32_t)pl.rows.size(), h.key});
+        const uint32_t ls = s ? pl.point(x.left_amount_sender, F_LEFT_AMOUNT_SENDER) : 0, lr = r ? pl.point(x.left_amount_recipient, F_LEFT_AMOUNT_RECIPIENT) : 0;
+        const uint32_t right = pl.point(x.right_randomness, F_RIGHT_RANDOMNESS), lf = s ? pl.point(x.left_fee, F_LEFT_FEE) : 0;
+        if (s) pl.row(ls, right, ZK_SCAN_FOUND_SENT, false);
+        if (s) pl.row(lf, right, ZK_SCAN_FOUND_FEE, false);
+        if (r) pl.row(lr, right, ZK_SCAN_FOUND_RECEIVED, false);
+    }
+    static void finish(const Plan& pl, const Found& f, size_t m, uint64_t limit, Result* o) {
+        const Match &a = pl.matches[m], &b = pl.matches[m + 1];
+        for (uint32_t r = a.row0; r < b.row0; r++) o->role |= pl.what[r] == ZK_SCAN_FOUND_RECEIVED ? ZK_SCAN_RECIPIENT : ZK_SCAN_SENDER;
+        if ((o->refusal = refusal_of(pl, f, m)) != 0) return;
+        for (uint32_t r = a.row0; r < b.row0; r++) {
+            const uint64_t x = f.x[pl.rows[r].out];
+            if (f.flags[r] || x >= limit) continue;   // (the search reports ~0 for none)
+            o->found |= pl.what[r];
+            (pl.what[r] == ZK_SCAN_FOUND_SENT ? o->amount_sent : pl.what[r] == ZK_SCAN_FOUND_FEE ? o->fee : o->amount_received) = (uint32_t)x;
+        }
+    }
+};
+struct Anonymous {
+    typedef zk_anonymous_xt Xt;
+    typedef zk_anonymous_scan_result Result;
+    static constexpr size_t ROWS_PER_XT = 2 * ZK_ANONYMOUS_SIZE;
+    static_assert(ZK_ANONYMOUS_SIZE <= MAX_HITS_PER_XT, "one hit per member at the most");
+    static size_t match(const Xt& x, const Keys& keys, Hit hits[MAX_HITS_PER_XT]) {
+        size_t n = 0;
+        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++) {
+            const int64_t key = keys.find(x.enc_keys[k]);
+            if (key < 0) continue;
+            size_t at = 0;
+            while (at < n && hits[at].key < (uint32_t)key) at++;
+            if (at == n || hits[at].key != (uint32_t)key) {
+                for (size_t j = n++; j > at; j--) hits[j] = hits[j - 1];
+                hits[at] = Hit{(uint32_t)key, 0};
+            }
+            hits[at].mask |= 1u << k;
+        }
+        return n;
+    }
+    static void add(Plan& pl, const Xt& x, size_t i, const Hit& h) {
+        const uint32_t members = h.mask;
+        pl.matches.push_back(Match{i, (uint32_t)pl.points(), (uint32_t)pl.rows.size(), h.key});
+        uint32_t left[ZK_ANONYMOUS_SIZE];
+        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++)
+            if (members >> k & 1) left[k] = pl.point(x.left_ciphertexts[k], (uint8_t)(F_LEFT_CIPHERTEXTS + k));
+        const uint32_t right = pl.point(x.right_ciphertext, F_RIGHT_CIPHERTEXT);
+        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++)
+            if (members >> k & 1) pl.row(left[k], right, (uint8_t)k, true);
+    }
+    static void finish(const Plan& pl, const Found& f, size_t m, uint64_t limit, Result* o) {
+        const Match &a = pl.matches[m], &b = pl.matches[m + 1];
+        for (uint32_t r = a.row0; r < b.row0; r++) o->members |= (uint16_t)(1u << pl.what[r]);
+        if ((o->refusal = refusal_of(pl, f, m)) != 0) return;
+        int64_t delta = 0;
+        for (uint32_t r = a.row0; r < b.row0; r++) {
+            const uint32_t s = pl.rows[r].out & ~ROW_ANON;
+            const uint64_t plus = f.x[s], minus = f.x[s + 1];   // x G == v, x G == -v (both for x = 0)
+            if (f.flags[r] || (plus >= limit && minus >= limit)) return;   // one occurrence without a value: found stays 0
+            delta += plus < limit ? (int64_t)plus : -(int64_t)minus;
+        }
+        o->found = 1;
+        o->delta = delta;
+    }
+};
+
+// Every match of the block, slice by slice (at most ELGAMAL_SEARCH_BLOCK search rows each):
+//   device(T, plan, keys, found)     the device form of the point stage
+//   slot(h, xt, key)                 where the result of match h - counted over the whole call, in (xt, key) order - goes; zeroed
+template <class Kind, class Device, class Slot>
+inline zk_status run(zk_elgamal_table* t, const Keys& keys, size_t n, const typename Kind::Xt* xts, uint64_t limit, Device device, Slot slot) {
+    Plan pl;
+    Found f;
+    size_t done = 0;
+    auto flush = [&]() -> zk_status {
+        ZK_TRY(decrypt_plan(t, pl, keys, limit, &f, device));
+        for (size_t m = 0; m + 1 < pl.matches.size(); m++) Kind::finish(pl, f, m, limit, slot(done + m, pl.matches[m].xt, pl.matches[m].key));
+        done += pl.matches.size() - 1;
+        f.wipe();
+        pl = Plan();
+        return ZK_OK;
+    };
+    Hit hits[MAX_HITS_PER_XT];
+    for (size_t i = 0; i < n; i++) {
+        if (pl.n_search + Kind::ROWS_PER_XT > ELGAMAL_SEARCH_BLOCK) ZK_TRY(flush());
+        const size_t nh = Kind::match(xts[i], keys, hits);
+        for (size_t h = 0; h < nh; h++) Kind::add(pl, xts[i], i, hits[h]);
+    }
+    return flush();
+}
+
+// one key: out[i] is the result of extrinsic i, all zero where it does not carry the key
+template <class Kind>
+inline zk_status scan(zk_elgamal_table* t, size_t n, const typename Kind::Xt* xts, const uint8_t dec_key[32], uint64_t limit, typename Kind::Result* out) {
     if (!t || (n && (!xts || !dec_key || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (limit == 0 || limit > (1ull << 32)) return fail(ZK_ERR_INVALID_ARGUMENT, "limit must be 1 .. 2^32");
     if (n == 0) return ZK_OK;
@@ -328,78 +473,18 @@ inline zk_status scan(zk_elgamal_table* t, size_t n, const Xt* xts, const uint8_
         const zkwit::JPoint pk = jubjub_fixed_mul(dk);   // EncryptionKey::from_decryption_key
         jubjub_encode(pk.x, pk.y, key);
     }
-    memset(out, 0, n * sizeof(Result));
-    Plan pl;
-    Found f;
-    auto flush = [&]() -> zk_status {
-        ZK_TRY(decrypt_plan(t, pl, dk, limit, &f));
-        for (size_t m = 0; m + 1 < pl.matches.size(); m++) finish(pl, f, m, &out[pl.matches[m].xt]);
-        f.wipe();
-        pl = Plan();
-        return ZK_OK;
-    };
-    for (size_t i = 0; i < n; i++) {
-        if (pl.n_search + rows_per_xt > ELGAMAL_SEARCH_BLOCK) ZK_TRY(flush());
-        add(pl, xts[i], key, i);
-    }
-    return flush();
+    memset(out, 0, n * sizeof(typename Kind::Result));
+    return run<Kind>(t, Keys{1, dk, key, nullptr}, n, xts, limit, points_one_key, [out](size_t, size_t xt, uint32_t) { return &out[xt]; });
 }
 
 inline zk_status confidential(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                               zk_confidential_scan_result* out) {
-    auto add = [](Plan& pl, const zk_confidential_xt& x, const uint8_t key[32], size_t i) {
-        const bool s = !memcmp(x.enc_key_sender, key, 32), r = !memcmp(x.enc_key_recipient, key, 32);
-        if (!s && !r) return;
-        pl.matches.push_back(Match{i, (uint32_t)pl.points(), (uint32_t)pl.rows.size()});
-        const uint32_t ls = s ? pl.point(x.left_amount_sender, F_LEFT_AMOUNT_SENDER) : 0, lr = r ? pl.point(x.left_amount_recipient, F_LEFT_AMOUNT_RECIPIENT) : 0;
-        const uint32_t right = pl.point(x.right_randomness, F_RIGHT_RANDOMNESS), lf = s ? pl.point(x.left_fee, F_LEFT_FEE) : 0;
-        if (s) pl.row(ls, right, ZK_SCAN_FOUND_SENT, false);
-        if (s) pl.row(lf, right, ZK_SCAN_FOUND_FEE, false);
-        if (r) pl.row(lr, right, ZK_SCAN_FOUND_RECEIVED, false);
-    };
-    auto finish = [limit](const Plan& pl, const Found& f, size_t m, zk_confidential_scan_result* o) {
-        const Match &a = pl.matches[m], &b = pl.matches[m + 1];
-        for (uint32_t r = a.row0; r < b.row0; r++) o->role |= pl.what[r] == ZK_SCAN_FOUND_RECEIVED ? ZK_SCAN_RECIPIENT : ZK_SCAN_SENDER;
-        if ((o->refusal = refusal_of(pl, f, m)) != 0) return;
-        for (uint32_t r = a.row0; r < b.row0; r++) {
-            const uint64_t x = f.x[pl.rows[r].out];
-            if (f.flags[r] || x >= limit) continue;   // (the search reports ~0 for none)
-            o->found |= pl.what[r];
-            (pl.what[r] == ZK_SCAN_FOUND_SENT ? o->amount_sent : pl.what[r] == ZK_SCAN_FOUND_FEE ? o->fee : o->amount_received) = (uint32_t)x;
-        }
-    };
-    return scan(t, n, xts, dec_key, limit, out, 3, add, finish);
+    return scan<Confidential>(t, n, xts, dec_key, limit, out);
 }
 
 inline zk_status anonymous(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                            zk_anonymous_scan_result* out) {
-    auto add = [](Plan& pl, const zk_anonymous_xt& x, const uint8_t key[32], size_t i) {
-        uint32_t members = 0;
-        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++) members |= (uint32_t)!memcmp(x.enc_keys[k], key, 32) << k;
-        if (!members) return;
-        pl.matches.push_back(Match{i, (uint32_t)pl.points(), (uint32_t)pl.rows.size()});
-        uint32_t left[ZK_ANONYMOUS_SIZE];
-        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++)
-            if (members >> k & 1) left[k] = pl.point(x.left_ciphertexts[k], (uint8_t)(F_LEFT_CIPHERTEXTS + k));
-        const uint32_t right = pl.point(x.right_ciphertext, F_RIGHT_CIPHERTEXT);
-        for (uint32_t k = 0; k < ZK_ANONYMOUS_SIZE; k++)
-            if (members >> k & 1) pl.row(left[k], right, (uint8_t)k, true);
-    };
-    auto finish = [limit](const Plan& pl, const Found& f, size_t m, zk_anonymous_scan_result* o) {
-        const Match &a = pl.matches[m], &b = pl.matches[m + 1];
-        for (uint32_t r = a.row0; r < b.row0; r++) o->members |= (uint16_t)(1u << pl.what[r]);
-        if ((o->refusal = refusal_of(pl, f, m)) != 0) return;
-        int64_t delta = 0;
-        for (uint32_t r = a.row0; r < b.row0; r++) {
-            const uint32_t s = pl.rows[r].out & ~ROW_ANON;
-            const uint64_t plus = f.x[s], minus = f.x[s + 1];   // x G == v, x G == -v (both for x = 0)
-            if (f.flags[r] || (plus >= limit && minus >= limit)) return;   // one occurrence without a value: found stays 0
-            delta += plus < limit ? (int64_t)plus : -(int64_t)minus;
-        }
-        o->found = 1;
-        o->delta = delta;
-    };
-    return scan(t, n, xts, dec_key, limit, out, 2 * ZK_ANONYMOUS_SIZE, add, finish);
+    return scan<Anonymous>(t, n, xts, dec_key, limit, out);
 }
 
 }  // namespace zkscan

@@ -79,7 +79,8 @@ struct zk_elgamal_table {
     // key-derived (left - dk right, the search's points, the logarithms): zeroed before release
     zkrt::DevBuf v, scratch, res;
     // the point stage of zk_confidential_scan / zk_anonymous_scan (elgamal_scan.h).  Public chain data: the encodings and the
-    // rows that pair them | their coordinates, statuses and the rows' flags.  Key-derived: the digits of dk and dk * right
+    // rows that pair them | their coordinates, statuses and the rows' flags.  Key-derived: the digits of dk (scan_keys.h: the
+    // scalar of every hit) and dk * right
     zkrt::DevBuf scan_in, scan_out, scan_key;
     zk_elgamal_table() {
         consts.is_public = baby_xy.is_public = slots.is_public = giant_xy.is_public = scan_in.is_public = scan_out.is_public = true;

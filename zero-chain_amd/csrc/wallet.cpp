@@ -244,6 +244,7 @@ zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_s
 
 #include "redjubjub.h"   // (here: it signs and hashes with the helpers above)
 #include "elgamal_scan.h"   // (and the scan decodes, multiplies and wipes with them)
+#include "scan_keys.h"      // (the same scan for a set of keys: a scalar per hit)
 
 extern "C" {
 
@@ -430,6 +431,28 @@ zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confident
 zk_status zk_anonymous_scan(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                             zk_anonymous_scan_result* out) try {
     return zkscan::anonymous(t, n, xts, dec_key, limit, out);
+} ZK_ABI_CATCH
+
+zk_status zk_scan_keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_keys** out) try {
+    return zkscan::keys_create(dec_keys, n_keys, out);
+} ZK_ABI_CATCH
+
+zk_status zk_scan_keys_get(const zk_scan_keys* k, size_t first, size_t count, uint8_t* enc_keys_out) try {
+    return zkscan::keys_get(k, first, count, enc_keys_out);
+} ZK_ABI_CATCH
+
+void zk_scan_keys_free(zk_scan_keys* k) {
+    delete k;   // (the scalars are wiped by the destructor)
+}
+
+zk_status zk_confidential_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n, const zk_confidential_xt* xts, uint64_t limit,
+                                    zk_confidential_scan_hit* hits_out, size_t hits_cap, size_t* n_hits_out) try {
+    return zkscan::scan_keys<zkscan::Confidential>(t, keys, n, xts, limit, hits_out, hits_cap, n_hits_out);
+} ZK_ABI_CATCH
+
+zk_status zk_anonymous_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n, const zk_anonymous_xt* xts, uint64_t limit,
+                                 zk_anonymous_scan_hit* hits_out, size_t hits_cap, size_t* n_hits_out) try {
+    return zkscan::scan_keys<zkscan::Anonymous>(t, keys, n, xts, limit, hits_out, hits_cap, n_hits_out);
 } ZK_ABI_CATCH
 
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
