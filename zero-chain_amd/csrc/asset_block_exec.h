@@ -2,8 +2,7 @@
 //   modules/encrypted-assets/src/lib.rs - issue (:32-83), confidential_transfer (:86-164), destroy (:167-215) - do to storage for
 //   every extrinsic of a block in order, with the reference's verdict for each, the accounts to store, the ids assigned and
 //   the ciphertexts an issue creates and a destroy takes.
-// The parts are those of block_exec.h (Keys32, Carve, Op, k_block_gather, the rounds) and k_into_xy, unchanged.  What this header
-// adds:
+// The frame is block_frame.h's, a transfer's encodings, field table and ops are block_exec.h's.  What is this module's:
 //   1. A scan that can FORGET.  destroy `take`s both stored ciphertexts: a slot's value after it is nothing plus the later ops,
 //      whatever it held.  The ledger's segmented scan can only add, so an op flag LEDGER_CLEAR joins the two public ones (it
 //      is internal: zk_elgamal_ledger_apply still refuses the bit).  A live CLEAR - neither skipped nor refused - adds nothing
@@ -35,9 +34,8 @@
 //      precedes a transfer from its account.
 //   4. Asset ids are assigned in one pass over the final verdicts.  Nothing in the call depends on them: an account, transfer
 //      or destroy with an id this call may assign is an argument error.
-// Two forms, the same bytes: up to ZKAMD_INTO_XY_HOST_MAX distinct encodings (read per call) the point work is a sequential walk
-// over the ops in extended coordinates on the host; the verification always runs on the key's device.
-// Only verify.cpp includes this header.  The data is public chain state: nothing here is constant-time.
+//   5. The host form is a sequential walk over the ops in extended coordinates (host_walk) under the skip bits as they stand -
+//      a CLEAR forgets, so the frame's per-account sums do not serve - and the effects: what an issue creates, a destroy takes.
 #pragma once
 #include <unordered_map>
 #include "block_exec.h"
@@ -248,11 +246,9 @@ k_asset_balance_xy(const uint32_t* xy, const uint32_t* st, const uint32_t* off, 
 }
 
 // ---- host side
-// the device pointers the scan and its consumers share
-struct AssetScanBufs {
-    const uint32_t *lxy, *lst, *off, *perm, *pos, *slotv, *flagv, *cstart;
-    uint32_t *pre, *tot, *agg, *carry, *cut, *cut_carry;
-    uint32_t n_slots, n_ops, n_blocks;
+// the device pointers the scan and its consumers share: the ledger's, and the cut words
+struct AssetScanBufs : zkledger::ScanBufs {
+    uint32_t *cut, *cut_carry;
 };
 inline zk_status asset_scan(const AssetScanBufs& B) {
     if (!B.n_blocks) return ZK_OK;
@@ -294,7 +290,7 @@ inline zk_status apply_clear(size_t n_slots, const uint8_t* slots, size_t n_ops,
     std::vector<uint8_t> pts(np * 32);
     if (n_slots) memcpy(pts.data(), slots, n_slots * 64);
     for (size_t i = 0; i < n_ops; i++) memcpy(&pts[(n_slots + i) * 64], ops[i].left, 64);
-    const zkledger::Grouping g(n_slots, n_ops, ops);
+    const zkledger::Grouping g(n_slots, n_ops, [&](size_t i) { return ops[i].slot; });
     Carve mc, wc;   // behind the encodings: the grouping; behind the statuses: what the kernels write
     const size_t m_off = mc.take(n_slots + 1), m_perm = mc.take(n_ops), m_pos = mc.take(n_ops), m_slotv = mc.take(n_ops), m_flagv = mc.take(n_ops),
                  m_cstart = mc.take(n_blocks), m_opv = mc.take(n_rows);
@@ -312,18 +308,16 @@ inline zk_status apply_clear(size_t n_slots, const uint8_t* slots, size_t n_ops,
         m[m_slotv + i] = ops[i].slot;
         m[m_flagv + i] = ops[i].flags;
     }
-    for (size_t b = 0, h = 0; b < n_blocks; b++) {
-        const size_t lastj = std::min(n_ops, (b + 1) * LEDGER_SCAN_W) - 1;
-        if (g.off[ops[g.perm[lastj]].slot] >= b * LEDGER_SCAN_W) h = b;
-        m[m_cstart + b] = (uint32_t)h;
-    }
+    std::copy(g.cstart.begin(), g.cstart.end(), m + m_cstart);
     for (size_t i = 0; i < n_rows; i++) m[m_opv + i] = (uint32_t)i;
     uint32_t* d_meta = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(bufs.in.p) + (np * 32 + 15) / 16 * 16);
     HIP_TRY(hipMemcpyAsync(d_meta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, zkrt::g_stream));
     const uint32_t *d_xy = bufs.out.as<const uint32_t>(), *d_st = d_xy + np * 16;
     uint32_t* dw = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(bufs.out.p) + (zkxt::into_xy_out_bytes(np) + 15) / 16 * 16);
-    const AssetScanBufs B{d_xy, d_st, d_meta + m_off, d_meta + m_perm, d_meta + m_pos, d_meta + m_slotv, d_meta + m_flagv, d_meta + m_cstart,
-                          dw + w_pre, dw + w_tot, dw + w_agg, dw + w_carry, dw + w_cut, dw + w_ccut, (uint32_t)n_slots, (uint32_t)n_ops, (uint32_t)n_blocks};
+    const AssetScanBufs B{{d_xy, d_st, d_meta + m_off, d_meta + m_perm, d_meta + m_pos, d_meta + m_slotv, d_meta + m_flagv, d_meta + m_cstart, dw + w_pre,
+                           dw + w_tot, dw + w_agg, dw + w_carry, (uint32_t)n_slots, (uint32_t)n_ops, (uint32_t)n_blocks},
+                          dw + w_cut,
+                          dw + w_ccut};
     ZK_TRY(asset_scan(B));
     asset_encode(B, nullptr, n_out, dw + w_enc);
     if (n_rows) asset_balance_xy(B, d_meta + m_opv, n_rows, dw + w_rows);
@@ -360,13 +354,11 @@ inline void canonical32(const uint8_t* e, uint8_t out[32]) {
 
 // verify(n_v, proofs, inputs, ok): zkrt::verify_batch on the key with 22 inputs (verify.cpp hands it in)
 template <class Verify>
-inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBuf* work, zkrt::PinBuf* pin, Verify&& verify, size_t n, const zk_confidential_xt* xts,
-                               const uint8_t* kinds, const uint32_t* asset_ids, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_offsets, size_t n_acc,
-                               const zk_block_account* accounts, const uint32_t* account_asset_ids, size_t n_pool, const uint8_t* nonce_pool,
-                               const uint8_t* g_epoch, uint32_t next_asset_id, zk_block_account* accounts_out, zk_block_verdict* verdicts_out,
-                               zk_asset_effect* effects_out, uint32_t* next_asset_id_out, zk_block_stats* stats_out) {
-    if ((n && (!xts || !kinds || !asset_ids || !verdicts_out || !effects_out || !g_epoch)) || (n_acc && (!accounts || !account_asset_ids || !accounts_out)) ||
-        (n_pool && !nonce_pool) || (n && sigs && !msg_offsets) || !next_asset_id_out)
+inline zk_status execute_asset(const BlockArgs& A, Verify&& verify, const zk_confidential_xt* xts, const uint8_t* kinds, const uint32_t* asset_ids,
+                               const uint32_t* account_asset_ids, uint32_t next_asset_id, zk_asset_effect* effects_out, uint32_t* next_asset_id_out) {
+    const size_t n = A.n, n_acc = A.n_acc;
+    const zk_block_account* accounts = A.accounts;
+    if (null_args(A, xts) || (n && (!kinds || !asset_ids || !effects_out)) || (n_acc && !account_asset_ids) || !next_asset_id_out)
         return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n > (size_t)1 << 24 || n_acc > (size_t)1 << 24) return fail(ZK_ERR_INVALID_ARGUMENT, "more than 2^24 extrinsics or accounts in one call");
     uint64_t n_issue = 0;
@@ -406,199 +398,79 @@ inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBu
         acc_r[i] = find_acc(asset_ids[i], xts[i].enc_key_recipient);
         if (acc_r[i] == NO_POINT) return fail(ZK_ERR_INVALID_ARGUMENT, "extrinsic " + std::to_string(i) + ": the asset id and the recipient's key are not among the accounts");
     }
-    if (sigs)
-        for (size_t i = 0; i < n; i++) {
-            if (msg_offsets[i + 1] < msg_offsets[i]) return fail(ZK_ERR_INVALID_ARGUMENT, "msg_offsets decrease at " + std::to_string(i));
-            if (msg_offsets[i + 1] > msg_offsets[i] && !msgs) return fail(ZK_ERR_INVALID_ARGUMENT, "msgs is null but message " + std::to_string(i) + " is not empty");
-        }
-    zk_block_stats stats = {0, 0, 0, 0};
+    ZK_TRY(check_messages(A));
     if (!n) {
-        if (n_acc) memcpy(accounts_out, accounts, n_acc * sizeof(zk_block_account));
+        empty_block(A);
         *next_asset_id_out = next_asset_id;
-        if (stats_out) *stats_out = stats;
         return ZK_OK;
     }
-    // ---- 1. the distinct encodings: eight per extrinsic, the halves of enc_balance of an issue or destroy, four per account, g_epoch
-    Keys32 D(n * (XT_POINTS + 2) + n_acc * 4 + 1);
-    std::vector<uint32_t> xp(n * XT_POINTS), eb(n * 2, NO_POINT), ap(n_acc * 4);
+    // ---- 1. the distinct encodings: a transfer's eight per extrinsic, and the halves of enc_balance of an issue or destroy
+    Decoded P(n * (XT_POINTS + 2) + n_acc * 4 + 1);
+    std::vector<uint32_t> xp(n * XT_POINTS), eb(n * 2, NO_POINT);
     size_t n_destroy = 0;
     for (size_t i = 0; i < n; i++) {
-        const zk_confidential_xt& x = xts[i];
-        const uint8_t* f[XT_POINTS] = {x.enc_key_sender, x.enc_key_recipient, x.left_amount_sender, x.left_amount_recipient,
-                                       x.right_randomness, x.left_fee, x.rvk, x.nonce};
-        for (uint32_t k = 0; k < XT_POINTS; k++) xp[i * XT_POINTS + k] = D.put(f[k]);
+        transfer_points(xts[i], &P.D, &xp[i * XT_POINTS]);
         if (kinds[i] == ZK_ASSET_TRANSFER) continue;
-        eb[2 * i] = D.put(x.enc_balance);
-        eb[2 * i + 1] = D.put(x.enc_balance + 32);
+        eb[2 * i] = P.D.put(xts[i].enc_balance);
+        eb[2 * i + 1] = P.D.put(xts[i].enc_balance + 32);
         n_destroy += kinds[i] == ZK_ASSET_DESTROY;
     }
-    for (size_t a = 0; a < n_acc; a++)
-        for (int k = 0; k < 2; k++) {
-            ap[a * 4 + k] = D.put(accounts[a].balance + 32 * k);
-            ap[a * 4 + 2 + k] = D.put(accounts[a].pending + 32 * k);
-        }
-    const uint32_t ge = D.put(g_epoch);
-    const size_t nd = D.size();
-    stats.points_decoded = (uint32_t)nd;
-    const char* e = getenv("ZKAMD_INTO_XY_HOST_MAX");
-    const size_t host_max = e && *e ? (size_t)strtoull(e, nullptr, 10) : zkxt::INTO_XY_HOST_MAX;
-    const bool on_host = nd <= host_max;
-    ZK_TRY(zkrt::use_device(device));
-    std::vector<uint32_t> dst(nd);
-    std::vector<zkwit::JPoint> hpt;
-    if (on_host) {
-        hpt.resize(nd);
-        const unsigned nth = zkrt::host_threads(nd, 64);
-        auto decode = [&](unsigned t) {
-            for (size_t p = nd * t / nth; p < nd * (t + 1) / nth; p++) {
-                uint8_t xy[64];
-                dst[p] = zkxt::into_xy_one(&D.enc[p * 32], xy);
-                zkhost::Fr x, y;
-                memcpy(x.l, xy, 32);
-                memcpy(y.l, xy + 32, 32);
-                hpt[p] = zkwit::JPoint{x.to_mont(), y.to_mont()};
-            }
-        };
-        zkrt::run_threads(nth, decode);
-    } else {
-        ZK_TRY(zkxt::into_xy_on_device(D.enc.data(), nd, xybufs, 0, 0));
-    }
+    collect_accounts(A, &P);
+    ZK_TRY(decode(A, &P, 0));
+    const std::vector<uint32_t>& ap = P.ap;
     // ---- 2. slots and ops, while the decoder runs: the order of the ops depends on no verdict
-    const size_t n_slots = 2 * n_acc;
     std::vector<Op> ops;
     ops.reserve(4 * n + 2 * n_acc);
     std::vector<uint32_t> first_op(n, NO_POINT), roll_op(n_acc, NO_POINT);   // first_op: a transfer's first subtraction, a destroy's first CLEAR
+    std::vector<uint32_t> destroy_at(n, NO_POINT), listv;   // the place of a destroy among the destroys: its two CLEARs are listed for the encoder
     for (size_t i = 0; i < n; i++) {
         if (kinds[i] == ZK_ASSET_ISSUE) continue;
-        first_op[i] = (uint32_t)ops.size();
         const uint32_t s = acc_s[i];
-        if (kinds[i] == ZK_ASSET_DESTROY) {   // (the points of a CLEAR are read and judged like any op's: the account's own balance)
-            ops.push_back(Op{2 * s, LEDGER_CLEAR | LEDGER_SKIP, ap[s * 4], ap[s * 4 + 1]});
-            ops.push_back(Op{2 * s + 1, LEDGER_CLEAR | LEDGER_SKIP, ap[s * 4], ap[s * 4 + 1]});
+        if (kinds[i] == ZK_ASSET_TRANSFER) {
+            push_rollover(A, P, s, &roll_op, &ops);
+            push_rollover(A, P, acc_r[i], &roll_op, &ops);
+            first_op[i] = (uint32_t)ops.size();
+            push_transfer(s, acc_r[i], &xp[i * XT_POINTS], &ops);
             continue;
         }
-        const uint32_t two[2] = {s, acc_r[i]};
-        for (int k = 0; k < 2; k++) {
-            const uint32_t a = two[k];
-            if (!(accounts[a].flags & ZK_BLOCK_ROLLOVER_DUE) || roll_op[a] != NO_POINT) continue;
-            roll_op[a] = (uint32_t)ops.size();
-            ops.push_back(Op{2 * a, 0, ap[a * 4 + 2], ap[a * 4 + 3]});
-            ops.push_back(Op{2 * a + 1, LEDGER_SUB, ap[a * 4 + 2], ap[a * 4 + 3]});
-        }
-        const uint32_t* p = &xp[i * XT_POINTS];
-        first_op[i] = (uint32_t)ops.size();
-        ops.push_back(Op{2 * s, LEDGER_SUB | LEDGER_SKIP, p[P_AMOUNT_SENDER], p[P_RANDOMNESS]});
-        ops.push_back(Op{2 * s, LEDGER_SUB | LEDGER_SKIP, p[P_FEE], p[P_RANDOMNESS]});
-        ops.push_back(Op{2 * acc_r[i] + 1, LEDGER_SKIP, p[P_AMOUNT_RECIPIENT], p[P_RANDOMNESS]});
+        first_op[i] = (uint32_t)ops.size();   // (the points of a CLEAR are read and judged like any op's: the account's own balance)
+        ops.push_back(Op{2 * s, LEDGER_CLEAR | LEDGER_SKIP, ap[s * 4], ap[s * 4 + 1]});
+        ops.push_back(Op{2 * s + 1, LEDGER_CLEAR | LEDGER_SKIP, ap[s * 4], ap[s * 4 + 1]});
+        destroy_at[i] = (uint32_t)(listv.size() / 2);
+        listv.push_back(first_op[i]);
+        listv.push_back(first_op[i] + 1);
     }
-    const size_t n_ops = ops.size(), np = 2 * (n_slots + n_ops), n_blocks = (n_ops + LEDGER_SCAN_W - 1) / LEDGER_SCAN_W;
-    std::vector<uint32_t> off(n_slots + 1, 0), perm(n_ops), pos(n_ops), cstart(n_blocks), listv;
-    {
-        for (size_t j = 0; j < n_ops; j++) off[ops[j].slot + 1]++;
-        for (size_t s = 0; s < n_slots; s++) off[s + 1] += off[s];
-        std::vector<uint32_t> at(off.begin(), off.end() - 1);
-        for (size_t j = 0; j < n_ops; j++) {
-            pos[j] = at[ops[j].slot]++;
-            perm[pos[j]] = (uint32_t)j;
-        }
-        for (size_t b = 0, h = 0; b < n_blocks; b++) {
-            const size_t lastj = std::min(n_ops, (b + 1) * LEDGER_SCAN_W) - 1;
-            if (off[ops[perm[lastj]].slot] >= b * LEDGER_SCAN_W) h = b;
-            cstart[b] = (uint32_t)h;
-        }
-    }
-    std::vector<uint32_t> destroy_at(n, NO_POINT);   // the place of a destroy among the destroys: its two CLEARs are listed for the encoder
-    for (size_t i = 0; i < n; i++)
-        if (kinds[i] == ZK_ASSET_DESTROY) {
-            destroy_at[i] = (uint32_t)(listv.size() / 2);
-            listv.push_back(first_op[i]);
-            listv.push_back(first_op[i] + 1);
-        }
-    // ---- the device form's workspace and the layout the scan's kernels read
-    Carve cv;
-    const size_t w_lxy = cv.take(np * 16), w_lst = cv.take(np), w_src = cv.take(np), w_off = cv.take(n_slots + 1), w_perm = cv.take(n_ops),
-                 w_pos = cv.take(n_ops), w_slotv = cv.take(n_ops), w_list = cv.take(2 * n_destroy), w_flagv = cv.take(n_ops), w_cstart = cv.take(n_blocks),
-                 w_pre = cv.take(2 * n_ops * 32), w_tot = cv.take(2 * n_slots * 32), w_agg = cv.take(2 * n_blocks * 32),
-                 w_carry = cv.take(2 * n_blocks * 32), w_cut = cv.take(n_ops + n_slots + n_blocks), w_ccut = cv.take(n_blocks),
-                 w_enc = cv.take((2 * n_slots + 4 * n_destroy) * 8), w_vsrc = cv.take(n * XT_FIELDS), w_opv = cv.take(n),
-                 w_inputs = cv.take(n * XT_INPUT_WORDS);
-    uint32_t* dw = nullptr;
-    const uint32_t *d_xy = nullptr, *d_st = nullptr;
-    AssetScanBufs B{};
-    std::vector<uint32_t> flagv(n_ops);
-    for (size_t j = 0; j < n_ops; j++) flagv[j] = ops[j].flags;
-    if (!on_host) {
-        ZK_TRY(work->ensure(cv.words * 4));
-        dw = work->as<uint32_t>();
-        d_xy = xybufs->out.as<const uint32_t>();
-        d_st = d_xy + nd * 16;
-        B = AssetScanBufs{dw + w_lxy, dw + w_lst, dw + w_off, dw + w_perm, dw + w_pos, dw + w_slotv, dw + w_flagv, dw + w_cstart, dw + w_pre, dw + w_tot,
-                          dw + w_agg, dw + w_carry, dw + w_cut, dw + w_ccut, (uint32_t)n_slots, (uint32_t)n_ops, (uint32_t)n_blocks};
-        // src | off | perm | pos | slotv | list lie side by side: one upload
-        std::vector<uint32_t> up(w_flagv - w_src, 0);
-        uint32_t* src = up.data();
-        for (size_t a = 0; a < n_acc; a++)
-            for (int k = 0; k < 4; k++) src[4 * a + k] = ap[a * 4 + k];
-        for (size_t j = 0; j < n_ops; j++) {
-            src[2 * (n_slots + j)] = ops[j].left;
-            src[2 * (n_slots + j) + 1] = ops[j].right;
-            up[w_slotv - w_src + j] = ops[j].slot;
-        }
-        std::copy(off.begin(), off.end(), up.begin() + (w_off - w_src));
-        std::copy(perm.begin(), perm.end(), up.begin() + (w_perm - w_src));
-        std::copy(pos.begin(), pos.end(), up.begin() + (w_pos - w_src));
-        std::copy(listv.begin(), listv.end(), up.begin() + (w_list - w_src));
-        HIP_TRY(hipMemcpyAsync(dw + w_src, up.data(), up.size() * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-        if (n_blocks) HIP_TRY(hipMemcpyAsync(dw + w_cstart, cstart.data(), n_blocks * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-        if (np) {   // (a block of issues alone may come without an account)
-            zkrt::ProfScope ps("block_gather");
-            ZK_LAUNCH(k_block_gather, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, zkrt::g_stream, d_xy, d_st, (const uint32_t*)(dw + w_src),
-                      (uint32_t)np, dw + w_lxy, dw + w_lst);
-        }
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(dst.data(), d_st, nd * 4, hipMemcpyDeviceToHost, zkrt::g_stream));
-    }
-    // ---- step 1 of every extrinsic: the signatures
-    std::vector<uint8_t> sig_ok(n, 1), sig_why(n, 0);
-    if (sigs) {
-        std::vector<uint8_t> vks(n * 32);
-        for (size_t i = 0; i < n; i++) memcpy(&vks[i * 32], xts[i].rvk, 32);
-        ZK_TRY(zk_redjubjub_verify_batch(n, vks.data(), sigs, msgs, msg_offsets, device, sig_ok.data(), sig_why.data()));
-        ZK_TRY(zkrt::use_device(device));
-    }
-    if (!on_host) HIP_TRY(hipStreamSynchronize(zkrt::g_stream));
+    Layout L(A, std::move(ops), XT_FIELDS, listv.size());
+    const size_t n_slots = L.n_slots, n_ops = L.n_ops, w_cut = L.cv.take(n_ops + n_slots + L.n_blocks), w_ccut = L.cv.take(L.n_blocks);
+    ZK_TRY(to_device(A, &P, &L, listv));
+    const AssetScanBufs B = P.on_host ? AssetScanBufs{} : AssetScanBufs{L.B, L.dw + w_cut, L.dw + w_ccut};
+    Judgement J(A);
+    ZK_TRY(check_signatures(A, xts, P.on_host, &J));
     // ---- what does not depend on the order: named and unreadable accounts, the transfer that rolls an account, refused points
-    auto acc_bad = [&](uint32_t a) { return (dst[ap[a * 4]] | dst[ap[a * 4 + 1]] | dst[ap[a * 4 + 2]] | dst[ap[a * 4 + 3]]) != 0; };
-    enum { OPEN = 255 };
-    std::vector<uint8_t> verdict(n, OPEN), refusal(n, 0), named(n_acc, 0), taken(n_acc, 0);
+    std::vector<uint8_t> taken(n_acc, 0);
     std::vector<uint32_t> roll_at(n_acc, NO_POINT);   // the first transfer that reaches step 3 and names the due account
-    size_t n_open = 0;
     auto fields_of = [&](size_t i, uint32_t* field) {
         const uint32_t* p = &xp[i * XT_POINTS];
-        if (kinds[i] == ZK_ASSET_TRANSFER) {
-            const uint32_t f[XT_FIELDS] = {p[P_SENDER], p[P_RECIPIENT], p[P_AMOUNT_SENDER], p[P_AMOUNT_RECIPIENT], p[P_RANDOMNESS], p[P_FEE],
-                                           NO_POINT,    NO_POINT,       p[P_RVK],           ge,                    p[P_NONCE]};
-            std::copy(f, f + XT_FIELDS, field);
-        } else {   // (issuer, issuer, total, total, enc_balance, ..): lib.rs:55-66, :189-200
-            const uint32_t f[XT_FIELDS] = {p[P_SENDER], p[P_SENDER], p[P_AMOUNT_SENDER], p[P_AMOUNT_SENDER], p[P_RANDOMNESS], p[P_FEE],
-                                           eb[2 * i],   eb[2 * i + 1], p[P_RVK],         ge,                 p[P_NONCE]};
-            std::copy(f, f + XT_FIELDS, field);
-        }
+        if (kinds[i] == ZK_ASSET_TRANSFER) return transfer_fields(p, P.ge, field);
+        // (issuer, issuer, total, total, enc_balance, ..): lib.rs:55-66, :189-200
+        const uint32_t f[XT_FIELDS] = {p[P_SENDER], p[P_SENDER],   p[P_AMOUNT_SENDER], p[P_AMOUNT_SENDER], p[P_RANDOMNESS], p[P_FEE],
+                                       eb[2 * i],   eb[2 * i + 1], p[P_RVK],           P.ge,               p[P_NONCE]};
+        std::copy(f, f + XT_FIELDS, field);
     };
     for (size_t i = 0; i < n; i++) {
-        if (!sig_ok[i]) {
-            verdict[i] = ZK_BLOCK_BAD_SIGNATURE;
+        if (!J.sig_ok[i]) {
+            J.verdict[i] = ZK_BLOCK_BAD_SIGNATURE;
             continue;
         }
         if (kinds[i] != ZK_ASSET_ISSUE) {
-            named[acc_s[i]] = 1;
-            bool bad = acc_bad(acc_s[i]);
+            J.named[acc_s[i]] = 1;
+            bool bad = acc_bad(P, acc_s[i]);
             if (kinds[i] == ZK_ASSET_TRANSFER) {
-                named[acc_r[i]] = 1;
-                bad = bad || acc_bad(acc_r[i]);
+                J.named[acc_r[i]] = 1;
+                bad = bad || acc_bad(P, acc_r[i]);
             }
             if (bad) {
-                verdict[i] = ZK_BLOCK_BAD_ACCOUNT;
+                J.verdict[i] = ZK_BLOCK_BAD_ACCOUNT;
                 continue;
             }
             if (kinds[i] == ZK_ASSET_TRANSFER)
@@ -607,142 +479,94 @@ inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBu
         }
         uint32_t field[XT_FIELDS];
         fields_of(i, field);
-        for (uint32_t k = 0; k < XT_FIELDS && !refusal[i]; k++)
-            if (field[k] != NO_POINT && dst[field[k]]) refusal[i] = (uint8_t)((k + 1) | (dst[field[k]] << 6));
-        n_open++;
+        J.refusal[i] = refusal_of(P, field, XT_FIELDS);
+        J.n_open++;
     }
     for (size_t a = 0; a < n_acc; a++)
-        if (roll_op[a] != NO_POINT && roll_at[a] == NO_POINT) flagv[roll_op[a]] |= LEDGER_SKIP, flagv[roll_op[a] + 1] |= LEDGER_SKIP;
+        if (roll_op[a] != NO_POINT && roll_at[a] == NO_POINT) L.skip_pair(roll_op[a]);
     // ---- the host form: a walk over the ops in order under the skip bits as they stand; want[j] >= 0 keeps the value op j meets
-    auto ext_of = [&](uint32_t p, bool negative) {
-        zkwit::EPoint a = zkwit::to_ext(hpt[p]);
-        if (negative) {
-            a.X = zkhost::Fr::zero() - a.X;
-            a.T = zkhost::Fr::zero() - a.T;
-        }
-        return a;
-    };
     std::vector<zkwit::EPoint> hcur;
-    std::vector<int32_t> want(on_host ? n_ops : 0, -1);
+    std::vector<int32_t> want(P.on_host ? n_ops : 0, -1);
     auto host_walk = [&](std::vector<zkwit::EPoint>& met) {   // met[2 want[j] + c]
         hcur.assign(2 * n_slots, zkwit::ext_zero());
         for (size_t a = 0; a < n_acc; a++)
-            if (named[a] && !acc_bad((uint32_t)a))
-                for (int k = 0; k < 4; k++) hcur[4 * a + k] = zkwit::to_ext(hpt[ap[a * 4 + k]]);
+            if (J.named[a] && !acc_bad(P, (uint32_t)a))
+                for (int k = 0; k < 4; k++) hcur[4 * a + k] = zkwit::to_ext(P.hpt[ap[a * 4 + k]]);
         for (size_t j = 0; j < n_ops; j++) {
-            const Op& o = ops[j];
+            const Op& o = L.ops[j];
             for (int c = 0; want[j] >= 0 && c < 2; c++) met[2 * want[j] + c] = hcur[2 * o.slot + c];
-            if (flagv[j] & LEDGER_SKIP) continue;
+            if (L.flagv[j] & LEDGER_SKIP) continue;
             for (int c = 0; c < 2; c++)
-                hcur[2 * o.slot + c] = o.flags & LEDGER_CLEAR ? zkwit::ext_zero() : zkwit::ext_add(hcur[2 * o.slot + c], ext_of(c ? o.right : o.left, (o.flags & LEDGER_SUB) != 0));
+                hcur[2 * o.slot + c] = o.flags & LEDGER_CLEAR
+                                           ? zkwit::ext_zero()
+                                           : zkwit::ext_add(hcur[2 * o.slot + c], zkledger::ext_signed(P.hpt[c ? o.right : o.left], (o.flags & LEDGER_SUB) != 0));
         }
-    };
-    auto scan = [&]() -> zk_status {
-        if (!n_blocks) return ZK_OK;
-        HIP_TRY(hipMemcpyAsync(dw + w_flagv, flagv.data(), n_ops * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-        return asset_scan(B);
     };
     // ---- 3. the rounds
-    std::vector<uint8_t> pool(nd, 0);
-    for (size_t k = 0; k < n_pool; k++) {
-        const uint32_t p = D.find(nonce_pool + 32 * k);
-        if (p != NO_POINT) pool[p] = 1;
-    }
-    std::vector<uint32_t> todo, vsrc, opv;
-    std::vector<uint8_t> proofs, inputs, ok, checked(n, 0), held_acc(n_acc), moved_acc(n_acc);
+    mark_pool(A, P, &J);
+    Rows R{XT_FIELDS};
+    R.checked.resize(n);
+    std::vector<uint8_t> held_acc(n_acc), moved_acc(n_acc);
     std::unordered_set<uint32_t> held_nonces;
-    while (n_open) {
-        stats.rounds++;
-        todo.clear();
+    while (J.n_open) {
+        J.stats.rounds++;
+        R.todo.clear();
         for (size_t i = 0; i < n; i++) {
-            if (kinds[i] == ZK_ASSET_TRANSFER) checked[i] = 0;   // (an issue's or a destroy's proof meets no balance of the ledger: verified once)
-            if (verdict[i] == OPEN && !refusal[i] && !checked[i] && !pool[xp[i * XT_POINTS + P_NONCE]]) todo.push_back((uint32_t)i);
+            if (kinds[i] == ZK_ASSET_TRANSFER) R.checked[i] = 0;   // (an issue's or a destroy's proof meets no balance of the ledger: verified once)
+            if (J.verdict[i] == OPEN && !J.refusal[i] && !R.checked[i] && !J.pool[xp[i * XT_POINTS + P_NONCE]]) R.todo.push_back((uint32_t)i);
         }
-        const size_t nv = todo.size();
+        const size_t nv = R.todo.size();
         if (nv) {
-            proofs.resize(nv * 192);
-            uint8_t* in_rows;
-            if (on_host) {
-                inputs.assign(nv * XT_INPUT_WORDS * 4, 0);
-                in_rows = inputs.data();
-            } else {
-                ZK_TRY(pin->ensure(nv * XT_INPUT_WORDS * 4));
-                in_rows = pin->as<uint8_t>();
+            ZK_TRY(begin_rows(A, P, xts, &R));
+            for (size_t v = 0; v < nv; v++) {
+                fields_of(R.todo[v], &R.vsrc[v * XT_FIELDS]);
+                R.opv[v] = kinds[R.todo[v]] == ZK_ASSET_TRANSFER ? first_op[R.todo[v]] : NO_POINT;
             }
-            ok.assign(nv, 0);
-            for (size_t v = 0; v < nv; v++) memcpy(&proofs[v * 192], xts[todo[v]].proof, 192);
-            if (on_host) {
+            if (P.on_host) {
                 std::fill(want.begin(), want.end(), -1);
                 for (size_t v = 0; v < nv; v++)
-                    if (kinds[todo[v]] == ZK_ASSET_TRANSFER) want[first_op[todo[v]]] = (int32_t)v;
+                    if (R.opv[v] != NO_POINT) want[R.opv[v]] = (int32_t)v;
                 std::vector<zkwit::EPoint> vals(2 * nv, zkwit::ext_zero());
                 host_walk(vals);
                 std::vector<zkwit::JPoint> aff(2 * nv);
                 zkwit::batch_to_affine(vals.data(), aff.data(), 2 * nv);
-                for (size_t v = 0; v < nv; v++) {
-                    uint32_t field[XT_FIELDS];
-                    fields_of(todo[v], field);
-                    for (uint32_t k = 0; k < XT_FIELDS; k++) {
-                        const zkwit::JPoint& q = field[k] == NO_POINT ? aff[2 * v + (k - 6)] : hpt[field[k]];
-                        const zkhost::Fr x = q.x.from_mont(), y = q.y.from_mont();
-                        memcpy(in_rows + (v * XT_FIELDS + k) * 64, x.l, 32);
-                        memcpy(in_rows + (v * XT_FIELDS + k) * 64 + 32, y.l, 32);
-                    }
-                }
+                host_rows(P, aff.data(), &R);
             } else {
-                ZK_TRY(scan());
-                vsrc.resize(nv * XT_FIELDS);
-                opv.resize(nv);
-                for (size_t v = 0; v < nv; v++) {
-                    fields_of(todo[v], &vsrc[v * XT_FIELDS]);
-                    opv[v] = kinds[todo[v]] == ZK_ASSET_TRANSFER ? first_op[todo[v]] : NO_POINT;
-                }
-                HIP_TRY(hipMemcpyAsync(dw + w_vsrc, vsrc.data(), vsrc.size() * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-                HIP_TRY(hipMemcpyAsync(dw + w_opv, opv.data(), nv * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-                {
-                    zkrt::ProfScope ps("block_gather");
-                    ZK_LAUNCH(k_block_gather, dim3((unsigned)((nv * XT_FIELDS + 255) / 256)), dim3(256), 0, zkrt::g_stream, d_xy, d_st,
-                              (const uint32_t*)(dw + w_vsrc), (uint32_t)(nv * XT_FIELDS), dw + w_inputs, (uint32_t*)nullptr);
-                }
-                asset_balance_xy(B, dw + w_opv, nv, dw + w_inputs);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(in_rows, dw + w_inputs, nv * XT_INPUT_WORDS * 4, hipMemcpyDeviceToHost, zkrt::g_stream));
-                HIP_TRY(hipStreamSynchronize(zkrt::g_stream));
+                ZK_TRY(upload_flags(L));
+                ZK_TRY(asset_scan(B));
+                ZK_TRY(device_rows(P, L, R, [&] { asset_balance_xy(B, L.dw + L.w_opv, nv, L.dw + L.w_inputs); }));
             }
-            ZK_TRY(verify(nv, proofs.data(), in_rows, ok.data()));
-            ZK_TRY(zkrt::use_device(device));
-            stats.proofs_verified += (uint32_t)nv;
-            for (size_t v = 0; v < nv; v++) checked[todo[v]] = (uint8_t)(1 + ok[v]);
+            ZK_TRY(verify_rows(A, verify, &R, &J));
         }
         // the sweep, in order
         std::fill(held_acc.begin(), held_acc.end(), 0);
         std::fill(moved_acc.begin(), moved_acc.end(), 0);
         held_nonces.clear();
         for (size_t i = 0; i < n; i++) {
-            if (verdict[i] != OPEN) continue;
+            if (J.verdict[i] != OPEN) continue;
             const uint32_t nonce = xp[i * XT_POINTS + P_NONCE], a = acc_s[i];
             const bool transfer = kinds[i] == ZK_ASSET_TRANSFER;
             bool hold = (transfer && held_acc[a]) || held_nonces.count(nonce);
             if (!hold) {
-                if (pool[nonce])
-                    verdict[i] = ZK_BLOCK_NONCE_USED;
-                else if (refusal[i])
-                    verdict[i] = ZK_BLOCK_REFUSED_POINT;
-                else if ((transfer && moved_acc[a]) || !checked[i])
+                if (J.pool[nonce])
+                    J.verdict[i] = ZK_BLOCK_NONCE_USED;
+                else if (J.refusal[i])
+                    J.verdict[i] = ZK_BLOCK_REFUSED_POINT;
+                else if ((transfer && moved_acc[a]) || !R.checked[i])
                     hold = true;   // its balance changed in this sweep: the next round verifies it against the new one
-                else if (checked[i] == 1)
-                    verdict[i] = ZK_BLOCK_INVALID_PROOF;
+                else if (R.checked[i] == 1)
+                    J.verdict[i] = ZK_BLOCK_INVALID_PROOF;
                 else {
-                    verdict[i] = ZK_BLOCK_ACCEPTED;
-                    pool[nonce] = 1;
+                    J.verdict[i] = ZK_BLOCK_ACCEPTED;
+                    J.pool[nonce] = 1;
                     if (transfer) {
                         moved_acc[a] = 1;
-                        for (uint32_t j = first_op[i]; j < first_op[i] + 3; j++) flagv[j] &= ~LEDGER_SKIP;
+                        for (uint32_t j = first_op[i]; j < first_op[i] + 3; j++) L.flagv[j] &= ~LEDGER_SKIP;
                     } else if (kinds[i] == ZK_ASSET_DESTROY) {
                         moved_acc[a] = taken[a] = 1;
-                        flagv[first_op[i]] &= ~LEDGER_SKIP, flagv[first_op[i] + 1] &= ~LEDGER_SKIP;
+                        L.flagv[first_op[i]] &= ~LEDGER_SKIP, L.flagv[first_op[i] + 1] &= ~LEDGER_SKIP;
                         // a rollover at a later transfer moves nothing: the pending transfer it would move was taken
-                        if (roll_op[a] != NO_POINT && roll_at[a] != NO_POINT && roll_at[a] > i) flagv[roll_op[a]] |= LEDGER_SKIP, flagv[roll_op[a] + 1] |= LEDGER_SKIP;
+                        if (roll_op[a] != NO_POINT && roll_at[a] != NO_POINT && roll_at[a] > i) L.skip_pair(roll_op[a]);
                     }
                 }
             }
@@ -750,14 +574,14 @@ inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBu
                 if (a != NO_POINT) held_acc[a] = 1;
                 held_nonces.insert(nonce);
             } else {
-                n_open--;
+                J.n_open--;
             }
         }
     }
     // ---- 4. the state to store and what the destroys took: one more scan under the final skip bits
-    const size_t n_enc = 2 * n_slots + 4 * n_destroy;
+    const size_t n_enc = 2 * n_slots + 2 * listv.size();
     std::vector<uint8_t> enc(n_enc * 32, 0);
-    if (on_host) {
+    if (P.on_host) {
         std::fill(want.begin(), want.end(), -1);
         for (size_t k = 0; k < listv.size(); k++) want[listv[k]] = (int32_t)k;
         std::vector<zkwit::EPoint> vals(2 * listv.size(), zkwit::ext_zero());
@@ -767,39 +591,26 @@ inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBu
         zkwit::batch_to_affine(vals.data(), aff.data(), vals.size());
         for (size_t k = 0; k < aff.size(); k++) zkledger::point_write(aff[k], &enc[k * 32]);
     } else if (n_enc) {
-        ZK_TRY(scan());
-        asset_encode(B, dw + w_list, n_enc, dw + w_enc);
+        ZK_TRY(upload_flags(L));
+        ZK_TRY(asset_scan(B));
+        asset_encode(B, L.dw + L.w_list, n_enc, L.dw + L.w_enc);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(enc.data(), dw + w_enc, n_enc * 32, hipMemcpyDeviceToHost, zkrt::g_stream));
+        HIP_TRY(hipMemcpyAsync(enc.data(), L.dw + L.w_enc, n_enc * 32, hipMemcpyDeviceToHost, zkrt::g_stream));
         HIP_TRY(hipStreamSynchronize(zkrt::g_stream));
     }
-    for (size_t a = 0; a < n_acc; a++) {
-        zk_block_account out = accounts[a];
-        if (named[a]) {
-            if (acc_bad((uint32_t)a)) {
-                memset(out.balance, 0, 64);
-                memset(out.pending, 0, 64);
-            } else {
-                memcpy(out.balance, &enc[(2 * a) * 64], 64);
-                memcpy(out.pending, &enc[(2 * a + 1) * 64], 64);
-            }
-            if (roll_at[a] != NO_POINT) out.flags |= ZK_BLOCK_ROLLED;
-            if (taken[a]) out.flags |= ZK_BLOCK_TAKEN;
-        }
-        accounts_out[a] = out;
-    }
+    write_accounts(A, P, J, enc.data(), [&](size_t a) { return (roll_at[a] != NO_POINT ? ZK_BLOCK_ROLLED : 0) | (taken[a] ? ZK_BLOCK_TAKEN : 0); });
+    write_verdicts(A, P, &J);
     uint32_t next_id = next_asset_id;
     for (size_t i = 0; i < n; i++) {
-        verdicts_out[i] = zk_block_verdict{verdict[i], (uint8_t)(verdict[i] == ZK_BLOCK_BAD_SIGNATURE ? sig_why[i] : verdict[i] == ZK_BLOCK_REFUSED_POINT ? refusal[i] : 0), 0};
         zk_asset_effect& fx = effects_out[i];
         memset(&fx, 0, sizeof fx);
         fx.asset_id = kinds[i] == ZK_ASSET_ISSUE ? 0 : asset_ids[i];
-        if (verdict[i] != ZK_BLOCK_ACCEPTED) continue;
+        if (J.verdict[i] != ZK_BLOCK_ACCEPTED) continue;
         if (kinds[i] == ZK_ASSET_ISSUE) {
             fx.asset_id = next_id++;
-            if (on_host) {
-                zkledger::point_write(hpt[xp[i * XT_POINTS + P_AMOUNT_SENDER]], fx.first);
-                zkledger::point_write(hpt[xp[i * XT_POINTS + P_RANDOMNESS]], fx.first + 32);
+            if (P.on_host) {
+                zkledger::point_write(P.hpt[xp[i * XT_POINTS + P_AMOUNT_SENDER]], fx.first);
+                zkledger::point_write(P.hpt[xp[i * XT_POINTS + P_RANDOMNESS]], fx.first + 32);
             } else {
                 canonical32(xts[i].left_amount_sender, fx.first);
                 canonical32(xts[i].right_randomness, fx.first + 32);
@@ -810,7 +621,6 @@ inline zk_status execute_asset(int device, zkxt::IntoXyBufs* xybufs, zkrt::DevBu
         }
     }
     *next_asset_id_out = next_id;
-    if (stats_out) *stats_out = stats;
     return ZK_OK;
 }
 

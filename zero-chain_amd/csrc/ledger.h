@@ -229,16 +229,24 @@ k_ledger_encode(const uint32_t* xy, const uint32_t* st, const uint32_t* off, con
 // status of a ciphertext from the IntoXY statuses of its points: 0, or (1 = left, 2 = right) | status << 6 of the first refused
 inline uint8_t ct_status(uint32_t left, uint32_t right) { return left ? (uint8_t)(1u | (left << 6)) : right ? (uint8_t)(2u | (right << 6)) : 0; }
 
-// the stable grouping of the ops by slot: off (n_slots + 1), perm (place -> op), pos (op -> place)
+// the stable grouping of the ops by slot, slot_of(i) the slot of op i: off (n_slots + 1), perm (place -> op), pos (op -> place),
+// and cstart, per workgroup of the scan the last one at or before it in which a slot starts (k_ledger_carry)
 struct Grouping {
-    std::vector<uint32_t> off, perm, pos;
-    Grouping(size_t n_slots, size_t n_ops, const zk_ledger_op* ops) : off(n_slots + 1, 0), perm(n_ops), pos(n_ops) {
-        for (size_t i = 0; i < n_ops; i++) off[ops[i].slot + 1]++;
+    std::vector<uint32_t> off, perm, pos, cstart;
+    template <class SlotOf>
+    Grouping(size_t n_slots, size_t n_ops, SlotOf&& slot_of)
+        : off(n_slots + 1, 0), perm(n_ops), pos(n_ops), cstart((n_ops + LEDGER_SCAN_W - 1) / LEDGER_SCAN_W) {
+        for (size_t i = 0; i < n_ops; i++) off[slot_of(i) + 1]++;
         for (size_t s = 0; s < n_slots; s++) off[s + 1] += off[s];
         std::vector<uint32_t> at(off.begin(), off.end() - 1);
         for (size_t i = 0; i < n_ops; i++) {
-            pos[i] = at[ops[i].slot]++;
+            pos[i] = at[slot_of(i)]++;
             perm[pos[i]] = (uint32_t)i;
+        }
+        for (size_t b = 0, h = 0; b < cstart.size(); b++) {   // a slot starts in workgroup b: the slot of its last place starts at or after its first
+            const size_t lastj = std::min(n_ops, (b + 1) * LEDGER_SCAN_W) - 1;
+            if (off[slot_of(perm[lastj])] >= b * LEDGER_SCAN_W) h = b;
+            cstart[b] = (uint32_t)h;
         }
     }
 };
@@ -249,31 +257,47 @@ inline void point_write(const zkwit::JPoint& p, uint8_t out[32]) {   // edwards:
     if (x.l[0] & 1) out[31] |= 0x80;
 }
 
+// a decoded point, or its negative, in extended coordinates
+inline zkwit::EPoint ext_signed(const zkwit::JPoint& p, bool negative) {
+    zkwit::EPoint a = zkwit::to_ext(p);
+    if (negative) {
+        a.X = zkhost::Fr::zero() - a.X;
+        a.T = zkhost::Fr::zero() - a.T;
+    }
+    return a;
+}
+
+// the device pointers the scan, the carry and the encoder share, named as the kernels' arguments
+struct ScanBufs {
+    const uint32_t *lxy, *lst, *off, *perm, *pos, *slotv, *flagv, *cstart;
+    uint32_t *pre, *tot, *agg, *carry;
+    uint32_t n_slots, n_ops, n_blocks;
+};
+inline void launch_scan(const ScanBufs& B) {
+    if (!B.n_blocks) return;
+    zkrt::ProfScope ps("ledger_scan");
+    ZK_LAUNCH_SYNC(k_ledger_scan, dim3(B.n_blocks, 2), dim3(LEDGER_SCAN_W), 0, zkrt::g_stream, B.lxy, B.lst, B.off, B.perm, B.slotv, B.flagv, B.n_slots,
+                   B.n_ops, B.pre, B.tot, B.agg);
+    ZK_LAUNCH_SYNC(k_ledger_carry, dim3(1, 2), dim3(LEDGER_SCAN_W), 0, zkrt::g_stream, (const uint32_t*)B.agg, B.cstart, B.n_blocks, B.carry);
+}
+inline void launch_encode(const ScanBufs& B, size_t n_out, uint32_t* enc) {
+    zkrt::ProfScope ps("ledger_encode");
+    ZK_LAUNCH(k_ledger_encode, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, zkrt::g_stream, B.lxy, B.lst, B.off, B.pos, B.slotv, (const uint32_t*)B.pre,
+              (const uint32_t*)B.tot, (const uint32_t*)B.carry, B.n_slots, B.n_ops, B.n_blocks, (uint32_t)n_out, enc);
+}
+
 inline zk_status apply_host(size_t n_slots, const uint8_t* slots, size_t n_ops, const zk_ledger_op* ops, uint8_t* slots_out, uint8_t* before_out,
                             uint8_t* slot_status_out, uint8_t* op_status_out) {
     const size_t np = 2 * (n_slots + n_ops);
     std::vector<zkwit::JPoint> pt(np);
-    std::vector<uint8_t> st(np);
+    std::vector<uint32_t> st(np);
     auto encoding = [&](size_t p) -> const uint8_t* {
         return p < 2 * n_slots ? slots + p * 32 : (p & 1 ? ops[(p - 2 * n_slots) >> 1].right : ops[(p - 2 * n_slots) >> 1].left);
     };
-    {
-        const unsigned nth = zkrt::host_threads(np, 64);
-        auto work = [&](unsigned t) {
-            for (size_t p = np * t / nth; p < np * (t + 1) / nth; p++) {
-                uint8_t xy[64];
-                st[p] = zkxt::into_xy_one(encoding(p), xy);
-                zkhost::Fr x, y;
-                memcpy(x.l, xy, 32);
-                memcpy(y.l, xy + 32, 32);
-                pt[p] = zkwit::JPoint{x.to_mont(), y.to_mont()};
-            }
-        };
-        zkrt::run_threads(nth, work);
-    }
+    zkxt::into_xy_points(np, encoding, st.data(), pt.data());
     for (size_t s = 0; s < n_slots; s++) slot_status_out[s] = ct_status(st[2 * s], st[2 * s + 1]);
     for (size_t i = 0; i < n_ops; i++) op_status_out[i] = ct_status(st[2 * (n_slots + i)], st[2 * (n_slots + i) + 1]);
-    const Grouping g(n_slots, n_ops, ops);
+    const Grouping g(n_slots, n_ops, [&](size_t i) { return ops[i].slot; });
     // a thread's share: consecutive slots of about equal weight, a slot weighing one more than its ops
     const size_t weight = n_slots + n_ops;
     const unsigned nth = zkrt::host_threads(weight / 32 + 1, 64);
@@ -296,14 +320,7 @@ inline zk_status apply_host(size_t n_slots, const uint8_t* slots, size_t n_ops, 
                     dst.push_back(before_out + i * 64 + 32 * c);
                 }
                 if (op_status_out[i] || (ops[i].flags & LEDGER_SKIP)) continue;
-                for (int c = 0; c < 2; c++) {
-                    zkwit::EPoint a = zkwit::to_ext(pt[2 * (n_slots + i) + c]);
-                    if (ops[i].flags & LEDGER_SUB) {
-                        a.X = zkhost::Fr::zero() - a.X;
-                        a.T = zkhost::Fr::zero() - a.T;
-                    }
-                    cur[c] = zkwit::ext_add(cur[c], a);
-                }
+                for (int c = 0; c < 2; c++) cur[c] = zkwit::ext_add(cur[c], ext_signed(pt[2 * (n_slots + i) + c], (ops[i].flags & LEDGER_SUB) != 0));
             }
             for (int c = 0; c < 2; c++) {
                 vals.push_back(cur[c]);
@@ -334,40 +351,26 @@ inline zk_status apply_device(size_t n_slots, const uint8_t* slots, size_t n_ops
     zkxt::IntoXyBufs bufs;
     ZK_TRY(zkxt::into_xy_on_device(pts.data(), np, &bufs, meta_words * 4, enc_bytes + work_bytes));
     // ... and while the decoder runs: the grouping
-    const Grouping g(n_slots, n_ops, ops);
+    const Grouping g(n_slots, n_ops, [&](size_t i) { return ops[i].slot; });
     std::vector<uint32_t> meta(meta_words);
-    uint32_t* m = meta.data();
-    std::copy(g.off.begin(), g.off.end(), m);
-    std::copy(g.perm.begin(), g.perm.end(), m + n_slots + 1);
-    std::copy(g.pos.begin(), g.pos.end(), m + n_slots + 1 + n_ops);
+    const size_t m_perm = n_slots + 1, m_pos = m_perm + n_ops, m_slotv = m_pos + n_ops, m_flagv = m_slotv + n_ops, m_cstart = m_flagv + n_ops;
+    std::copy(g.off.begin(), g.off.end(), meta.begin());
+    std::copy(g.perm.begin(), g.perm.end(), meta.begin() + m_perm);
+    std::copy(g.pos.begin(), g.pos.end(), meta.begin() + m_pos);
     for (size_t i = 0; i < n_ops; i++) {
-        m[n_slots + 1 + 2 * n_ops + i] = ops[i].slot;
-        m[n_slots + 1 + 3 * n_ops + i] = ops[i].flags;
+        meta[m_slotv + i] = ops[i].slot;
+        meta[m_flagv + i] = ops[i].flags;
     }
-    for (size_t b = 0, h = 0; b < n_blocks; b++) {   // a slot starts in workgroup b: the slot of its last place starts at or after its first
-        const size_t lastj = std::min(n_ops, (b + 1) * LEDGER_SCAN_W) - 1;
-        if (g.off[ops[g.perm[lastj]].slot] >= b * LEDGER_SCAN_W) h = b;
-        m[n_slots + 1 + 4 * n_ops + b] = (uint32_t)h;
-    }
+    std::copy(g.cstart.begin(), g.cstart.end(), meta.begin() + m_cstart);
     uint32_t* d_meta = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(bufs.in.p) + np * 32);
     HIP_TRY(hipMemcpyAsync(d_meta, meta.data(), meta_words * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-    const uint32_t *d_off = d_meta, *d_perm = d_off + n_slots + 1, *d_pos = d_perm + n_ops, *d_slotv = d_pos + n_ops, *d_flagv = d_slotv + n_ops,
-                   *d_cstart = d_flagv + n_ops;
-    const uint32_t *d_xy = bufs.out.as<const uint32_t>(), *d_st = d_xy + np * 16;
+    const uint32_t* d_xy = bufs.out.as<const uint32_t>();
     uint32_t* d_enc = reinterpret_cast<uint32_t*>(static_cast<uint8_t*>(bufs.out.p) + zkxt::into_xy_out_bytes(np));
     uint32_t *d_pre = d_enc + n_out * 8, *d_tot = d_pre + 2 * n_ops * 32, *d_agg = d_tot + 2 * n_slots * 32, *d_carry = d_agg + 2 * n_blocks * 32;
-    if (n_blocks) {
-        zkrt::ProfScope ps("ledger_scan");
-        ZK_LAUNCH_SYNC(k_ledger_scan, dim3((unsigned)n_blocks, 2), dim3(LEDGER_SCAN_W), 0, zkrt::g_stream, d_xy, d_st, d_off, d_perm, d_slotv, d_flagv,
-                       (uint32_t)n_slots, (uint32_t)n_ops, d_pre, d_tot, d_agg);
-        ZK_LAUNCH_SYNC(k_ledger_carry, dim3(1, 2), dim3(LEDGER_SCAN_W), 0, zkrt::g_stream, (const uint32_t*)d_agg, d_cstart, (uint32_t)n_blocks, d_carry);
-    }
-    {
-        zkrt::ProfScope ps("ledger_encode");
-        ZK_LAUNCH(k_ledger_encode, dim3((unsigned)((n_out + 63) / 64)), dim3(64), 0, zkrt::g_stream, d_xy, d_st, d_off, d_pos, d_slotv,
-                  (const uint32_t*)d_pre, (const uint32_t*)d_tot, (const uint32_t*)d_carry, (uint32_t)n_slots, (uint32_t)n_ops, (uint32_t)n_blocks,
-                  (uint32_t)n_out, d_enc);
-    }
+    const ScanBufs B{d_xy,  d_xy + np * 16, d_meta, d_meta + m_perm, d_meta + m_pos,    d_meta + m_slotv, d_meta + m_flagv, d_meta + m_cstart,
+                     d_pre, d_tot,          d_agg,  d_carry,         (uint32_t)n_slots, (uint32_t)n_ops,  (uint32_t)n_blocks};
+    launch_scan(B);
+    launch_encode(B, n_out, d_enc);
     HIP_TRY(hipGetLastError());
     // one copy back: the statuses of all points, the padding up to the encodings, the encodings
     const size_t st_at = np * 64, back_bytes = zkxt::into_xy_out_bytes(np) - st_at + enc_bytes;
@@ -393,9 +396,7 @@ inline zk_status apply(size_t n_slots, const uint8_t* slots, size_t n_ops, const
         if (ops[i].slot >= n_slots) return fail(ZK_ERR_INVALID_ARGUMENT, "op " + std::to_string(i) + ": slot " + std::to_string(ops[i].slot) + " of " + std::to_string(n_slots));
         if (ops[i].flags & ~(LEDGER_SUB | LEDGER_SKIP)) return fail(ZK_ERR_INVALID_ARGUMENT, "op " + std::to_string(i) + ": unknown flag bits");
     }
-    const char* e = getenv("ZKAMD_INTO_XY_HOST_MAX");
-    const size_t host_max = e && *e ? (size_t)strtoull(e, nullptr, 10) : zkxt::INTO_XY_HOST_MAX;
-    if (device < 0 || 2 * (n_slots + n_ops) <= host_max) return apply_host(n_slots, slots, n_ops, ops, slots_out, before_out, slot_status_out, op_status_out);
+    if (device < 0 || 2 * (n_slots + n_ops) <= zkxt::into_xy_host_max()) return apply_host(n_slots, slots, n_ops, ops, slots_out, before_out, slot_status_out, op_status_out);
     return apply_device(n_slots, slots, n_ops, ops, device, slots_out, before_out, slot_status_out, op_status_out);
 }
 

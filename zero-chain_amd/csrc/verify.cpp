@@ -1075,8 +1075,9 @@ zk_status zk_confidential_block_execute(zk_vk* vk, size_t n, const zk_confidenti
     auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
         return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::XT_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
     };
-    return zkblock::execute(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool, nonce_pool,
-                            g_epoch, accounts_out, verdicts_out, stats_out);
+    const zkblock::BlockArgs A{vk->device, &vk->xt,    &vk->block, &vk->block_rows, n,       sigs,         msgs,         msg_offsets,
+                               n_accounts, accounts,   n_pool,     nonce_pool,      g_epoch, accounts_out, verdicts_out, stats_out};
+    return zkblock::execute(A, verify, xts);
 } ZK_ABI_CATCH
 zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt* xts, const uint8_t* sigs, const uint8_t* msgs,
                                      const uint64_t* msg_offsets, size_t n_accounts, const zk_block_account* accounts, size_t n_pool,
@@ -1088,8 +1089,9 @@ zk_status zk_anonymous_block_execute(zk_vk* vk, size_t n, const zk_anonymous_xt*
     auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
         return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::AX_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
     };
-    return zkblock::execute_anonymous(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, sigs, msgs, msg_offsets, n_accounts, accounts, n_pool,
-                                      nonce_pool, g_epoch, accounts_out, verdicts_out, stats_out);
+    const zkblock::BlockArgs A{vk->device, &vk->xt,    &vk->block, &vk->block_rows, n,       sigs,         msgs,         msg_offsets,
+                               n_accounts, accounts,   n_pool,     nonce_pool,      g_epoch, accounts_out, verdicts_out, stats_out};
+    return zkblock::execute_anonymous(A, verify, xts);
 } ZK_ABI_CATCH
 zk_status zk_asset_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* xts, const uint8_t* kinds, const uint32_t* asset_ids, const uint8_t* sigs,
                                  const uint8_t* msgs, const uint64_t* msg_offsets, size_t n_accounts, const zk_block_account* accounts,
@@ -1102,9 +1104,9 @@ zk_status zk_asset_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* 
     auto verify = [&](size_t nv, const uint8_t* proofs, const uint8_t* inputs, uint8_t* ok) {
         return zkrt::verify_batch(vk, nv, proofs, inputs, 2 * zkblock::XT_FIELDS, ok, false, zkrt::VERIFY_AUTO, nullptr);
     };
-    return zkblock::execute_asset(vk->device, &vk->xt, &vk->block, &vk->block_rows, verify, n, xts, kinds, asset_ids, sigs, msgs, msg_offsets, n_accounts,
-                                  accounts, account_asset_ids, n_pool, nonce_pool, g_epoch, next_asset_id, accounts_out, verdicts_out, effects_out,
-                                  next_asset_id_out, stats_out);
+    const zkblock::BlockArgs A{vk->device, &vk->xt,    &vk->block, &vk->block_rows, n,       sigs,         msgs,         msg_offsets,
+                               n_accounts, accounts,   n_pool,     nonce_pool,      g_epoch, accounts_out, verdicts_out, stats_out};
+    return zkblock::execute_asset(A, verify, xts, kinds, asset_ids, account_asset_ids, next_asset_id, effects_out, next_asset_id_out);
 } ZK_ABI_CATCH
 zk_status zk_g_epoch(uint32_t epoch, uint8_t out[32]) try {
     if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");

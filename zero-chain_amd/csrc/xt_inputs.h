@@ -73,6 +73,30 @@ inline uint8_t into_xy_one(const uint8_t b[32], uint8_t xy[64]) {
     return INTO_XY_OK;
 }
 
+// the one reader of ZKAMD_INTO_XY_HOST_MAX (per call): zk_jubjub_into_xy, zk_elgamal_ledger_apply and the block executors
+inline size_t into_xy_host_max() {
+    const char* e = getenv("ZKAMD_INTO_XY_HOST_MAX");
+    return e && *e ? (size_t)strtoull(e, nullptr, 10) : INTO_XY_HOST_MAX;
+}
+
+// The host form for callers that go on computing: the n encodings enc_of(0 .. n - 1) on the host threads, the status and the
+// point in Montgomery form of each (x = y = 0 where refused)
+template <class EncOf>
+inline void into_xy_points(size_t n, EncOf&& enc_of, uint32_t* st, zkwit::JPoint* pt) {
+    const unsigned nth = zkrt::host_threads(n, 64);
+    auto work = [&](unsigned t) {
+        for (size_t p = n * t / nth; p < n * (t + 1) / nth; p++) {
+            uint8_t xy[64];
+            st[p] = into_xy_one(enc_of(p), xy);
+            zkhost::Fr x, y;
+            memcpy(x.l, xy, 32);
+            memcpy(y.l, xy + 32, 32);
+            pt[p] = zkwit::JPoint{x.to_mont(), y.to_mont()};
+        }
+    };
+    zkrt::run_threads(nth, work);
+}
+
 // the workspaces of the device form (public data: no wipe)
 struct IntoXyBufs {
     zkrt::DevBuf in, out;
@@ -83,9 +107,7 @@ struct IntoXyBufs {
 // device form): the host form.  Else the kernel on the library stream of `device`, coordinates and statuses back in one copy.
 inline zk_status into_xy(const uint8_t* points, size_t n, int device, IntoXyBufs* bufs, uint8_t* xy_out, uint8_t* status_out) {
     if (!n) return ZK_OK;
-    const char* e = getenv("ZKAMD_INTO_XY_HOST_MAX");
-    const size_t host_max = e && *e ? (size_t)strtoull(e, nullptr, 10) : INTO_XY_HOST_MAX;
-    if (device < 0 || n <= host_max) {
+    if (device < 0 || n <= into_xy_host_max()) {
         const unsigned nth = zkrt::host_threads(n, 64);
         auto work = [&](unsigned t) {
             for (size_t i = n * t / nth; i < n * (t + 1) / nth; i++) status_out[i] = into_xy_one(points + i * 32, xy_out + i * 64);
