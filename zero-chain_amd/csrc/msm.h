@@ -41,6 +41,39 @@ struct MsmJob {
     uint32_t n_digits;        // variable-base mode: digit positions per scalar
 };
 
+// Value runs (ntt.h k_build_scalars): which base a pair slot of a job takes this proof.  A launch set has up to two RANGES of
+// jobs with such slots (the C' jobs and the A jobs of one set); the jobs themselves stay as they are.  In job job0 + p, p <
+// n_jobs, slot first + k, k < n, is a pair slot whose byte sel[p * stride + k] names the length l of the term it holds this
+// proof: l >= 3 takes the base alt[k * alt_w + (l - 3)] in place of map[slot] (static: positions like map's, -1 where the
+// table has no such base).  k_build_scalars writes a length only where its word for the variable has the bit, and the bits
+// and alt are made in one loop (zkamd.cpp derived_pairs; tests/test_value_runs.py holds the two against each other), so a
+// byte that names no base does not occur; if it did, the slot is skipped in both passes of the sort alike - never a read
+// outside alt or the table.  All zero: a set without them.
+struct MsmSelRange {
+    const uint8_t* sel;
+    const int32_t* alt;
+    uint32_t job0, n_jobs, stride, first, n, alt_w;
+};
+struct MsmSelSet {
+    MsmSelRange r[2];
+};
+
+// where the base of scalar i of job j of a set lies in the slice-0 table, or -1 (skip)
+ZK_DI int32_t msm_job_pos(const MsmJob& job, const MsmSelSet& S, uint32_t j, uint32_t i) {
+    if (!job.map) return (int32_t)i;
+    int32_t pos = job.map[i];
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const MsmSelRange& r = S.r[h];
+        const uint32_t p = j - r.job0, k = i - r.first;
+        if (r.sel && p < r.n_jobs && k < r.n) {
+            const uint32_t l = r.sel[(size_t)p * r.stride + k];
+            if (l >= 3u) pos = l - 3u < r.alt_w ? r.alt[(size_t)k * r.alt_w + (l - 3u)] : -1;
+        }
+    }
+    return pos;
+}
+
 // Register budgets.  hipcc sizes a kernel's VGPR allocation from its launch bounds alone (it will
 // happily take 256 registers and one wave per SIMD); the second __launch_bounds__ argument (minimum
 // waves per SIMD) pins the occupancy the dependent carry chains of the Montgomery product need.
@@ -260,7 +293,7 @@ constexpr uint32_t MSM_COARSE_SCALARS = 1024;  // scalars per workgroup of passe
 
 static __global__ void __launch_bounds__(256)
 k_msm_coarse_count(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_log, uint32_t n_coarse, uint32_t* coarse_cnt,
-                   uint32_t* blockbase, uint32_t per_wg) {
+                   uint32_t* blockbase, uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}) {
     ZK_SHARED uint32_t h[MSM_COARSE_MAX];
     const MsmJob job = jobs[blockIdx.y];
     const uint32_t tid = threadIdx.x;
@@ -269,7 +302,7 @@ k_msm_coarse_count(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_lo
     __syncthreads();
     for (uint32_t e = 0; e < per_wg / 256; e++) {
         const uint32_t i = blockIdx.x * per_wg + e * 256 + tid;
-        if (i >= job.n || (job.map && job.map[i] < 0)) continue;
+        if (i >= job.n || msm_job_pos(job, sels, blockIdx.y, i) < 0) continue;
         msm_digits(job, i, c, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[(mag >> 1) >> fine_log], 1u); });
     }
     __syncthreads();
@@ -312,7 +345,7 @@ k_msm_coarse_scan(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, u
 static __global__ void __launch_bounds__(256)
 k_msm_coarse_scatter(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_log, uint32_t n_coarse,
                      const uint32_t* __restrict__ coarse_off, const uint32_t* __restrict__ blockbase, uint2* __restrict__ rec,
-                     uint32_t per_wg) {
+                     uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}) {
     ZK_SHARED uint32_t h[MSM_COARSE_MAX];
     const MsmJob job = jobs[blockIdx.y];
     const uint32_t tid = threadIdx.x;
@@ -326,7 +359,7 @@ k_msm_coarse_scatter(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_
     for (uint32_t e = 0; e < per_wg / 256; e++) {
         const uint32_t i = blockIdx.x * per_wg + e * 256 + tid;
         if (i >= job.n) continue;
-        const int32_t pos = job.map ? job.map[i] : (int32_t)i;
+        const int32_t pos = msm_job_pos(job, sels, blockIdx.y, i);
         if (pos < 0) continue;
         const uint32_t tbase = job.table_base + (uint32_t)pos, tstride = job.n_table;
         msm_digits(job, i, c, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {
@@ -432,7 +465,7 @@ constexpr uint32_t MSM_SORT_THREADS = 1024;
 #endif
 static __global__ void __launch_bounds__(MSM_SORT_THREADS)
 k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint32_t* off, uint32_t* toff,
-               uint32_t* ntasks, uint32_t* pairs, uint32_t seg, uint32_t dbg) {
+               uint32_t* ntasks, uint32_t* pairs, uint32_t seg, uint32_t dbg, const MsmSelSet sels = MsmSelSet{}) {
     ZK_DYN_SHARED(uint32_t, h);   // [nb] histogram, then running slot cursors
     ZK_SHARED uint32_t part[MSM_SORT_THREADS];
     ZK_SHARED uint32_t tpart[MSM_SORT_THREADS];
@@ -441,7 +474,7 @@ k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint3
     for (uint32_t b = tid; b < nb; b += nt) h[b] = 0;
     __syncthreads();
     for (uint32_t i = tid; i < job.n; i += nt) {
-        if (job.map && job.map[i] < 0) continue;
+        if (msm_job_pos(job, sels, blockIdx.x, i) < 0) continue;
         msm_digits(job, i, c, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[mag >> 1], 1u); });
     }
     __syncthreads();
@@ -484,7 +517,7 @@ k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint3
     uint32_t* jpairs = pairs + job.pair_base;
     if (dbg & 2u) return;   // diagnostics (ZKAMD_DEBUG_SORT): the count pass and the scan alone
     for (uint32_t i = tid; i < job.n; i += nt) {
-        int32_t pos = job.map ? job.map[i] : (int32_t)i;
+        const int32_t pos = msm_job_pos(job, sels, blockIdx.x, i);
         if (pos < 0) continue;
         const uint32_t tbase = job.table_base + (uint32_t)pos, tstride = job.n_table;
         msm_digits(job, i, c, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {

@@ -209,7 +209,9 @@ struct MsmGroup {
 
     // jobs[i].pair_base is filled in here.  Everything, including the copy of the results (one XYZZ
     // per job) into `out`, is enqueued on `st`; collect() waits for it.
-    zk_status enqueue(std::vector<MsmJob>& jobs, std::vector<HPoint>& out, hipStream_t st, bool to_host = true);
+    // sels: the pair slots of the set's jobs whose bases follow the bytes of this call's proofs (msm.h MsmSelSet), or null.
+    zk_status enqueue(std::vector<MsmJob>& jobs, std::vector<HPoint>& out, hipStream_t st, bool to_host = true,
+                      const zkdev::MsmSelSet* sels = nullptr);
     // out[i] = affine form of src[i] (host layout, zz = zzz = 1), enqueued on st
     zk_status normalize_to_host(const DPoint* src, size_t n, HPoint* out, DevBuf& stage, hipStream_t st);
     // out[i] = src[i] as it is (host layout, zz and zzz NOT normalised: zkhost::to_affine inverts), enqueued on st.  For a
@@ -223,7 +225,7 @@ struct MsmGroup {
         HIP_TRY(hipStreamSynchronize(st));
         return ZK_OK;
     }
-    zk_status run(std::vector<MsmJob>& jobs, std::vector<HPoint>& out);
+    zk_status run(std::vector<MsmJob>& jobs, std::vector<HPoint>& out, const zkdev::MsmSelSet* sels = nullptr);
     // The (digit, point) pairs of the last launch set, nj jobs, counted from its buckets; after collect() and before the next
     // enqueue on this group.  For measurements (ZKAMD_TRACE_HOST): it reads nj * nb words back.
     zk_status count_pairs(size_t nj, uint64_t* total) {
@@ -241,7 +243,7 @@ private:
     // the stages of enqueue(), in its order, each over the plan of the set (msm_plan.h)
     zk_status reserve(const MsmPlan& p, bool to_host);
     zk_status upload_jobs(const std::vector<MsmJob>& jobs, const MsmPlan& p, hipStream_t st);
-    zk_status sort_pairs(const MsmPlan& p, hipStream_t st);
+    zk_status sort_pairs(const MsmPlan& p, hipStream_t st, const zkdev::MsmSelSet& sel_set);
     zk_status order_tasks(const MsmPlan& p, hipStream_t st);
     zk_status accumulate(const MsmPlan& p, hipStream_t st);
     zk_status merge_partials(const MsmPlan& p, hipStream_t st);

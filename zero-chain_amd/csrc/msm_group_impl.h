@@ -122,7 +122,8 @@ zk_status MsmGroup<HF, DF>::build_with_tail(const std::vector<typename MsmGroup<
 // One launch set: plan (msm_plan.h: every decision about its shape, nothing enqueued before a refusal), then the stages
 // below in this order.
 template <class HF, class DF>
-zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typename MsmGroup<HF, DF>::HPoint>& out, hipStream_t st, bool to_host) {
+zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typename MsmGroup<HF, DF>::HPoint>& out, hipStream_t st, bool to_host,
+                                    const zkdev::MsmSelSet* sels) {
     const size_t nj = jobs.size();
     out.resize(nj);
     res_dev = nullptr;
@@ -133,7 +134,7 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     for (size_t k = 0; k < nj; k++) jobs[k].pair_base = p.pair_base[k];
     ZK_TRY(reserve(p, to_host));
     ZK_TRY(upload_jobs(jobs, p, st));
-    ZK_TRY(sort_pairs(p, st));
+    ZK_TRY(sort_pairs(p, st, sels ? *sels : zkdev::MsmSelSet{}));
     ZK_TRY(order_tasks(p, st));
     ZK_TRY(accumulate(p, st));
     {
@@ -176,7 +177,7 @@ zk_status MsmGroup<HF, DF>::upload_jobs(const std::vector<MsmJob>& jobs, const M
 
 // the (digit, point) pairs of every job sorted by bucket: cnt / off of every bucket, toff = its first task
 template <class HF, class DF>
-zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st) {
+zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st, const zkdev::MsmSelSet& sel_set) {
     const size_t nj = p.nj;
     const MsmJob* dj = jobs_d.as<MsmJob>();
     if (p.lds_sort) {
@@ -184,7 +185,7 @@ zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st) {
         ProfScope ps("msm_sort_lds", st);
         ZK_LAUNCH_SYNC(zkdev::k_msm_sort_lds, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), (size_t)nb * 4, st, dj, c,
                        cnt.as<uint32_t>(), off.as<uint32_t>(), toff.as<uint32_t>(), ntasks.as<uint32_t>(),
-                       pairs.as<uint32_t>(), p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u);
+                       pairs.as<uint32_t>(), p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u, sel_set);
         return ZK_OK;
     }
     // two-level counting sort, every per-digit atomic in LDS (msm.h)
@@ -198,11 +199,11 @@ zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st) {
     {
         ProfScope ps("msm_sort_coarse", st);
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_count, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse, coarse_cnt,
-                       blockbase.as<uint32_t>(), per_wg);
+                       blockbase.as<uint32_t>(), per_wg, sel_set);
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
                        (const uint32_t*)coarse_cnt, coarse_off, (uint32_t*)nullptr, n_coarse);
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scatter, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse,
-                       (const uint32_t*)coarse_off, (const uint32_t*)blockbase.as<uint32_t>(), rank.as<uint2>(), per_wg);
+                       (const uint32_t*)coarse_off, (const uint32_t*)blockbase.as<uint32_t>(), rank.as<uint2>(), per_wg, sel_set);
     }
     {
         ProfScope ps("msm_sort_fine", st);
@@ -444,8 +445,8 @@ zk_status MsmGroup<HF, DF>::normalize2_to_host(const typename MsmGroup<HF, DF>::
 }
 
 template <class HF, class DF>
-zk_status MsmGroup<HF, DF>::run(std::vector<MsmJob>& jobs, std::vector<typename MsmGroup<HF, DF>::HPoint>& out) {
-    ZK_TRY(enqueue(jobs, out, g_stream));
+zk_status MsmGroup<HF, DF>::run(std::vector<MsmJob>& jobs, std::vector<typename MsmGroup<HF, DF>::HPoint>& out, const zkdev::MsmSelSet* sels) {
+    ZK_TRY(enqueue(jobs, out, g_stream, true, sels));
     return collect(g_stream);
 }
 

@@ -379,37 +379,75 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 // z_j P_j = z_j (P_p + P_j) whenever z_p = z_j: an identity in the group, for every assignment.
 // A member of a group of equal bases takes part with its own point (the group's): the group's sum leaves out the members whose
 // term went into a pair.
+//
+// Longer terms (`sel_w` / `sel_c` given, cap <= PAIR_RUN_CAP; without them cap = 2 and everything is as above).  A run is cut
+// into BLOCKS of `cap` members: the member at position t is member t mod cap of block t / cap.  Behind the q* arrays, pairs then
+// has one more word per variable, a byte per query [a | b_g2 | l | b_g1]: bit l - 1 is set where the query has the base of
+// the l chain members that end at this variable, l = 3 ... cap (l = 2 is q*[j] >= 0; such a base exists only where the l - 1
+// links behind it all have their pair bases).  A block is split into terms from its start: the LONGEST term that starts at
+// the first member not yet taken and whose base the query has - one member alone where there is none - then on behind it.
+// So a link without a pair base ends a term, and where a longer base is absent (the sum came out as the identity) the block
+// falls back to the longest shorter one that is there: the same split in every thread of the block and in the host's counter
+// (value_pairs.h count_merges).  A term of l >= 2 members is emitted by its LAST variable into the pair slot that variable
+// owns, with l in the byte beside the slot (sel_w: the [pa | pb2] slots of the witness vector, sel_c: the [pl | pb1 | (fold:
+// pa)] slots of the C job, per proof); the other members' own slots get 0, and a pair slot that is 0 has the byte 0.  The sort
+// of the job picks the base of l members by the byte (msm.h MsmSelSet).
 constexpr uint32_t PAIR_WALK_MAX = 32;
+constexpr uint32_t PAIR_RUN_CAP = 8;   // (a byte per member in a 64-bit word, a nibble per query for the length: pair_decide)
 // Which queries keep the term of variable i of the witness zp, whose value is raw (canonical) - bits: A, B2, L, B1 - and in
-// *emit the queries in which it is the second variable of a merged pair (its pair's slot gets the value where there is one).
-// Only the chains that serve a query of `mask` are walked: the bits of the others stay set in the answer.
+// *emit the queries in which it is the last variable of a merged term, as the term's length in the query's nibble (its pair's
+// slot gets the value where there is one).  Only the chains that serve a query of `mask` are walked: the bits of the others
+// stay set in the answer.  longer: pairs has the words of the longer bases.
 ZK_DI uint32_t pair_decide(const int32_t* __restrict__ pairs, uint32_t nv, const uint32_t* __restrict__ zp, uint32_t i, const Fr& raw,
-                           uint32_t* emit, uint32_t mask = 15u) {
+                           uint32_t* emit, uint32_t mask = 15u, uint32_t cap = 2u, bool longer = false) {
     uint32_t own = 15u;
     *emit = 0u;
     if (raw == Fr::zero()) return own;
     const int32_t* q = pairs + 6 * (size_t)nv;
+    const int32_t* avail = pairs + 10 * (size_t)nv;
+    const uint32_t lmask = 0xfcu & ((1u << cap) - 1u);
 #pragma unroll 1
     for (uint32_t c = 0; c < 3; c++) {   // the chains of A, B, L; the queries each serves as bits
-        if (!(mask & (c == 0 ? 1u : c == 1 ? 10u : 4u))) continue;
+        const uint32_t serves = c == 0 ? 1u : c == 1 ? 10u : 4u;
+        if (!(mask & serves)) continue;
         const int32_t* pred = pairs + 2 * c * (size_t)nv;
         const int32_t* succ = pred + nv;
+        const uint32_t q0 = c == 0 ? 0u : c == 1 ? 1u : 2u, q1 = 3u;   // the queries of the chain (q1: the B chains' second)
         uint32_t t = 0;
         for (int32_t k = pred[i]; k >= 0 && t < PAIR_WALK_MAX && ld_fr(zp + (size_t)k * 8) == raw; k = pred[k]) t++;
-        // the link whose pair takes the variable's term, where the query has that pair
-        int32_t e = -1;
-        if (t & 1u) {
-            e = (int32_t)i;
-            *emit |= c == 0 ? 1u : c == 1 ? 10u : 4u;
-        } else {
-            const int32_t sc = succ[i];
-            if (sc >= 0 && ld_fr(zp + (size_t)sc * 8) == raw) e = sc;
+        // the block of i: n members, i at position u; byte e of a0 / a1 = the lengths of the terms that can end at member e
+        const uint32_t u = t % cap;
+        uint32_t n = u + 1;
+        uint64_t a0 = 0, a1 = 0;
+        auto member = [&](int32_t k, uint32_t e) {
+            const uint32_t w = longer ? (uint32_t)avail[k] : 0u;
+            a0 |= (uint64_t)((q[q0 * (size_t)nv + k] >= 0 ? 2u : 0u) | ((w >> (8 * q0)) & lmask)) << (8 * e);
+            if (c == 1) a1 |= (uint64_t)((q[q1 * (size_t)nv + k] >= 0 ? 2u : 0u) | ((w >> (8 * q1)) & lmask)) << (8 * e);
+        };
+        {
+            int32_t k = (int32_t)i;
+            for (uint32_t e = u + 1; e-- > 0; k = e ? pred[k] : k) member(k, e);
         }
-        if (e >= 0) {
-            if (c == 0 && q[e] >= 0) own &= ~1u;
-            if (c == 1 && q[nv + e] >= 0) own &= ~2u;
-            if (c == 2 && q[2 * (size_t)nv + e] >= 0) own &= ~4u;
-            if (c == 1 && q[3 * (size_t)nv + e] >= 0) own &= ~8u;
+        for (int32_t k = succ[i]; n < cap && k >= 0 && ld_fr(zp + (size_t)k * 8) == raw; k = succ[k]) member(k, n++);
+#pragma unroll 1
+        for (uint32_t h = 0; h < (c == 1 ? 2u : 1u); h++) {
+            const uint64_t a = h ? a1 : a0;
+            const uint32_t query = h ? q1 : q0;
+            uint32_t s = 0, len;
+            for (;;) {   // the terms of the block from its start, up to the one that holds i
+                len = 1;
+                for (uint32_t l = n - s; l >= 2; l--)
+                    if ((a >> (8 * (s + l - 1) + (l - 1))) & 1u) {
+                        len = l;
+                        break;
+                    }
+                if (u < s + len) break;
+                s += len;
+            }
+            if (len >= 2) {
+                own &= ~(1u << query);
+                if (u == s + len - 1) *emit |= len << (4 * query);
+            }
         }
     }
     return own;
@@ -417,7 +455,7 @@ ZK_DI uint32_t pair_decide(const int32_t* __restrict__ pairs, uint32_t nv, const
 static __global__ void __launch_bounds__(256)
 k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ wit, const uint32_t* __restrict__ tail,
                 const zkrt::CJobLayout L, uint32_t mont, uint32_t* bad, const uint32_t* __restrict__ groups,
-                const int32_t* __restrict__ pairs = nullptr) {
+                const int32_t* __restrict__ pairs = nullptr, uint8_t* sel_w = nullptr, uint8_t* sel_c = nullptr, uint32_t cap = 2u) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= L.w_end + L.gb1) return;
     const size_t p = blockIdx.y;
@@ -426,6 +464,7 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
     Fr r = ld_fr(tail + (p * 3 + 1) * 8);   // plain
     Fr sR = fold ? mul(ld_fr(tail + (p * 3 + 2) * 8), Fr::r2()) : Fr::zero();   // s in Montgomery form
     Fr v;
+    const bool longer = sel_w != nullptr && sel_c != nullptr;   // (terms of up to `cap` members, their lengths in the bytes)
     if (i >= L.w_sum_a) {
         const uint32_t g = i - L.w_sum_a;
         const uint32_t* mem = groups + (L.ga + L.gb2 + L.gb1 + 1);
@@ -436,7 +475,7 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
             const Fr raw = ld_fr(wit + (p * nv + mem[k]) * 8);
             if (fr_geq_r(raw)) continue;   // (the member's own thread raises the flag)
             uint32_t emit;
-            if (with_pairs && !(pair_decide(pairs, nv, wit + p * (size_t)nv * 8, mem[k], raw, &emit, bit) & bit)) continue;   // (in a pair)
+            if (with_pairs && !(pair_decide(pairs, nv, wit + p * (size_t)nv * 8, mem[k], raw, &emit, bit, longer ? cap : 2u, longer) & bit)) continue;   // (in a pair)
             sum = add(sum, raw);
         }
         if (i < L.w_end) {
@@ -472,14 +511,24 @@ k_build_scalars(uint32_t* wit_out, uint32_t* cvec, const uint32_t* __restrict__ 
         if (pairs && L.w_b2v) {
             const int32_t* q = pairs + 6 * (size_t)nv;
             qa = q[i]; qb2 = q[nv + i]; ql = q[2 * (size_t)nv + i]; qb1 = q[3 * (size_t)nv + i];
-            own = pair_decide(pairs, nv, wit + p * (size_t)nv * 8, i, raw, &emit);
+            own = pair_decide(pairs, nv, wit + p * (size_t)nv * 8, i, raw, &emit, 15u, longer ? cap : 2u, longer);
+            const uint32_t la = emit & 15u, lb2 = (emit >> 4) & 15u, ll = (emit >> 8) & 15u, lb1 = (emit >> 12) & 15u;
             const Fr zero = Fr::zero();
             st_fr(wit_out + (p * L.wstride + L.w_b2v + i) * 8, own & 2u ? v : zero);
-            if (qa >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_a + qa) * 8, emit & 1u ? v : zero);
-            if (qb2 >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_b2 + qb2) * 8, emit & 2u ? v : zero);
-            if (ql >= 0) st_fr(cv + (size_t)(L.pair_l + ql) * 8, emit & 4u ? v : zero);
-            if (qb1 >= 0) st_fr(cv + (size_t)(L.pair_b1 + qb1) * 8, emit & 8u ? rz : zero);
-            if (fold && qa >= 0) st_fr(cv + (size_t)(L.pair_a + qa) * 8, emit & 1u ? sz : zero);
+            if (qa >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_a + qa) * 8, la ? v : zero);
+            if (qb2 >= 0) st_fr(wit_out + (p * L.wstride + L.w_pair_b2 + qb2) * 8, lb2 ? v : zero);
+            if (ql >= 0) st_fr(cv + (size_t)(L.pair_l + ql) * 8, ll ? v : zero);
+            if (qb1 >= 0) st_fr(cv + (size_t)(L.pair_b1 + qb1) * 8, lb1 ? rz : zero);
+            if (fold && qa >= 0) st_fr(cv + (size_t)(L.pair_a + qa) * 8, la ? sz : zero);
+            if (longer) {   // the length beside every pair slot written above (a zero value emits nothing: 0)
+                uint8_t* sw = sel_w + p * (size_t)L.sel_w;
+                uint8_t* sc = sel_c + p * (size_t)L.sel_c;
+                if (qa >= 0) sw[qa] = (uint8_t)la;
+                if (qb2 >= 0) sw[L.pa + qb2] = (uint8_t)lb2;
+                if (ql >= 0) sc[ql] = (uint8_t)ll;
+                if (qb1 >= 0) sc[L.pl + qb1] = (uint8_t)lb1;
+                if (fold && qa >= 0) sc[L.pl + L.pb1 + qa] = (uint8_t)la;
+            }
         }
         if (i >= L.n_in) st_fr(cv + (size_t)(L.aux + (i - L.n_in)) * 8, own & 4u ? v : Fr::zero());
         st_fr(cv + (size_t)(L.rz + i) * 8, own & 8u ? rz : Fr::zero());

@@ -77,6 +77,9 @@ struct CJobLayout {
     uint32_t w_end;                                            // witness vector: the end of the sums (its stride without pairs)
     uint32_t w_b2v, w_pair_a, w_pair_b2;                       // ... with pairs
     uint32_t pair_l, pair_b1, pair_a;                          // C job, with pairs (pair_a: with fold)
+    // the bytes beside the pair slots (ntt.h k_build_scalars: the length of the term in the slot), per proof: the strides of
+    // the array of the witness vector's slots [pa | pb2] and of the C job's [pl | pb1 | (fold: pa)]
+    uint32_t sel_w, sel_c;
 };
 
 // The counts of value pairs per query, in the order the layout takes them
@@ -118,6 +121,8 @@ inline CJobLayout cjob_layout(uint32_t n_in, uint32_t n_aux, uint32_t head, uint
         L.pair_l = section(pc.l);
         L.pair_b1 = section(pc.b1);
         if (fold) L.pair_a = section(pc.a);
+        L.sel_w = pc.a + pc.b2;
+        L.sel_c = pc.l + pc.b1 + (fold ? pc.a : 0);
     }
     L.cstride = at;
     return L;

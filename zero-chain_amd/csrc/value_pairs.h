@@ -6,6 +6,8 @@
 // per LINKED pair of variables (zkamd.cpp derived_pairs) and k_build_scalars (ntt.h) decides proof by proof, on the values,
 // which links merge.  The links are static: the chains below are a function of the circuit alone.  They affect what a proof
 // costs and never its bytes - the identity holds for every assignment.
+// The same holds for a stretch of up to RUN_MAX consecutive members of a chain that hold one value, z (P_1 + ... + P_l): a base
+// more per link and length (RUN_MAX below).
 //
 // The chains come from PROBES: the library's own host calculator (transfer_witness.h) on eight built-in statements with fixed
 // seeds.  For every variable of a probe, the nearest earlier variable with the same full-width value is recorded; a link is
@@ -193,15 +195,48 @@ inline std::vector<int32_t> chains_of(const std::vector<std::vector<Fr>>& probes
     return out;
 }
 
-// The rule of k_build_scalars (ntt.h) on one witness, counted: how many terms a query merges.  pred: the chains of the query,
-// q[j] >= 0 where it has the pair base of the link (pred[j], j).
-inline uint64_t count_merges(const int32_t* pred, const int32_t* q, const std::vector<Fr>& z) {
+// The longest stretch of a run that becomes ONE term z (P_1 + ... + P_l): a run is cut into blocks of RUN_MAX members (ntt.h
+// k_build_scalars has the rule).  Every size follows from it: RUN_MAX - 2 more bases per link (zkamd.cpp derived_pairs), as
+// many alternates per pair slot (msm.h MsmSelRange::alt), one bit per length in the words of k_build_scalars.  2 ... 8; 2 is the
+// rule of pairs alone.  (ZK_RUN_MAX: a second library for measurements.)
+#ifndef ZK_RUN_MAX
+#define ZK_RUN_MAX 4
+#endif
+constexpr uint32_t RUN_MAX = ZK_RUN_MAX;
+static_assert(RUN_MAX >= 2 && RUN_MAX <= 8, "a term's length is a nibble and a bit of a byte in k_build_scalars");
+
+// The word k_build_scalars reads per variable j beside q*[j]: a byte per query [a | b_g2 | l | b_g1], bit l - 1 set where the
+// query has the base of the l chain members that end at j, l = 3 ... RUN_MAX (l = 2 is q*[j] >= 0)
+inline uint32_t avail_byte(const int32_t* q, const int32_t* avail, uint32_t query, size_t j, uint32_t cap) {
+    uint32_t b = q[j] >= 0 ? 2u : 0u;
+    if (avail) b |= ((uint32_t)avail[j] >> (8 * query)) & 0xfcu & ((1u << cap) - 1u);
+    return b;
+}
+
+// The rule of k_build_scalars (ntt.h) on one witness, counted: how many terms a query saves.  pred, succ: the chains of the
+// query; q[j] >= 0 where it has the pair base of the link (pred[j], j); avail (or null: pairs alone): the words above, `query`
+// the byte of this query in them; cap: the longest term, <= RUN_MAX.  The same blocks and the same split as the kernel's.
+inline uint64_t count_merges(const int32_t* pred, const int32_t* succ, const int32_t* q, const int32_t* avail, uint32_t query,
+                             const std::vector<Fr>& z, uint32_t cap = RUN_MAX) {
     uint64_t merged = 0;
     for (size_t j = 0; j < z.size(); j++) {
-        if (q[j] < 0 || z[j].is_zero()) continue;
+        if (z[j].is_zero()) continue;
         uint32_t t = 0;
         for (int32_t k = pred[j]; k >= 0 && t < CHAIN_MAX && z[k] == z[j]; k = pred[k]) t++;
-        merged += t & 1u;
+        if (t % cap) continue;   // j starts a block
+        uint32_t av[8], n = 1;
+        av[0] = 0;
+        for (int32_t k = succ[j]; n < cap && k >= 0 && z[k] == z[j]; k = succ[k]) av[n++] = avail_byte(q, avail, query, (size_t)k, cap);
+        for (uint32_t s = 0; s < n;) {   // the longest term that starts at s and has its base, then on behind it
+            uint32_t len = 1;
+            for (uint32_t l = n - s; l >= 2; l--)
+                if ((av[s + l - 1] >> (l - 1)) & 1u) {
+                    len = l;
+                    break;
+                }
+            merged += len - 1;
+            s += len;
+        }
     }
     return merged;
 }

@@ -283,10 +283,26 @@ struct zk_params {
         uint32_t base_l = 0, base_b1 = 0, base_a = 0, base_b2 = 0;
         PairCounts n;
         uint32_t exp_a = 0, exp_b2 = 0, exp_l = 0, exp_b1 = 0;
+        // Value runs (value_pairs.h RUN_MAX): for every link j and l = 3 ... RUN_MAX one more base, the sum of the l chain
+        // members that end at j, where the l - 1 links behind it all have their pair bases and the sum is not the identity.
+        // Per query [a | b_g2 | l | b_g1]: alt[pair slot * (RUN_MAX - 2) + (l - 3)] = the base's place among the query's
+        // longer bases or -1; xbase = where those lie (behind the pair sections of g1d; behind the pairs of g2p); xn = how
+        // many there are per l.  links carries one more word per variable, their bits (ntt.h k_build_scalars).
+        std::vector<int32_t> alt[4];
+        uint32_t xbase[4] = {0, 0, 0, 0};
+        uint32_t xn[4][7] = {};
+#ifdef ZK_TEST_HOOKS
+        // (zk_hook_value_runs: what ensure_derived put into the tables at the places the longer bases have - G1 [l | b_g1 | a] from
+        // xbase[2] on, G2 from xbase[1] on - and the D block of the derived set, whose aux points the sums of the l query are over)
+        std::vector<HG1A> hook_g1, hook_d;
+        std::vector<HG2A> hook_g2;
+#endif
     } prs;
     MsmG1 g1da;                     // the A jobs of a split chunk over g1d's table (its copy of the A query + the pairs)
-    MsmG2 g2p, g2p_lone;            // [b_g2 | beta_2 | delta_2 | pairs]
+    MsmG2 g2p, g2p_lone;            // [b_g2 | beta_2 | delta_2 | pairs | longer runs]
     DevBuf map_ad, map_b2d, pairs_dev;
+    DevBuf alt_c, alt_a, alt_b2;    // MsmSelRange::alt of the C, A and B2 jobs: absolute table positions per pair slot and length
+    DevBuf sel_w, sel_c;            // MsmSelRange::sel: the bytes k_build_scalars writes beside the pair slots, per proof
     PairCounts mpairs;              // the pairs the maps in use were built with (ensure_maps; none under ZKAMD_MERGE_VALUES=0)
     std::vector<uint8_t> enc_a, enc_b1, enc_b2;   // the encodings of the three queries (the sums of two bases are made from them)
     // cached per-circuit index maps (keyed by the density bytes)
@@ -628,7 +644,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
     key.push_back(merge ? 1 : 0);
     const uint32_t nv = n_in + n_aux;
     // value pairs: over the derived set that carries them (its serial is in the key), unless ZKAMD_MERGE_VALUES=0
-    const bool pairs = merge_values_on() && P->drv.ready && P->prs.ready && P->prs.links.size() == 10 * (size_t)nv;
+    const bool pairs = merge_values_on() && P->drv.ready && P->prs.ready && P->prs.links.size() == 11 * (size_t)nv;
     key.push_back(pairs ? 1 : 0);
     if (key == P->dens_key) return ZK_OK;
     const PairCounts pc = pairs ? P->prs.n : PairCounts();
@@ -788,6 +804,19 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
         ZK_TRY(upload(P->map_ad, mad));
         ZK_TRY(upload(P->map_b2d, mbd));
         ZK_TRY(upload(P->pairs_dev, P->prs.links));
+        // MsmSelRange::alt: per pair slot of the job, in the order of its sections, the table positions of the longer bases
+        auto alts = [&](std::initializer_list<uint32_t> queries) {
+            std::vector<int32_t> out;
+            for (uint32_t query : queries)
+                for (int32_t x : P->prs.alt[query]) out.push_back(x < 0 ? -1 : (int32_t)(P->prs.xbase[query] + (uint32_t)x));
+            if (out.empty()) out.push_back(-1);
+            return out;
+        };
+        if (zkpairs::RUN_MAX > 2) {
+            ZK_TRY(upload(P->alt_c, alts({2u, 3u, 0u})));   // [pl | pb1 | (fold: pa)]
+            ZK_TRY(upload(P->alt_a, alts({0u})));
+            ZK_TRY(upload(P->alt_b2, alts({1u})));
+        }
     }
     gptr.insert(gptr.end(), gmem.begin(), gmem.end());
     ZK_TRY(upload(P->grp_dev, gptr));
@@ -812,6 +841,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // One chunk of proofs: the plan (prove_plan.h), what its stages hand to each other, and the stages in the order they run.
 // derived: a, b, c are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over
 // the derived bases (ensure_derived), whose H scalars are those of the live rows.
+static_assert(zkpairs::RUN_MAX <= zkdev::PAIR_RUN_CAP, "k_build_scalars holds a block of a run in one 64-bit word");
 static_assert(PROVE_FOLD_IN_MSM_MAX == MSM_FEW_JOBS, "the fold rides in the multiexp up to the few-jobs limit of a launch set");
 typedef zkdev::XYZZ<zkdev::Fq> DP1;
 struct ChunkRun {
@@ -828,6 +858,7 @@ struct ChunkRun {
     uint32_t *wit, *cvec, *bad;
     const DP1* a_dev = nullptr;   // A of every proof, where the G1 launch sets left it
     bool pairs = false;      // the layout has the sections of the value pairs: the A and B2 jobs over their tables and maps
+    static constexpr uint32_t RUN_W = zkpairs::RUN_MAX - 2;   // longer bases per pair slot (none: the jobs go without bytes)
 
     // ---- scalars [inputs | aux | 1 | r | s | sums of the A groups | of the B2 groups] per proof, plain, and the merged C job's
     // but for its H block (prove_plan.h CJobLayout)
@@ -857,10 +888,16 @@ struct ChunkRun {
         HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
         ZK_TRY(P->cvec.ensure(np * (size_t)L.cstride * 32));
         cvec = P->cvec.as<uint32_t>();
+        const bool bytes = pairs && RUN_W;   // (at RUN_MAX = 2 a pair slot is its pair: nothing to name)
+        if (bytes) {   // (every byte is written: by the thread that writes its pair slot)
+            ZK_TRY(P->sel_w.ensure(np * (size_t)L.sel_w + 1));
+            ZK_TRY(P->sel_c.ensure(np * (size_t)L.sel_c + 1));
+        }
         // (the same launch: a thread per variable, three for the tail, one per group)
         ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.w_end + L.gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
                   (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), L, mont ? 1u : 0u, bad,
-                  P->grp_dev.as<uint32_t>(), pairs ? (const int32_t*)P->pairs_dev.as<int32_t>() : (const int32_t*)nullptr);
+                  P->grp_dev.as<uint32_t>(), pairs ? (const int32_t*)P->pairs_dev.as<int32_t>() : (const int32_t*)nullptr,
+                  bytes ? P->sel_w.as<uint8_t>() : (uint8_t*)nullptr, bytes ? P->sel_c.as<uint8_t>() : (uint8_t*)nullptr, zkpairs::RUN_MAX);
         return ZK_OK;
     }
 
@@ -876,7 +913,11 @@ struct ChunkRun {
         }
         HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
         HIP_TRY(hipStreamWaitEvent(side, g_ev_fork, 0));
-        ZK_TRY(G2->enqueue(P->jobs2, P->res2, side, false));
+        // the bytes of the jobs' pair slots: the lengths of their terms pick the bases (msm.h MsmSelSet)
+        const CJobLayout& L = plan.layout;
+        zkdev::MsmSelSet sels = {};
+        if (pairs && RUN_W) sels.r[0] = {P->sel_w.as<uint8_t>() + L.pa, P->alt_b2.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_b2, L.pb2, RUN_W};
+        ZK_TRY(G2->enqueue(P->jobs2, P->res2, side, false, &sels));
         ZK_TRY(P->pin_g2.ensure(np * sizeof(HG2)));
         if (plan.host_norm) ZK_TRY(G2->export_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));
         else ZK_TRY(G2->normalize_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));   // B in affine form
@@ -950,15 +991,26 @@ struct ChunkRun {
             }
             (split ? P->jobs1a : P->jobs1).push_back(ja);
         }
+        // the ranges of jobs whose pair slots follow the bytes (msm.h MsmSelSet): the C' jobs, the A jobs
+        const CJobLayout& L = plan.layout;
+        zkdev::MsmSelSet sc = {}, sa = {};
+        if (pairs && RUN_W) {
+            sc.r[0] = {P->sel_c.as<uint8_t>(), P->alt_c.as<int32_t>(), 0u, (uint32_t)np, L.sel_c, L.pair_l, L.sel_c, RUN_W};
+            sa.r[0] = {P->sel_w.as<uint8_t>(), P->alt_a.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_a, L.pa, RUN_W};
+            if (!split) {   // (one set: the A jobs behind the C' jobs)
+                sc.r[1] = sa.r[0];
+                sc.r[1].job0 = (uint32_t)np;
+            }
+        }
         if (split) {
             MsmG1& G1A = pairs ? P->g1da : P->g1a;
-            ZK_TRY(G1A.enqueue(P->jobs1a, P->res1a, side, false));
+            ZK_TRY(G1A.enqueue(P->jobs1a, P->res1a, side, false, &sa));
             a_dev = G1A.res_dev;
             HIP_TRY(hipEventRecord(g_ev_join, side));
-            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false));
+            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false, &sc));
             HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when the side stream is the main one)
         } else {
-            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false));
+            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false, &sc));
             a_dev = G1C->res_dev + np;
         }
         return ZK_OK;
@@ -1294,6 +1346,8 @@ const zkr1cs::System& builtin_system(zkpairs::Circuit c) {
 struct PairBases {
     std::vector<HG1A> l, b1, a;
     std::vector<HG2A> b2;
+    std::vector<HG1A> xl, xb1, xa;   // the longer runs' (value_pairs.h RUN_MAX), behind all of the above
+    std::vector<HG2A> xb2;
 };
 template <class A>
 A sum_of_two(const A& x, const A& y) {
@@ -1382,8 +1436,9 @@ void derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>& set,
     };
     run_threads(nthreads, part);
     // links = [the chains | qa | qb2 | ql | qb1]
-    X.links.assign(10 * (size_t)nv, -1);
+    X.links.assign(11 * (size_t)nv, -1);
     std::copy(chains.begin(), chains.end(), X.links.begin());
+    std::fill(X.links.begin() + 10 * (size_t)nv, X.links.end(), 0);   // (the bits of the longer bases, below)
     auto keep = [&](const std::vector<Cand>& c, const auto& sums, auto& bases, int32_t* q) {
         for (size_t k = 0; k < c.size(); k++)
             if (!sums[k].is_inf()) {
@@ -1397,13 +1452,57 @@ void derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>& set,
     X.n.b2 = keep(cb2, sb2, out.b2, q + nv);
     X.n.l = keep(cl, sl, out.l, q + 2 * (size_t)nv);
     X.n.b1 = keep(cb1, sb1, out.b1, q + 3 * (size_t)nv);
+    // The longer runs: for every link j that has its pair base and l = 3 ... RUN_MAX, the sum of the l chain members that end at
+    // j, as long as the links behind it have their pair bases.  The thread of j walks back from j, adding one member per length
+    // (so P_j + P_pred is added again, per link) and normalises every length it keeps (an inversion each): 49 ms of binding for
+    // the transfer key at 4.  A sum that comes out as the identity has no base and no bit: k_build_scalars then splits the run
+    // into shorter terms.
+    int32_t* const avail = &X.links[10 * (size_t)nv];
+    auto longer = [&](uint32_t query, uint32_t n_pairs, const int32_t* pred, const int32_t* qq, const std::vector<int32_t>& pos, auto&& point,
+                      auto& bases) {
+        typedef typename std::decay_t<decltype(bases)>::value_type A;
+        typedef decltype(A().x) F;
+        constexpr uint32_t W = zkpairs::RUN_MAX - 2;
+        X.alt[query].assign((size_t)n_pairs * W, -1);
+        if (!W) return;
+        std::vector<uint32_t> js;
+        for (uint32_t j = 0; j < nv; j++)
+            if (qq[j] >= 0 && qq[pred[j]] >= 0) js.push_back(j);
+        std::vector<A> sums(js.size() * W, A::inf());
+        const unsigned nt = host_threads(js.size() / 64 + 1, 32);
+        auto work = [&](unsigned t) {
+            for (size_t k = js.size() * t / nt; k < js.size() * (t + 1) / nt; k++) {
+                const uint32_t j = js[k];
+                int32_t cur = pred[j];
+                auto acc = zkhost::padd(zkhost::Point<F>::from_affine(point(pos[j])), zkhost::Point<F>::from_affine(point(pos[cur])));
+                for (uint32_t l = 3; l <= zkpairs::RUN_MAX && qq[cur] >= 0; l++) {
+                    cur = pred[cur];
+                    acc = zkhost::padd(acc, zkhost::Point<F>::from_affine(point(pos[cur])));
+                    sums[k * W + (l - 3)] = zkhost::to_affine(acc);
+                }
+            }
+        };
+        run_threads(nt, work);
+        for (size_t k = 0; k < js.size(); k++)
+            for (uint32_t l = 3; l <= zkpairs::RUN_MAX; l++)
+                if (!sums[k * W + (l - 3)].is_inf()) {
+                    X.alt[query][(size_t)qq[js[k]] * W + (l - 3)] = (int32_t)bases.size();
+                    bases.push_back(sums[k * W + (l - 3)]);
+                    avail[js[k]] |= (int32_t)(1u << (8 * query + (l - 1)));
+                    X.xn[query][l - 3]++;
+                }
+    };
+    longer(0, X.n.a, pred_a, q, pa, [&](int32_t at) { return g1_at(P->enc_a, at); }, out.xa);
+    longer(1, X.n.b2, pred_b, q + nv, pb2, [&](int32_t at) { return g2_at(P->enc_b2, at); }, out.xb2);
+    longer(2, X.n.l, pred_l, q + 2 * (size_t)nv, pl, [&](int32_t at) { return set[at]; }, out.xl);
+    longer(3, X.n.b1, pred_b, q + 3 * (size_t)nv, pb1, [&](int32_t at) { return g1_at(P->enc_b1, at); }, out.xb1);
     // what a proof is expected to merge, from the probes
     uint64_t merged[4] = {0, 0, 0, 0};
     for (const std::vector<Fr>& z : probes) {
-        merged[0] += zkpairs::count_merges(pred_a, q, z);
-        merged[1] += zkpairs::count_merges(pred_b, q + nv, z);
-        merged[2] += zkpairs::count_merges(pred_l, q + 2 * (size_t)nv, z);
-        merged[3] += zkpairs::count_merges(pred_b, q + 3 * (size_t)nv, z);
+        merged[0] += zkpairs::count_merges(pred_a, pred_a + nv, q, avail, 0, z);
+        merged[1] += zkpairs::count_merges(pred_b, pred_b + nv, q + nv, avail, 1, z);
+        merged[2] += zkpairs::count_merges(pred_l, pred_l + nv, q + 2 * (size_t)nv, avail, 2, z);
+        merged[3] += zkpairs::count_merges(pred_b, pred_b + nv, q + 3 * (size_t)nv, avail, 3, z);
     }
     const uint64_t np = probes.size();
     X.exp_a = (uint32_t)(merged[0] / np);
@@ -1540,6 +1639,18 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
     X.base_a = (uint32_t)pts.size();
     pts.insert(pts.end(), pb.a.begin(), pb.a.end());
     X.base_b2 = P->n_b2 + 2;
+    // (the longer runs' bases behind every pair section: the pair sections stay where a set without them has them)
+    X.xbase[2] = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.xl.begin(), pb.xl.end());
+    X.xbase[3] = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.xb1.begin(), pb.xb1.end());
+    X.xbase[0] = (uint32_t)pts.size();
+    pts.insert(pts.end(), pb.xa.begin(), pb.xa.end());
+    X.xbase[1] = X.base_b2 + X.n.b2;
+#ifdef ZK_TEST_HOOKS
+    X.hook_g1.assign(pts.begin() + X.xbase[2], pts.end());
+    X.hook_d.assign(pts.begin() + 2 * (size_t)n_rows, pts.begin() + 2 * (size_t)n_rows + nv);
+#endif
     const bool values = merge_values_on();   // (the widths of a run with the switch off stay those of a set without pairs)
     const uint32_t c_set = pick_window(live + P->n_b1 - (values ? std::min<size_t>(X.exp_l + X.exp_b1, live) : 0), 1);
     ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, c_set));
@@ -1553,6 +1664,10 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
              zkhost::g2_from_uncompressed(P->vk_bytes.data() + 672, &pts2[P->n_b2 + 1]) == zkhost::DEC_OK;
         if (!ok) return fail(ZK_ERR_IO, "internal: the b_g2 query does not decode a second time");
         pts2.insert(pts2.end(), pb.b2.begin(), pb.b2.end());
+        pts2.insert(pts2.end(), pb.xb2.begin(), pb.xb2.end());
+#ifdef ZK_TEST_HOOKS
+        X.hook_g2.assign(pts2.begin() + X.xbase[1], pts2.end());
+#endif
         const uint32_t c2 = values ? pick_window(P->n_b2 - std::min(X.exp_b2, P->n_b2), 2) : P->g2.c;
         ZK_TRY(P->g2p.build(pts2, c2, false, "pair bases (G2)"));
         P->g2p_lone.alias(P->g2p, getenv("ZKAMD_WINDOW_BITS_G2") || c2 <= 10 ? c2 : 10u);
@@ -1572,6 +1687,10 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
         fprintf(stderr, "[zkamd] value pairs: bases a %u, b_g2 %u, l %u, b_g1 %u; merges expected per proof %u, %u, %u, %u; widths "
                         "C' %u, A %u, G2 %u; G2 table %.2f GB\n", X.n.a, X.n.b2, X.n.l, X.n.b1, X.exp_a, X.exp_b2, X.exp_l, X.exp_b1,
                 c_set, P->g1da.c, P->g2p.c, (double)P->g2p.bytes / 1e9);
+    if (getenv("ZKAMD_TRACE_HOST") && X.ready)
+        for (uint32_t l = 3; l <= zkpairs::RUN_MAX; l++)
+            fprintf(stderr, "[zkamd] value runs: bases of %u members: a %u, b_g2 %u, l %u, b_g1 %u\n", l, X.xn[0][l - 3], X.xn[1][l - 3],
+                    X.xn[2][l - 3], X.xn[3][l - 3]);
     return ZK_OK;
 }
 
@@ -2405,9 +2524,11 @@ zk_status zk_hook_chains_finalize(int32_t* pred, int32_t* succ, uint32_t nv) try
 // ql | qb1] as the kernel reads them (chains as zk_hook_chains_finalize leaves them), counts = the pairs per query [a, b_g2,
 // l, b_g1].  wit_out / cvec_out: the two scalar vectors (layout[0] and layout[1] scalars of 32 bytes; the H block has length 0); layout = [wstride, cstride, w_b2v,
 // w_pair_a, w_pair_b2, aux, rz, r, sz, s, rs, in_tail, pair_l, pair_b1, pair_a, w_one, w_sum_a, w_sum_b2, sum_b1, sum_a].
-zk_status zk_hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t counts[4], const int32_t* links, const uint32_t ngroups[3],
-                                const uint32_t* groups, int fold, const uint8_t* wit, const uint8_t r[32], const uint8_t s[32],
-                                uint8_t* wit_out, size_t wit_cap, uint8_t* cvec_out, size_t cvec_cap, uint32_t layout[20]) try {
+// (avail, cap, sel_*, merges: zk_hook_build_scalars_runs below; null / 2 for the rule of pairs alone)
+static zk_status hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t counts[4], const int32_t* links, const uint32_t ngroups[3],
+                                    const uint32_t* groups, int fold, const uint8_t* wit, const uint8_t r[32], const uint8_t s[32],
+                                    uint8_t* wit_out, size_t wit_cap, uint8_t* cvec_out, size_t cvec_cap, uint32_t layout[20],
+                                    const int32_t* avail, uint32_t cap, uint8_t* sel_w_out, uint8_t* sel_c_out, uint64_t* merges) {
     if (!counts || !links || !ngroups || !groups || !wit || !r || !s || !layout || !n_in) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     ZK_TRY(use_device(0));
     const uint32_t nv = n_in + n_aux;
@@ -2429,10 +2550,17 @@ zk_status zk_hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t co
     std::copy(f, f + 20, layout);
     if (!wit_out || !cvec_out) return ZK_OK;
     if (wit_cap < (size_t)L.wstride * 32 || cvec_cap < (size_t)L.cstride * 32) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
-    DevBuf d_wit, d_tail, d_links, d_grp, d_out, d_cv, d_bad;
+    DevBuf d_wit, d_tail, d_links, d_grp, d_out, d_cv, d_bad, d_sw, d_sc;
     ZK_TRY(d_wit.ensure((size_t)nv * 32));
     ZK_TRY(d_tail.ensure(96));
-    ZK_TRY(d_links.ensure(10 * (size_t)nv * 4));
+    ZK_TRY(d_links.ensure(11 * (size_t)nv * 4));
+    if (avail) {
+        ZK_TRY(d_sw.ensure((size_t)L.sel_w + 1));
+        ZK_TRY(d_sc.ensure((size_t)L.sel_c + 1));
+        HIP_TRY(hipMemcpy(d_links.as<int32_t>() + 10 * (size_t)nv, avail, (size_t)nv * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemset(d_sw.p, 0xff, (size_t)L.sel_w + 1));   // (a byte nobody writes shows)
+        HIP_TRY(hipMemset(d_sc.p, 0xff, (size_t)L.sel_c + 1));
+    }
     const size_t grp_words = (size_t)ng + 1 + groups[ng];
     ZK_TRY(d_grp.ensure(grp_words * 4));
     ZK_TRY(d_out.ensure((size_t)L.wstride * 32));
@@ -2450,11 +2578,102 @@ zk_status zk_hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t co
     HIP_TRY(hipMemset(d_bad.p, 0, 8));
     ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.w_end + L.gb1 + 255) / 256, 1u), dim3(256), 0, g_stream, d_out.as<uint32_t>(),
               d_cv.as<uint32_t>(), (const uint32_t*)d_wit.as<uint32_t>(), (const uint32_t*)d_tail.as<uint32_t>(), L, 0u, d_bad.as<uint32_t>(),
-              (const uint32_t*)d_grp.as<uint32_t>(), (const int32_t*)d_links.as<int32_t>());
+              (const uint32_t*)d_grp.as<uint32_t>(), (const int32_t*)d_links.as<int32_t>(), avail ? d_sw.as<uint8_t>() : (uint8_t*)nullptr,
+              avail ? d_sc.as<uint8_t>() : (uint8_t*)nullptr, cap);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));
     HIP_TRY(hipMemcpy(wit_out, d_out.p, (size_t)L.wstride * 32, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(cvec_out, d_cv.p, (size_t)L.cstride * 32, hipMemcpyDeviceToHost));
+    if (avail) {
+        if (L.sel_w) HIP_TRY(hipMemcpy(sel_w_out, d_sw.p, L.sel_w, hipMemcpyDeviceToHost));
+        if (L.sel_c) HIP_TRY(hipMemcpy(sel_c_out, d_sc.p, L.sel_c, hipMemcpyDeviceToHost));
+        // the host's counter on the same values (value_pairs.h count_merges), per query [a, b_g2, l, b_g1]
+        std::vector<Fr> z(nv);
+        for (uint32_t i = 0; i < nv; i++) memcpy(&z[i], wit + (size_t)i * 32, 32);   // (plain words: only compared)
+        const int32_t* q = links + 6 * (size_t)nv;
+        for (uint32_t k = 0; k < 4; k++) {
+            const int32_t* pred = links + 2 * (size_t)nv * (k == 0 ? 0 : k == 2 ? 2 : 1);
+            merges[k] = zkpairs::count_merges(pred, pred + nv, q + k * (size_t)nv, avail, k, z, cap);
+        }
+    }
+    return ZK_OK;
+}
+zk_status zk_hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_t counts[4], const int32_t* links, const uint32_t ngroups[3],
+                                const uint32_t* groups, int fold, const uint8_t* wit, const uint8_t r[32], const uint8_t s[32],
+                                uint8_t* wit_out, size_t wit_cap, uint8_t* cvec_out, size_t cvec_cap, uint32_t layout[20]) try {
+    return hook_build_scalars(n_in, n_aux, counts, links, ngroups, groups, fold, wit, r, s, wit_out, wit_cap, cvec_out, cvec_cap, layout,
+                              nullptr, 2u, nullptr, nullptr, nullptr);
+} ZK_ABI_CATCH
+// Test hook: the same with terms of up to `cap` members (2 ... value_pairs.h RUN_MAX).  avail: the word per variable that
+// follows the q arrays (a byte per query [a, b_g2, l, b_g1], bit l - 1 = the query has the base of the l members that end
+// there, l >= 3).  sel_w_out / sel_c_out: the bytes beside the pair slots, counts[0] + counts[1] and counts[2] + counts[3]
+// (+ counts[0] with fold) of them; merges: value_pairs.h count_merges on the same values, per query [a, b_g2, l, b_g1].
+zk_status zk_hook_build_scalars_runs(uint32_t n_in, uint32_t n_aux, const uint32_t counts[4], const int32_t* links, const int32_t* avail,
+                                     uint32_t cap, const uint32_t ngroups[3], const uint32_t* groups, int fold, const uint8_t* wit,
+                                     const uint8_t r[32], const uint8_t s[32], uint8_t* wit_out, size_t wit_cap, uint8_t* cvec_out,
+                                     size_t cvec_cap, uint8_t* sel_w_out, uint8_t* sel_c_out, uint64_t merges[4], uint32_t layout[20]) try {
+    if (!avail || !sel_w_out || !sel_c_out || !merges) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (cap < 2 || cap > zkpairs::RUN_MAX) return fail(ZK_ERR_INVALID_ARGUMENT, "the cap is not in 2 ... RUN_MAX");
+    return hook_build_scalars(n_in, n_aux, counts, links, ngroups, groups, fold, wit, r, s, wit_out, wit_cap, cvec_out, cvec_cap, layout,
+                              avail, cap, sel_w_out, sel_c_out, merges);
+} ZK_ABI_CATCH
+// Test hook: the largest cap the library was built for (value_pairs.h RUN_MAX)
+uint32_t zk_hook_run_max(void) { return zkpairs::RUN_MAX; }
+// Test hook: the longer bases of the (key, circuit) pair as ensure_derived bound them.  info = [RUN_MAX, nv, pairs a, b_g2, l,
+// b_g1, xbase a, b_g2, l, b_g1, points in g1, in g2]; with the outputs given: links (11 nv words, as k_build_scalars reads
+// them), alt ([a | b_g2 | l | b_g1], (RUN_MAX - 2) words per pair slot, places among the query's longer bases), g1 / g2 (the
+// uncompressed points the tables got from xbase l / xbase b_g2 on), d (nv uncompressed points: the D block of the derived set)
+zk_status zk_hook_value_runs(const zk_params* p, uint32_t info[12], int32_t* links, int32_t* alt, uint8_t* g1, uint8_t* g2, uint8_t* d) try {
+    if (!p || !info) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    const zk_params::Pairs& X = p->prs;
+    if (!p->drv.ready || !X.ready) return fail(ZK_ERR_INVALID_ARGUMENT, "the key has no value pairs");
+    const uint32_t nv = (uint32_t)(X.links.size() / 11);
+    const uint32_t f[12] = {zkpairs::RUN_MAX, nv, X.n.a, X.n.b2, X.n.l, X.n.b1, X.xbase[0], X.xbase[1], X.xbase[2], X.xbase[3],
+                            (uint32_t)X.hook_g1.size(), (uint32_t)X.hook_g2.size()};
+    std::copy(f, f + 12, info);
+    if (!links) return ZK_OK;
+    if (!alt || !g1 || !g2 || !d) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    std::copy(X.links.begin(), X.links.end(), links);
+    for (int k = 0; k < 4; k++) alt = std::copy(X.alt[k].begin(), X.alt[k].end(), alt);
+    for (size_t i = 0; i < X.hook_g1.size(); i++) zkhost::g1_to_uncompressed(X.hook_g1[i], g1 + i * 96);
+    for (size_t i = 0; i < X.hook_g2.size(); i++) zkhost::g2_to_uncompressed(X.hook_g2[i], g2 + i * 192);
+    for (size_t i = 0; i < X.hook_d.size(); i++) zkhost::g1_to_uncompressed(X.hook_d[i], d + i * 96);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// Test hook: n_jobs multiexp jobs over the bases of a G1 handle, each of n scalars (plain words) through one map, with the
+// bytes and alternates of msm.h MsmSelRange over the slots [sel_first, sel_first + sel_n) (sel: sel_n bytes per job, or
+// null: jobs without them); out: n_jobs uncompressed points
+zk_status zk_hook_msm_select(zk_msm* M, uint32_t n_jobs, uint32_t n, const uint8_t* scalars, const int32_t* map, const uint8_t* sel,
+                             const int32_t* alt, uint32_t sel_first, uint32_t sel_n, uint32_t alt_w, uint8_t* out) try {
+    if (!M || M->group != 1 || M->vb_window || M->slice || !scalars || !map || !out || !n || !n_jobs)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "null argument or not a plain G1 handle");
+    if (sel && (!alt || (size_t)sel_first + sel_n > n || alt_w > 6)) return fail(ZK_ERR_INVALID_ARGUMENT, "the bytes do not fit the job");
+    for (uint32_t i = 0; i < n; i++)
+        if (map[i] < -1 || map[i] >= (int32_t)M->n) return fail(ZK_ERR_INVALID_ARGUMENT, "map out of range");
+    for (size_t i = 0; sel && i < (size_t)sel_n * alt_w; i++)
+        if (alt[i] < -1 || alt[i] >= (int32_t)M->n) return fail(ZK_ERR_INVALID_ARGUMENT, "alternate out of range");
+    ZK_TRY(use_device(M->device));
+    DevBuf d_sc, d_map, d_sel, d_alt;
+    ZK_TRY(d_sc.ensure((size_t)n_jobs * n * 32));
+    ZK_TRY(d_map.ensure((size_t)n * 4));
+    HIP_TRY(hipMemcpy(d_sc.p, scalars, (size_t)n_jobs * n * 32, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d_map.p, map, (size_t)n * 4, hipMemcpyHostToDevice));
+    if (sel) {
+        ZK_TRY(d_sel.ensure((size_t)n_jobs * sel_n + 1));
+        ZK_TRY(d_alt.ensure((size_t)sel_n * alt_w * 4 + 4));
+        HIP_TRY(hipMemcpy(d_sel.p, sel, (size_t)n_jobs * sel_n, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(d_alt.p, alt, (size_t)sel_n * alt_w * 4, hipMemcpyHostToDevice));
+    }
+    std::vector<MsmJob> jobs;
+    for (uint32_t p = 0; p < n_jobs; p++) {
+        MsmJob j = {d_sc.as<uint32_t>() + (size_t)p * n * 8, d_map.as<int32_t>(), n, 0u, (uint32_t)M->n, 0, 0, 0};
+        jobs.push_back(j);
+    }
+    zkdev::MsmSelSet sels = {};
+    if (sel) sels.r[0] = {d_sel.as<uint8_t>(), d_alt.as<int32_t>(), 0u, n_jobs, sel_n, sel_first, sel_n, alt_w};
+    std::vector<HG1> res;
+    ZK_TRY(M->g1.run(jobs, res, &sels));
+    for (uint32_t p = 0; p < n_jobs; p++) zkhost::g1_to_uncompressed(zkhost::to_affine(res[p]), out + (size_t)p * 96);
     return ZK_OK;
 } ZK_ABI_CATCH
 #endif
