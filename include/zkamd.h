@@ -63,6 +63,8 @@
  *                                   EncryptionKey::from_decryption_key, no_std_aliases/keys.rs:250-261, once per key)
  *   zk_confidential_scan_keys, zk_anonymous_scan_keys   - (a block read with every key of such a set in one call: the parts of the
  *                                   two scans above, keys.rs:250-261, elgamal.rs:85-108, crypto_components.rs:168-220)
+ *   zk_balance_keys                 BalanceQuery::get_balance_from_decryption_key for the accounts of a key set in one call
+ *                                   zface/src/utils/getter.rs:135-175 (Ciphertext::add, ::write, ::decrypt: elgamal.rs:85-158)
  *   zk_elgamal_ledger_apply        rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
  *                                   modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350,
  *                                   modules/anonymous-balances/src/lib.rs:169-225, core/primitives/src/ciphertext.rs:90-100
@@ -833,6 +835,43 @@ zk_status zk_asset_block_execute(zk_vk* vk, size_t n, const zk_confidential_xt* 
     size_t n_pool, const uint8_t* nonce_pool, const uint8_t g_epoch[32], uint32_t next_asset_id,
     zk_block_account* accounts_out, zk_block_verdict* verdicts_out, zk_asset_effect* effects_out,
     uint32_t* next_asset_id_out, zk_block_stats* stats_out /* may be NULL */);
+/* The balance query at the head of a transfer (BalanceQuery::get_balance_from_decryption_key, zface/src/utils/getter.rs:135-175)
+ * for the accounts of a key set in ONE call: EncryptedBalance + PendingTransfer (Ciphertext::add), the 64 bytes of the total
+ * (Ciphertext::write), and Ciphertext::decrypt of it over [0, limit) with the search of zk_elgamal_decrypt on the table's device.
+ * accounts: n_accounts x zk_block_account, what the block executors take and return - accounts_out of a block can be passed
+ *   straight in; None is Ciphertext::zero(), the identity encoding twice.  A hit is an account whose enc_key has the 32 bytes of a
+ *   key of `keys`; hits come in account order, and the same key may own several accounts (one per asset id): each is a hit.
+ *   Nothing but the enc_key of an account without a hit is looked at.
+ * The total of a hit is balance + pending where the account carries ZK_BLOCK_ROLLOVER_DUE - what the chain meets at the account's
+ *   next extrinsic, and what the reference's getter always computes: set the bit everywhere for its behaviour - and balance alone
+ *   where it does not; pending is then not read.  No other flag is looked at: accounts_out keeps the bit beside ZK_BLOCK_ROLLED on
+ *   an account its block rolled over, and a caller that wants such an account read as the chain meets it next clears the bit where
+ *   ROLLED is set, as it sets LastRollOver there.  enc_total is what a transfer request carries as enc_balance_left |
+ *   enc_balance_right, value the number remaining_balance = value - amount - fee starts from.
+ * A used point that Ciphertext::read refuses (what zk_jubjub_into_xy decides) is not an error of the call: the hit reports it in
+ *   `refusal` and its neighbours are untouched.
+ * hits_cap, n_hits_out and the NULL / n_accounts == 0 conventions are those of zk_confidential_scan_keys: matching runs first, on
+ *   the host; with more hits than hits_cap the call fails with ZK_ERR_INVALID_ARGUMENT, *n_hits_out holds the number needed,
+ *   hits_out is untouched and nothing is launched (hits_out = NULL, hits_cap = 0 is the sizing call; n_accounts always suffices).
+ *   On success *n_hits_out is the number of hits written, on any other failure 0, and a half-written array never leaves the call.
+ * limit 1 .. 2^32.  Up to ZKAMD_SCAN_HOST_MAX hits (the variable of the scans) the point work - decoding, the sums, one dec_key *
+ *   right per hit - runs on the host threads, above it in two kernels on the table's device (csrc/balance_keys.h); the bytes
+ *   written do not depend on the form.  The scalars of the hits and everything derived from them (dec_key * right, the point that
+ *   is searched, the logarithms) travel per call: wiped on the host, zeroed on the device before the call returns, hits_out zeroed
+ *   on failure.  The host form multiplies without branching on a key; the device form is NOT constant-time. */
+typedef struct {
+    uint8_t  found;          /* 1: value is the plaintext of enc_total; 0: no x < limit is (value = 0) */
+    uint8_t  refusal;        /* 0, or field | status << 6 of the first refused point among those USED, in the order
+                                1 balance left, 2 balance right, 3 pending left, 4 pending right (the zkxt::INTO_XY_* statuses,
+                                the convention of the scans); then found = 0, value = 0, enc_total = 64 zero bytes */
+    uint8_t  pending_added;  /* 1 where the account carried ZK_BLOCK_ROLLOVER_DUE */
+    uint8_t  reserved;       /* 0 */
+    uint32_t value;
+    uint8_t  enc_total[64];  /* Ciphertext::write of the total, left | right */
+} zk_balance_result;                                                    /* 72 bytes */
+typedef struct { uint32_t account, key; zk_balance_result r; } zk_balance_hit;   /* 80 bytes */
+zk_status zk_balance_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n_accounts, const zk_block_account* accounts,
+                          uint64_t limit, zk_balance_hit* hits_out, size_t hits_cap, size_t* n_hits_out);
 /* GEpoch::group_hash (core/primitives/src/g_epoch.rs:102-110): the Jubjub group hash (core/jubjub/src/group_hash.rs:17-46,
  * find_group_hash curve/mod.rs:223-247) personalised "zcgepoch" over the four little-endian bytes of `epoch` and a counter byte
  * from 0 - the g_epoch every wallet and verifier entry takes.  Host only.  out: Point::write of the point. */

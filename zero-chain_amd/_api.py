@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -569,13 +569,7 @@ def _execute_block(pvk, fn, arr, names, accounts, nonce_pool, g_epoch, sigs, msg
     of extrinsics and accounts beside it, and (effects, next_asset_id) between accounts_out and stats in the result"""
     lib = pvk._lib
     n, na = len(arr), len(accounts)
-    acc, out = (_lib.BlockAccount * max(na, 1))(), (_lib.BlockAccount * max(na, 1))()
-    for dst, a in zip(acc, accounts):
-        dst.enc_key[:] = bytes(a["enc_key"])
-        for f in ("balance", "pending"):
-            left, right = a.get(f) or ZERO_CIPHERTEXT
-            getattr(dst, f)[:] = bytes(left) + bytes(right)
-        dst.flags = int(a.get("flags", 0))
+    acc, out = _account_array(accounts), (_lib.BlockAccount * max(na, 1))()
     pool = _u8(b"".join(bytes(x) for x in nonce_pool), 32 * len(nonce_pool)) if len(nonce_pool) else None
     sb = blob = offs = None
     if sigs is not None:
@@ -944,6 +938,38 @@ def _anonymous_scan_dict(r):
             "delta": r.delta if r.found else None}
 
 
+BALANCE_POINTS = ("balance_left", "balance_right", "pending_left", "pending_right")   # zk_balance_result.refusal: field k is name k - 1
+
+
+def _balance_dict(r):
+    refused = bool(r.refusal)
+    return {"value": r.value if r.found else None, "enc_total": None if refused else bytes(r.enc_total), "pending_added": bool(r.pending_added),
+            "refusal": _scan_refusal(r.refusal, BALANCE_POINTS)}
+
+
+def _account_array(accounts):
+    """zk_block_account[]: from dicts (enc_key, balance, pending as (left, right) pairs, 64 bytes or None, flags), from a packed
+    array, or from its raw bytes"""
+    if isinstance(accounts, C.Array) and accounts._type_ is _lib.BlockAccount:
+        return accounts
+    if isinstance(accounts, (bytes, bytearray, memoryview)):
+        raw = bytes(accounts)
+        if len(raw) % C.sizeof(_lib.BlockAccount):
+            raise ValueError("%d bytes are no whole number of BlockAccount" % len(raw))
+        return (_lib.BlockAccount * (len(raw) // C.sizeof(_lib.BlockAccount))).from_buffer_copy(raw)
+    arr = (_lib.BlockAccount * len(accounts))()
+    for dst, a in zip(arr, accounts):
+        dst.enc_key[:] = bytes(a["enc_key"])
+        for f in ("balance", "pending"):
+            c = a.get(f) or ZERO_CIPHERTEXT
+            b = bytes(c) if isinstance(c, (bytes, bytearray)) else bytes(c[0]) + bytes(c[1])
+            if len(b) != 64:
+                raise ValueError("a ciphertext is 64 bytes (left || right)")
+            getattr(dst, f)[:] = b
+        dst.flags = int(a.get("flags", 0))
+    return arr
+
+
 def _points(encodings, n):
     return _u8(b"".join(bytes(e) for e in encodings), 32 * n)
 
@@ -1094,6 +1120,24 @@ class ElGamalTable:
         res = self._scan_keys(self._lib.zk_anonymous_scan_keys, _lib.AnonymousXt, _fill_anonymous_xt, _lib.AnonymousScanHit, ANONYMOUS_SIZE, xts, keys, limit)
         return [(h.xt, h.key, _anonymous_scan_dict(h.r)) for h in res]
 
+    def balances(self, accounts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+        """zk_balance_keys = BalanceQuery::get_balance_from_decryption_key (zface/src/utils/getter.rs:135-175) for every account
+        that a key of the ScanKeys `keys` owns, in one call.  accounts: dicts as execute_confidential_block takes and returns
+        them (enc_key, balance, pending, flags; its accounts_out can be passed straight in), an array of _lib.BlockAccount, or
+        its raw bytes.  An account with BLOCK_ROLLOVER_DUE in its flags is read as balance + pending - set the bit everywhere
+        for the reference's getter - any other as balance alone.  Returns [(account, key, dict)] in account order: value (an
+        int, or None where no value below `limit` was found), enc_total (the 64 bytes left | right a transfer request carries as
+        its encrypted balance), pending_added, and refusal (None, or (name of BALANCE_POINTS, reason) of the first used point
+        that Ciphertext::read refuses; value and enc_total are then None)."""
+        if keys._lib is not self._lib:
+            raise ValueError("the key set and the table belong to different libraries")
+        arr = _account_array(accounts)
+        n = len(arr)
+        cap = n   # (every account a hit at the most)
+        out, count = (_lib.BalanceHit * max(cap, 1))(), C.c_size_t(0)
+        self._lib.check(self._lib.zk_balance_keys(self._h, keys._h, n, arr if n else None, int(limit), out, cap, C.byref(count)))
+        return [(h.account, h.key, _balance_dict(h.r)) for h in out[:count.value]]
+
     def close(self):
         if self._h:
             self._lib.zk_elgamal_table_free(self._h)
@@ -1121,6 +1165,21 @@ def scan_confidential_keys(table, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
 def scan_anonymous_keys(table, xts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
     """ElGamalTable.scan_anonymous_keys of `table`"""
     return table.scan_anonymous_keys(xts, keys, limit)
+
+
+def balances_keys(table, accounts, keys, limit=ELGAMAL_DECRYPT_LIMIT):
+    """ElGamalTable.balances of `table`"""
+    return table.balances(accounts, keys, limit)
+
+
+def balance(table, account, dec_key, limit=ELGAMAL_DECRYPT_LIMIT):
+    """zk_balance_keys for ONE account and the key that owns it (an Fs integer): the dict of ElGamalTable.balances.  A dec_key
+    whose encryption key is not the account's enc_key is a ValueError."""
+    with ScanKeys([int(dec_key)], lib=table._lib) as keys:
+        res = table.balances([account], keys, limit)
+    if not res:
+        raise ValueError("the account does not belong to this decryption key")
+    return res[0][2]
 
 
 def elgamal_add(left_a, right_a, left_b, right_b, subtract=False, lib=None):

@@ -123,6 +123,15 @@ class AnonymousScanHit(C.Structure):
     _fields_ = [("xt", C.c_uint32), ("key", C.c_uint32), ("r", AnonymousScanResult)]
 
 
+class BalanceResult(C.Structure):
+    _fields_ = [("found", C.c_uint8), ("refusal", C.c_uint8), ("pending_added", C.c_uint8), ("reserved", C.c_uint8), ("value", C.c_uint32),
+                ("enc_total", C.c_uint8 * 64)]
+
+
+class BalanceHit(C.Structure):
+    _fields_ = [("account", C.c_uint32), ("key", C.c_uint32), ("r", BalanceResult)]
+
+
 class BatchDev(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("n_inputs", C.c_uint32), ("n_aux", C.c_uint32), ("flags", C.c_uint32),
                 ("d_a", C.c_void_p), ("d_b", C.c_void_p), ("d_c", C.c_void_p), ("d_wit", C.c_void_p),
@@ -182,6 +191,8 @@ _PROTOS = {
                                               C.POINTER(ConfidentialScanHit), C.c_size_t, C.POINTER(C.c_size_t)]),
     "zk_anonymous_scan_keys": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousXt), C.c_uint64,
                                            C.POINTER(AnonymousScanHit), C.c_size_t, C.POINTER(C.c_size_t)]),
+    "zk_balance_keys": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BlockAccount), C.c_uint64, C.POINTER(BalanceHit), C.c_size_t,
+                                    C.POINTER(C.c_size_t)]),
     "zk_elgamal_ledger_apply": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LedgerOp), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "zk_transfer_derive": (C.c_int32, [C.POINTER(TransferRequest), C.c_size_t, C.POINTER(TransferStatement), C.c_void_p]),

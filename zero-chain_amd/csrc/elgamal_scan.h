@@ -45,6 +45,11 @@ using zkxt::Lds;
 // threads, recipient rows at limit 10^6): the device form is 2.85 - 2.95 ms from 64 to 1024 rows, the host form 2.45 ms at 128 rows
 // and 4.60 ms at 256 - 128 is the largest probed size at which the host form is still the faster one.
 constexpr size_t HOST_MAX = 128;
+// (read per call; zk_balance_keys counts its hits against the same value, balance_keys.h)
+inline size_t host_max() {
+    const char* e = getenv("ZKAMD_SCAN_HOST_MAX");
+    return e && *e ? (size_t)strtoull(e, nullptr, 10) : HOST_MAX;
+}
 constexpr uint32_t ROW_ANON = 1u << 31;       // in a row's fourth word: also store -v, one search row further
 constexpr size_t DIGITS_BYTES = 272;          // 256 digits, their top index as an int32, padded to 16 bytes
 // field numbers of zk_confidential_verify_batch / zk_anonymous_verify_batch
@@ -333,9 +338,7 @@ inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const Keys& keys, u
     f->flags.assign(pl.rows.size(), 0);
     f->x.assign(pl.n_search, ~0ull);
     if (pl.rows.empty()) return ZK_OK;
-    const char* e = getenv("ZKAMD_SCAN_HOST_MAX");
-    const size_t host_max = e && *e ? (size_t)strtoull(e, nullptr, 10) : HOST_MAX;
-    ZK_TRY(pl.rows.size() <= host_max ? points_on_host(T, pl, keys, f) : device(T, pl, keys, f));
+    ZK_TRY(pl.rows.size() <= host_max() ?points_on_host(T, pl, keys, f) : device(T, pl, keys, f));
     return elgamal_dlog_search_resident(T, pl.n_search, limit, f->x.data());
 }
 // field | status << 6 of the first refused point of match m in push order, or 0

@@ -9,8 +9,9 @@
 //   check_proof + ConfidentialXt / AnonymousXt packing   confidential.rs:208-361, anonymous.rs:200-352
 //   redjubjub PrivateKey::sign / PublicKey::verify       core/jubjub/src/redjubjub.rs:73-103, 127-155 (redjubjub.h)
 //   a block read with one decryption key                 - (elgamal.rs:85-108 per value, crypto_components.rs:168-220; elgamal_scan.h)
+//   BalanceQuery::get_balance_from_decryption_key        zface/src/utils/getter.rs:135-175, for the accounts of a key set (balance_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
-// the signature check (redjubjub.h) and the two of the scan's point stage (elgamal_scan.h).
+// the signature check (redjubjub.h), those of the scans' point stage (elgamal_scan.h, scan_keys.h) and the combine of balance_keys.h.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -120,9 +121,8 @@ void jubjub_encode(const zkhost::Fr& x_mont, const zkhost::Fr& y_mont, uint8_t o
 }
 
 // k * p for a point of the statement (double-and-add over the complete addition law; k < 2^252)
-zkwit::EPoint jubjub_var_mul(const zkwit::JPoint& p, const uint64_t k[4]) {
+zkwit::EPoint jubjub_var_mul(const zkwit::EPoint& base, const uint64_t k[4]) {
     zkwit::EPoint acc = zkwit::ext_zero();
-    const zkwit::EPoint base = zkwit::to_ext(p);
     const zkwit::EPoint zero = zkwit::ext_zero();
     for (int bit = 251; bit >= 0; bit--) {
         acc = zkwit::ext_add(acc, acc);
@@ -132,6 +132,7 @@ zkwit::EPoint jubjub_var_mul(const zkwit::JPoint& p, const uint64_t k[4]) {
     }
     return acc;
 }
+zkwit::EPoint jubjub_var_mul(const zkwit::JPoint& p, const uint64_t k[4]) { return jubjub_var_mul(zkwit::to_ext(p), k); }
 
 // secrets (spending keys, decryption keys, rsk, the statements that carry them) do not outlive the call that held
 // them: wiped on every exit path
@@ -245,6 +246,7 @@ zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_s
 #include "redjubjub.h"   // (here: it signs and hashes with the helpers above)
 #include "elgamal_scan.h"   // (and the scan decodes, multiplies and wipes with them)
 #include "scan_keys.h"      // (the same scan for a set of keys: a scalar per hit)
+#include "balance_keys.h"   // (the balances of such a set's accounts: the same point kernel, a combine of its own)
 
 extern "C" {
 
@@ -453,6 +455,11 @@ zk_status zk_confidential_scan_keys(zk_elgamal_table* t, const zk_scan_keys* key
 zk_status zk_anonymous_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n, const zk_anonymous_xt* xts, uint64_t limit,
                                  zk_anonymous_scan_hit* hits_out, size_t hits_cap, size_t* n_hits_out) try {
     return zkscan::scan_keys<zkscan::Anonymous>(t, keys, n, xts, limit, hits_out, hits_cap, n_hits_out);
+} ZK_ABI_CATCH
+
+zk_status zk_balance_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n_accounts, const zk_block_account* accounts, uint64_t limit,
+                          zk_balance_hit* hits_out, size_t hits_cap, size_t* n_hits_out) try {
+    return zkscan::balance_keys(t, keys, n_accounts, accounts, limit, hits_out, hits_cap, n_hits_out);
 } ZK_ABI_CATCH
 
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
