@@ -165,6 +165,28 @@ def test_refusals(emu_lib):
     assert zk.elgamal_add([], [], [], [], lib=emu_lib) == ([], [])
 
 
+def test_the_lowest_failing_index_is_reported_whatever_the_thread_count(emu_lib):
+    """The host entries fan out over contiguous ranges (host_common.h for_each_status): with one thread and with eight - the two
+    bad items then lie in different ranges, the higher one in an earlier position of its range - the caller hears of the lower."""
+    import zero_chain_amd as zk
+    scalars = list(range(1, 201))
+    scalars[150] = scalars[30] = jj.FS_MOD
+    left, right = encrypt(emu_lib, [1], fs(6, 1))
+    lefts = [left[0]] * 100
+    lefts[90] = lefts[12] = bytes([0xff] * 32)
+    try:
+        for threads in (1, 8):
+            zk.set_host_threads(threads, lib=emu_lib)
+            with pytest.raises(zk.ZkError) as e:
+                zk.jubjub_base_mul(scalars, lib=emu_lib)
+            assert e.value.variant == "InvalidArgument" and "scalar 30 is not a canonical Fs scalar" in str(e.value), threads
+            with pytest.raises(zk.ZkError) as e:
+                zk.elgamal_add(lefts, right * 100, [left[0]] * 100, right * 100, lib=emu_lib)
+            assert e.value.variant == "InvalidArgument" and "ciphertext 12: left_a is not a Jubjub point" in str(e.value), threads
+    finally:
+        zk.set_host_threads(0, lib=emu_lib)
+
+
 def test_fingerprint_collisions_change_no_result(emu_lib, monkeypatch):
     """ZKAMD_DEBUG_DLOG_FP_BITS (test hooks only) narrows the fingerprint of a hash slot: with 0 bits every occupied slot
     a probe passes is a fingerprint hit that only the full coordinates can tell apart."""

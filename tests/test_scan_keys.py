@@ -116,6 +116,23 @@ def test_lane_layout(emu_lib, emu_table, logs5000, monkeypatch):
     assert [(g[0], g[1], g[2][:2]) for g in got] == [(5, 3, bytes([sc.RECIPIENT, sc.FOUND_RECEIVED]))]
 
 
+@pytest.mark.parametrize("matches", [1, 65])
+def test_a_one_key_set_is_the_one_key_scan_in_the_device_form(emu_lib, emu_table, monkeypatch, matches):
+    """The two point kernels share one lane body and differ in the multiplier (csrc/wallet_stage.h): the shared width-4 NAF of
+    zk_confidential_scan's one key, the fixed windows over the lane's own scalar of a key set.  With the kernels forced, a set of
+    that one key writes the 16 bytes of the one-key entry for every matching extrinsic - one multiplication lane, and a second wave of
+    them."""
+    import zero_chain_amd as zk
+    specs = [(sc.ALICE, sc.BOB, 5, 1)] + [(sc.ALICE, sc.WALLET, 100 + j, 1) for j in range(matches)]
+    xts = sc.confidential_xts(emu_lib, specs, seed=38)
+    monkeypatch.setenv("ZKAMD_SCAN_HOST_MAX", DEVICE)
+    with zk.ScanKeys([sc.WALLET], lib=emu_lib) as keys:
+        got = hits_raw(emu_table, "confidential", xts, keys, 5000)
+    assert [(g[0], g[1], g[2][:2], int.from_bytes(g[2][12:], "little")) for g in got] == \
+        [(1 + j, 0, bytes([sc.RECIPIENT, sc.FOUND_RECEIVED]), 100 + j) for j in range(matches)]
+    assert got == loop_raw(emu_table, "confidential", xts, [sc.WALLET], 5000)
+
+
 def test_anonymous_rings(emu_lib, emu_table, logs5000, monkeypatch):
     import zero_chain_amd as zk
     xts, _ = skc.ring_cases(emu_lib, [1, 255, 256, 4999])

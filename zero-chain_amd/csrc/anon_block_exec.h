@@ -45,7 +45,7 @@ k_ring_balance_xy(const uint32_t* xy, const uint32_t* src, uint32_t n_lanes, uin
     if (q >= n_lanes) return;
     const zkxt::Lds L{table + threadIdx.x};
     const uint32_t b = src[2 * (size_t)q], p = src[2 * (size_t)q + 1];
-    const EP v = ext_add(zkledger::ep_from_xy(xy + (size_t)b * 16, false), zkledger::ep_from_xy(xy + (size_t)p * 16, false), zkledger::edwards_2d());
+    const EP v = ext_add(zkledger::ep_from_xy(xy + (size_t)b * 16, false), zkledger::ep_from_xy(xy + (size_t)p * 16, false), zkxt::jubjub_d2());
     constexpr zkxt::PowDigits EI = zkxt::digits_inverse();
     // Z != 0: both addends passed as_prime_order in k_into_xy (the host rolls readable accounts only), the prime-order points are
     // a subgroup, and the addition law is complete there

@@ -43,7 +43,6 @@
 namespace zkblock {
 
 constexpr uint32_t LEDGER_CLEAR = 4;   // internal: a live op with this flag forgets the slot's stored value and every op before it
-using zkledger::ep_identity;
 using zkledger::ep_load;
 using zkledger::ep_store;
 
@@ -70,8 +69,8 @@ k_asset_scan(const uint32_t* xy, const uint32_t* st, const uint32_t* off, const 
     ZK_SHARED uint32_t clr[LEDGER_SCAN_W];
     const uint32_t t = threadIdx.x, c = blockIdx.y, b0 = blockIdx.x * LEDGER_SCAN_W, j = b0 + t;
     const bool live = j < n_ops;
-    const Fr d2 = zkledger::edwards_2d();
-    EP v = ep_identity();
+    const Fr d2 = zkxt::jubjub_d2();
+    EP v = zkxt::ep_neutral();
     uint32_t s = 0, first = b0, m = 0;   // first: the slot's first place in this workgroup; m: place + 1 of a live CLEAR
     if (live) {
         const uint32_t i = perm[j], fl = flagv[i];
@@ -95,7 +94,7 @@ k_asset_scan(const uint32_t* xy, const uint32_t* st, const uint32_t* off, const 
     uint32_t *cut_pre = cut, *cut_tot = cut + n_ops, *cut_agg = cut_tot + n_slots;
     if (live) {
         const bool inner = j > first;   // lane t - 1 holds the slot's place before this one
-        const EP e = inner ? zkledger::scan_ld(lds, t - 1) : ep_identity();
+        const EP e = inner ? zkledger::scan_ld(lds, t - 1) : zkxt::ep_neutral();
         ep_store(pre + ((size_t)c * n_ops + j) * 32, e);
         if (c == 0) cut_pre[j] = inner && clr[t - 1] > first;
         if (j + 1 == off[s + 1]) {
@@ -115,8 +114,8 @@ k_asset_carry(const uint32_t* agg, const uint32_t* cut_agg, const uint32_t* csta
     ZK_SHARED uint32_t lds[4 * 8 * LEDGER_SCAN_W];
     ZK_SHARED uint32_t clr[LEDGER_SCAN_W];
     const uint32_t t = threadIdx.x, c = blockIdx.y;
-    const Fr d2 = zkledger::edwards_2d();
-    EP run = ep_identity();
+    const Fr d2 = zkxt::jubjub_d2();
+    EP run = zkxt::ep_neutral();
     uint32_t run_cut = 0;   // workgroup + 1 of the last cut tail of the passes so far
     if (t == 0) {
         ep_store(carry + (size_t)c * n_blocks * 32, run);
@@ -126,7 +125,7 @@ k_asset_carry(const uint32_t* agg, const uint32_t* cut_agg, const uint32_t* csta
     for (uint32_t base = 0; base < n_blocks; base += LEDGER_SCAN_W) {
         const uint32_t b = base + t;
         const bool live = b < n_blocks;
-        EP v = ep_identity();
+        EP v = zkxt::ep_neutral();
         uint32_t h = 0, m = 0;
         if (live) {
             v = ep_load(agg + ((size_t)c * n_blocks + b) * 32);
@@ -159,7 +158,7 @@ k_asset_carry(const uint32_t* agg, const uint32_t* cut_agg, const uint32_t* csta
 // stored value is refused and no CLEAR lies before the place).
 ZK_DI bool asset_value(const uint32_t* xy, const uint32_t* st, const uint32_t* off, const uint32_t* carry, const uint32_t* cut_carry, uint32_t n_blocks,
                        uint32_t s, uint32_t c, uint32_t last, const uint32_t* src, uint32_t src_cut, EP* v) {
-    const Fr d2 = zkledger::edwards_2d();
+    const Fr d2 = zkxt::jubjub_d2();
     const bool readable = (st[2 * (size_t)s] | st[2 * (size_t)s + 1]) == 0;
     if (!src) {
         if (readable) *v = zkledger::ep_from_xy(xy + (2 * (size_t)s + c) * 16, false);
@@ -207,14 +206,12 @@ k_asset_encode(const uint32_t* xy, const uint32_t* st, const uint32_t* off, cons
         src = pre + ((size_t)c * n_ops + last) * 32;
         src_cut = cut[last];
     }
-    Fr x = Fr::zero(), y = Fr::zero();
+    Fr y = Fr::zero();
     EP v;
     if (asset_value(xy, st, off, carry, cut_carry, n_blocks, s, c, last, src, src_cut, &v)) {
         constexpr zkxt::PowDigits EI = zkxt::digits_inverse();
         const Fr zi = zkxt::pow_windows(L, v.Z, EI);   // Z != 0: a sum of prime-order points
-        x = zkdev::from_mont(mul(v.X, zi));
-        y = zkdev::from_mont(mul(v.Y, zi));
-        y.l[7] |= (x.l[0] & 1u) << 31;
+        y = zkxt::point_words(mul(v.X, zi), mul(v.Y, zi));
     }
     zkledger::fr_store(enc + (size_t)q * 8, y);
 }

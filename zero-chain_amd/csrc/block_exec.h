@@ -50,7 +50,7 @@ k_block_balance_xy(const uint32_t* xy, const uint32_t* st, const uint32_t* off, 
     const uint32_t c = q & 1, i = opv[q >> 1], s = slotv[i], last = pos[i];
     Fr x = Fr::zero(), y = Fr::zero();
     if ((st[2 * (size_t)s] | st[2 * (size_t)s + 1]) == 0) {
-        const Fr d2 = zkledger::edwards_2d();
+        const Fr d2 = zkxt::jubjub_d2();
         EP sum = zkledger::ep_load(pre + ((size_t)c * n_ops + last) * 32);
         const uint32_t b = last / LEDGER_SCAN_W;
         if (off[s] < b * LEDGER_SCAN_W) sum = ext_add(zkledger::ep_load(carry + ((size_t)c * n_blocks + b) * 32), sum, d2);

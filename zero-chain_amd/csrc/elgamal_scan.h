@@ -2,99 +2,31 @@
 // and by how much.  The reference has no counterpart; the pieces are EncryptionKey::from_decryption_key (keys.rs:250-261) for
 // the match, Ciphertext::read (elgamal.rs:116-133) for the points the wallet's role uses, Ciphertext::decrypt (elgamal.rs:85-108)
 // for every value, and the signs of MultiCiphertexts::<Anonymous>::encrypt (crypto_components.rs:168-220).
-// Included by wallet.cpp below redjubjub.h (fs_lt_mod, jubjub_fixed_mul, jubjub_var_mul, jubjub_encode, WipeOnExit, zkrj::ld_fr).
+// Included by wallet.cpp below wallet_stage.h (the point stage: device_stage, HostRows, the point kernels), and by no other unit.
 // The host side below serves a SET of keys as well (scan_keys.h): a match carries the number of its key (always 0 here), the plan,
-// the host form and the slicing are shared, and only the kernel that multiplies differs.
+// the host form and the slicing are shared, and only the multiplier of the point kernel differs.
 //
 // The host matches the 32 bytes of the wallet's key against the keys of every extrinsic and gathers, for the matching ones only,
 //   points   every used left half and the right half, in the push order of the verifiers' field numbers
 //   rights   the right half again, once per matching extrinsic: dk * right is shared by all its values
 //   rows     one per value to decrypt: (left point, right point, right)
-// and then brings every row to v = left - dk right, affine, in the table's v buffer, where the search of zk_elgamal_decrypt
-// (witness.cpp elgamal_dlog_search_resident) finds the logarithms.  An anonymous row is searched twice, as v and as -v: the
-// sender's ciphertext holds -amount.  Two forms of the point work, the same bytes:
-//   host    zkwit::decode_point + is_prime_order, jubjub_var_mul once per extrinsic and batch_to_affine on the
-//           zk_set_host_threads pool, one upload of v
-//   device  two launches on the library stream, one wave per block:
-//     k_scan_points   one lane per task, the two kinds split at a wave boundary (the point count is padded to 64)
-//                       lanes [0, P)          read_point + is_prime_order: k_into_xy's body, the coordinates left in Montgomery form
-//                       lanes [P64, P64 + R)  read_point of a right half, then D = [dk] right over the width-4 NAF of dk, recoded
-//                                             on the host once per call: 252 doublings and an addition per non-zero digit against
-//                                             +-R, +-3R, +-5R, +-7R cached in LDS - is_prime_order's steps and its chain length.
-//                                             Every lane reads the same digits, so a wave takes one path.
-//                     LDS as k_into_xy: [slot][word][lane], 16 slots, 32 768 B per block, nothing in scratch memory.
+// and the point stage (wallet_stage.h) brings every row to v = left - dk right.  An anonymous row is searched twice, as v and as
+// -v: the sender's ciphertext holds -amount.  Its two forms here:
+//   host    zkwit::decode_point + is_prime_order, jubjub_var_mul once per match, then HostRows
+//   device  k_scan_points (one key: the width-4 NAF of dk) or k_keys_points (a set: the scalar of every match), then
 //     k_scan_combine  one lane per row: v = left - D (one addition), to affine form by one inversion, stored as two Montgomery
 //                     Fr straight into the table's v buffer (and -v behind it for an anonymous row).  A row whose left or right
 //                     half was refused stores the neutral element and raises its flag: the host ignores what the search finds.
-// Secrets: the digits of dk, D, v and the logarithms are key-derived - their device buffers are zeroed after every call and
-// before release, the host copies wiped on every way out.  The encodings, coordinates and statuses are public chain data.
-// The device form is NOT constant-time: the digits of dk decide where the shared chain adds, as the bits of the keys decide the
-// shape of the witness kernels' chains today; the host form multiplies with jubjub_var_mul, whose steps do not depend on dk.
 #pragma once
-#include "redjubjub.h"
-#include "handles.h"
+#include "wallet_stage.h"
 
 namespace zkscan {
 
-using zkdev::Fr;
-using zkrt::fail;
-using zkxt::EP;
-using zkxt::Lds;
-
-// ZKAMD_SCAN_HOST_MAX: rows (values to decrypt) up to which the host form runs.  Measured (profiles/r14_scan_probe.json, 16 host
-// threads, recipient rows at limit 10^6): the device form is 2.85 - 2.95 ms from 64 to 1024 rows, the host form 2.45 ms at 128 rows
-// and 4.60 ms at 256 - 128 is the largest probed size at which the host form is still the faster one.
-constexpr size_t HOST_MAX = 128;
-// (read per call; zk_balance_keys counts its hits against the same value, balance_keys.h)
-inline size_t host_max() {
-    const char* e = getenv("ZKAMD_SCAN_HOST_MAX");
-    return e && *e ? (size_t)strtoull(e, nullptr, 10) : HOST_MAX;
-}
-constexpr uint32_t ROW_ANON = 1u << 31;       // in a row's fourth word: also store -v, one search row further
-constexpr size_t DIGITS_BYTES = 272;          // 256 digits, their top index as an int32, padded to 16 bytes
 // field numbers of zk_confidential_verify_batch / zk_anonymous_verify_batch
 enum { F_LEFT_AMOUNT_SENDER = 3, F_LEFT_AMOUNT_RECIPIENT = 4, F_RIGHT_RANDOMNESS = 5, F_LEFT_FEE = 6, F_LEFT_CIPHERTEXTS = 13, F_RIGHT_CIPHERTEXT = 49 };
 
-ZK_DI void st_fr(uint32_t* p, const Fr& v) {
-    uint4* q = reinterpret_cast<uint4*>(p);
-    q[0] = make_uint4(v.l[0], v.l[1], v.l[2], v.l[3]);
-    q[1] = make_uint4(v.l[4], v.l[5], v.l[6], v.l[7]);
-}
-
-// enc: p64 x 8 words (n_points of them used).  xy: n_points x 16 words, x then y in Montgomery form, zero where refused.  status:
-// n_points words, zkxt::INTO_XY_*.  enc_right: n_rights x 8 words.  digits: 256 signed digits, then their top index (int32).
-// d_out: n_rights x 32 words, X Y Z T of [dk] right (the neutral element where the encoding is no point: kind 1 reports it).
-static __global__ void __launch_bounds__(64)
-k_scan_points(const uint32_t* enc, uint32_t n_points, uint32_t p64, const uint32_t* enc_right, uint32_t n_rights, const int8_t* digits,
-              uint32_t* xy, uint32_t* status, uint32_t* d_out) {
-    ZK_SHARED uint32_t table[16 * 8 * 64];
-    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-    const Lds L{table + threadIdx.x};
-    Fr x = Fr::zero(), y, xm = Fr::zero(), ym = Fr::zero(), d;
-    if (t < p64) {
-        if (t >= n_points) return;
-        uint32_t st = zkxt::read_point(L, enc + (size_t)t * 8, &x, &y, &xm, &ym, &d);
-        if (st == zkxt::INTO_XY_OK && !zkxt::is_prime_order(L, xm, ym, dbl(d))) st = zkxt::INTO_XY_NOT_PRIME_ORDER;
-        if (st != zkxt::INTO_XY_OK) xm = ym = Fr::zero();
-        st_fr(xy + (size_t)t * 16, xm);
-        st_fr(xy + (size_t)t * 16 + 8, ym);
-        status[t] = st;
-    } else {
-        const uint32_t r = t - p64;
-        if (r >= n_rights) return;
-        EP acc{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()};
-        if (zkxt::read_point(L, enc_right + (size_t)r * 8, &x, &y, &xm, &ym, &d) == zkxt::INTO_XY_OK)
-            acc = zkxt::mul_naf(L, xm, ym, dbl(d), digits, *reinterpret_cast<const int32_t*>(digits + 256));
-        uint32_t* o = d_out + (size_t)r * 32;
-        st_fr(o, acc.X);
-        st_fr(o + 8, acc.Y);
-        st_fr(o + 16, acc.Z);
-        st_fr(o + 24, acc.T);
-    }
-}
-
-// rows: n_rows x 4 words - left point, right point, right, first search row | ROW_ANON.  xy, status: k_scan_points' of the points,
-// d_in its d_out.  v: the table's buffer (zkdlog::Search::v: per search row x then y, Montgomery).  flags: n_rows words.
+// rows: n_rows x 4 words - left point, right point, right, first search row | ROW_ANON.  xy, status: the point kernel's of the
+// points, d_in its d_out.  v: the table's buffer (zkdlog::Search::v: per search row x then y, Montgomery).  flags: n_rows words.
 static __global__ void __launch_bounds__(64)
 k_scan_combine(const uint32_t* rows, uint32_t n_rows, const uint32_t* xy, const uint32_t* status, const uint32_t* d_in, uint32_t* v,
                uint32_t* flags) {
@@ -104,16 +36,10 @@ k_scan_combine(const uint32_t* rows, uint32_t n_rows, const uint32_t* xy, const 
     const bool refused = status[row.x] != zkxt::INTO_XY_OK || status[row.y] != zkxt::INTO_XY_OK;
     Fr x = Fr::zero(), y = Fr::one();
     if (!refused) {
-        Fr d;
-        {
-            const uint64_t dp[4] = ZK_JUBJUB_D_PLAIN_64;
-#pragma unroll
-            for (int k = 0; k < 8; k++) d.l[k] = (uint32_t)(dp[k >> 1] >> (32 * (k & 1)));
-        }
         const Fr lx = zkrj::ld_fr(xy + (size_t)row.x * 16), ly = zkrj::ld_fr(xy + (size_t)row.x * 16 + 8);
         const uint32_t* dd = d_in + (size_t)row.z * 32;
         const EP minus_d{neg(zkrj::ld_fr(dd)), zkrj::ld_fr(dd + 8), zkrj::ld_fr(dd + 16), neg(zkrj::ld_fr(dd + 24))};
-        const EP s = zkxt::ext_add(EP{lx, ly, Fr::one(), mul(lx, ly)}, minus_d, dbl(zkdev::to_mont(d)));
+        const EP s = zkxt::ext_add(EP{lx, ly, Fr::one(), mul(lx, ly)}, minus_d, zkxt::jubjub_d2());
         const uint32_t rm2[8] = ZK_FR_EXP_RM2_32;
         const Fr zi = zkdev::pow_limbs(s.Z, rm2);   // (Z != 0: the addition law is complete on the prime-order subgroup)
         x = mul(s.X, zi);
@@ -144,7 +70,7 @@ struct Keys {
     size_t n;
     const uint64_t* dk;      // n x 4 words, plain
     const uint8_t* enc;      // n x 32 bytes: EncryptionKey::from_decryption_key of each
-    const uint32_t* order;   // the key numbers sorted by those bytes (memcmp order); NULL where n == 1
+    const uint32_t* order;   // the key numbers sorted by those bytes (memcmp order); NULL for the one key of zk_*_scan
     const uint64_t* scalar(uint32_t k) const { return dk + 4 * (size_t)k; }
     // the number of the key whose 32 bytes are b, or -1
     int64_t find(const uint8_t b[32]) const {
@@ -232,14 +158,16 @@ inline uint8_t read_prime_order(const uint8_t b[32], zkwit::JPoint* out) {
     return zkxt::INTO_XY_OK;
 }
 
+inline void launch_scan_combine(const StageBufs& B) {
+    ZK_LAUNCH(k_scan_combine, B.row_grid(), dim3(64), 0, zkrt::g_stream, B.rows, B.n_rows, (const uint32_t*)B.xy, (const uint32_t*)B.status,
+              (const uint32_t*)B.d, B.v, B.flags);
+}
+const StageKernel SCAN_COMBINE{"scan_combine", launch_scan_combine};
+
 // the host form: the statuses, the flags, and v of every search row into T->v
 inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const Keys& keys, Found* f) {
-    const size_t nm = pl.matches.size() - 1;
-    std::vector<zkwit::JPoint> v(pl.n_search);
-    WipeOnExit wipe_v{v.data(), v.size() * sizeof(zkwit::JPoint)};
-    const unsigned nth = zkrt::host_threads(nm, 64);
-    auto work = [&](unsigned th) {
-        const size_t m0 = nm * th / nth, m1 = nm * (th + 1) / nth;
+    HostRows hr(pl.n_search);
+    ZK_TRY(zkrt::for_each_range(pl.matches.size() - 1, 64, [&](size_t m0, size_t m1) -> zk_status {
         const uint32_t r0 = pl.matches[m0].row0, r1 = pl.matches[m1].row0;
         std::vector<zkwit::EPoint> proj(r1 - r0, zkwit::ext_zero());
         std::vector<zkwit::JPoint> aff(r1 - r0), pts;
@@ -256,89 +184,36 @@ inline zk_status points_on_host(zk_elgamal_table* T, const Plan& pl, const Keys&
             const zkwit::EPoint minus_s{zkhost::Fr::zero() - s.X, s.Y, s.Z, zkhost::Fr::zero() - s.T};
             for (uint32_t r = a.row0; r < b.row0; r++) proj[r - r0] = zkwit::ext_add(zkwit::to_ext(pts[pl.rows[r].left - a.pt0]), minus_s);
         }
-        zkwit::batch_to_affine(proj.data(), aff.data(), proj.size());
-        for (uint32_t r = r0; r < r1; r++) {
-            const uint32_t out = pl.rows[r].out & ~ROW_ANON;
-            v[out] = aff[r - r0];
-            if (pl.rows[r].out & ROW_ANON) v[out + 1] = zkwit::JPoint{zkhost::Fr::zero() - aff[r - r0].x, aff[r - r0].y};
-        }
-    };
-    zkrt::run_threads(nth, work);
-    static_assert(sizeof(zkwit::JPoint) == 64, "x | y, the layout of zkdlog::Search::v");
-    ZK_TRY(T->v.ensure(v.size() * 64));
-    HIP_TRY(hipMemcpyAsync(T->v.p, v.data(), v.size() * 64, hipMemcpyHostToDevice, zkrt::g_stream));
-    return ZK_OK;
+        hr.land(proj, aff, 0, 1, [&](size_t k) { return pl.rows[r0 + k].out; });
+        return ZK_OK;
+    }));
+    return hr.upload(T);
 }
 
-// the device form: the same three, by two kernels.  head: the key-derived bytes the point kernel reads, at the start of scan_key
-// (a multiple of 16; D follows them); launch_points starts that kernel.
-template <class LaunchPoints>
-inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const std::vector<uint8_t>& head, Found* f, LaunchPoints launch_points) {
-    const size_t np = pl.points(), p64 = (np + 63) / 64 * 64, nm = pl.matches.size() - 1, nr = pl.rows.size();
-    // scan_in: encodings (padded) | rights | rows.  scan_out: coordinates | statuses | flags.  scan_key: head | D
-    std::vector<uint8_t> in(p64 * 32 + nm * 32 + nr * 16, 0);
-    memcpy(in.data(), pl.enc.data(), np * 32);
-    for (size_t m = 0; m < nm; m++) memcpy(&in[p64 * 32 + m * 32], &pl.enc[(size_t)pl.rows[pl.matches[m].row0].right_pt * 32], 32);
-    static_assert(sizeof(Row) == 16, "four words");
-    memcpy(&in[p64 * 32 + nm * 32], pl.rows.data(), nr * 16);
-    const size_t key_bytes = head.size() + nm * 128;
-    ZK_TRY(T->scan_in.ensure(in.size()));
-    ZK_TRY(T->scan_out.ensure(np * 68 + nr * 4));
-    ZK_TRY(T->scan_key.ensure(key_bytes));
-    ZK_TRY(T->v.ensure((size_t)pl.n_search * 64));
-    const uint32_t* d_enc = T->scan_in.as<uint32_t>();
-    const uint32_t *d_right = d_enc + p64 * 8, *d_rows = d_right + nm * 8;
-    uint32_t* d_xy = T->scan_out.as<uint32_t>();
-    uint32_t *d_status = d_xy + np * 16, *d_flags = d_status + np;
-    uint32_t* d_d = T->scan_key.as<uint32_t>() + head.size() / 4;
-    auto run = [&]() -> zk_status {
-        HIP_TRY(hipMemcpyAsync(T->scan_in.p, in.data(), in.size(), hipMemcpyHostToDevice, zkrt::g_stream));
-        HIP_TRY(hipMemcpyAsync(T->scan_key.p, head.data(), head.size(), hipMemcpyHostToDevice, zkrt::g_stream));
-        launch_points(dim3((unsigned)(p64 / 64 + (nm + 63) / 64)), d_enc, (uint32_t)np, (uint32_t)p64, d_right, (uint32_t)nm, T->scan_key.p, d_xy, d_status, d_d);
-        HIP_TRY(hipGetLastError());
-        {
-            zkrt::ProfScope ps("scan_combine");
-            ZK_LAUNCH(k_scan_combine, dim3((unsigned)((nr + 63) / 64)), dim3(64), 0, zkrt::g_stream, d_rows, (uint32_t)nr, (const uint32_t*)d_xy,
-                      (const uint32_t*)d_status, (const uint32_t*)d_d, T->v.as<uint32_t>(), d_flags);
-        }
-        HIP_TRY(hipGetLastError());
-        std::vector<uint32_t> back(np + nr);
-        HIP_TRY(hipMemcpyAsync(back.data(), d_status, back.size() * 4, hipMemcpyDeviceToHost, zkrt::g_stream));
-        HIP_TRY(hipMemsetAsync(T->scan_key.p, 0, key_bytes, zkrt::g_stream));
-        HIP_TRY(hipStreamSynchronize(zkrt::g_stream));
-        for (size_t p = 0; p < np; p++) f->status[p] = (uint8_t)back[p];
-        memcpy(f->flags.data(), &back[np], nr * 4);
-        return ZK_OK;
-    };
-    const zk_status rc = run();
-    if (rc != ZK_OK) {   // the head, D and v do not stay behind a failure either
-        (void)hipMemsetAsync(T->scan_key.p, 0, key_bytes, zkrt::g_stream);
-        (void)hipMemsetAsync(T->v.p, 0, (size_t)pl.n_search * 64, zkrt::g_stream);
-        (void)hipStreamSynchronize(zkrt::g_stream);
+// the device form: the same three.  One key (keys.order == NULL): its width-4 NAF, recoded here once per call, and k_scan_points;
+// a set: the scalar of every match, gathered for this slice, and k_keys_points
+inline zk_status points_on_device(zk_elgamal_table* T, const Plan& pl, const Keys& keys, Found* f) {
+    const size_t nm = pl.matches.size() - 1;
+    std::vector<uint8_t> rights(nm * 32), head(keys.order ? nm * 32 : DIGITS_BYTES);
+    WipeOnExit wipe_head{head.data(), head.size()};
+    static_assert(sizeof(uint64_t[4]) == 32 && sizeof(Row) == 16, "eight plain words, little-endian; four words");
+    for (size_t m = 0; m < nm; m++) {
+        memcpy(&rights[m * 32], &pl.enc[(size_t)pl.rows[pl.matches[m].row0].right_pt * 32], 32);
+        if (keys.order) memcpy(&head[m * 32], keys.scalar(pl.matches[m].key), 32);
     }
-    return rc;
-}
-// one key: its width-4 NAF, recoded here once per call, and k_scan_points
-inline zk_status points_one_key(zk_elgamal_table* T, const Plan& pl, const Keys& keys, Found* f) {
-    std::vector<uint8_t> digits(DIGITS_BYTES);
-    WipeOnExit wipe_digits{digits.data(), digits.size()};
-    naf_recode(keys.scalar(0), digits.data());
-    return points_on_device(T, pl, digits, f, [](dim3 grid, const uint32_t* enc, uint32_t np, uint32_t p64, const uint32_t* right, uint32_t nm, void* head,
-                                                 uint32_t* xy, uint32_t* status, uint32_t* d) {
-        zkrt::ProfScope ps("scan_points");
-        ZK_LAUNCH(k_scan_points, grid, dim3(64), 0, zkrt::g_stream, enc, np, p64, right, nm, (const int8_t*)head, xy, status, d);
-    });
+    if (!keys.order) naf_recode(keys.scalar(0), head.data());
+    const Slice s{pl.enc, rights, head, pl.rows.data(), pl.rows.size(), 16, 4, pl.n_search, keys.order ? KEYS_POINTS : SCAN_POINTS, SCAN_COMBINE};
+    return device_stage(T, s, f->flags.data(), f->status.data());
 }
 
 // one slice: the point stage in the form the row count asks for, then the search over the rows resident in T->v
-template <class Device>
-inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const Keys& keys, uint64_t limit, Found* f, Device device) {
+inline zk_status decrypt_plan(zk_elgamal_table* T, Plan& pl, const Keys& keys, uint64_t limit, Found* f) {
     pl.close();
     f->status.assign(pl.points(), 0);
     f->flags.assign(pl.rows.size(), 0);
     f->x.assign(pl.n_search, ~0ull);
     if (pl.rows.empty()) return ZK_OK;
-    ZK_TRY(pl.rows.size() <= host_max() ?points_on_host(T, pl, keys, f) : device(T, pl, keys, f));
+    ZK_TRY((pl.rows.size() <= host_max() ? points_on_host : points_on_device)(T, pl, keys, f));
     return elgamal_dlog_search_resident(T, pl.n_search, limit, f->x.data());
 }
 // field | status << 6 of the first refused point of match m in push order, or 0
@@ -436,15 +311,14 @@ struct Anonymous {
 };
 
 // Every match of the block, slice by slice (at most ELGAMAL_SEARCH_BLOCK search rows each):
-//   device(T, plan, keys, found)     the device form of the point stage
 //   slot(h, xt, key)                 where the result of match h - counted over the whole call, in (xt, key) order - goes; zeroed
-template <class Kind, class Device, class Slot>
-inline zk_status run(zk_elgamal_table* t, const Keys& keys, size_t n, const typename Kind::Xt* xts, uint64_t limit, Device device, Slot slot) {
+template <class Kind, class Slot>
+inline zk_status run(zk_elgamal_table* t, const Keys& keys, size_t n, const typename Kind::Xt* xts, uint64_t limit, Slot slot) {
     Plan pl;
     Found f;
     size_t done = 0;
     auto flush = [&]() -> zk_status {
-        ZK_TRY(decrypt_plan(t, pl, keys, limit, &f, device));
+        ZK_TRY(decrypt_plan(t, pl, keys, limit, &f));
         for (size_t m = 0; m + 1 < pl.matches.size(); m++) Kind::finish(pl, f, m, limit, slot(done + m, pl.matches[m].xt, pl.matches[m].key));
         done += pl.matches.size() - 1;
         f.wipe();
@@ -464,7 +338,7 @@ inline zk_status run(zk_elgamal_table* t, const Keys& keys, size_t n, const type
 template <class Kind>
 inline zk_status scan(zk_elgamal_table* t, size_t n, const typename Kind::Xt* xts, const uint8_t dec_key[32], uint64_t limit, typename Kind::Result* out) {
     if (!t || (n && (!xts || !dec_key || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (limit == 0 || limit > (1ull << 32)) return fail(ZK_ERR_INVALID_ARGUMENT, "limit must be 1 .. 2^32");
+    ZK_TRY(check_limit(limit));
     if (n == 0) return ZK_OK;
     uint64_t dk[4];
     WipeOnExit wipe_dk{dk, sizeof(dk)};
@@ -477,17 +351,7 @@ inline zk_status scan(zk_elgamal_table* t, size_t n, const typename Kind::Xt* xt
         jubjub_encode(pk.x, pk.y, key);
     }
     memset(out, 0, n * sizeof(typename Kind::Result));
-    return run<Kind>(t, Keys{1, dk, key, nullptr}, n, xts, limit, points_one_key, [out](size_t, size_t xt, uint32_t) { return &out[xt]; });
-}
-
-inline zk_status confidential(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
-                              zk_confidential_scan_result* out) {
-    return scan<Confidential>(t, n, xts, dec_key, limit, out);
-}
-
-inline zk_status anonymous(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
-                           zk_anonymous_scan_result* out) {
-    return scan<Anonymous>(t, n, xts, dec_key, limit, out);
+    return run<Kind>(t, Keys{1, dk, key, nullptr}, n, xts, limit, [out](size_t, size_t xt, uint32_t) { return &out[xt]; });
 }
 
 }  // namespace zkscan

@@ -78,9 +78,9 @@ struct zk_elgamal_table {
     zkrt::DevBuf consts, baby_xy, slots, giant_xy;
     // key-derived (left - dk right, the search's points, the logarithms): zeroed before release
     zkrt::DevBuf v, scratch, res;
-    // the point stage of zk_confidential_scan / zk_anonymous_scan (elgamal_scan.h).  Public chain data: the encodings and the
-    // rows that pair them | their coordinates, statuses and the rows' flags.  Key-derived: the digits of dk (scan_keys.h: the
-    // scalar of every hit) and dk * right
+    // the point stage of the scans and the balance query (wallet_stage.h device_stage, which alone lays them out).  Public chain
+    // data: the encodings and the rows that pair them | their coordinates, statuses and what the combine leaves per row.
+    // Key-derived: the digits of dk (a key set: the scalar of every hit) and dk * right
     zkrt::DevBuf scan_in, scan_out, scan_key;
     zk_elgamal_table() {
         consts.is_public = baby_xy.is_public = slots.is_public = giant_xy.is_public = scan_in.is_public = scan_out.is_public = true;

@@ -181,6 +181,31 @@ inline void run_threads(unsigned nthreads, Fn& work) {
     if (first) std::rethrow_exception(first);
 }
 
+// fn(i0, i1) -> zk_status on contiguous ranges of [0, n), one per host thread (host_threads(n, cap)): for work that keeps buffers
+// per thread.  The caller gets the status and the message of the lowest range that failed.
+template <class Fn>
+inline zk_status for_each_range(size_t n, unsigned cap, Fn&& fn) {
+    const unsigned nth = host_threads(n, cap);
+    std::vector<zk_status> sts(nth, ZK_OK);
+    std::vector<std::string> msgs(nth);
+    auto work = [&](unsigned t) {
+        if ((sts[t] = fn(n * t / nth, n * (t + 1) / nth)) != ZK_OK) msgs[t] = g_err;
+    };
+    run_threads(nth, work);
+    for (unsigned t = 0; t < nth; t++)
+        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
+    return ZK_OK;
+}
+// fn(i) -> zk_status for every i of [0, n) on the same ranges: a thread stops at its first failure, and the caller gets the status
+// and the message of the lowest failing index
+template <class Fn>
+inline zk_status for_each_status(size_t n, unsigned cap, Fn&& fn) {
+    return for_each_range(n, cap, [&](size_t i0, size_t i1) -> zk_status {
+        for (size_t i = i0; i < i1; i++) ZK_TRY(fn(i));
+        return ZK_OK;
+    });
+}
+
 // one helper thread beside the caller (the staging of the next block of a batch); joined on every path out of the scope
 struct SideThread {
     std::thread t;

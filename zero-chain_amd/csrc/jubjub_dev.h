@@ -6,6 +6,7 @@
 //   sqrt_one_pow             square root in Fr with ONE exponentiation, then Tonelli-Shanks (~290 + <= 500)
 //   ext_dbl, cache_put, ext_add_cached   extended twisted Edwards, a = -1: dbl-2008-hwcd, addends cached as (Y + X, Y - X, 2 d T, 2 Z)
 //   ext_add                  two extended points, add-2008-hwcd-3 (9 products): the operator of ledger.h's scan
+//   ep_neutral, jubjub_d2, point_words, point_write   the neutral element, 2 d in Montgomery form, edwards::Point::write of an affine point
 //   naf_chain                sum of signed odd digits times the cached P, 3P, 5P, 7P: 252 doublings, an addition per non-zero digit
 //   is_prime_order           [s]P == O over the width-4 NAF of s recoded at compile time (~2 200)
 //   mul_naf                  [k]P over a width-4 NAF recoded by the host at run time (elgamal_scan.h: ~2 400)
@@ -147,6 +148,29 @@ ZK_DI bool sqrt_one_pow(const Lds& L, const Fr& a, Fr* out) {
 struct EP {   // extended twisted Edwards, a = -1
     Fr X, Y, Z, T;
 };
+ZK_DI EP ep_neutral() { return EP{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()}; }
+// the curve's d and 2 d (the k of ext_add, cache_put), in Montgomery form
+ZK_DI Fr jubjub_d() {
+    Fr d;
+    const uint64_t dp[4] = ZK_JUBJUB_D_PLAIN_64;
+#pragma unroll
+    for (int i = 0; i < 8; i++) d.l[i] = (uint32_t)(dp[i >> 1] >> (32 * (i & 1)));
+    return zkdev::to_mont(d);
+}
+ZK_DI Fr jubjub_d2() { return dbl(jubjub_d()); }
+// edwards::Point::write of an affine point in Montgomery form: y, the parity of x in the top bit - as 8 words, and into those at o
+ZK_DI Fr point_words(const Fr& x_mont, const Fr& y_mont) {
+    const Fr x = zkdev::from_mont(x_mont);
+    Fr y = zkdev::from_mont(y_mont);
+    y.l[7] |= (x.l[0] & 1u) << 31;
+    return y;
+}
+ZK_DI void point_write(uint32_t* o, const Fr& x_mont, const Fr& y_mont) {
+    const Fr y = point_words(x_mont, y_mont);
+    uint4* q = reinterpret_cast<uint4*>(o);
+    q[0] = make_uint4(y.l[0], y.l[1], y.l[2], y.l[3]);
+    q[1] = make_uint4(y.l[4], y.l[5], y.l[6], y.l[7]);
+}
 // dbl-2008-hwcd, a = -1; T only where the next step reads it (an addition)
 ZK_DI EP ext_dbl(const EP& p, bool want_t) {
     const Fr a = sqr(p.X), b = sqr(p.Y), c = dbl(sqr(p.Z));
@@ -202,7 +226,7 @@ ZK_DI void cache_odd_multiples(const Lds& L, const EP& p1, const Fr& d2) {
 // in every lane of the wave.  T of the result only where want_t.
 template <class Digit>
 ZK_DI EP naf_chain(const Lds& L, int top, Digit digit, bool want_t) {
-    EP acc{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()};
+    EP acc = ep_neutral();
 #pragma unroll 1
     for (int i = top; i >= 0; i--) {
         const int v = digit(i);
@@ -247,13 +271,7 @@ ZK_DI uint32_t read_point(const Lds& L, const uint32_t* enc, Fr* x, Fr* y_out, F
         }
         if (bo == 0) return INTO_XY_NOT_IN_FIELD;
     }
-    Fr d;
-    {
-        const uint64_t dp[4] = ZK_JUBJUB_D_PLAIN_64;
-#pragma unroll
-        for (int i = 0; i < 8; i++) d.l[i] = (uint32_t)(dp[i >> 1] >> (32 * (i & 1)));
-    }
-    d = zkdev::to_mont(d);
+    const Fr d = jubjub_d();
     const Fr ym = zkdev::to_mont(y);
     const Fr y2 = sqr(ym);
     constexpr PowDigits EI = digits_inverse();

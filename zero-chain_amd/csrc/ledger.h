@@ -64,20 +64,12 @@ ZK_DI void ep_store(uint32_t* g, const EP& p) {
     fr_store(g + 16, p.Z);
     fr_store(g + 24, p.T);
 }
-ZK_DI EP ep_identity() { return EP{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()}; }
 // the point k_into_xy left at xy (x then y, plain), or its negative
 ZK_DI EP ep_from_xy(const uint32_t* xy, bool negative) {
     Fr x = zkdev::to_mont(fr_load(xy));
     const Fr y = zkdev::to_mont(fr_load(xy + 8));
     if (negative) x = neg(x);
     return EP{x, y, Fr::one(), mul(x, y)};
-}
-ZK_DI Fr edwards_2d() {
-    Fr d;
-    const uint64_t dp[4] = ZK_JUBJUB_D_PLAIN_64;
-#pragma unroll
-    for (int i = 0; i < 8; i++) d.l[i] = (uint32_t)(dp[i >> 1] >> (32 * (i & 1)));
-    return dbl(zkdev::to_mont(d));
 }
 // lane t's EP of the scan's LDS: [X Y Z T][word][lane]
 ZK_DI void scan_st(uint32_t* lds, uint32_t t, const EP& v) {
@@ -127,8 +119,8 @@ k_ledger_scan(const uint32_t* xy, const uint32_t* st, const uint32_t* off, const
     ZK_SHARED uint32_t lds[4 * 8 * LEDGER_SCAN_W];
     const uint32_t t = threadIdx.x, c = blockIdx.y, b0 = blockIdx.x * LEDGER_SCAN_W, j = b0 + t;
     const bool live = j < n_ops;
-    const Fr d2 = edwards_2d();
-    EP v = ep_identity();
+    const Fr d2 = zkxt::jubjub_d2();
+    EP v = zkxt::ep_neutral();
     uint32_t s = 0, reach = 0;
     if (live) {
         const uint32_t i = perm[j], fl = flagv[i];
@@ -142,7 +134,7 @@ k_ledger_scan(const uint32_t* xy, const uint32_t* st, const uint32_t* off, const
     scan_st(lds, t, v);
     __syncthreads();
     if (live) {
-        const EP e = reach ? scan_ld(lds, t - 1) : ep_identity();
+        const EP e = reach ? scan_ld(lds, t - 1) : zkxt::ep_neutral();
         ep_store(pre + ((size_t)c * n_ops + j) * 32, e);
         if (j + 1 == off[s + 1]) ep_store(tot + ((size_t)c * n_slots + s) * 32, v);
     }
@@ -156,14 +148,14 @@ static __global__ void __launch_bounds__(LEDGER_SCAN_W)
 k_ledger_carry(const uint32_t* agg, const uint32_t* cstart, uint32_t n_blocks, uint32_t* carry) {
     ZK_SHARED uint32_t lds[4 * 8 * LEDGER_SCAN_W];
     const uint32_t t = threadIdx.x, c = blockIdx.y;
-    const Fr d2 = edwards_2d();
-    EP run = ep_identity();
+    const Fr d2 = zkxt::jubjub_d2();
+    EP run = zkxt::ep_neutral();
     if (t == 0) ep_store(carry + (size_t)c * n_blocks * 32, run);
 #pragma unroll 1
     for (uint32_t base = 0; base < n_blocks; base += LEDGER_SCAN_W) {
         const uint32_t b = base + t;
         const bool live = b < n_blocks;
-        EP v = ep_identity();
+        EP v = zkxt::ep_neutral();
         uint32_t reach = 0;
         bool open = false;   // the segment of b began before `base`: the running sum belongs to it
         if (live) {
@@ -206,9 +198,9 @@ k_ledger_encode(const uint32_t* xy, const uint32_t* st, const uint32_t* off, con
         last = pos[i];
         src = pre + ((size_t)c * n_ops + last) * 32;
     }
-    Fr x = Fr::zero(), y = Fr::zero();
+    Fr y = Fr::zero();
     if ((st[2 * (size_t)s] | st[2 * (size_t)s + 1]) == 0) {
-        const Fr d2 = edwards_2d();
+        const Fr d2 = zkxt::jubjub_d2();
         EP v = ep_from_xy(xy + (2 * (size_t)s + c) * 16, false);
         if (src) {
             EP sum = ep_load(src);
@@ -218,9 +210,7 @@ k_ledger_encode(const uint32_t* xy, const uint32_t* st, const uint32_t* off, con
         }
         constexpr zkxt::PowDigits EI = zkxt::digits_inverse();
         const Fr zi = zkxt::pow_windows(L, v.Z, EI);   // Z != 0: the addition law is complete on the prime-order subgroup
-        x = zkdev::from_mont(mul(v.X, zi));
-        y = zkdev::from_mont(mul(v.Y, zi));
-        y.l[7] |= (x.l[0] & 1u) << 31;
+        y = zkxt::point_words(mul(v.X, zi), mul(v.Y, zi));
     }
     fr_store(enc + (size_t)q * 8, y);
 }

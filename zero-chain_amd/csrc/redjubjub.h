@@ -152,7 +152,7 @@ k_rj_check(const uint32_t* gtab, const uint32_t* xy, const uint32_t* status, con
                 zkxt::cache_put(L, i, q, d2);
             }
         }
-        EP acc{Fr::zero(), Fr::one(), Fr::one(), Fr::zero()};
+        EP acc = zkxt::ep_neutral();
 #pragma unroll 1
         for (int j = 252 / VK_WINDOW; j >= 0; j--) {
             if (j != 252 / VK_WINDOW) {
@@ -276,40 +276,28 @@ inline zk_status check_offsets(size_t n, const uint8_t* msgs, const uint64_t* of
 inline zk_status sign(size_t n, const uint8_t* rsk, const uint8_t* t80, const uint8_t* msgs, const uint64_t* offs, uint8_t* sigs_out) {
     ZK_TRY(check_offsets(n, msgs, offs));
     (void)zkwit::tables();
-    const unsigned nth = zkrt::host_threads(n, 64);
-    std::vector<zk_status> sts(nth, ZK_OK);
-    std::vector<std::string> errs(nth);
-    auto work = [&](unsigned th) {
-        for (size_t i = n * th / nth; i < n * (th + 1) / nth; i++) {
-            uint64_t sk[4], r[4], c[4], cs[4], s[4];
-            uint8_t digest[64];
-            zkhash::Blake2b h(H_STAR_PERSON);   // of r = H*(T || M): its state is a secret's
-            WipeOnExit wipe_sk{sk, sizeof(sk)}, wipe_r{r, sizeof(r)}, wipe_cs{cs, sizeof(cs)}, wipe_d{digest, sizeof(digest)}, wipe_h{&h, sizeof(h)};
-            zkrt::load_scalar_le(rsk + 32 * i, sk);
-            if (!fs_lt_mod_ct(sk)) {
-                sts[th] = fail(ZK_ERR_INVALID_ARGUMENT, "rsk " + std::to_string(i) + " is not a canonical Fs scalar");
-                errs[th] = zkrt::g_err;
-                return;
-            }
-            const uint8_t* m = msgs ? msgs + offs[i] : nullptr;
-            const size_t m_len = (size_t)(offs[i + 1] - offs[i]);
-            h.update(t80 + 80 * i, 80);
-            h.update(m, m_len);
-            h.finish(digest);
-            fs_to_uniform_ct(digest, r);
-            const zkwit::JPoint rg = jubjub_fixed_mul(r);
-            uint8_t* sig = sigs_out + 64 * i;
-            jubjub_encode(rg.x, rg.y, sig);
-            h_star(sig, 32, m, m_len, c);
-            fs_mul_public(c, sk, cs);
-            fs_add_ct(cs, r, s);
-            memcpy(sig + 32, s, 32);
-        }
-    };
-    zkrt::run_threads(nth, work);
-    for (unsigned th = 0; th < nth; th++)
-        if (sts[th] != ZK_OK) return fail(sts[th], errs[th]);
-    return ZK_OK;
+    return zkrt::for_each_status(n, 64, [&](size_t i) -> zk_status {
+        uint64_t sk[4], r[4], c[4], cs[4], s[4];
+        uint8_t digest[64];
+        zkhash::Blake2b h(H_STAR_PERSON);   // of r = H*(T || M): its state is a secret's
+        WipeOnExit wipe_sk{sk, sizeof(sk)}, wipe_r{r, sizeof(r)}, wipe_cs{cs, sizeof(cs)}, wipe_d{digest, sizeof(digest)}, wipe_h{&h, sizeof(h)};
+        zkrt::load_scalar_le(rsk + 32 * i, sk);
+        if (!fs_lt_mod_ct(sk)) return fail(ZK_ERR_INVALID_ARGUMENT, "rsk " + std::to_string(i) + " is not a canonical Fs scalar");
+        const uint8_t* m = msgs ? msgs + offs[i] : nullptr;
+        const size_t m_len = (size_t)(offs[i + 1] - offs[i]);
+        h.update(t80 + 80 * i, 80);
+        h.update(m, m_len);
+        h.finish(digest);
+        fs_to_uniform_ct(digest, r);
+        const zkwit::JPoint rg = jubjub_fixed_mul(r);
+        uint8_t* sig = sigs_out + 64 * i;
+        jubjub_encode(rg.x, rg.y, sig);
+        h_star(sig, 32, m, m_len, c);
+        fs_mul_public(c, sk, cs);
+        fs_add_ct(cs, r, s);
+        memcpy(sig + 32, s, 32);
+        return ZK_OK;
+    });
 }
 
 // PublicKey::verify of one signature, c = H*(Rbar || M) given

@@ -11,7 +11,8 @@
 //   a block read with one decryption key                 - (elgamal.rs:85-108 per value, crypto_components.rs:168-220; elgamal_scan.h)
 //   BalanceQuery::get_balance_from_decryption_key        zface/src/utils/getter.rs:135-175, for the accounts of a key set (balance_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
-// the signature check (redjubjub.h), those of the scans' point stage (elgamal_scan.h, scan_keys.h) and the combine of balance_keys.h.
+// the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h) and
+// its two combines (elgamal_scan.h, balance_keys.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -221,30 +222,15 @@ zk_status transfer_derive_one(const zk_transfer_request& rq, size_t index, zk_tr
 zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_statement* st, uint8_t* rsk, bool check_points) {
     if (n == 0) return ZK_OK;
     (void)zkwit::tables();
-    const unsigned nthreads = host_threads(n, 64);
     const bool spread = check_points && n * 4 <= host_threads(4 * n, 64);   // a handful of requests: the four decodings of each on their own threads
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned t) {
-        for (size_t i = n * t / nthreads; i < n * (t + 1) / nthreads; i++) {
-            zk_status rc = transfer_derive_one(rq[i], i, &st[i], rsk + i * 32, check_points, spread);
-            if (rc != ZK_OK) {
-                sts[t] = rc;
-                msgs[t] = g_err;
-                return;
-            }
-        }
-    };
-    run_threads(nthreads, work);
-    for (unsigned t = 0; t < nthreads; t++)
-        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
-    return ZK_OK;
+    return for_each_status(n, 64, [&](size_t i) -> zk_status { return transfer_derive_one(rq[i], i, &st[i], rsk + i * 32, check_points, spread); });
 }
 
 }  // namespace
 
 #include "redjubjub.h"   // (here: it signs and hashes with the helpers above)
-#include "elgamal_scan.h"   // (and the scan decodes, multiplies and wipes with them)
+#include "wallet_stage.h"   // (the point stage of the three below: two point kernels, the device form, the host forms' tail)
+#include "elgamal_scan.h"   // (the scan decodes, multiplies and wipes with the helpers above)
 #include "scan_keys.h"      // (the same scan for a set of keys: a scalar per hit)
 #include "balance_keys.h"   // (the balances of such a set's accounts: the same point kernel, a combine of its own)
 
@@ -282,30 +268,18 @@ zk_status zk_jubjub_base_mul(const uint8_t* scalars, size_t n, uint8_t* points_o
     if (n && (!scalars || !points_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
     (void)zkwit::tables();
-    const unsigned nthreads = host_threads(n, 64);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
     // test hook (tests/test_gen_proof.py): the LAST worker thread fails an allocation - the exception must reach the caller as
     // a status, through run_threads and the barrier of this entry, not unwind into it
     const bool inject = hook_env("ZKAMD_INJECT_THROW") != nullptr;
-    auto work = [&](unsigned t) {
-        if (inject && t + 1 == nthreads) throw std::bad_alloc();
-        for (size_t i = n * t / nthreads; i < n * (t + 1) / nthreads; i++) {
-            uint64_t k[4];
-            load_scalar_le(scalars + 32 * i, k);
-            if (!fs_lt_mod(k)) {
-                sts[t] = fail(ZK_ERR_INVALID_ARGUMENT, "scalar " + std::to_string(i) + " is not a canonical Fs scalar");
-                msgs[t] = g_err;
-                return;
-            }
-            const zkwit::JPoint p = jubjub_fixed_mul(k);
-            jubjub_encode(p.x, p.y, points_out + 32 * i);
-        }
-    };
-    run_threads(nthreads, work);
-    for (unsigned t = 0; t < nthreads; t++)
-        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
-    return ZK_OK;
+    return for_each_status(n, 64, [&](size_t i) -> zk_status {
+        if (inject && i + 1 == n) throw std::bad_alloc();
+        uint64_t k[4];
+        load_scalar_le(scalars + 32 * i, k);
+        if (!fs_lt_mod(k)) return fail(ZK_ERR_INVALID_ARGUMENT, "scalar " + std::to_string(i) + " is not a canonical Fs scalar");
+        const zkwit::JPoint p = jubjub_fixed_mul(k);
+        jubjub_encode(p.x, p.y, points_out + 32 * i);
+        return ZK_OK;
+    });
 } ZK_ABI_CATCH
 
 zk_status zk_elgamal_encrypt(const uint32_t* values, const uint8_t* randomness, const uint8_t* enc_keys, size_t n, uint8_t* left_out,
@@ -313,34 +287,20 @@ zk_status zk_elgamal_encrypt(const uint32_t* values, const uint8_t* randomness, 
     if (n && (!values || !randomness || !enc_keys || !left_out || !right_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
     (void)zkwit::tables();
-    const unsigned nthreads = host_threads(n, 16);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned t) {
-        for (size_t i = n * t / nthreads; i < n * (t + 1) / nthreads; i++) {
-            uint64_t r[4], v[4] = {values[i], 0, 0, 0};
-            load_scalar_le(randomness + 32 * i, r);
-            zkwit::JPoint key;
-            zk_status rc = fs_lt_mod(r) ? ZK_OK : fail(ZK_ERR_INVALID_ARGUMENT, "randomness " + std::to_string(i) + " is not a canonical Fs scalar");
-            if (rc == ZK_OK) rc = decode_prime_order(enc_keys + 32 * i, &key, "enc_key " + std::to_string(i));
-            if (rc != ZK_OK) {
-                sts[t] = rc;
-                msgs[t] = g_err;
-                return;
-            }
-            // left = v G + r pk, right = r G  (no_std_aliases/elgamal.rs:46-63)
-            zkwit::EPoint proj[2] = {zkwit::ext_add(zkwit::to_ext(jubjub_fixed_mul(v)), jubjub_var_mul(key, r)),
-                                     zkwit::to_ext(jubjub_fixed_mul(r))};
-            zkwit::JPoint aff[2];
-            zkwit::batch_to_affine(proj, aff, 2);
-            jubjub_encode(aff[0].x, aff[0].y, left_out + 32 * i);
-            jubjub_encode(aff[1].x, aff[1].y, right_out + 32 * i);
-        }
-    };
-    run_threads(nthreads, work);
-    for (unsigned t = 0; t < nthreads; t++)
-        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
-    return ZK_OK;
+    return for_each_status(n, 16, [&](size_t i) -> zk_status {
+        uint64_t r[4], v[4] = {values[i], 0, 0, 0};
+        load_scalar_le(randomness + 32 * i, r);
+        zkwit::JPoint key;
+        if (!fs_lt_mod(r)) return fail(ZK_ERR_INVALID_ARGUMENT, "randomness " + std::to_string(i) + " is not a canonical Fs scalar");
+        ZK_TRY(decode_prime_order(enc_keys + 32 * i, &key, "enc_key " + std::to_string(i)));
+        // left = v G + r pk, right = r G  (no_std_aliases/elgamal.rs:46-63)
+        zkwit::EPoint proj[2] = {zkwit::ext_add(zkwit::to_ext(jubjub_fixed_mul(v)), jubjub_var_mul(key, r)), zkwit::to_ext(jubjub_fixed_mul(r))};
+        zkwit::JPoint aff[2];
+        zkwit::batch_to_affine(proj, aff, 2);
+        jubjub_encode(aff[0].x, aff[0].y, left_out + 32 * i);
+        jubjub_encode(aff[1].x, aff[1].y, right_out + 32 * i);
+        return ZK_OK;
+    });
 } ZK_ABI_CATCH
 
 // ElGamal decryption (elgamal.rs:85-108) as a baby-step giant-step search: the table and the search are witness.cpp's
@@ -376,17 +336,13 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
     if (!t || (n && (!left || !right || !dec_keys || !values_out || !found_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (dec_key_stride != 0 && dec_key_stride != 32)
         return fail(ZK_ERR_INVALID_ARGUMENT, "dec_key_stride must be 0 (one key for all) or 32 (one key per ciphertext)");
-    if (limit == 0 || limit > (1ull << 32)) return fail(ZK_ERR_INVALID_ARGUMENT, "limit must be 1 .. 2^32");
+    ZK_TRY(zkscan::check_limit(limit));
     if (n == 0) return ZK_OK;
     ZK_TRY(use_device(t->device));
     // v = left - dk right (elgamal.rs:92-94), affine: the value is its logarithm
     std::vector<zkwit::JPoint> v(n);
     WipeOnExit wipe_v{v.data(), n * sizeof(zkwit::JPoint)};
-    const unsigned nthreads = host_threads(n, 16);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned th) {
-        const size_t i0 = n * th / nthreads, i1 = n * (th + 1) / nthreads;
+    ZK_TRY(for_each_range(n, 16, [&](size_t i0, size_t i1) -> zk_status {
         std::vector<zkwit::EPoint> proj(i1 - i0);
         WipeOnExit wipe_p{proj.data(), proj.size() * sizeof(zkwit::EPoint)};
         for (size_t i = i0; i < i1; i++) {
@@ -395,24 +351,16 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
             load_scalar_le(dec_keys + dec_key_stride * i, dk);
             const std::string who = "ciphertext " + std::to_string(i) + ": ";
             zkwit::JPoint l, r;
-            zk_status rc = fs_lt_mod(dk) ? ZK_OK
-                                         : fail(ZK_ERR_INVALID_ARGUMENT, (dec_key_stride ? "dec_key " + std::to_string(i) : std::string("dec_key")) +
-                                                                             " is not a canonical Fs scalar");
-            if (rc == ZK_OK) rc = decode_prime_order(left + 32 * i, &l, who + "left");
-            if (rc == ZK_OK) rc = decode_prime_order(right + 32 * i, &r, who + "right");
-            if (rc != ZK_OK) {
-                sts[th] = rc;
-                msgs[th] = g_err;
-                return;
-            }
+            if (!fs_lt_mod(dk))
+                return fail(ZK_ERR_INVALID_ARGUMENT, (dec_key_stride ? "dec_key " + std::to_string(i) : std::string("dec_key")) + " is not a canonical Fs scalar");
+            ZK_TRY(decode_prime_order(left + 32 * i, &l, who + "left"));
+            ZK_TRY(decode_prime_order(right + 32 * i, &r, who + "right"));
             const zkwit::EPoint s = jubjub_var_mul(r, dk);
             proj[i - i0] = zkwit::ext_add(zkwit::to_ext(l), zkwit::EPoint{zkhost::Fr::zero() - s.X, s.Y, s.Z, zkhost::Fr::zero() - s.T});
         }
         zkwit::batch_to_affine(proj.data(), v.data() + i0, i1 - i0);
-    };
-    run_threads(nthreads, work);
-    for (unsigned th = 0; th < nthreads; th++)
-        if (sts[th] != ZK_OK) return fail(sts[th], msgs[th]);
+        return ZK_OK;
+    }));
     std::vector<uint64_t> x(n);
     WipeOnExit wipe_x{x.data(), n * sizeof(uint64_t)};
     static_assert(sizeof(zkwit::JPoint) == 2 * sizeof(zkhost::Fr), "x | y");
@@ -427,12 +375,12 @@ zk_status zk_elgamal_decrypt(zk_elgamal_table* t, size_t n, const uint8_t* left,
 
 zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                                zk_confidential_scan_result* out) try {
-    return zkscan::confidential(t, n, xts, dec_key, limit, out);
+    return zkscan::scan<zkscan::Confidential>(t, n, xts, dec_key, limit, out);
 } ZK_ABI_CATCH
 
 zk_status zk_anonymous_scan(zk_elgamal_table* t, size_t n, const zk_anonymous_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                             zk_anonymous_scan_result* out) try {
-    return zkscan::anonymous(t, n, xts, dec_key, limit, out);
+    return zkscan::scan<zkscan::Anonymous>(t, n, xts, dec_key, limit, out);
 } ZK_ABI_CATCH
 
 zk_status zk_scan_keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_keys** out) try {
@@ -466,38 +414,23 @@ zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const ui
                          int subtract, uint8_t* left_out, uint8_t* right_out) try {
     if (n && (!left_a || !right_a || !left_b || !right_b || !left_out || !right_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
-    const unsigned nthreads = host_threads(n, 16);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned th) {
-        for (size_t i = n * th / nthreads; i < n * (th + 1) / nthreads; i++) {
-            // Ciphertext::read of both operands (elgamal.rs:116-133), then left_a +- left_b, right_a +- right_b
-            const uint8_t* in[4] = {left_a + 32 * i, right_a + 32 * i, left_b + 32 * i, right_b + 32 * i};
-            static const char* const name[4] = {"left_a", "right_a", "left_b", "right_b"};
-            zkwit::JPoint p[4];
-            zk_status rc = ZK_OK;
-            for (int k = 0; k < 4 && rc == ZK_OK; k++) rc = decode_prime_order(in[k], &p[k], "ciphertext " + std::to_string(i) + ": " + name[k]);
-            if (rc != ZK_OK) {
-                sts[th] = rc;
-                msgs[th] = g_err;
-                return;
-            }
-            if (subtract) {
-                p[2].x = zkhost::Fr::zero() - p[2].x;
-                p[3].x = zkhost::Fr::zero() - p[3].x;
-            }
-            const zkwit::EPoint sum[2] = {zkwit::ext_add(zkwit::to_ext(p[0]), zkwit::to_ext(p[2])),
-                                          zkwit::ext_add(zkwit::to_ext(p[1]), zkwit::to_ext(p[3]))};
-            zkwit::JPoint aff[2];
-            zkwit::batch_to_affine(sum, aff, 2);
-            jubjub_encode(aff[0].x, aff[0].y, left_out + 32 * i);
-            jubjub_encode(aff[1].x, aff[1].y, right_out + 32 * i);
+    return for_each_status(n, 16, [&](size_t i) -> zk_status {
+        // Ciphertext::read of both operands (elgamal.rs:116-133), then left_a +- left_b, right_a +- right_b
+        const uint8_t* in[4] = {left_a + 32 * i, right_a + 32 * i, left_b + 32 * i, right_b + 32 * i};
+        static const char* const name[4] = {"left_a", "right_a", "left_b", "right_b"};
+        zkwit::JPoint p[4];
+        for (int k = 0; k < 4; k++) ZK_TRY(decode_prime_order(in[k], &p[k], "ciphertext " + std::to_string(i) + ": " + name[k]));
+        if (subtract) {
+            p[2].x = zkhost::Fr::zero() - p[2].x;
+            p[3].x = zkhost::Fr::zero() - p[3].x;
         }
-    };
-    run_threads(nthreads, work);
-    for (unsigned th = 0; th < nthreads; th++)
-        if (sts[th] != ZK_OK) return fail(sts[th], msgs[th]);
-    return ZK_OK;
+        const zkwit::EPoint sum[2] = {zkwit::ext_add(zkwit::to_ext(p[0]), zkwit::to_ext(p[2])), zkwit::ext_add(zkwit::to_ext(p[1]), zkwit::to_ext(p[3]))};
+        zkwit::JPoint aff[2];
+        zkwit::batch_to_affine(sum, aff, 2);
+        jubjub_encode(aff[0].x, aff[0].y, left_out + 32 * i);
+        jubjub_encode(aff[1].x, aff[1].y, right_out + 32 * i);
+        return ZK_OK;
+    });
 } ZK_ABI_CATCH
 
 zk_status zk_transfer_derive(const zk_transfer_request* req, size_t n, zk_transfer_statement* statements_out, uint8_t* rsk_out) try {
@@ -711,23 +644,7 @@ zk_status anonymous_derive_one(const zk_anonymous_request& rq, size_t index, zk_
 zk_status anonymous_derive(const zk_anonymous_request* rq, size_t n, zk_anonymous_statement* st, uint8_t* rsk, AnonDerived* der) {
     if (n == 0) return ZK_OK;
     (void)zkwit::tables();
-    const unsigned nthreads = host_threads(n, 8);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    auto work = [&](unsigned t) {
-        for (size_t i = n * t / nthreads; i < n * (t + 1) / nthreads; i++) {
-            zk_status rc = anonymous_derive_one(rq[i], i, &st[i], rsk + i * 32, der ? &der[i] : nullptr);
-            if (rc != ZK_OK) {
-                sts[t] = rc;
-                msgs[t] = g_err;
-                return;
-            }
-        }
-    };
-    run_threads(nthreads, work);
-    for (unsigned t = 0; t < nthreads; t++)
-        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
-    return ZK_OK;
+    return for_each_status(n, 8, [&](size_t i) -> zk_status { return anonymous_derive_one(rq[i], i, &st[i], rsk + i * 32, der ? &der[i] : nullptr); });
 }
 
 }  // namespace
