@@ -1,4 +1,4 @@
-"""The four-transform form of the prover (zkamd.cpp ensure_derived / prove_chunk): the H query on the coset-Lagrange basis and
+"""The four-transform form of the prover (prover_binding.h ensure_derived, zkamd.cpp prove_chunk): the H query on the coset-Lagrange basis and
 the c part of H folded into the bases of the variables, bound to one (key, circuit) pair.
 
 The statement-to-proof entries take it; zk_prove_batch_witness keeps the six transforms over the key's own bases.  Synthetic

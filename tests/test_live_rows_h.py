@@ -1,4 +1,4 @@
-"""The H part of the four-transform prover on the live rows only (zkamd.cpp ensure_derived / prove_chunk, ntt.h k_h_live_rows).
+"""The H part of the four-transform prover on the live rows only (prover_binding.h ensure_derived, zkamd.cpp prove_chunk, ntt.h k_h_live_rows).
 
 A circuit with n_rows = n_con + n_in rows on a domain of m points has m - n_rows rows of zero padding: a_j = b_j = c_j = 0 there
 for every assignment.  With w the m-th root, H'_t = H_t (t <= m - 2), H'_(m-1) = 0 (bellman's truncation), a_t the coefficients

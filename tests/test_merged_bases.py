@@ -1,4 +1,4 @@
-"""One term per distinct base in the A and B queries (zkamd.cpp group_equal_points / ensure_maps, ntt.h k_build_scalars).
+"""One term per distinct base in the A and B queries (prover_key.h group_equal_points, prover_binding.h ensure_maps, ntt.h k_build_scalars).
 
 Variables with identical QAP columns have EQUAL points in a key, whatever its toxic waste: z_i P + z_j P = (z_i + z_j) P, so
 the multiexps of a proof take such a group as one term under the sum of its scalars.  The groups are found from the points of

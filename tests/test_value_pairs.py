@@ -1,4 +1,4 @@
-"""Value pairs (csrc/value_pairs.h, zkamd.cpp derived_pairs, ntt.h k_build_scalars): two linked variables of a proof that hold
+"""Value pairs (csrc/value_pairs.h, prover_binding.h derived_pairs, ntt.h k_build_scalars): two linked variables of a proof that hold
 the same value are ONE term of a multiexp over the sum of their two bases.
 
     z_p P_p + z_j P_j = z_j (P_p + P_j)        whenever z_p = z_j

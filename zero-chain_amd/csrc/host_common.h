@@ -321,6 +321,17 @@ struct DevBuf {
     T* as() const {
         return reinterpret_cast<T*>(p);
     }
+    // room for n elements of the host array v, then a blocking copy of them (a std::vector: all of it)
+    template <class T>
+    zk_status upload(const T* v, size_t n) {
+        ZK_TRY(ensure(n * sizeof(T)));
+        HIP_TRY(hipMemcpy(p, v, n * sizeof(T), hipMemcpyHostToDevice));
+        return ZK_OK;
+    }
+    template <class T>
+    zk_status upload(const std::vector<T>& v) {
+        return upload(v.data(), v.size());
+    }
 };
 
 // page-locked host memory: asynchronous copies into pageable memory block the calling thread until

@@ -57,9 +57,9 @@ struct ProveTunables {
 //   C job:  [ H block (head) | aux | r z (nv) | r | (fold: s z (nv) | s | r s) | (derived: inputs) | r * sums of the B1 groups
 //             (gb1) | (fold: s * sums of the A groups (ga)) ]
 // head: bellman's m coefficients, or [s | e] of the live rows (2 n_rows) over the derived bases, whose input variables carry
-// the c part of H (zkamd.cpp ensure_derived).  fold: the job is C = s * A + C' itself, over the bases of the A query, alpha_1
+// the c part of H (prover_binding.h ensure_derived).  fold: the job is C = s * A + C' itself, over the bases of the A query, alpha_1
 // and delta_1 behind the r.  A section the form does not have is at offset 0 (k_build_scalars tests in_tail for that).
-// Value pairs (zkamd.cpp derived_pairs, value_pairs.h; all lengths 0 without them): two linked variables that hold the same
+// Value pairs (prover_binding.h derived_pairs, value_pairs.h; all lengths 0 without them): two linked variables that hold the same
 // value in a proof are one term over the sum of their two bases, whose slots lie behind everything above -
 //   witness vector:  ... | the variables again, for the B2 job (nv) | pairs of the A query (pa) | of the B2 query (pb2) ]
 //   C job:           ... | pairs of the L section (pl) | r * pairs of the B1 query (pb1) | (fold: s * pairs of the A query (pa)) ]
@@ -86,6 +86,13 @@ struct CJobLayout {
 struct PairCounts {
     uint32_t a = 0, b2 = 0, l = 0, b1 = 0;
     bool any() const { return (a | b2 | l | b1) != 0; }
+    // the same counts by query number, [a, b_g2, l, b_g1] (value_pairs.h Query): the one place that pairs names with numbers
+    static PairCounts of(const uint32_t n[4]) {
+        PairCounts pc;
+        pc.a = n[0]; pc.b2 = n[1]; pc.l = n[2]; pc.b1 = n[3];
+        return pc;
+    }
+    uint32_t operator[](int query) const { return query == 0 ? a : query == 1 ? b2 : query == 2 ? l : b1; }
 };
 
 inline CJobLayout cjob_layout(uint32_t n_in, uint32_t n_aux, uint32_t head, uint32_t ga, uint32_t gb2, uint32_t gb1, bool fold,

@@ -79,7 +79,7 @@ extern "C" zk_status zk_generate_parameters(zk_r1cs* R, const uint8_t g1_bytes[9
                                             const uint8_t tau_b[32], uint8_t* out, size_t cap, size_t* len) try {
     if (!R || !g1_bytes || !g2_bytes || !alpha_b || !beta_b || !gamma_b || !delta_b || !tau_b || !len)
         return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    ZK_TRY(use_device(R->device));
+    ZK_TRY(use_device(R->sys.device));
     HG1A g1;
     HG2A g2;
     if (zkhost::g1_from_uncompressed(g1_bytes, &g1) != zkhost::DEC_OK || g1.is_inf() || !zkhost::on_curve(g1))
@@ -101,7 +101,7 @@ extern "C" zk_status zk_generate_parameters(zk_r1cs* R, const uint8_t g1_bytes[9
         return fail(ZK_ERR_INVALID_ARGUMENT, "a trapdoor scalar is not a canonical field element (>= r)");
     // bellman: gamma.inverse() / delta.inverse() -> SynthesisError::UnexpectedIdentity
     if (gamma.is_zero() || delta.is_zero()) return fail(ZK_ERR_UNEXPECTED_IDENTITY, "gamma or delta is zero");
-    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, n_rows = n_con + n_in;
+    const uint32_t n_in = R->sys.n_in, n_aux = R->sys.n_aux, nv = n_in + n_aux, n_con = R->sys.n_con, n_rows = n_con + n_in;
     uint32_t log_m = 0;
     while (((size_t)1 << log_m) < n_rows) log_m++;
     if (log_m > 27) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "evaluation domain larger than 2^27");
@@ -117,8 +117,8 @@ extern "C" zk_status zk_generate_parameters(zk_r1cs* R, const uint8_t g1_bytes[9
     DevBuf d_colptr[3], d_row[3], d_coeff[3];
     zkdev::CscMat csc[3];
     for (int k = 0; k < 3; k++) {
-        const std::vector<uint32_t>& rp = R->h_row_ptr[k];
-        const std::vector<uint32_t>& cl = R->h_col[k];
+        const std::vector<uint32_t>& rp = R->sys.h_row_ptr[k];
+        const std::vector<uint32_t>& cl = R->sys.h_col[k];
         const size_t nnz = cl.size();
         std::vector<uint32_t> col_ptr(nv + 1, 0), row(nnz ? nnz : 1);
         std::vector<Fr> co(nnz ? nnz : 1);
@@ -129,7 +129,7 @@ extern "C" zk_status zk_generate_parameters(zk_r1cs* R, const uint8_t g1_bytes[9
             for (uint32_t e = rp[r]; e < rp[r + 1]; e++) {
                 const uint32_t at = cursor[cl[e]]++;
                 row[at] = r;
-                co[at] = R->h_coeff[k][e];
+                co[at] = R->sys.h_coeff[k][e];
             }
         ZK_TRY(upload(d_colptr[k], col_ptr.data(), col_ptr.size() * 4));
         ZK_TRY(upload(d_row[k], row.data(), row.size() * 4));
@@ -161,7 +161,7 @@ extern "C" zk_status zk_generate_parameters(zk_r1cs* R, const uint8_t g1_bytes[9
         HIP_TRY(hipStreamSynchronize(g_stream));
         if (log_m) {
             zk_ntt* plan = nullptr;
-            ZK_TRY(zk_ntt_create(log_m, R->device, &plan));
+            ZK_TRY(zk_ntt_create(log_m, R->sys.device, &plan));
             const zk_status st = zk_ntt_run_dev(plan, lag.p, 1, ZK_NTT_INVERSE);
             const zk_status sy = zk_synchronize();
             zk_ntt_free(plan);

@@ -3,7 +3,7 @@
 // A conditional selection or a conditional addition of the transfer circuits copies a coordinate whenever its bit is 0, so
 // about a quarter of the full-width values of a witness repeat what another variable of the same witness already holds.
 // z_p P_p + z_j P_j = z_j (P_p + P_j) when z_p = z_j, and P_p + P_j depends on the key alone: the prover keeps one more base
-// per LINKED pair of variables (zkamd.cpp derived_pairs) and k_build_scalars (ntt.h) decides proof by proof, on the values,
+// per LINKED pair of variables (prover_binding.h derived_pairs) and k_build_scalars (ntt.h) decides proof by proof, on the values,
 // which links merge.  The links are static: the chains below are a function of the circuit alone.  They affect what a proof
 // costs and never its bytes - the identity holds for every assignment.
 // The same holds for a stretch of up to RUN_MAX consecutive members of a chain that hold one value, z (P_1 + ... + P_l): a base
@@ -178,6 +178,12 @@ inline const std::vector<std::vector<Fr>>& circuit_probes(Circuit c) {
 }
 constexpr int N_CHAINS = 3;   // A, B, L
 
+// The four queries that can have pair bases, in the order of the q arrays and of the bytes of the availability word that
+// k_build_scalars reads, of count_merges below and of the test hooks.  b_g2 and b_g1 follow the chains of B.
+enum Query { QA = 0, QB2 = 1, QL = 2, QB1 = 3 };
+constexpr int N_QUERIES = 4;
+constexpr int chain_of(Query q) { return q == QA ? 0 : q == QL ? 2 : 1; }   // its place among [A | B | L] in chains_of
+
 // The chains of a circuit, [pred A | succ A | pred B | succ B | pred L | succ L] over its variables (inputs, then aux): a
 // function of the probes and of which variables are dense in the A and in the B query
 inline std::vector<int32_t> chains_of(const std::vector<std::vector<Fr>>& probes, uint32_t n_in, const std::vector<uint8_t>& a_dense,
@@ -196,7 +202,7 @@ inline std::vector<int32_t> chains_of(const std::vector<std::vector<Fr>>& probes
 }
 
 // The longest stretch of a run that becomes ONE term z (P_1 + ... + P_l): a run is cut into blocks of RUN_MAX members (ntt.h
-// k_build_scalars has the rule).  Every size follows from it: RUN_MAX - 2 more bases per link (zkamd.cpp derived_pairs), as
+// k_build_scalars has the rule).  Every size follows from it: RUN_MAX - 2 more bases per link (prover_binding.h derived_pairs), as
 // many alternates per pair slot (msm.h MsmSelRange::alt), one bit per length in the words of k_build_scalars.  2 ... 8; 2 is the
 // rule of pairs alone.  (ZK_RUN_MAX: a second library for measurements.)
 #ifndef ZK_RUN_MAX

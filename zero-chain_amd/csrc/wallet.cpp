@@ -444,12 +444,12 @@ extern "C" {
 zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk, size_t n, const zk_transfer_request* req,
                                       const uint8_t* rs, zk_confidential_xt* out) try {
     if (!p || !circuit || !vk || (n && (!req || !rs || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->n_in != ZK_TRANSFER_N_INPUTS || circuit->n_aux != ZK_TRANSFER_N_AUX)
+    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->device != lib_params_device(p)) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+    if (circuit->sys.device != lib_params_device(p)) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
     if (n == 0) return ZK_OK;
     ZK_TRY(use_device(lib_params_device(p)));
-    if ((size_t)circuit->n_con + circuit->n_in > lib_params_domain(p))
+    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > lib_params_domain(p))
         return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     std::vector<zk_transfer_statement> st(n);
     std::vector<uint8_t> rsk(n * 32), proofs(n * 192), ok(n);
@@ -494,7 +494,7 @@ zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk,
         } else {
             ZK_TRY(witness_gpu_finish(circuit, np, slot, first));
             if (next < n) ZK_TRY(witness_gpu_enqueue(circuit, st.data() + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream, true));
-            HIP_TRY(hipMemcpy2DAsync(pin_in.p, ZK_TRANSFER_N_INPUTS * 32, circuit->z[slot].p, nv * 32, ZK_TRANSFER_N_INPUTS * 32, np,
+            HIP_TRY(hipMemcpy2DAsync(pin_in.p, ZK_TRANSFER_N_INPUTS * 32, circuit->work.z[slot].p, nv * 32, ZK_TRANSFER_N_INPUTS * 32, np,
                                      hipMemcpyDeviceToHost, g_stream));
             if (timing) fprintf(stderr, "[gen_proof] chunk %zu witness ready %.1f ms\n", first / chunk, since());
             ZK_TRY(lib_prove_from_z(p, circuit, np, slot, rs + first * 64, proofs.data() + first * 192));

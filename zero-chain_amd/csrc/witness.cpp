@@ -10,43 +10,43 @@
 
 using namespace zkrt;
 
-// ---- the same on the GPU (witness_gpu.h): np statements -> R->z[slot], enqueued on `stream`
+// ---- the same on the GPU (witness_gpu.h): np statements -> R->work.z[slot], enqueued on `stream`
 static zk_status witness_gpu_init(zk_r1cs* R) {
-    if (R->wit_ready) return ZK_OK;
+    if (R->work.wit_ready) return ZK_OK;
     static_assert(sizeof(zkwitdev::Stmt) == sizeof(zk_transfer_statement), "statement layout");
     const zkwit::Tables& t = zkwit::tables();
     static_assert(sizeof(zkwit::JPoint) == 64, "Jubjub point layout");
-    ZK_TRY(R->wit_table.ensure(84 * 8 * sizeof(zkwit::JPoint)));
-    HIP_TRY(hipMemcpy(R->wit_table.p, t.win.data(), 84 * 8 * sizeof(zkwit::JPoint), hipMemcpyHostToDevice));
+    ZK_TRY(R->work.wit_table.ensure(84 * 8 * sizeof(zkwit::JPoint)));
+    HIP_TRY(hipMemcpy(R->work.wit_table.p, t.win.data(), 84 * 8 * sizeof(zkwit::JPoint), hipMemcpyHostToDevice));
     const zkhost::Fr dd[2] = {zkwit::edwards_d(), zkwit::edwards_d().dbl()};
-    ZK_TRY(R->wit_consts.ensure(sizeof(dd)));
-    HIP_TRY(hipMemcpy(R->wit_consts.p, dd, sizeof(dd), hipMemcpyHostToDevice));
+    ZK_TRY(R->work.wit_consts.ensure(sizeof(dd)));
+    HIP_TRY(hipMemcpy(R->work.wit_consts.p, dd, sizeof(dd), hipMemcpyHostToDevice));
     for (int k = 0; k < 2; k++)
-        if (!R->wit_done[k]) HIP_TRY(hipEventCreate(&R->wit_done[k]));
-    R->wit_ready = true;
+        if (!R->work.wit_done[k]) HIP_TRY(hipEventCreate(&R->work.wit_done[k]));
+    R->work.wit_ready = true;
     return ZK_OK;
 }
 zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_t np, int slot, hipStream_t stream, bool typed_inputs) {
     ZK_TRY(witness_gpu_init(R));
     const size_t nv = zkwitdev::NV;
-    ZK_TRY(R->z[slot].ensure(np * nv * 32));
-    ZK_TRY(R->wit_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
-    ZK_TRY(R->wit_bad[slot].ensure(np * 4));
-    ZK_TRY(R->pin_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
-    ZK_TRY(R->pin_bad[slot].ensure(np * 4));
-    ZK_TRY(R->wit_pts.ensure(np * (size_t)zkwitdev::P_COUNT * 64));
-    ZK_TRY(R->wit_scratch.ensure((size_t)zkwitdev::L1_SCRATCH_ROLES * zkwitdev::SCRATCH_SLOTS * np * 32));
-    memcpy(R->pin_st[slot].p, st, np * sizeof(zkwitdev::Stmt));
-    HIP_TRY(hipMemcpyAsync(R->wit_st[slot].p, R->pin_st[slot].p, np * sizeof(zkwitdev::Stmt), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(R->wit_bad[slot].p, 0, np * 4, stream));
+    ZK_TRY(R->work.z[slot].ensure(np * nv * 32));
+    ZK_TRY(R->work.wit_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
+    ZK_TRY(R->work.wit_bad[slot].ensure(np * 4));
+    ZK_TRY(R->work.pin_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
+    ZK_TRY(R->work.pin_bad[slot].ensure(np * 4));
+    ZK_TRY(R->work.wit_pts.ensure(np * (size_t)zkwitdev::P_COUNT * 64));
+    ZK_TRY(R->work.wit_scratch.ensure((size_t)zkwitdev::L1_SCRATCH_ROLES * zkwitdev::SCRATCH_SLOTS * np * 32));
+    memcpy(R->work.pin_st[slot].p, st, np * sizeof(zkwitdev::Stmt));
+    HIP_TRY(hipMemcpyAsync(R->work.wit_st[slot].p, R->work.pin_st[slot].p, np * sizeof(zkwitdev::Stmt), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(R->work.wit_bad[slot].p, 0, np * 4, stream));
     zkwitdev::Ctx c;
-    c.z = R->z[slot].as<uint32_t>();
-    c.st = R->wit_st[slot].as<zkwitdev::Stmt>();
-    c.pts = R->wit_pts.as<uint32_t>();
-    c.table = R->wit_table.as<uint32_t>();
-    c.consts = R->wit_consts.as<uint32_t>();
-    c.scratch = R->wit_scratch.as<uint32_t>();
-    c.bad = R->wit_bad[slot].as<uint32_t>();
+    c.z = R->work.z[slot].as<uint32_t>();
+    c.st = R->work.wit_st[slot].as<zkwitdev::Stmt>();
+    c.pts = R->work.wit_pts.as<uint32_t>();
+    c.table = R->work.wit_table.as<uint32_t>();
+    c.consts = R->work.wit_consts.as<uint32_t>();
+    c.scratch = R->work.wit_scratch.as<uint32_t>();
+    c.bad = R->work.wit_bad[slot].as<uint32_t>();
     c.n = (uint32_t)np;
     const unsigned b64 = (unsigned)((np + 63) / 64);
     {
@@ -58,14 +58,14 @@ zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_
         ZK_LAUNCH(zkwitdev::k_wit_level2, dim3(b64, zkwitdev::L2_ROLES), dim3(64), 0, stream, c);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(R->pin_bad[slot].p, R->wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(R->wit_done[slot], stream));
+    HIP_TRY(hipMemcpyAsync(R->work.pin_bad[slot].p, R->work.wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(R->work.wit_done[slot], stream));
     return ZK_OK;
 }
 // waits for the witness kernels of `slot`; a malformed statement is reported with its absolute index
 zk_status witness_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base) {
-    HIP_TRY(hipEventSynchronize(R->wit_done[slot]));
-    const uint32_t* bad = R->pin_bad[slot].as<uint32_t>();
+    HIP_TRY(hipEventSynchronize(R->work.wit_done[slot]));
+    const uint32_t* bad = R->work.pin_bad[slot].as<uint32_t>();
     static const char* const points[5] = {"proof_generation_key", "enc_key_recipient", "enc_balance_left", "enc_balance_right", "g_epoch"};
     static const char* const scalars[3] = {"randomness", "alpha", "dec_key_sender"};
     for (size_t i = 0; i < np; i++) {
@@ -85,44 +85,44 @@ zk_status witness_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base)
 }
 
 
-// ---- the anonymous-transfer circuit (witness_anon_gpu.h): np statements -> R->z[slot], enqueued on `stream`.  The
+// ---- the anonymous-transfer circuit (witness_anon_gpu.h): np statements -> R->work.z[slot], enqueued on `stream`.  The
 // handle's witness buffers are shared with the transfer generator (a zk_r1cs holds ONE circuit).
 zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st, size_t np, int slot, hipStream_t stream, size_t index_base) {
     using namespace zkwitdev;
     ZK_TRY(witness_gpu_init(R));
     static_assert(sizeof(AStmt) == sizeof(zk_anonymous_statement), "statement layout");
-    ZK_TRY(R->z[slot].ensure(np * (size_t)A_NV * 32));
-    ZK_TRY(R->wit_st[slot].ensure(np * sizeof(AStmt)));
-    ZK_TRY(R->wit_bad[slot].ensure(np * 4));
-    ZK_TRY(R->pin_st[slot].ensure(np * sizeof(AStmt)));
-    ZK_TRY(R->pin_bad[slot].ensure(np * 4));
-    ZK_TRY(R->wit_pts.ensure(np * (size_t)AP_COUNT * 64));
-    ZK_TRY(R->wit_scratch.ensure((size_t)A1_ROLES * SCRATCH_SLOTS * np * 32));
-    memcpy(R->pin_st[slot].p, st, np * sizeof(AStmt));
+    ZK_TRY(R->work.z[slot].ensure(np * (size_t)A_NV * 32));
+    ZK_TRY(R->work.wit_st[slot].ensure(np * sizeof(AStmt)));
+    ZK_TRY(R->work.wit_bad[slot].ensure(np * 4));
+    ZK_TRY(R->work.pin_st[slot].ensure(np * sizeof(AStmt)));
+    ZK_TRY(R->work.pin_bad[slot].ensure(np * 4));
+    ZK_TRY(R->work.wit_pts.ensure(np * (size_t)AP_COUNT * 64));
+    ZK_TRY(R->work.wit_scratch.ensure((size_t)A1_ROLES * SCRATCH_SLOTS * np * 32));
+    memcpy(R->work.pin_st[slot].p, st, np * sizeof(AStmt));
     // A member index out of range is reported by witness_anon_gpu_finish, in statement order with everything else the
     // kernels find - exactly where the host calculator reports it (zkamd.cpp anonymous_decode; ADVICE r4: refused here, a
     // bad index in chunk k + 1 was reported before chunk k had been proved).  The kernels see the index clamped.
-    R->anon_index_bad[slot] = (size_t)-1;
+    R->work.anon_index_bad[slot] = (size_t)-1;
     {
-        zk_anonymous_statement* ps = (zk_anonymous_statement*)R->pin_st[slot].p;
+        zk_anonymous_statement* ps = (zk_anonymous_statement*)R->work.pin_st[slot].p;
         for (size_t i = 0; i < np; i++)
             if (ps[i].s_index >= ZK_ANONYMOUS_SIZE || ps[i].t_index >= ZK_ANONYMOUS_SIZE) {
-                if (R->anon_index_bad[slot] == (size_t)-1) R->anon_index_bad[slot] = i;
+                if (R->work.anon_index_bad[slot] == (size_t)-1) R->work.anon_index_bad[slot] = i;
                 ps[i].s_index = 0;
                 ps[i].t_index = 1;
             }
     }
-    HIP_TRY(hipMemcpyAsync(R->wit_st[slot].p, R->pin_st[slot].p, np * sizeof(AStmt), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(R->wit_bad[slot].p, 0xff, np * 4, stream));   // A_BAD_NONE
+    HIP_TRY(hipMemcpyAsync(R->work.wit_st[slot].p, R->work.pin_st[slot].p, np * sizeof(AStmt), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(R->work.wit_bad[slot].p, 0xff, np * 4, stream));   // A_BAD_NONE
     ACtx c;
-    c.z = R->z[slot].as<uint32_t>();
+    c.z = R->work.z[slot].as<uint32_t>();
     c.st = nullptr;
-    c.ast = R->wit_st[slot].as<AStmt>();
-    c.pts = R->wit_pts.as<uint32_t>();
-    c.table = R->wit_table.as<uint32_t>();
-    c.consts = R->wit_consts.as<uint32_t>();
-    c.scratch = R->wit_scratch.as<uint32_t>();
-    c.bad = R->wit_bad[slot].as<uint32_t>();
+    c.ast = R->work.wit_st[slot].as<AStmt>();
+    c.pts = R->work.wit_pts.as<uint32_t>();
+    c.table = R->work.wit_table.as<uint32_t>();
+    c.consts = R->work.wit_consts.as<uint32_t>();
+    c.scratch = R->work.wit_scratch.as<uint32_t>();
+    c.bad = R->work.wit_bad[slot].as<uint32_t>();
     c.n = (uint32_t)np;
     const unsigned b64 = (unsigned)((np + 63) / 64);
     {
@@ -138,21 +138,21 @@ zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st,
         ZK_LAUNCH(k_awit_level4, dim3(b64), dim3(64), 0, stream, c);
     }
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(R->pin_bad[slot].p, R->wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(R->wit_done[slot], stream));
+    HIP_TRY(hipMemcpyAsync(R->work.pin_bad[slot].p, R->work.wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(R->work.wit_done[slot], stream));
     return ZK_OK;
 }
 // waits for the witness kernels of `slot`; a malformed statement is reported with its absolute index, in the words and the
 // order of the host calculator (zkamd.cpp anonymous_decode)
 zk_status witness_anon_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base) {
     using namespace zkwitdev;
-    HIP_TRY(hipEventSynchronize(R->wit_done[slot]));
-    const uint32_t* bad = R->pin_bad[slot].as<uint32_t>();
+    HIP_TRY(hipEventSynchronize(R->work.wit_done[slot]));
+    const uint32_t* bad = R->work.pin_bad[slot].as<uint32_t>();
     static const char* const scalars[3] = {"randomness", "alpha", "dec_key"};
     static const char* const sets[4] = {"enc_keys", "left_ciphertexts", "enc_balances_left", "enc_balances_right"};
     for (size_t i = 0; i < np; i++) {
         // (the index check comes first inside a statement, as in anonymous_decode)
-        if (i == R->anon_index_bad[slot])
+        if (i == R->work.anon_index_bad[slot])
             return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index_base + i) + ": member index out of range");
         const uint32_t code = bad[i];
         if (code == A_BAD_NONE) continue;

@@ -5,7 +5,7 @@
 //   create_proof step 3  (EvaluationDomain H pipeline)   -> ntt.h kernels, NttPlan below
 //   create_proof step 4  (8 x multiexp)                  -> msm.h kernels, MsmGroup below
 //   create_proof step 6  (final fold, into_affine)       -> k_ct_scale_add (coop_tail.cpp) / k_xyzz_normalize_export (msm.h)
-//   Parameters::read                                     -> Params::load below
+//   Parameters::read                                     -> prover_key.h params_load
 //   Proof::write                                         -> host_math.h g1/g2_to_compressed
 #include <stdio.h>
 #include <stdlib.h>
@@ -37,799 +37,10 @@
 #include "value_pairs.h"
 #include "handles.h"
 #include "transfer_r1cs.h"
-
-using zkdev::MsmJob;
-using zkdev::NttPass;
-
-namespace {
-
-using namespace zkrt;
-
-// ------------------------------------------------------------------------------------------
-// NTT plan: twiddles and fused scaling tables for one domain size, resident in HBM
-// ------------------------------------------------------------------------------------------
-using zkhost::Fr;
-
-Fr fr_from_u64(uint64_t v) {
-    Fr x = Fr::zero();
-    x.l[0] = v;
-    return x.to_mont();
-}
-Fr fr_const(const uint64_t (&v)[4]) {
-    Fr x;
-    for (int i = 0; i < 4; i++) x.l[i] = v[i];
-    return x;
-}
-
-
-struct NttPlan {
-    uint32_t log_n = 0;
-    size_t n = 0;
-    DevBuf tw_fwd, tw_inv;           // w^e, w^-e, e < n/2 (Montgomery)
-    DevBuf s1_plain, s1_mont, s2;    // prover tables, bit-reversed order (see prove_chunk)
-    DevBuf sc_plain, sc_mont;        // constant 1 / (n (g^n - 1)): the scaling of c's coefficients (k_h_pointwise)
-    DevBuf coset_fwd, coset_inv;     // g^i and g^-i / n, natural order (Montgomery)
-    DevBuf dt;                       // t / n at the bit-reversed position of t (Montgomery): a's coefficients -> those of x a'(x)
-    DevBuf consts;                   // [0] = 1/n, [1] = 1/(g^n - 1)   (Montgomery)
-    Fr w_inv, n_inv, z_inv;          // w^-1, 1/n, 1/(g^n - 1) (Montgomery): the transforms of the derived bases make their own tables
-    DevBuf scratch;                  // permutation scratch for the stand-alone entry
-    size_t bytes = 0;
-
-    // The tile choice of the transforms of 2^17 and more, read once per process (ZKAMD_NTT_TILES, ntt_plan.h ntt_tiles), and the
-    // form of a chain of `batch` transforms of this size under it: the product's one place that decides a form.
-    static NttForm tiles() {
-        static const NttForm f = ntt_tiles(getenv("ZKAMD_NTT_TILES"));
-        return f;
-    }
-    NttForm form(uint32_t batch) const { return ntt_form(tiles(), log_n, batch); }
-
-    zk_status upload_fr(DevBuf& buf, const Fr* v, size_t count) {
-        ZK_TRY(buf.ensure(count * 32));
-        HIP_TRY(hipMemcpy(buf.p, v, count * 32, hipMemcpyHostToDevice));
-        return ZK_OK;
-    }
-
-    zk_status pow_table(DevBuf& out, const Fr& base, const Fr& scale, uint32_t mode, uint32_t raw, size_t count) {
-        DevBuf tmp;
-        Fr bs[2] = {base, scale};
-        ZK_TRY(upload_fr(tmp, bs, 2));
-        ZK_TRY(out.ensure(count * 32));
-        bytes += count * 32;
-        if (count == 0) return ZK_OK;
-        ZK_LAUNCH(zkdev::k_fr_pow_table, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream,
-                  out.as<uint32_t>(), tmp.as<uint32_t>(), tmp.as<uint32_t>() + 8, log_n, mode, raw, (uint32_t)count);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        return ZK_OK;
-    }
-
-    zk_status init(uint32_t k) {
-        if (k > 27) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "domain larger than 2^27");
-        log_n = k;
-        n = (size_t)1 << k;
-        static const uint64_t root_v[4] = ZK_FR_ROOT_OF_UNITY_MONT_64;
-        static const uint64_t gen_v[4] = ZK_FR_GENERATOR_MONT_64;
-        static const uint64_t r2_v[4] = ZK_FR_R2_64;
-        Fr w = fr_const(root_v);
-        for (uint32_t i = k; i < ZK_FR_S; i++) w = w.sqr();   // w = ROOT^(2^(S-k))  (domain.rs)
-        Fr winv = zkhost::fr_inv(w);
-        Fr g = fr_const(gen_v), ginv = zkhost::fr_inv(g);
-        Fr ninv = zkhost::fr_inv(fr_from_u64((uint64_t)n));
-        Fr r_elem = fr_const(r2_v);   // Montgomery form of the field element R
-        Fr gn = g;
-        for (uint32_t i = 0; i < k; i++) gn = gn.sqr();
-        Fr zinv = zkhost::fr_inv(gn - Fr::one());   // divide_by_z_on_coset
-        Fr cs[2] = {ninv, zinv};
-        ZK_TRY(upload_fr(consts, cs, 2));
-        w_inv = winv;
-        n_inv = ninv;
-        z_inv = zinv;
-        ZK_TRY(pow_table(tw_fwd, w, Fr::one(), 0, 0, n / 2));
-        ZK_TRY(pow_table(tw_inv, winv, Fr::one(), 0, 0, n / 2));
-        // after the first inverse transform: * g^i / n, and lift the (plain or Montgomery) input
-        // into Montgomery form in the same multiplication
-        ZK_TRY(pow_table(s1_plain, g, ninv * r_elem, 1, 0, n));
-        ZK_TRY(pow_table(s1_mont, g, ninv, 1, 0, n));
-        // after the last inverse transform: * g^-i / n and drop the Montgomery factor
-        ZK_TRY(pow_table(s2, ginv, ninv, 1, 1, n));
-        // after the inverse transform of a or b over the derived bases: * t / n, coefficient t of x a'(x) (prove_chunk)
-        ZK_TRY(pow_table(dt, Fr::one(), ninv, 3, 0, n));
-        // c's inverse transform: * 1 / (n (g^n - 1)), result plain (from a plain or a Montgomery input)
-        ZK_TRY(pow_table(sc_plain, Fr::one(), ninv * zinv, 2, 0, n));
-        ZK_TRY(pow_table(sc_mont, Fr::one(), ninv * zinv, 2, 1, n));
-        ZK_TRY(pow_table(coset_fwd, g, Fr::one(), 0, 0, n));
-        ZK_TRY(pow_table(coset_inv, ginv, ninv, 2, 0, n));
-        return ZK_OK;
-    }
-
-    // Run one chain of passes, in the tile form `form` (ntt_plan.h), over `batch` polynomials laid out with `stride` elements.
-    // [first, first + count) cuts the launches out of the chain's pass list (the test hooks run one pass on a state of their
-    // own); pre, src and bad go with the chain's first pass, post and sub with its last.
-    zk_status chain(NttForm form, uint32_t* data, uint32_t batch, uint32_t stride, bool dif, bool inverse,
-                    const uint32_t* pre, const uint32_t* post, const uint32_t* src = nullptr,
-                    uint32_t src_stride = 0, uint32_t src_valid = 0, uint32_t* bad = nullptr,
-                    const uint32_t* sub = nullptr, uint32_t sub_stride = 0, size_t first = 0, size_t count = SIZE_MAX) {
-        std::vector<NttLaunch> ps;
-        if (!ntt_passes(log_n, dif, stride, form, &ps)) return fail(ZK_ERR_INVALID_ARGUMENT, "no such tile form for this size");
-        const uint32_t* tw = inverse ? tw_inv.as<uint32_t>() : tw_fwd.as<uint32_t>();
-        for (size_t i = first; i < ps.size() && i - first < count; i++) {
-            NttPass p = ps[i].pass;
-            const uint32_t* s = nullptr;
-            if (i == 0 && src) {
-                s = src;
-                p.src_stride = src_stride;
-                p.src_valid = src_valid;
-            }
-            dim3 grid(ps[i].grid_x, batch);
-            size_t shmem = ps[i].lds_bytes;
-            ProfScope ps_(dif ? "ntt_pass_dif" : "ntt_pass_dit");
-#ifndef ZK_EMU
-            if (shmem > 65536) {
-                // more than 64 KiB of dynamic LDS has to be asked for, once per device
-                static std::mutex mu;
-                static uint64_t raised = 0;
-                std::lock_guard<std::mutex> lock(mu);
-                const uint64_t bit = 1ull << (g_device & 63);
-                if (!(raised & bit)) {
-                    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(zkdev::k_ntt_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)NTT_LDS_MAX));
-                    raised |= bit;
-                }
-            }
-#endif
-            ZK_LAUNCH_SYNC(zkdev::k_ntt_pass, grid, dim3(ps[i].threads), shmem, g_stream, data, s, tw,
-                           i == 0 ? pre : (const uint32_t*)nullptr,
-                           i + 1 == ps.size() ? post : (const uint32_t*)nullptr, p, i == 0 && s ? bad : (uint32_t*)nullptr,
-                           i + 1 == ps.size() ? sub : (const uint32_t*)nullptr, sub_stride);
-        }
-        if (ps.empty() && (pre || post || src)) return fail(ZK_ERR_INVALID_ARGUMENT, "size-1 transform");
-        HIP_TRY(hipGetLastError());
-        return ZK_OK;
-    }
-};
-
-// (the MSM group - tables of a set of bases + the bucket pipeline over a list of jobs - lives in msm_group.h; its two
-// instantiations are compiled in msm_g1.cpp and msm_g2.cpp, side by side with this unit)
-
-
-// ------------------------------------------------------------------------------------------
-// byte reader for the Parameters format
-// ------------------------------------------------------------------------------------------
-struct Reader {
-    const uint8_t* p;
-    size_t left;
-    bool take(size_t n, const uint8_t** out) {
-        if (left < n) return false;
-        *out = p;
-        p += n;
-        left -= n;
-        return true;
-    }
-    bool u32be(uint32_t* v) {
-        const uint8_t* b;
-        if (!take(4, &b)) return false;
-        *v = ((uint32_t)b[0] << 24) | ((uint32_t)b[1] << 16) | ((uint32_t)b[2] << 8) | b[3];
-        return true;
-    }
-};
-
-// bellman: the query vectors and vk.ic reject the point at infinity in both modes (Parameters::read,
-// VerifyingKey::read); alpha, beta, gamma, delta are read with a plain into_affine(), which accepts it
-// (in-tree twin: core/bellman-verifier/src/lib.rs:310-327) - create_proof then answers a delta at
-// infinity with SynthesisError::UnexpectedIdentity.
-zk_status read_g1(Reader& r, HG1A* out, const char* what, bool allow_inf = false) {
-    const uint8_t* b;
-    if (!r.take(96, &b)) return fail(ZK_ERR_IO, std::string("unexpected end of parameters in ") + what);
-    if (zkhost::g1_from_uncompressed(b, out) != zkhost::DEC_OK) return fail(ZK_ERR_IO, std::string("invalid G1 encoding in ") + what);
-    if (!allow_inf && out->is_inf()) return fail(ZK_ERR_IO, std::string("point at infinity in ") + what);
-    return ZK_OK;
-}
-zk_status read_g2(Reader& r, HG2A* out, const char* what, bool allow_inf = false) {
-    const uint8_t* b;
-    if (!r.take(192, &b)) return fail(ZK_ERR_IO, std::string("unexpected end of parameters in ") + what);
-    if (zkhost::g2_from_uncompressed(b, out) != zkhost::DEC_OK) return fail(ZK_ERR_IO, std::string("invalid G2 encoding in ") + what);
-    if (!allow_inf && out->is_inf()) return fail(ZK_ERR_IO, std::string("point at infinity in ") + what);
-    return ZK_OK;
-}
-
-bool scalar_lt_r(const uint64_t v[4]) { return !Fr::geq_p(v); }
-
-}  // namespace
-
-// ------------------------------------------------------------------------------------------
-// zk_params
-// ------------------------------------------------------------------------------------------
-struct zk_params {
-    int device = 0;
-    uint32_t n_ic = 0, n_h = 0, n_l = 0, n_a = 0, n_b1 = 0, n_b2 = 0;
-    uint32_t log_m = 0;
-    size_t m = 0;
-    // offsets of each query inside the G1 group table (window slice 0)
-    uint32_t off_h = 0, off_l = 0, off_a = 0, off_b1 = 0;
-    MsmG1 g1;
-    // The two G1 jobs of a proof differ fourfold in size (A: ~15.6 k terms, C' = H + L + r B1: ~65 k for the transfer
-    // circuit), so a batch runs them as TWO launch sets over the same doubling table, each with the recoding width of its
-    // own size (one width for both held the large job at c = 15).  g1 = the C' set; g1a = the A set;
-    // g1_lone = both jobs in one set under the width of their average, for a few proofs made alone (fewer launches).
-    MsmG1 g1a, g1_lone;
-    MsmG2 g2;
-    // the G2 group again over the SAME table with a narrower recoding, for a proof made alone: its side stream is the
-    // critical path and the depth of the bucket reduction (bit planes, doublings) is what it waits for - 256 buckets
-    // instead of 2048 (c = 10 against the throughput optimum 13) cut a lone proof from 3.54 to 3.16 ms
-    MsmG2 g2_lone;
-    NttPlan ntt;
-    // The derived bases of this key and ONE circuit (ensure_derived): the H query on the Lagrange basis of the domain for the
-    // circuit's live rows, with the part of H that is linear in the row products folded into the bases of the variables and
-    // of the rows' residuals.  g1d = [Lambda (n_rows) | E (n_rows) | D (inputs, aux) | (the value pairs' bases: prs below) | a | alpha_1 |
-    // delta_1 | b_g1 | beta_1] with its own table of doublings; g1d_lone = the same table under the width of a few proofs made alone.
-    struct Derived {
-        bool ready = false;
-        uint64_t circuit = 0;       // zk_r1cs::id it was built for
-        uint32_t serial = 0;        // changes with every build: part of the key of the cached maps
-        uint32_t n_rows = 0;        // live rows of the circuit: constraints + inputs
-        uint32_t off_a = 0, off_b1 = 0;
-        std::vector<int32_t> pos;   // [Lambda | E | D]: position in slice 0, or -1 for a base that came out as the identity
-        double bind_ms = 0;
-    } drv;
-    MsmG1 g1d, g1d_lone;
-    DevBuf map_cd, map_cfd;         // map_c / map_cf over the derived bases
-    // Value pairs of the (key, circuit) pair the derived set was built for (value_pairs.h; derived_pairs below): one more
-    // base P_j + P_pred[j] per link of the circuit's chains and query that has both ends, behind the derived set in g1d (L, B1
-    // and A queries) and behind the B2 query in a table of its own, g2p.  links = [chains of A, B, L | qa | qb2 | ql | qb1] as
-    // k_build_scalars reads it; base_* = where the pair bases lie (absolute in g1d; in g2p); exp_* = the terms a proof is
-    // expected to merge per query (the mean over the probe statements), for the recoding widths.
-    struct Pairs {
-        bool ready = false;
-        std::vector<int32_t> links;
-        uint32_t base_l = 0, base_b1 = 0, base_a = 0, base_b2 = 0;
-        PairCounts n;
-        uint32_t exp_a = 0, exp_b2 = 0, exp_l = 0, exp_b1 = 0;
-        // Value runs (value_pairs.h RUN_MAX): for every link j and l = 3 ... RUN_MAX one more base, the sum of the l chain
-        // members that end at j, where the l - 1 links behind it all have their pair bases and the sum is not the identity.
-        // Per query [a | b_g2 | l | b_g1]: alt[pair slot * (RUN_MAX - 2) + (l - 3)] = the base's place among the query's
-        // longer bases or -1; xbase = where those lie (behind the pair sections of g1d; behind the pairs of g2p); xn = how
-        // many there are per l.  links carries one more word per variable, their bits (ntt.h k_build_scalars).
-        std::vector<int32_t> alt[4];
-        uint32_t xbase[4] = {0, 0, 0, 0};
-        uint32_t xn[4][7] = {};
-#ifdef ZK_TEST_HOOKS
-        // (zk_hook_value_runs: what ensure_derived put into the tables at the places the longer bases have - G1 [l | b_g1 | a] from
-        // xbase[2] on, G2 from xbase[1] on - and the D block of the derived set, whose aux points the sums of the l query are over)
-        std::vector<HG1A> hook_g1, hook_d;
-        std::vector<HG2A> hook_g2;
-#endif
-    } prs;
-    MsmG1 g1da;                     // the A jobs of a split chunk over g1d's table (its copy of the A query + the pairs)
-    MsmG2 g2p, g2p_lone;            // [b_g2 | beta_2 | delta_2 | pairs | longer runs]
-    DevBuf map_ad, map_b2d, pairs_dev;
-    DevBuf alt_c, alt_a, alt_b2;    // MsmSelRange::alt of the C, A and B2 jobs: absolute table positions per pair slot and length
-    DevBuf sel_w, sel_c;            // MsmSelRange::sel: the bytes k_build_scalars writes beside the pair slots, per proof
-    PairCounts mpairs;              // the pairs the maps in use were built with (ensure_maps; none under ZKAMD_MERGE_VALUES=0)
-    std::vector<uint8_t> enc_a, enc_b1, enc_b2;   // the encodings of the three queries (the sums of two bases are made from them)
-    // cached per-circuit index maps (keyed by the density bytes)
-    std::vector<uint8_t> dens_key;
-    DevBuf map_a, map_b2, map_c, map_cf;   // (map_cf: the C job with the fold s * A inside, for a few proofs made alone)
-    uint32_t map_nv = 0;
-    // Entries of a query whose affine points are EQUAL (variables with identical QAP columns), found once at load from the
-    // encodings: z_i P + z_j P = (z_i + z_j) P, so a job carries ONE term per distinct base and k_build_scalars sums the
-    // members' scalars.  CSR, group -> member positions in the query, groups in the order of their first members; a point
-    // that occurs once is in no group.  Each query on its own points: b_g1 and b_g2 need not agree.
-    struct Groups {
-        std::vector<uint32_t> ptr, mem;
-        uint32_t count() const { return ptr.empty() ? 0u : (uint32_t)ptr.size() - 1; }
-        uint32_t merged() const { return (uint32_t)mem.size() - count(); }   // entries - distinct points
-    } grp_a, grp_b1, grp_b2;
-    // what the maps in use were built with (ensure_maps; all 0 under ZKAMD_MERGE_BASES=0): the groups of the A, B2 and B1
-    // jobs and their CSR lists in VARIABLE indices, [ptr (ga + gb2 + gb1 + 1) | members], for k_build_scalars
-    uint32_t mg_a = 0, mg_b2 = 0, mg_b1 = 0;
-    DevBuf grp_dev;
-    // workspaces
-    DevBuf abc, wit, cvec, tail, stage_a, stage_b, stage_c, stage_w, fold_tbl, fold_c, fold_a1, fold_c1, fold_b2;
-    PinBuf pin_g1, pin_g2, pin_tail;   // affine A, C / B of a chunk; [1 | r | s] per proof
-    // [0]: raised by the kernels of a chunk that read caller scalars (non-canonical value, ONE != 1);
-    // [1]: the same for the conversion pass of zk_prove_batch_witness
-    DevBuf bad;
-    PinBuf pin_bad;
-    // vk points bellman accepts at infinity (VerifyingKey::read does not reject them)
-    bool alpha_g1_inf = false, beta_g1_inf = false, beta_g2_inf = false, delta_g1_inf = false, delta_g2_inf = false;
-    std::vector<uint8_t> vk_bytes;   // VerifyingKey::write of the key (the head of the parameter file)
-    std::vector<MsmJob> jobs1, jobs1a, jobs2;
-    std::vector<HG1> res1, res1a;
-    std::vector<HG2> res2;
-};
+#include "prover_key.h"
+#include "prover_binding.h"
 
 namespace {
-
-zk_status calibrate_kernel_forms(zk_params* P);
-
-// The groups of equal points of one query, from its uncompressed encodings (canonical: equal bytes are equal points, and an
-// encoding the decoder later refuses fails the load).  The point at infinity joins no group (in a query it fails the load as well).
-void group_equal_points(const uint8_t* enc, uint32_t n, size_t size, zk_params::Groups& G) {
-    std::vector<uint32_t> order;
-    order.reserve(n);
-    for (uint32_t i = 0; i < n; i++)
-        if (!(enc[i * size] & 0x40)) order.push_back(i);
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        const int c = memcmp(enc + x * size, enc + y * size, size);
-        return c ? c < 0 : x < y;
-    });
-    std::vector<std::pair<uint32_t, uint32_t>> runs;   // (first member, its place in `order`)
-    for (size_t i = 0, j; i < order.size(); i = j) {
-        for (j = i + 1; j < order.size() && !memcmp(enc + order[i] * size, enc + order[j] * size, size);) j++;
-        if (j - i > 1) runs.push_back({order[i], (uint32_t)i});
-    }
-    std::sort(runs.begin(), runs.end());
-    G.ptr.assign(1, 0u);
-    G.mem.clear();
-    for (const auto& run : runs) {
-        for (size_t j = run.second; j < order.size() && !memcmp(enc + run.first * size, enc + order[j] * size, size); j++)
-            G.mem.push_back(order[j]);
-        G.ptr.push_back((uint32_t)G.mem.size());
-    }
-}
-
-zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk_params** out) {
-    ZK_TRY(use_device(device));
-    zk_params* P = new (std::nothrow) zk_params();
-    if (!P) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
-    struct Guard {
-        zk_params* p;
-        ~Guard() { delete p; }
-    } guard{P};
-    P->device = device;
-    Reader r{pk, len};
-    HG1A alpha_g1, beta_g1, delta_g1;
-    HG2A beta_g2, gamma_g2, delta_g2;
-    ZK_TRY(read_g1(r, &alpha_g1, "vk.alpha_g1", true));
-    ZK_TRY(read_g1(r, &beta_g1, "vk.beta_g1", true));
-    ZK_TRY(read_g2(r, &beta_g2, "vk.beta_g2", true));
-    ZK_TRY(read_g2(r, &gamma_g2, "vk.gamma_g2", true));
-    ZK_TRY(read_g1(r, &delta_g1, "vk.delta_g1", true));
-    ZK_TRY(read_g2(r, &delta_g2, "vk.delta_g2", true));
-    P->alpha_g1_inf = alpha_g1.is_inf();
-    P->beta_g1_inf = beta_g1.is_inf();
-    P->beta_g2_inf = beta_g2.is_inf();
-    P->delta_g1_inf = delta_g1.is_inf();
-    P->delta_g2_inf = delta_g2.is_inf();
-    if (!r.u32be(&P->n_ic)) return fail(ZK_ERR_IO, "unexpected end of parameters (ic length)");
-    if ((size_t)P->n_ic * 96 > r.left) return fail(ZK_ERR_IO, "unexpected end of parameters in vk.ic");   // (before the allocation)
-    std::vector<HG1A> ic(P->n_ic);
-    for (uint32_t i = 0; i < P->n_ic; i++) ZK_TRY(read_g1(r, &ic[i], "vk.ic"));
-
-    P->vk_bytes.assign(pk, pk + (len - r.left));
-    // The query vectors are only LOCATED here; their 10 MB of encodings are gathered in table order and decoded on the
-    // device (msm.h k_decode_uncompressed: round 5 - the host loop it replaces was a quarter of the load).
-    // G1 table order: h | l | a | alpha_g1 | delta_g1 | b_g1 | beta_g1   (the tails carry the scalars 1, r / 1)
-    // G2 table order: b_g2 | beta_g2 | delta_g2                            (scalars 1, s)
-    struct Section {
-        const uint8_t* at;
-        uint32_t n;
-        const char* what;
-        bool inf_ok;   // alpha, beta, delta may be the point at infinity (bellman reads them with a plain into_affine())
-    };
-    auto locate = [&](uint32_t* n, size_t size, const char* what, const uint8_t** at) -> zk_status {
-        if (!r.u32be(n)) return fail(ZK_ERR_IO, std::string("unexpected end of parameters (length of ") + what + ")");
-        if ((size_t)*n * size > r.left) return fail(ZK_ERR_IO, std::string("unexpected end of parameters in ") + what);
-        (void)r.take((size_t)*n * size, at);
-        return ZK_OK;
-    };
-    const uint8_t *at_h, *at_l, *at_a, *at_b1, *at_b2;
-    ZK_TRY(locate(&P->n_h, 96, "h", &at_h));
-    ZK_TRY(locate(&P->n_l, 96, "l", &at_l));
-    ZK_TRY(locate(&P->n_a, 96, "a", &at_a));
-    ZK_TRY(locate(&P->n_b1, 96, "b_g1", &at_b1));
-    ZK_TRY(locate(&P->n_b2, 192, "b_g2", &at_b2));
-    group_equal_points(at_a, P->n_a, 96, P->grp_a);
-    group_equal_points(at_b1, P->n_b1, 96, P->grp_b1);
-    group_equal_points(at_b2, P->n_b2, 192, P->grp_b2);
-    // (kept for the keys that can have value pairs alone - those of the two built-in circuits, by their counts: 6 MB for the
-    //  transfer key; the points the pairs need are decoded from them a second time, on the host, when the key is bound)
-    if ((P->n_ic == ZK_TRANSFER_N_INPUTS && P->n_l == ZK_TRANSFER_N_AUX) || (P->n_ic == ZK_ANONYMOUS_N_INPUTS && P->n_l == ZK_ANONYMOUS_N_AUX)) {
-        P->enc_a.assign(at_a, at_a + (size_t)P->n_a * 96);
-        P->enc_b1.assign(at_b1, at_b1 + (size_t)P->n_b1 * 96);
-        P->enc_b2.assign(at_b2, at_b2 + (size_t)P->n_b2 * 192);
-    }
-    const Section sec1[7] = {{at_h, P->n_h, "h", false},       {at_l, P->n_l, "l", false},          {at_a, P->n_a, "a", false},
-                             {pk, 1, "vk.alpha_g1", true},     {pk + 576, 1, "vk.delta_g1", true},  {at_b1, P->n_b1, "b_g1", false},
-                             {pk + 96, 1, "vk.beta_g1", true}};
-    const Section sec2[3] = {{at_b2, P->n_b2, "b_g2", false}, {pk + 192, 1, "vk.beta_g2", true}, {pk + 672, 1, "vk.delta_g2", true}};
-    P->off_h = 0;
-    P->off_l = P->n_h;
-    P->off_a = P->off_l + P->n_l;
-    P->off_b1 = P->off_a + P->n_a + 2;
-    auto gather = [](const Section* sec, int k, size_t size, std::vector<uint8_t>& out) {
-        size_t total = 0;
-        for (int i = 0; i < k; i++) total += sec[i].n;
-        out.resize(total * size);
-        size_t at = 0;
-        for (int i = 0; i < k; i++) {
-            memcpy(out.data() + at, sec[i].at, (size_t)sec[i].n * size);
-            at += (size_t)sec[i].n * size;
-        }
-        return total;
-    };
-    std::vector<uint8_t> enc1, enc2;
-    const size_t n1 = gather(sec1, 7, 96, enc1), n2 = gather(sec2, 3, 192, enc2);
-    // a refused encoding / an unexpected point at infinity is named by the query it sits in
-    auto name_of = [](const Section* sec, int k, size_t idx) -> const Section& {
-        for (int i = 0; i < k; i++) {
-            if (idx < sec[i].n) return sec[i];
-            idx -= sec[i].n;
-        }
-        return sec[k - 1];
-    };
-    auto infinity_check = [&](const Section* sec, int k, size_t size, const std::vector<uint8_t>& enc, uint32_t n_inf) -> zk_status {
-        if (!n_inf) return ZK_OK;
-        size_t idx = 0;
-        for (int i = 0; i < k; i++)
-            for (uint32_t j = 0; j < sec[i].n; j++, idx++)
-                if ((enc[idx * size] & 0x40) && !sec[i].inf_ok) return fail(ZK_ERR_IO, std::string("point at infinity in ") + sec[i].what);
-        return ZK_OK;
-    };
-
-    // the evaluation domain: bellman writes h with m - 1 entries
-    size_t m = (size_t)P->n_h + 1;
-    if (m < 2 || (m & (m - 1))) return fail(ZK_ERR_IO, "h query length + 1 is not a power of two");
-    P->m = m;
-    while (((size_t)1 << P->log_m) < m) P->log_m++;
-    {
-        // the verifying key is validated in BOTH modes (bellman reads it with the checked into_affine())
-        std::vector<HG1A> vk1 = ic;
-        vk1.push_back(alpha_g1);
-        vk1.push_back(beta_g1);
-        vk1.push_back(delta_g1);
-        ZK_TRY((check_points_host<zkhost::Fq, zkdev::Fq>(vk1, "vk (G1: ic | alpha | beta | delta)")));
-        ZK_TRY((check_points_host<zkhost::Fq2, DevFq2>(std::vector<HG2A>{beta_g2, gamma_g2, delta_g2}, "vk (G2: beta | gamma | delta)")));
-    }
-    // two G1 jobs per proof: A, and the merged C' = H + L + r * B1 - each with the width of its own size
-    // (a few proofs made alone never reach the assembly level 1 of the reduction: bucket cost of the compiled few-jobs
-    //  path, group 4 - ADVICE r4; the split launch sets below: group 1 / 3)
-    const uint32_t c_avg = pick_window(((size_t)P->n_h + P->n_l + P->n_a + P->n_b1) / 2, 4);
-    const uint32_t c1 = pick_window((size_t)P->n_h + P->n_l + P->n_b1, 1);
-    const uint32_t c2 = pick_window(P->n_b2, 2);
-    {
-        // both groups decoded side by side, then both tables of doublings built side by side (each is one thread per base
-        // walking 254 doublings: latency, not work - 19 + 23 ms one after the other)
-        DevBuf raw1, raw2, map1, map2, scratch1, scratch2;
-        ZK_TRY(P->g1.decode_enqueue(enc1.data(), n1, c1, true, raw1, map1, g_stream));
-        ZK_TRY(P->g2.decode_enqueue(enc2.data(), n2, c2, true, raw2, map2, g_stream2));
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipStreamSynchronize(g_stream2));
-        uint32_t inf1 = 0, inf2 = 0;
-        // (a refused encoding is named by its section; any other failure of the read-back - a device error - is passed on
-        //  as it is: ADVICE r5, the index used to be parsed out of the message)
-        size_t bad1 = (size_t)-1, bad2 = (size_t)-1;
-        zk_status d1 = P->g1.decode_finish("", &inf1, &bad1);
-        if (d1 != ZK_OK) return bad1 != (size_t)-1 ? fail(ZK_ERR_IO, std::string("invalid G1 encoding in ") + name_of(sec1, 7, bad1).what) : d1;
-        zk_status d2 = P->g2.decode_finish("", &inf2, &bad2);
-        if (d2 != ZK_OK) return bad2 != (size_t)-1 ? fail(ZK_ERR_IO, std::string("invalid G2 encoding in ") + name_of(sec2, 3, bad2).what) : d2;
-        ZK_TRY(infinity_check(sec1, 7, 96, enc1, inf1));
-        ZK_TRY(infinity_check(sec2, 3, 192, enc2, inf2));
-        if (checked) {
-            ZK_TRY((check_points_dev<zkhost::Fq, zkdev::Fq>(P->g1.table.as<zkdev::Affine<zkdev::Fq>>(), n1, "parameters (G1)")));
-            ZK_TRY((check_points_dev<zkhost::Fq2, DevFq2>(P->g2.table.as<zkdev::Affine<DevFq2>>(), n2, "parameters (G2)")));
-        }
-        ZK_TRY(P->g1.table_enqueue(scratch1, g_stream));
-        ZK_TRY(P->g2.table_enqueue(scratch2, g_stream2));
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipStreamSynchronize(g_stream2));
-    }
-    P->g1a.alias(P->g1, pick_window(P->n_a, 3));
-    P->g1_lone.alias(P->g1, c_avg);
-    P->g2_lone.alias(P->g2, getenv("ZKAMD_WINDOW_BITS_G2") || c2 <= 10 ? c2 : 10u);
-    ZK_TRY(P->ntt.init(P->log_m));
-    ZK_TRY(calibrate_kernel_forms(P));
-    guard.p = nullptr;
-    *out = P;
-    return ZK_OK;
-}
-
-// Load-time choice between the two forms of the scratch-using assembly kernels.  One box in seventeen of
-// round 4 ran the first form of exactly these two kernels at a third of its speed in every process (204 instead of 67.6 ms,
-// 11.7 instead of 4.0: profiles/r04k_*_slow_box.*) - what a low scratch-wave limit looks like - while on a healthy box the
-// scratch-free form is 1-2 % slower in the overlapped step.  So: when the first key is loaded on a device, one machine-filling
-// launch of each form over synthetic tasks on the key's own tables (0.4 ms each, twice), and the scratch-free form is taken
-// where the first form is slower than 1.4 x it.  ZKAMD_INJECT_SCRATCH_SLOW=1 (tests) triples the first form's measured time.
-zk_status calibrate_kernel_forms(zk_params* P) {
-#if defined(ZK_HAVE_MADD_ASM) && defined(ZK_HAVE_RED_ASM)
-    std::lock_guard<std::mutex> lock(g_forms_mu);
-    KernelForms& F = g_forms[P->device & 63];
-    if (F.done) return ZK_OK;
-    const uint32_t n2 = (uint32_t)std::min<size_t>(P->g2.n_points * (size_t)zkdev::MSM_NPOS, 1u << 24);
-    const uint32_t n1 = (uint32_t)std::min<size_t>(P->g1.n_points * (size_t)zkdev::MSM_NPOS, 1u << 24);
-    if (n1 < 1024 || n2 < 1024 || getenv("ZKAMD_NO_CALIBRATE")) {   // (a toy key: nothing to measure on, the first form stays)
-        F.done = true;
-        return ZK_OK;
-    }
-    // each half next to the kernels it launches (msm_g2.cpp, msm_g1.cpp)
-    ZK_TRY(calibrate_g2_accumulate(P->g2.table.as<zkdev::Affine<DevFq2>>(), n2, &F.ms[0]));
-    ZK_TRY(calibrate_g1_reduce(P->g1.table.as<zkdev::Affine<zkdev::Fq28>>(), n1, &F.ms[2]));
-    const float slow = hook_env("ZKAMD_INJECT_SCRATCH_SLOW") && atoi(hook_env("ZKAMD_INJECT_SCRATCH_SLOW")) ? 3.0f : 1.0f;
-    F.ms[0] *= slow;
-    F.ms[2] *= slow;
-    F.form[0] = F.ms[0] > 1.4f * F.ms[1] ? 1u : 0u;
-    F.form[1] = F.ms[2] > 1.4f * F.ms[3] ? 1u : 0u;
-    F.done = true;
-#else
-    (void)P;
-#endif
-    return ZK_OK;
-}
-
-// A second handle over the SAME key for another lane of a pipeline: the tables (doubling tables, NTT tables)
-// are borrowed, the per-chunk workspaces are its own.  The original must outlive the clone.
-zk_params* params_clone_for_lane(const zk_params* P) {
-    zk_params* Q = new (std::nothrow) zk_params();
-    if (!Q) return nullptr;
-    Q->device = P->device;
-    Q->n_ic = P->n_ic; Q->n_h = P->n_h; Q->n_l = P->n_l; Q->n_a = P->n_a; Q->n_b1 = P->n_b1; Q->n_b2 = P->n_b2;
-    Q->log_m = P->log_m;
-    Q->m = P->m;
-    Q->off_h = P->off_h; Q->off_l = P->off_l; Q->off_a = P->off_a; Q->off_b1 = P->off_b1;
-    Q->g1.alias(P->g1, P->g1.c);
-    Q->g1a.alias(P->g1, P->g1a.c);
-    Q->g1_lone.alias(P->g1, P->g1_lone.c);
-    Q->g2.c = P->g2.c; Q->g2.maxd = P->g2.maxd; Q->g2.nb = P->g2.nb; Q->g2.n_points = P->g2.n_points;
-    Q->g2.table.borrow(P->g2.table);
-    Q->g2_lone.alias(P->g2, P->g2_lone.c);
-    if (P->drv.ready) {
-        Q->drv = P->drv;
-        Q->g1d.alias(P->g1d, P->g1d.c);
-        Q->g1d_lone.alias(P->g1d, P->g1d_lone.c);
-        if (P->prs.ready) {
-            Q->prs = P->prs;
-            Q->g1da.alias(P->g1d, P->g1da.c);
-            Q->g2p.c = P->g2p.c; Q->g2p.maxd = P->g2p.maxd; Q->g2p.nb = P->g2p.nb; Q->g2p.n_points = P->g2p.n_points;
-            Q->g2p.table.borrow(P->g2p.table);
-            Q->g2p_lone.alias(P->g2p, P->g2p_lone.c);
-        }
-    }
-    Q->ntt.log_n = P->ntt.log_n;
-    Q->ntt.n = P->ntt.n;
-    Q->ntt.tw_fwd.borrow(P->ntt.tw_fwd);
-    Q->ntt.tw_inv.borrow(P->ntt.tw_inv);
-    Q->ntt.s1_plain.borrow(P->ntt.s1_plain);
-    Q->ntt.s1_mont.borrow(P->ntt.s1_mont);
-    Q->ntt.s2.borrow(P->ntt.s2);
-    Q->ntt.dt.borrow(P->ntt.dt);
-    Q->ntt.sc_plain.borrow(P->ntt.sc_plain);
-    Q->ntt.sc_mont.borrow(P->ntt.sc_mont);
-    Q->ntt.coset_fwd.borrow(P->ntt.coset_fwd);
-    Q->ntt.coset_inv.borrow(P->ntt.coset_inv);
-    Q->ntt.consts.borrow(P->ntt.consts);
-    Q->alpha_g1_inf = P->alpha_g1_inf; Q->beta_g1_inf = P->beta_g1_inf; Q->beta_g2_inf = P->beta_g2_inf;
-    Q->delta_g1_inf = P->delta_g1_inf; Q->delta_g2_inf = P->delta_g2_inf;
-    Q->vk_bytes = P->vk_bytes;
-    Q->grp_a = P->grp_a; Q->grp_b1 = P->grp_b1; Q->grp_b2 = P->grp_b2;
-    return Q;
-}
-zk_r1cs* r1cs_clone_for_lane(const zk_r1cs* R) {
-    zk_r1cs* Q = new (std::nothrow) zk_r1cs();
-    if (!Q) return nullptr;
-    Q->device = R->device;
-    Q->id = R->id;
-    Q->n_in = R->n_in; Q->n_aux = R->n_aux; Q->n_con = R->n_con;
-    for (int m = 0; m < 3; m++) {
-        Q->row_ptr[m].borrow(R->row_ptr[m]);
-        Q->col[m].borrow(R->col[m]);
-        Q->coeff[m].borrow(R->coeff[m]);
-    }
-    Q->a_aux_density = R->a_aux_density;
-    Q->b_input_density = R->b_input_density;
-    Q->b_aux_density = R->b_aux_density;
-    return Q;
-}
-
-// ZKAMD_MERGE_VALUES=0: the maps are built without value pairs (a term per variable), for measurements and parity
-bool merge_values_on() {
-    const char* e = getenv("ZKAMD_MERGE_VALUES");
-    return !(e && atoi(e) == 0);
-}
-
-// Build (or reuse) the per-circuit index maps from the density trackers.
-// Equal points of a query (zk_params::Groups) become ONE term of its job: every member's slot maps to -1 and a slot appended
-// for the group, whose scalar k_build_scalars makes the sum of the members', maps to the group's first point.
-// ZKAMD_MERGE_BASES=0 builds the maps without groups (a term per query entry), for measurements and parity.
-zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t* a_aux_d, const uint8_t* b_in_d,
-                      const uint8_t* b_aux_d) {
-    const char* merge_env = getenv("ZKAMD_MERGE_BASES");
-    const bool merge = !(merge_env && atoi(merge_env) == 0);
-    std::vector<uint8_t> key;
-    key.reserve(9 + n_in + 2 * (size_t)n_aux);
-    for (int i = 0; i < 4; i++) key.push_back((uint8_t)(n_in >> (8 * i)));
-    for (int i = 0; i < 4; i++) key.push_back((uint8_t)(n_aux >> (8 * i)));
-    key.insert(key.end(), a_aux_d, a_aux_d + n_aux);
-    key.insert(key.end(), b_in_d, b_in_d + n_in);
-    key.insert(key.end(), b_aux_d, b_aux_d + n_aux);
-    for (int i = 0; i < 4; i++) key.push_back((uint8_t)((P->drv.ready ? P->drv.serial : 0u) >> (8 * i)));
-    key.push_back(merge ? 1 : 0);
-    const uint32_t nv = n_in + n_aux;
-    // value pairs: over the derived set that carries them (its serial is in the key), unless ZKAMD_MERGE_VALUES=0
-    const bool pairs = merge_values_on() && P->drv.ready && P->prs.ready && P->prs.links.size() == 11 * (size_t)nv;
-    key.push_back(pairs ? 1 : 0);
-    if (key == P->dens_key) return ZK_OK;
-    const PairCounts pc = pairs ? P->prs.n : PairCounts();
-    // scalar layout per proof: [inputs | aux | 1 | r | s | sums of the A groups | sums of the B2 groups] (prove_plan.h CJobLayout)
-    std::vector<int32_t> ma(nv + 3, -1), mb1(nv + 3, -1), mb2(nv + 3, -1);
-    std::vector<uint32_t> var_a, var_b;   // query position -> variable
-    var_a.reserve(P->n_a);
-    var_b.reserve(P->n_b1);
-    uint32_t pa = n_in;
-    for (uint32_t i = 0; i < n_in; i++) {   // A inputs: full density
-        ma[i] = (int32_t)i;
-        var_a.push_back(i);
-    }
-    for (uint32_t j = 0; j < n_aux; j++)
-        if (a_aux_d[j]) {
-            ma[n_in + j] = (int32_t)pa++;
-            var_a.push_back(n_in + j);
-        }
-    // bellman's generator emits exactly one `a` entry per input and per dense aux variable (and the
-    // b queries likewise): a different count means the assignment belongs to another circuit than the key
-    if (pa != P->n_a)
-        return fail(ZK_ERR_IO, "the A density of the assignment (" + std::to_string(pa) + ") differs from the key's a query (" +
-                                   std::to_string(P->n_a) + ")");
-    if (!P->alpha_g1_inf) ma[nv] = (int32_t)P->n_a;   // 1 * alpha_g1
-    ma[nv + 1] = (int32_t)P->n_a + 1;                 // r * delta_g1 (never at infinity here: prove_* refuse)
-    uint32_t pb = 0;
-    for (uint32_t i = 0; i < n_in; i++)
-        if (b_in_d[i]) {
-            mb1[i] = mb2[i] = (int32_t)pb++;
-            var_b.push_back(i);
-        }
-    for (uint32_t j = 0; j < n_aux; j++)
-        if (b_aux_d[j]) {
-            mb1[n_in + j] = mb2[n_in + j] = (int32_t)pb++;
-            var_b.push_back(n_in + j);
-        }
-    if (pb != P->n_b1 || pb != P->n_b2)
-        return fail(ZK_ERR_IO, "the B density of the assignment (" + std::to_string(pb) + ") differs from the key's b queries (" +
-                                   std::to_string(P->n_b1) + " in G1, " + std::to_string(P->n_b2) + " in G2)");
-    if (!P->beta_g1_inf) mb1[nv] = (int32_t)P->n_b1;   // 1 * beta_g1
-    if (!P->beta_g2_inf) mb2[nv] = (int32_t)P->n_b2;   // 1 * beta_g2
-    mb2[nv + 2] = (int32_t)P->n_b2 + 1;                // s * delta_g2
-    // the groups of each query: members muted in that query's map; base[g] = the query position the group's sum goes to;
-    // the CSR lists in variable indices, A | B2 | B1, are what k_build_scalars sums over
-    static const zk_params::Groups none;
-    std::vector<uint32_t> gptr(1, 0u), gmem;
-    auto mute = [&](const zk_params::Groups& G, const std::vector<uint32_t>& var, std::vector<int32_t>& map, std::vector<int32_t>& base) {
-        for (uint32_t g = 0; g < G.count(); g++) {
-            base.push_back((int32_t)G.mem[G.ptr[g]]);
-            for (uint32_t k = G.ptr[g]; k < G.ptr[g + 1]; k++) {
-                map[var[G.mem[k]]] = -1;
-                gmem.push_back(var[G.mem[k]]);
-            }
-            gptr.push_back((uint32_t)gmem.size());
-        }
-    };
-    std::vector<int32_t> base_a, base_b2, base_b1;
-    mute(merge ? P->grp_a : none, var_a, ma, base_a);
-    mute(merge ? P->grp_b2 : none, var_b, mb2, base_b2);
-    mute(merge ? P->grp_b1 : none, var_b, mb1, base_b1);
-    const uint32_t ga = (uint32_t)base_a.size(), gb2 = (uint32_t)base_b2.size(), gb1 = (uint32_t)base_b1.size();
-    // (each of the two jobs over this vector selects its own sums; the other's stay -1)
-    const CJobLayout W = cjob_layout(n_in, n_aux, (uint32_t)P->m, ga, gb2, gb1, false, false);
-    ma.resize(W.wstride, -1);
-    mb2.resize(W.wstride, -1);
-    for (uint32_t g = 0; g < ga; g++) ma[W.w_sum_a + g] = base_a[g];
-    for (uint32_t g = 0; g < gb2; g++) mb2[W.w_sum_b2 + g] = base_b2[g];
-    // h coefficients leave the last transform in bit-reversed order; the top coefficient
-    // (degree m - 1) is dropped exactly as bellman truncates it
-    std::vector<int32_t> mh(P->m);
-    for (size_t pos = 0; pos < P->m; pos++) {
-        uint32_t e = P->log_m ? (__builtin_bitreverse32((uint32_t)pos) >> (32 - P->log_m)) : 0;
-        mh[pos] = e < P->n_h ? (int32_t)e : -1;
-    }
-    auto upload = [](DevBuf& dst, const auto& v) -> zk_status {
-        ZK_TRY(dst.ensure(v.size() * 4));
-        HIP_TRY(hipMemcpy(dst.p, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-        return ZK_OK;
-    };
-    // The index map of the merged C job, absolute positions in the G1 group table, section by section where the layout has
-    // them (prove_plan.h CJobLayout: what k_build_scalars stores by): the H block, the aux and - derived - the input variables
-    // on the bases given, the r and fold sections and the sums of the groups on the copies of the b_g1 and A queries.
-    auto upload_c_map = [&](DevBuf& dst, const CJobLayout& L, const int32_t* head, const int32_t* aux, const int32_t* inputs,
-                            uint32_t off_a, uint32_t off_b1) -> zk_status {
-        std::vector<int32_t> map(head, head + L.head);
-        map.reserve(L.cstride);
-        bool fits = true;
-        auto section = [&](uint32_t off) { fits = fits && map.size() == off; };
-        auto query = [&](const std::vector<int32_t>& q, uint32_t from, uint32_t n, uint32_t off) {
-            for (uint32_t i = from; i < from + n; i++) map.push_back(q[i] < 0 ? -1 : (int32_t)(off + q[i]));
-        };
-        section(L.aux);
-        map.insert(map.end(), aux, aux + n_aux);
-        section(L.rz);
-        query(mb1, 0, nv, off_b1);
-        section(L.r);
-        query(mb1, nv, 1, off_b1);   // r * beta_1
-        if (L.fold) {   // [s z (nv) | s | r s] over the A query, alpha_1, delta_1
-            section(L.sz);
-            query(ma, 0, nv, off_a);
-            section(L.s);
-            query(ma, nv, 1, off_a);
-            section(L.rs);
-            query(ma, nv + 1, 1, off_a);
-        }
-        if (L.derived) {
-            section(L.in_tail);
-            map.insert(map.end(), inputs, inputs + n_in);
-        }
-        section(L.sum_b1);
-        query(base_b1, 0, gb1, off_b1);
-        if (L.fold) {
-            section(L.sum_a);
-            query(base_a, 0, ga, off_a);
-        }
-        if (L.w_b2v) {   // the pair bases lie in the table as the layout orders them (ensure_derived)
-            section(L.pair_l);
-            for (uint32_t k = 0; k < L.pl; k++) map.push_back((int32_t)(P->prs.base_l + k));
-            section(L.pair_b1);
-            for (uint32_t k = 0; k < L.pb1; k++) map.push_back((int32_t)(P->prs.base_b1 + k));
-            if (L.fold) {
-                section(L.pair_a);
-                for (uint32_t k = 0; k < L.pa; k++) map.push_back((int32_t)(P->prs.base_a + k));
-            }
-        }
-        section(L.cstride);
-        if (!fits) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the C map does not follow its layout");
-        return upload(dst, map);
-    };
-    std::vector<int32_t> hk;   // the key's own bases: [h (m) | l (n_aux)]
-    hk.reserve(P->m + n_aux);
-    for (size_t pos = 0; pos < P->m; pos++) hk.push_back(mh[pos] < 0 ? -1 : (int32_t)(P->off_h + mh[pos]));
-    for (uint32_t j = 0; j < n_aux; j++) hk.push_back((int32_t)(P->off_l + j));
-    for (bool fold : {false, true})
-        ZK_TRY(upload_c_map(fold ? P->map_cf : P->map_c, cjob_layout(n_in, n_aux, (uint32_t)P->m, ga, gb2, gb1, fold, false), hk.data(),
-                            hk.data() + P->m, nullptr, P->off_a, P->off_b1));
-    if (P->drv.ready && P->drv.pos.size() == 2 * (size_t)P->drv.n_rows + nv) {
-        // the same job over the derived bases, pos = [s (n_rows) | e (n_rows) | inputs | aux]
-        const zk_params::Derived& D = P->drv;
-        const uint32_t head = 2 * D.n_rows;
-        for (bool fold : {false, true})
-            ZK_TRY(upload_c_map(fold ? P->map_cfd : P->map_cd, cjob_layout(n_in, n_aux, head, ga, gb2, gb1, fold, true, pc), D.pos.data(),
-                                D.pos.data() + head + n_in, D.pos.data() + head, D.off_a, D.off_b1));
-    }
-    if (pairs) {
-        // The A and B2 jobs of a chunk with pairs: the A map in absolute positions of the derived table (its copy of the A query,
-        // the pair bases in front of it), the B2 map over its own copy of the variables' slots and the table with its pairs
-        const CJobLayout Wp = cjob_layout(n_in, n_aux, 0, ga, gb2, gb1, false, true, pc);
-        std::vector<int32_t> mad(Wp.wstride, -1), mbd(Wp.wstride, -1);
-        for (uint32_t i = 0; i < W.wstride; i++) {
-            if (ma[i] >= 0) mad[i] = (int32_t)(P->drv.off_a + ma[i]);
-            if (i >= nv) mbd[i] = mb2[i];
-        }
-        for (uint32_t i = 0; i < nv; i++) mbd[Wp.w_b2v + i] = mb2[i];
-        for (uint32_t k = 0; k < pc.a; k++) mad[Wp.w_pair_a + k] = (int32_t)(P->prs.base_a + k);
-        for (uint32_t k = 0; k < pc.b2; k++) mbd[Wp.w_pair_b2 + k] = (int32_t)(P->prs.base_b2 + k);
-        ZK_TRY(upload(P->map_ad, mad));
-        ZK_TRY(upload(P->map_b2d, mbd));
-        ZK_TRY(upload(P->pairs_dev, P->prs.links));
-        // MsmSelRange::alt: per pair slot of the job, in the order of its sections, the table positions of the longer bases
-        auto alts = [&](std::initializer_list<uint32_t> queries) {
-            std::vector<int32_t> out;
-            for (uint32_t query : queries)
-                for (int32_t x : P->prs.alt[query]) out.push_back(x < 0 ? -1 : (int32_t)(P->prs.xbase[query] + (uint32_t)x));
-            if (out.empty()) out.push_back(-1);
-            return out;
-        };
-        if (zkpairs::RUN_MAX > 2) {
-            ZK_TRY(upload(P->alt_c, alts({2u, 3u, 0u})));   // [pl | pb1 | (fold: pa)]
-            ZK_TRY(upload(P->alt_a, alts({0u})));
-            ZK_TRY(upload(P->alt_b2, alts({1u})));
-        }
-    }
-    gptr.insert(gptr.end(), gmem.begin(), gmem.end());
-    ZK_TRY(upload(P->grp_dev, gptr));
-    ZK_TRY(upload(P->map_a, ma));
-    ZK_TRY(upload(P->map_b2, mb2));
-    P->dens_key.swap(key);
-    P->map_nv = nv;
-    P->mg_a = ga;
-    P->mg_b2 = gb2;
-    P->mg_b1 = gb1;
-    P->mpairs = pc;
-    return ZK_OK;
-}
 
 // create_proof step 6, rearranged:  with A = alpha + sum_A + r*delta (already
 // complete, the alpha and r*delta terms rode along in the A multiexp) and
@@ -839,7 +50,7 @@ zk_status ensure_maps(zk_params* P, uint32_t n_in, uint32_t n_aux, const uint8_t
 // k_xyzz_normalize_export; the host encodes the 192 bytes.)
 
 // One chunk of proofs: the plan (prove_plan.h), what its stages hand to each other, and the stages in the order they run.
-// derived: a, b, c are the library's own row evaluations of the circuit P->drv was built for - the four-transform form over
+// derived: a, b, c are the library's own row evaluations of the circuit P->bind.drv was built for - the four-transform form over
 // the derived bases (ensure_derived), whose H scalars are those of the live rows.
 static_assert(zkpairs::RUN_MAX <= zkdev::PAIR_RUN_CAP, "k_build_scalars holds a block of a run in one 64-bit word");
 static_assert(PROVE_FOLD_IN_MSM_MAX == MSM_FEW_JOBS, "the fold rides in the multiexp up to the few-jobs limit of a launch set");
@@ -865,10 +76,10 @@ struct ChunkRun {
     zk_status scalars(const uint8_t* rs) {
         const CJobLayout& L = plan.layout;
         const uint32_t nv = L.n_in + L.n_aux;
-        ZK_TRY(P->wit.ensure(np * (size_t)L.wstride * 32));
-        wit = P->wit.as<uint32_t>();
-        ZK_TRY(P->pin_tail.ensure(np * 96));
-        uint8_t* tail = P->pin_tail.as<uint8_t>();
+        ZK_TRY(P->work.wit.ensure(np * (size_t)L.wstride * 32));
+        wit = P->work.wit.as<uint32_t>();
+        ZK_TRY(P->work.pin_tail.ensure(np * 96));
+        uint8_t* tail = P->work.pin_tail.as<uint8_t>();
         memset(tail, 0, np * 96);
         std::vector<uint64_t> rsv(np * 8);
         for (size_t p = 0; p < np; p++) {
@@ -880,24 +91,24 @@ struct ChunkRun {
             tail[p * 96] = 1;
             memcpy(&tail[p * 96 + 32], rr, 64);
         }
-        ZK_TRY(P->tail.ensure(np * 96));
-        HIP_TRY(hipMemcpyAsync(P->tail.p, tail, np * 96, hipMemcpyHostToDevice, g_stream));
-        ZK_TRY(P->bad.ensure(8));
-        ZK_TRY(P->pin_bad.ensure(8));
-        bad = P->bad.as<uint32_t>();
+        ZK_TRY(P->work.tail.ensure(np * 96));
+        HIP_TRY(hipMemcpyAsync(P->work.tail.p, tail, np * 96, hipMemcpyHostToDevice, g_stream));
+        ZK_TRY(P->work.bad.ensure(8));
+        ZK_TRY(P->work.pin_bad.ensure(8));
+        bad = P->work.bad.as<uint32_t>();
         HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
-        ZK_TRY(P->cvec.ensure(np * (size_t)L.cstride * 32));
-        cvec = P->cvec.as<uint32_t>();
+        ZK_TRY(P->work.cvec.ensure(np * (size_t)L.cstride * 32));
+        cvec = P->work.cvec.as<uint32_t>();
         const bool bytes = pairs && RUN_W;   // (at RUN_MAX = 2 a pair slot is its pair: nothing to name)
         if (bytes) {   // (every byte is written: by the thread that writes its pair slot)
-            ZK_TRY(P->sel_w.ensure(np * (size_t)L.sel_w + 1));
-            ZK_TRY(P->sel_c.ensure(np * (size_t)L.sel_c + 1));
+            ZK_TRY(P->work.sel_w.ensure(np * (size_t)L.sel_w + 1));
+            ZK_TRY(P->work.sel_c.ensure(np * (size_t)L.sel_c + 1));
         }
         // (the same launch: a thread per variable, three for the tail, one per group)
         ZK_LAUNCH(zkdev::k_build_scalars, dim3((L.w_end + L.gb1 + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, wit, cvec,
-                  (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->tail.as<uint32_t>(), L, mont ? 1u : 0u, bad,
-                  P->grp_dev.as<uint32_t>(), pairs ? (const int32_t*)P->pairs_dev.as<int32_t>() : (const int32_t*)nullptr,
-                  bytes ? P->sel_w.as<uint8_t>() : (uint8_t*)nullptr, bytes ? P->sel_c.as<uint8_t>() : (uint8_t*)nullptr, zkpairs::RUN_MAX);
+                  (const uint32_t*)bt->d_wit + first * (size_t)nv * 8, P->work.tail.as<uint32_t>(), L, mont ? 1u : 0u, bad,
+                  P->maps.grp_dev.as<uint32_t>(), pairs ? (const int32_t*)P->maps.pairs_dev.as<int32_t>() : (const int32_t*)nullptr,
+                  bytes ? P->work.sel_w.as<uint8_t>() : (uint8_t*)nullptr, bytes ? P->work.sel_c.as<uint8_t>() : (uint8_t*)nullptr, zkpairs::RUN_MAX);
         return ZK_OK;
     }
 
@@ -906,30 +117,30 @@ struct ChunkRun {
     // reduction tree is latency-bound with one job per proof; the G1 work fills the machine).
     zk_status g2_set() {
         const uint32_t wstride = plan.layout.wstride;
-        P->jobs2.clear();
+        P->work.jobs2.clear();
         for (size_t p = 0; p < np; p++) {
-            MsmJob j2 = {wit + p * (size_t)wstride * 8, (pairs ? P->map_b2d : P->map_b2).as<int32_t>(), wstride, 0, (uint32_t)G2->n_points, 0, 0, 0};
-            P->jobs2.push_back(j2);
+            MsmJob j2 = {wit + p * (size_t)wstride * 8, (pairs ? P->maps.map_b2d : P->maps.map_b2).as<int32_t>(), wstride, 0, (uint32_t)G2->n_points, 0, 0, 0};
+            P->work.jobs2.push_back(j2);
         }
         HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
         HIP_TRY(hipStreamWaitEvent(side, g_ev_fork, 0));
         // the bytes of the jobs' pair slots: the lengths of their terms pick the bases (msm.h MsmSelSet)
         const CJobLayout& L = plan.layout;
         zkdev::MsmSelSet sels = {};
-        if (pairs && RUN_W) sels.r[0] = {P->sel_w.as<uint8_t>() + L.pa, P->alt_b2.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_b2, L.pb2, RUN_W};
-        ZK_TRY(G2->enqueue(P->jobs2, P->res2, side, false, &sels));
-        ZK_TRY(P->pin_g2.ensure(np * sizeof(HG2)));
-        if (plan.host_norm) ZK_TRY(G2->export_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));
-        else ZK_TRY(G2->normalize_to_host(G2->res_dev, np, P->pin_g2.as<HG2>(), P->fold_b2, side));   // B in affine form
+        if (pairs && RUN_W) sels.r[0] = {P->work.sel_w.as<uint8_t>() + L.pa, P->maps.alt_b2.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_b2, L.pb2, RUN_W};
+        ZK_TRY(G2->enqueue(P->work.jobs2, P->work.res2, side, false, &sels));
+        ZK_TRY(P->work.pin_g2.ensure(np * sizeof(HG2)));
+        if (plan.host_norm) ZK_TRY(G2->export_to_host(G2->res_dev, np, P->work.pin_g2.as<HG2>(), P->work.fold_b2, side));
+        else ZK_TRY(G2->normalize_to_host(G2->res_dev, np, P->work.pin_g2.as<HG2>(), P->work.fold_b2, side));   // B in affine form
         return ZK_OK;
     }
 
     // ---- H pipeline (create_proof step 3): the H block of every C job
     zk_status h_pipeline() {
-        const size_t m = P->m;
+        const size_t m = P->key.m;
         const uint32_t n_rows = bt->n_rows, cstride = plan.layout.cstride;
-        ZK_TRY(P->abc.ensure((derived ? 2 : 3) * np * m * 32));
-        uint32_t* A = P->abc.as<uint32_t>();
+        ZK_TRY(P->work.abc.ensure((derived ? 2 : 3) * np * m * 32));
+        uint32_t* A = P->work.abc.as<uint32_t>();
         uint32_t* B = A + np * m * 8;
         uint32_t* C = B + np * m * 8;
         const uint32_t* srcs[3] = {(const uint32_t*)bt->d_a + first * (size_t)n_rows * 8,
@@ -940,12 +151,12 @@ struct ChunkRun {
         // coefficients are all the H pipeline needs of c (ntt.h k_h_pointwise: 6 transforms per proof instead of bellman's 7).
         // Over the derived bases: a and b only, * t / m - the coefficients of x a'(x) - and the forward chain below is a plain
         // transform back onto the domain; the row evaluations themselves stay where they are (the chains load out of place).
-        const uint32_t* s1 = derived ? P->ntt.dt.as<uint32_t>() : mont ? P->ntt.s1_mont.as<uint32_t>() : P->ntt.s1_plain.as<uint32_t>();
-        const uint32_t* sc = mont ? P->ntt.sc_mont.as<uint32_t>() : P->ntt.sc_plain.as<uint32_t>();
+        const uint32_t* s1 = derived ? P->tab.ntt.dt.as<uint32_t>() : mont ? P->tab.ntt.s1_mont.as<uint32_t>() : P->tab.ntt.s1_plain.as<uint32_t>();
+        const uint32_t* sc = mont ? P->tab.ntt.sc_mont.as<uint32_t>() : P->tab.ntt.sc_plain.as<uint32_t>();
         for (int k = 0; k < (derived ? 2 : 3); k++)
-            ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)np), dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
+            ZK_TRY(P->tab.ntt.chain(P->tab.ntt.form((uint32_t)np), dsts[k], (uint32_t)np, (uint32_t)m, true, true, nullptr, k < 2 ? s1 : sc, srcs[k], n_rows, n_rows, bad));
         // (coset) fft (bit-reversed -> natural) of a and b at once
-        ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)(2 * np)), A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
+        ZK_TRY(P->tab.ntt.chain(P->tab.ntt.form((uint32_t)(2 * np)), A, (uint32_t)(2 * np), (uint32_t)m, false, false, nullptr, nullptr));
         {
             ProfScope ps("h_pointwise");
             if (derived) {
@@ -956,13 +167,13 @@ struct ChunkRun {
             } else {
                 const size_t count = np * m;
                 ZK_LAUNCH(zkdev::k_h_pointwise, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)A,
-                          (const uint32_t*)B, (const uint32_t*)nullptr, P->ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
+                          (const uint32_t*)B, (const uint32_t*)nullptr, P->tab.ntt.consts.as<uint32_t>() + 8, cvec, (uint32_t)m, cstride, count);
             }
         }
         // icoset fft of a b / (g^m - 1): ifft (natural -> bit-reversed), * g^-i / m, Montgomery factor dropped, minus the
         // scaled coefficients of c (same bit-reversed order); in place inside the merged scalar vectors
         if (!derived)
-            ZK_TRY(P->ntt.chain(P->ntt.form((uint32_t)np), cvec, (uint32_t)np, cstride, true, true, nullptr, P->ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
+            ZK_TRY(P->tab.ntt.chain(P->tab.ntt.form((uint32_t)np), cvec, (uint32_t)np, cstride, true, true, nullptr, P->tab.ntt.s2.as<uint32_t>(), nullptr, 0, 0, nullptr,
                                 (const uint32_t*)C, (uint32_t)m));
         return ZK_OK;
     }
@@ -972,45 +183,45 @@ struct ChunkRun {
     zk_status g1_sets() {
         const bool split = plan.split;
         const uint32_t wstride = plan.layout.wstride, cstride = plan.layout.cstride;
-        const uint32_t npts1 = (uint32_t)P->g1.n_points, npts1c = (uint32_t)G1C->n_points;
-        P->jobs1.clear();
-        P->jobs1a.clear();
+        const uint32_t npts1 = (uint32_t)P->tab.g1.n_points, npts1c = (uint32_t)G1C->n_points;
+        P->work.jobs1.clear();
+        P->work.jobs1a.clear();
         for (size_t p = 0; p < np; p++) {
             MsmJob jc = {cvec + p * (size_t)cstride * 8, map_c, cstride, 0, npts1c, 0, 0, 0};
-            P->jobs1.push_back(jc);
+            P->work.jobs1.push_back(jc);
         }
         for (size_t p = 0; p < np; p++) {
-            MsmJob ja = {wit + p * (size_t)wstride * 8, P->map_a.as<int32_t>(), wstride, P->off_a, npts1, 0, 0, 0};
+            MsmJob ja = {wit + p * (size_t)wstride * 8, P->maps.map_a.as<int32_t>(), wstride, P->key.off_a, npts1, 0, 0, 0};
             if (pairs) {   // (absolute positions in the derived table: the pair bases lie in front of its copy of the A query)
-                ja.map = P->map_ad.as<int32_t>();
+                ja.map = P->maps.map_ad.as<int32_t>();
                 ja.table_base = 0;
-                ja.n_table = (uint32_t)P->g1d.n_points;
+                ja.n_table = (uint32_t)P->bind.g1d.n_points;
             } else if (!split && derived) {   // (one set with the C' jobs: the A query's copy behind the derived bases)
-                ja.table_base = P->drv.off_a;
+                ja.table_base = P->bind.drv.off_a;
                 ja.n_table = npts1c;
             }
-            (split ? P->jobs1a : P->jobs1).push_back(ja);
+            (split ? P->work.jobs1a : P->work.jobs1).push_back(ja);
         }
         // the ranges of jobs whose pair slots follow the bytes (msm.h MsmSelSet): the C' jobs, the A jobs
         const CJobLayout& L = plan.layout;
         zkdev::MsmSelSet sc = {}, sa = {};
         if (pairs && RUN_W) {
-            sc.r[0] = {P->sel_c.as<uint8_t>(), P->alt_c.as<int32_t>(), 0u, (uint32_t)np, L.sel_c, L.pair_l, L.sel_c, RUN_W};
-            sa.r[0] = {P->sel_w.as<uint8_t>(), P->alt_a.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_a, L.pa, RUN_W};
+            sc.r[0] = {P->work.sel_c.as<uint8_t>(), P->maps.alt_c.as<int32_t>(), 0u, (uint32_t)np, L.sel_c, L.pair_l, L.sel_c, RUN_W};
+            sa.r[0] = {P->work.sel_w.as<uint8_t>(), P->maps.alt_a.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_a, L.pa, RUN_W};
             if (!split) {   // (one set: the A jobs behind the C' jobs)
                 sc.r[1] = sa.r[0];
                 sc.r[1].job0 = (uint32_t)np;
             }
         }
         if (split) {
-            MsmG1& G1A = pairs ? P->g1da : P->g1a;
-            ZK_TRY(G1A.enqueue(P->jobs1a, P->res1a, side, false, &sa));
+            MsmG1& G1A = pairs ? P->bind.g1da : P->tab.g1a;
+            ZK_TRY(G1A.enqueue(P->work.jobs1a, P->work.res1a, side, false, &sa));
             a_dev = G1A.res_dev;
             HIP_TRY(hipEventRecord(g_ev_join, side));
-            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false, &sc));
+            ZK_TRY(G1C->enqueue(P->work.jobs1, P->work.res1, g_stream, false, &sc));
             HIP_TRY(hipStreamWaitEvent(g_stream, g_ev_join, 0));   // (a no-op when the side stream is the main one)
         } else {
-            ZK_TRY(G1C->enqueue(P->jobs1, P->res1, g_stream, false, &sc));
+            ZK_TRY(G1C->enqueue(P->work.jobs1, P->work.res1, g_stream, false, &sc));
             a_dev = G1C->res_dev + np;
         }
         return ZK_OK;
@@ -1023,32 +234,32 @@ struct ChunkRun {
         const DP1* cprime = G1C->res_dev;
         const DP1* cfin = cprime;   // the C job was s * A + C' already
         if (!plan.fold_in_msm) {
-            ZK_TRY(P->fold_tbl.ensure(np * 15 * sizeof(DP1)));
-            ZK_TRY(P->fold_c.ensure(np * sizeof(DP1)));
+            ZK_TRY(P->work.fold_tbl.ensure(np * 15 * sizeof(DP1)));
+            ZK_TRY(P->work.fold_c.ensure(np * sizeof(DP1)));
             // one row of 16 lanes per proof (coop_tail.cpp): 256 waves, each chain 4 - 5 x shorter than a lane's
-            zkcoop::scale_add(a_dev, cprime, (const uint32_t*)P->tail.as<uint32_t>() + 16, 24u, P->fold_tbl.as<DP1>(),
-                              P->fold_c.as<DP1>(), (uint32_t)np, g_stream);
-            cfin = P->fold_c.as<DP1>();
+            zkcoop::scale_add(a_dev, cprime, (const uint32_t*)P->work.tail.as<uint32_t>() + 16, 24u, P->work.fold_tbl.as<DP1>(),
+                              P->work.fold_c.as<DP1>(), (uint32_t)np, g_stream);
+            cfin = P->work.fold_c.as<DP1>();
         }
-        ZK_TRY(P->pin_g1.ensure(2 * np * sizeof(HG1)));
+        ZK_TRY(P->work.pin_g1.ensure(2 * np * sizeof(HG1)));
         if (plan.host_norm) {
-            ZK_TRY(G1C->export_to_host(a_dev, np, P->pin_g1.as<HG1>() + np, P->fold_a1, g_stream));
-            ZK_TRY(G1C->export_to_host(cfin, np, P->pin_g1.as<HG1>(), P->fold_c1, g_stream));
+            ZK_TRY(G1C->export_to_host(a_dev, np, P->work.pin_g1.as<HG1>() + np, P->work.fold_a1, g_stream));
+            ZK_TRY(G1C->export_to_host(cfin, np, P->work.pin_g1.as<HG1>(), P->work.fold_c1, g_stream));
         } else {
-            ZK_TRY(G1C->normalize2_to_host(a_dev, cfin, np, P->pin_g1.as<HG1>() + np, P->pin_g1.as<HG1>(), P->fold_a1, P->fold_c1, g_stream));
+            ZK_TRY(G1C->normalize2_to_host(a_dev, cfin, np, P->work.pin_g1.as<HG1>() + np, P->work.pin_g1.as<HG1>(), P->work.fold_a1, P->work.fold_c1, g_stream));
         }
         return ZK_OK;
     }
 
     // ---- wait for the GPU; the flags the kernels raised over the caller's scalars
     zk_status collect(std::chrono::steady_clock::time_point& t_wait) {
-        HIP_TRY(hipMemcpyAsync(P->pin_bad.p, bad, 8, hipMemcpyDeviceToHost, g_stream));
+        HIP_TRY(hipMemcpyAsync(P->work.pin_bad.p, bad, 8, hipMemcpyDeviceToHost, g_stream));
         t_wait = std::chrono::steady_clock::now();
         ZK_TRY(G1C->collect(g_stream));
         ZK_TRY(G2->collect(side));
         // the reference cannot even represent these assignments (FrRepr -> Fr fails for values >= r,
         // fr.rs:276-289; ProvingAssignment starts with alloc_input(ONE = 1))
-        const uint32_t flags = P->pin_bad.as<uint32_t>()[0];
+        const uint32_t flags = P->work.pin_bad.as<uint32_t>()[0];
         if (flags & zkdev::ZK_BAD_SCALAR)
             return fail(ZK_ERR_INVALID_ARGUMENT, "an assignment scalar (a, b, c, input or aux) is not a canonical field element (>= r)");
         if (flags & zkdev::ZK_BAD_ONE) return fail(ZK_ERR_INVALID_ARGUMENT, "input 0 of an assignment is not ONE = 1");
@@ -1063,8 +274,8 @@ struct ChunkRun {
             for (size_t p = lo; p < hi; p++)
             {
                 uint8_t* out = proofs_out + (first + p) * 192;
-                const HG1A pa = zkhost::to_affine(P->pin_g1.as<HG1>()[np + p]), pc = zkhost::to_affine(P->pin_g1.as<HG1>()[p]);
-                const HG2A pb = zkhost::to_affine(P->pin_g2.as<HG2>()[p]);
+                const HG1A pa = zkhost::to_affine(P->work.pin_g1.as<HG1>()[np + p]), pc = zkhost::to_affine(P->work.pin_g1.as<HG1>()[p]);
+                const HG2A pb = zkhost::to_affine(P->work.pin_g2.as<HG2>()[p]);
                 zkhost::g1_to_compressed(pa, out);
                 zkhost::g2_to_compressed(pb, out + 48);
                 zkhost::g1_to_compressed(pc, out + 144);
@@ -1089,14 +300,14 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
     const auto t_begin = std::chrono::steady_clock::now();
     const ProveTunables tun = ProveTunables::read();
     const bool mont = (bt->flags & ZK_FR_MONTGOMERY) != 0;
-    if (derived && (!mont || P->drv.n_rows != bt->n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
+    if (derived && (!mont || P->bind.drv.n_rows != bt->n_rows)) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: the batch is not the derived set's");
     ChunkRun c = {P, np, bt, first, derived, mont,
-                  prove_plan(np, bt->n_inputs, bt->n_aux, bt->n_rows, P->m, P->mg_a, P->mg_b2, P->mg_b1, derived, tun, P->mpairs)};
+                  prove_plan(np, bt->n_inputs, bt->n_aux, bt->n_rows, P->key.m, P->maps.mg_a, P->maps.mg_b2, P->maps.mg_b1, derived, tun, P->maps.mpairs)};
     c.pairs = c.plan.layout.w_b2v != 0;
     c.side = c.plan.one_stream ? g_stream : g_stream2;
-    c.G2 = c.pairs ? (c.plan.g2_lone ? &P->g2p_lone : &P->g2p) : (c.plan.g2_lone ? &P->g2_lone : &P->g2);
-    MsmG1* const g1s[] = {&P->g1, &P->g1_lone, &P->g1d, &P->g1d_lone};   // in the order of PG1 and PMap
-    DevBuf* const maps[] = {&P->map_c, &P->map_cf, &P->map_cd, &P->map_cfd};
+    c.G2 = c.pairs ? (c.plan.g2_lone ? &P->bind.g2p_lone : &P->bind.g2p) : (c.plan.g2_lone ? &P->tab.g2_lone : &P->tab.g2);
+    MsmG1* const g1s[] = {&P->tab.g1, &P->tab.g1_lone, &P->bind.g1d, &P->bind.g1d_lone};   // in the order of PG1 and PMap
+    DevBuf* const maps[] = {&P->maps.map_c, &P->maps.map_cf, &P->maps.map_cd, &P->maps.map_cfd};
     c.G1C = g1s[(int)c.plan.g1];
     c.map_c = maps[(int)c.plan.map]->as<int32_t>();
     ZK_TRY(c.scalars(rs));
@@ -1117,7 +328,7 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
         // the (digit, point) pairs of the chunk's launch sets, counted from their buckets
         uint64_t pc1 = 0, pa1 = 0, p2 = 0;
         ZK_TRY(c.G1C->count_pairs(c.plan.split ? np : 2 * np, &pc1));
-        if (c.plan.split) ZK_TRY((c.pairs ? P->g1da : P->g1a).count_pairs(np, &pa1));
+        if (c.plan.split) ZK_TRY((c.pairs ? P->bind.g1da : P->tab.g1a).count_pairs(np, &pa1));
         ZK_TRY(c.G2->count_pairs(np, &p2));
         fprintf(stderr, "[zkamd] chunk of %zu: pairs per proof: %s %.0f, A set %.0f, G2 set %.0f\n", np, c.plan.split ? "C' set" : "C' and A set",
                 (double)pc1 / (double)np, (double)pa1 / (double)np, (double)p2 / (double)np);
@@ -1128,13 +339,13 @@ zk_status prove_chunk(zk_params* P, size_t np, const zk_batch_dev* bt, size_t fi
 zk_status prove_batch_dev(zk_params* P, size_t n, const zk_batch_dev* bt, const uint8_t* rs, uint8_t* proofs_out, bool derived = false) {
     if (!P || !bt || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
-    ZK_TRY(use_device(P->device));
+    ZK_TRY(use_device(P->key.device));
     // bellman create_proof: `if vk.delta_g1.is_zero() || vk.delta_g2.is_zero() { return Err(UnexpectedIdentity) }`
-    if (P->delta_g1_inf || P->delta_g2_inf) return fail(ZK_ERR_UNEXPECTED_IDENTITY, "vk.delta is the point at infinity");
+    if (P->key.delta_g1_inf || P->key.delta_g2_inf) return fail(ZK_ERR_UNEXPECTED_IDENTITY, "vk.delta is the point at infinity");
     if (bt->n_inputs == 0) return fail(ZK_ERR_INVALID_ARGUMENT, "n_inputs must include ONE");
-    if (bt->n_rows > P->m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
-    if (bt->n_inputs != P->n_ic) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "number of inputs differs from vk.ic");
-    if (bt->n_aux != P->n_l) return fail(ZK_ERR_IO, "number of aux variables differs from the l query");
+    if (bt->n_rows > P->key.m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
+    if (bt->n_inputs != P->key.n_ic) return fail(ZK_ERR_MALFORMED_VERIFYING_KEY, "number of inputs differs from vk.ic");
+    if (bt->n_aux != P->key.n_l) return fail(ZK_ERR_IO, "number of aux variables differs from the l query");
     if (!bt->d_a || !bt->d_b || !bt->d_c || !bt->d_wit || !bt->a_aux_density || !bt->b_input_density || !bt->b_aux_density)
         return fail(ZK_ERR_ASSIGNMENT_MISSING, "assignment pointer is null");
     ZK_TRY(ensure_maps(P, bt->n_inputs, bt->n_aux, bt->a_aux_density, bt->b_input_density, bt->b_aux_density));
@@ -1156,7 +367,7 @@ bool same_circuit(const zk_assignment& x, const zk_assignment& y) {
 zk_status prove_batch_host(zk_params* P, size_t n, const zk_assignment* asgs, const uint8_t* rs, uint8_t* proofs_out) {
     if (!P || !asgs || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
-    ZK_TRY(use_device(P->device));
+    ZK_TRY(use_device(P->key.device));
     const zk_assignment& z = asgs[0];
     for (size_t i = 0; i < n; i++) {
         const zk_assignment& x = asgs[i];
@@ -1176,17 +387,17 @@ zk_status prove_batch_host(zk_params* P, size_t n, const zk_assignment* asgs, co
     if (tun.host_chunk) hc = std::min(chunk, tun.host_chunk);
     hc = std::min(hc, n);
     const size_t slots = n > hc ? 2 : 1;
-    ZK_TRY(P->stage_a.ensure(slots * hc * rb));
-    ZK_TRY(P->stage_b.ensure(slots * hc * rb));
-    ZK_TRY(P->stage_c.ensure(slots * hc * rb));
-    ZK_TRY(P->stage_w.ensure(slots * hc * nvb));
+    ZK_TRY(P->work.stage_a.ensure(slots * hc * rb));
+    ZK_TRY(P->work.stage_b.ensure(slots * hc * rb));
+    ZK_TRY(P->work.stage_c.ensure(slots * hc * rb));
+    ZK_TRY(P->work.stage_w.ensure(slots * hc * nvb));
     const hipStream_t copy_stream = g_copy_stream;   // thread-local view: the helper thread gets it by value
     auto stage = [&, copy_stream](size_t slot, size_t first, size_t np) -> zk_status {
-        HIP_TRY(hipSetDevice(P->device));   // the current device is per host thread
-        uint8_t* da = (uint8_t*)P->stage_a.p + slot * hc * rb;
-        uint8_t* db = (uint8_t*)P->stage_b.p + slot * hc * rb;
-        uint8_t* dc = (uint8_t*)P->stage_c.p + slot * hc * rb;
-        uint8_t* dw = (uint8_t*)P->stage_w.p + slot * hc * nvb;
+        HIP_TRY(hipSetDevice(P->key.device));   // the current device is per host thread
+        uint8_t* da = (uint8_t*)P->work.stage_a.p + slot * hc * rb;
+        uint8_t* db = (uint8_t*)P->work.stage_b.p + slot * hc * rb;
+        uint8_t* dc = (uint8_t*)P->work.stage_c.p + slot * hc * rb;
+        uint8_t* dw = (uint8_t*)P->work.stage_w.p + slot * hc * nvb;
         for (size_t i = 0; i < np; i++) {
             const zk_assignment& x = asgs[first + i];
             HIP_TRY(hipMemcpyAsync(da + i * rb, x.a, rb, hipMemcpyHostToDevice, copy_stream));
@@ -1216,10 +427,10 @@ zk_status prove_batch_host(zk_params* P, size_t n, const zk_assignment* asgs, co
         bt.n_inputs = z.n_inputs;
         bt.n_aux = z.n_aux;
         bt.flags = z.flags;
-        bt.d_a = (uint8_t*)P->stage_a.p + cur * hc * rb;
-        bt.d_b = (uint8_t*)P->stage_b.p + cur * hc * rb;
-        bt.d_c = (uint8_t*)P->stage_c.p + cur * hc * rb;
-        bt.d_wit = (uint8_t*)P->stage_w.p + cur * hc * nvb;
+        bt.d_a = (uint8_t*)P->work.stage_a.p + cur * hc * rb;
+        bt.d_b = (uint8_t*)P->work.stage_b.p + cur * hc * rb;
+        bt.d_c = (uint8_t*)P->work.stage_c.p + cur * hc * rb;
+        bt.d_wit = (uint8_t*)P->work.stage_w.p + cur * hc * nvb;
         bt.a_aux_density = z.a_aux_density;
         bt.b_input_density = z.b_input_density;
         bt.b_aux_density = z.b_aux_density;
@@ -1245,16 +456,16 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
         zk_r1cs* p;
         ~Guard() { delete p; }
     } guard{R};
-    R->device = device;
+    R->sys.device = device;
     static std::atomic<uint64_t> next_id{1};
-    R->id = next_id++;
-    R->n_in = n_in;
-    R->n_aux = n_aux;
-    R->n_con = n_con;
+    R->sys.id = next_id++;
+    R->sys.n_in = n_in;
+    R->sys.n_aux = n_aux;
+    R->sys.n_con = n_con;
     const uint32_t nv = n_in + n_aux;
-    R->a_aux_density.assign(n_aux, 0);
-    R->b_input_density.assign(n_in, 0);
-    R->b_aux_density.assign(n_aux, 0);
+    R->sys.a_aux_density.assign(n_aux, 0);
+    R->sys.b_input_density.assign(n_in, 0);
+    R->sys.b_aux_density.assign(n_aux, 0);
     for (int m = 0; m < 3; m++) {
         const zk_csr* M = mats[m];
         if (!M || !M->row_ptr || (n_con && M->row_ptr[n_con] && (!M->col || !M->coeff)))
@@ -1270,31 +481,31 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
             load_scalar_le(M->coeff + (size_t)k * 32, c);
             if (!scalar_lt_r(c)) return fail(ZK_ERR_INVALID_ARGUMENT, "coefficient is not < r");
             // bellman's density trackers: a variable counts as soon as it APPEARS in a row of A / B
-            if (m == 0 && v >= n_in) R->a_aux_density[v - n_in] = 1;
+            if (m == 0 && v >= n_in) R->sys.a_aux_density[v - n_in] = 1;
             if (m == 1) {
                 if (v >= n_in)
-                    R->b_aux_density[v - n_in] = 1;
+                    R->sys.b_aux_density[v - n_in] = 1;
                 else
-                    R->b_input_density[v] = 1;
+                    R->sys.b_input_density[v] = 1;
             }
         }
-        R->h_row_ptr[m].assign(M->row_ptr, M->row_ptr + n_con + 1);
-        R->h_col[m].assign(M->col, M->col + nnz);
-        R->h_coeff[m].resize(nnz);
+        R->sys.h_row_ptr[m].assign(M->row_ptr, M->row_ptr + n_con + 1);
+        R->sys.h_col[m].assign(M->col, M->col + nnz);
+        R->sys.h_coeff[m].resize(nnz);
         for (uint32_t k = 0; k < nnz; k++) {
             zkhost::Fr c;
             load_scalar_le(M->coeff + (size_t)k * 32, c.l);
-            R->h_coeff[m][k] = c.to_mont();
+            R->sys.h_coeff[m][k] = c.to_mont();
         }
-        ZK_TRY(R->row_ptr[m].ensure(((size_t)n_con + 1) * 4));
-        ZK_TRY(R->col[m].ensure((size_t)(nnz ? nnz : 1) * 4));
-        ZK_TRY(R->coeff[m].ensure((size_t)(nnz ? nnz : 1) * 32));
-        HIP_TRY(hipMemcpy(R->row_ptr[m].p, M->row_ptr, ((size_t)n_con + 1) * 4, hipMemcpyHostToDevice));
+        ZK_TRY(R->sys.row_ptr[m].ensure(((size_t)n_con + 1) * 4));
+        ZK_TRY(R->sys.col[m].ensure((size_t)(nnz ? nnz : 1) * 4));
+        ZK_TRY(R->sys.coeff[m].ensure((size_t)(nnz ? nnz : 1) * 32));
+        HIP_TRY(hipMemcpy(R->sys.row_ptr[m].p, M->row_ptr, ((size_t)n_con + 1) * 4, hipMemcpyHostToDevice));
         if (nnz) {
-            HIP_TRY(hipMemcpy(R->col[m].p, M->col, (size_t)nnz * 4, hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(R->coeff[m].p, M->coeff, (size_t)nnz * 32, hipMemcpyHostToDevice));
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((nnz + 255) / 256), dim3(256), 0, g_stream, R->coeff[m].as<uint32_t>(),
-                      (const uint32_t*)R->coeff[m].as<uint32_t>(), 0u, (size_t)nnz);
+            HIP_TRY(hipMemcpy(R->sys.col[m].p, M->col, (size_t)nnz * 4, hipMemcpyHostToDevice));
+            HIP_TRY(hipMemcpy(R->sys.coeff[m].p, M->coeff, (size_t)nnz * 32, hipMemcpyHostToDevice));
+            ZK_LAUNCH(zkdev::k_fr_convert, dim3((nnz + 255) / 256), dim3(256), 0, g_stream, R->sys.coeff[m].as<uint32_t>(),
+                      (const uint32_t*)R->sys.coeff[m].as<uint32_t>(), 0u, (size_t)nnz);
         }
     }
     HIP_TRY(hipGetLastError());
@@ -1304,428 +515,38 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
     return ZK_OK;
 }
 
-// ------------------------------------------------------------------------------------------
-// Derived bases of a (key, circuit) pair: four transforms per proof instead of six, H scalars on the live rows only
-// ------------------------------------------------------------------------------------------
-// With p = a b - c = q Z + R (Z = x^m - 1, deg R < m), bellman's h is q + R / (g^m - 1): q is the quotient and R = sum_k e_k L_k
-// interpolates the residuals e_k = a_k b_k - c_k of the rows, for ANY a, b, c; bellman drops h_(m-1).  On the DOMAIN
-//     q(w^j) = (a b - W)'(w^j) w^j / m,        W = the interpolant of the row products w_k = c_k + e_k
-// (differentiate p - R = q Z at a root of Z).  Its a b part is s_j / m with s_j = da_j b_j + a_j db_j, da_j = w^j a'(w^j) =
-// sum_t t a_t w^(jt): one plain forward transform of the coefficients times their index.  Its W part is LINEAR in w, and so
-// is R: both transpose onto the bases once.  With H'_t = H_t, H'_(m-1) := the identity (the truncation),
-//     Lambda_k = (1/m) sum_t w^-kt H'_t,      M_k = -(1/m^2) sum_t t w^-kt H'_t
-// - two inverse transforms "in the exponent" - and c_k = sum_i C_ki z_i the library's own row evaluations (k_r1cs_eval),
-//     sum_t h_t H_t = sum_j s_j (Lambda_j / m) + sum_i z_i (sum_k C_ki M_k) + sum_k e_k (M_k + Lambda_k / (g^m - 1)).
-// A padding row j >= n_rows = n_con + n_in has a_j = b_j = c_j = 0 for every assignment, so s_j = e_j = 0: the job has
-// n_rows H scalars of full width (of m), n_rows residuals that are zero - no digits, no pairs - unless a constraint fails,
-// and the variables' terms it had anyway:
-//     C' = sum_j s_j Lambda_j / m + sum_k e_k E_k + sum_aux z_i (L_i + D_i) + sum_inputs z_i D_i + r (beta_1 + sum B1).
-// Exact for every assignment, satisfying or not; nothing assumes that Z divides a b - c.
-//
-// Built on the GPU, one row of lanes per point (coop_tail.h basis_*): a scaling pass and log2 m butterfly stages per
-// transform, every butterfly one 255-bit scalar product; D_i as one scalar product per entry of C summed per column, E_k
-// as one per live row.  The set goes through into_affine and its own table of doublings, under the recoding width of its
-// own term count; a base that comes out as the identity - D_i of an input that C never mentions - is mapped out like an
-// identity in a key file.  Nothing happens when the pair cannot have one (a lane's clone, another circuit's shape): the
-// caller then keeps the six-transform form.
-// The value pairs of a (key, circuit) pair (value_pairs.h): for every link (p, j) of the circuit's chains and every query in
-// which both variables have a term - dense there, the base not the identity - one more base P_j + P_p.  A member of a group
-// of equal bases takes part with its own point, which is the group's: k_build_scalars leaves it out of the group's sum when
-// its term goes into a pair.  set = the derived set [Lambda | E | D] in host form (the L terms of the job are its D block).  The
-// sums are made on the host cores from the key's encodings; a sum that comes out as the identity has no base (both keep
-// their terms).  Fills P->prs but for where the bases lie; a circuit without built-in probes has no pairs.
-// the natively emitted constraint systems of the two built-in circuits (transfer_r1cs.h), each built once per process
-const zkr1cs::System& builtin_system(zkpairs::Circuit c) {
-    if (c == zkpairs::TRANSFER) {
-        static const zkr1cs::System sys = zkr1cs::transfer_system();
-        return sys;
-    }
-    static const zkr1cs::System sys = zkr1cs::anonymous_system();
-    return sys;
-}
-struct PairBases {
-    std::vector<HG1A> l, b1, a;
-    std::vector<HG2A> b2;
-    std::vector<HG1A> xl, xb1, xa;   // the longer runs' (value_pairs.h RUN_MAX), behind all of the above
-    std::vector<HG2A> xb2;
-};
-template <class A>
-A sum_of_two(const A& x, const A& y) {
-    typedef decltype(x.x) F;
-    return zkhost::to_affine(zkhost::padd(zkhost::Point<F>::from_affine(x), zkhost::Point<F>::from_affine(y)));
-}
-void derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>& set, uint32_t n_rows, PairBases& out) {
-    zk_params::Pairs& X = P->prs;
-    X = zk_params::Pairs();
-    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux;
-    zkpairs::Circuit kind;
-    if (n_in == ZK_TRANSFER_N_INPUTS && n_aux == ZK_TRANSFER_N_AUX) kind = zkpairs::TRANSFER;
-    else if (n_in == ZK_ANONYMOUS_N_INPUTS && n_aux == ZK_ANONYMOUS_N_AUX) kind = zkpairs::ANONYMOUS;
-    else return;
-    if (P->enc_a.size() != (size_t)P->n_a * 96 || P->enc_b1.size() != (size_t)P->n_b1 * 96 || P->enc_b2.size() != (size_t)P->n_b2 * 192) return;
-    std::vector<uint8_t> a_dense(nv, 1), b_dense(nv, 0);
-    for (uint32_t i = 0; i < nv; i++) {
-        if (i >= n_in) a_dense[i] = R->a_aux_density[i - n_in];
-        b_dense[i] = i < n_in ? R->b_input_density[i] : R->b_aux_density[i - n_in];
-    }
-    {
-        // The probes are witnesses of the BUILT-IN circuit: another circuit with its counts would get chains that merge nothing
-        // and pay for their bases and tables.  The caller's matrices must have the built-in system's constraint count and
-        // densities (which variables occur in A and in B) - what the chains are made from.
-        const zkr1cs::System& sys = builtin_system(kind);
-        if (sys.n_inputs != n_in || sys.n_aux != n_aux || sys.n_constraints != R->n_con) return;
-        std::vector<uint8_t> sa(nv, 0), sb(nv, 0);
-        for (uint32_t i = 0; i < n_in; i++) sa[i] = 1;
-        for (uint32_t v : sys.m[0].col) sa[v] = 1;
-        for (uint32_t v : sys.m[1].col) sb[v] = 1;
-        if (sa != a_dense || sb != b_dense) return;
-    }
-    const std::vector<std::vector<Fr>>& probes = zkpairs::circuit_probes(kind);
-    if (probes.empty() || probes[0].size() != nv || set.size() != 2 * (size_t)n_rows + nv) return;
-    // [pred A | succ A | pred B | succ B | pred L | succ L]
-    const std::vector<int32_t> chains = zkpairs::chains_of(probes, n_in, a_dense, b_dense);
-    const int32_t *pred_a = chains.data(), *pred_b = pred_a + 2 * (size_t)nv, *pred_l = pred_a + 4 * (size_t)nv;
-    // variable -> position in the A query / the B queries / the set, -1 where it has no term
-    std::vector<int32_t> pa(nv, -1), pb1(nv, -1), pb2(nv, -1), pl(nv, -1);
-    uint32_t at = 0;
-    for (uint32_t i = 0; i < nv; i++)
-        if (i < n_in || R->a_aux_density[i - n_in]) pa[i] = (int32_t)at++;
-    if (at != P->n_a) return;
-    at = 0;
-    for (uint32_t i = 0; i < nv; i++)
-        if (i < n_in ? R->b_input_density[i] : R->b_aux_density[i - n_in]) pb1[i] = pb2[i] = (int32_t)at++;
-    if (at != P->n_b1 || at != P->n_b2) return;
-    for (uint32_t i = n_in; i < nv; i++)
-        if (!set[2 * (size_t)n_rows + i].is_inf()) pl[i] = (int32_t)(2 * n_rows + i);
-    struct Cand {
-        uint32_t j;
-        int32_t p, q;   // positions of the two bases
-    };
-    std::vector<Cand> ca, cb1, cb2, cl;
-    for (uint32_t j = 0; j < nv; j++) {
-        int32_t p = pred_a[j];
-        if (p >= 0 && pa[j] >= 0 && pa[p] >= 0) ca.push_back({j, pa[p], pa[j]});
-        p = pred_b[j];
-        if (p >= 0 && pb1[j] >= 0 && pb1[p] >= 0) cb1.push_back({j, pb1[p], pb1[j]});
-        if (p >= 0 && pb2[j] >= 0 && pb2[p] >= 0) cb2.push_back({j, pb2[p], pb2[j]});
-        p = pred_l[j];
-        if (p >= 0 && pl[j] >= 0 && pl[p] >= 0) cl.push_back({j, pl[p], pl[j]});
-    }
-    std::vector<HG1A> sa(ca.size()), sb1(cb1.size()), sl(cl.size());
-    std::vector<HG2A> sb2(cb2.size());
-    auto g1_at = [](const std::vector<uint8_t>& enc, int32_t pos) {
-        HG1A pt = HG1A::inf();
-        if (zkhost::g1_from_uncompressed(enc.data() + (size_t)pos * 96, &pt) != zkhost::DEC_OK) pt = HG1A::inf();
-        return pt;
-    };
-    auto g2_at = [](const std::vector<uint8_t>& enc, int32_t pos) {
-        HG2A pt = HG2A::inf();
-        if (zkhost::g2_from_uncompressed(enc.data() + (size_t)pos * 192, &pt) != zkhost::DEC_OK) pt = HG2A::inf();
-        return pt;
-    };
-    const size_t total = ca.size() + cb1.size() + cb2.size() + cl.size();
-    const unsigned nthreads = host_threads(total / 64 + 1, 32);
-    auto part = [&](unsigned t) {
-        auto range = [&](size_t n, auto&& fn) {
-            for (size_t k = n * t / nthreads; k < n * (t + 1) / nthreads; k++) fn(k);
-        };
-        range(ca.size(), [&](size_t k) { sa[k] = sum_of_two(g1_at(P->enc_a, ca[k].p), g1_at(P->enc_a, ca[k].q)); });
-        range(cb1.size(), [&](size_t k) { sb1[k] = sum_of_two(g1_at(P->enc_b1, cb1[k].p), g1_at(P->enc_b1, cb1[k].q)); });
-        range(cb2.size(), [&](size_t k) { sb2[k] = sum_of_two(g2_at(P->enc_b2, cb2[k].p), g2_at(P->enc_b2, cb2[k].q)); });
-        range(cl.size(), [&](size_t k) { sl[k] = sum_of_two(set[cl[k].p], set[cl[k].q]); });
-    };
-    run_threads(nthreads, part);
-    // links = [the chains | qa | qb2 | ql | qb1]
-    X.links.assign(11 * (size_t)nv, -1);
-    std::copy(chains.begin(), chains.end(), X.links.begin());
-    std::fill(X.links.begin() + 10 * (size_t)nv, X.links.end(), 0);   // (the bits of the longer bases, below)
-    auto keep = [&](const std::vector<Cand>& c, const auto& sums, auto& bases, int32_t* q) {
-        for (size_t k = 0; k < c.size(); k++)
-            if (!sums[k].is_inf()) {
-                q[c[k].j] = (int32_t)bases.size();
-                bases.push_back(sums[k]);
-            }
-        return (uint32_t)bases.size();
-    };
-    int32_t* q = &X.links[6 * (size_t)nv];
-    X.n.a = keep(ca, sa, out.a, q);
-    X.n.b2 = keep(cb2, sb2, out.b2, q + nv);
-    X.n.l = keep(cl, sl, out.l, q + 2 * (size_t)nv);
-    X.n.b1 = keep(cb1, sb1, out.b1, q + 3 * (size_t)nv);
-    // The longer runs: for every link j that has its pair base and l = 3 ... RUN_MAX, the sum of the l chain members that end at
-    // j, as long as the links behind it have their pair bases.  The thread of j walks back from j, adding one member per length
-    // (so P_j + P_pred is added again, per link) and normalises every length it keeps (an inversion each): 49 ms of binding for
-    // the transfer key at 4.  A sum that comes out as the identity has no base and no bit: k_build_scalars then splits the run
-    // into shorter terms.
-    int32_t* const avail = &X.links[10 * (size_t)nv];
-    auto longer = [&](uint32_t query, uint32_t n_pairs, const int32_t* pred, const int32_t* qq, const std::vector<int32_t>& pos, auto&& point,
-                      auto& bases) {
-        typedef typename std::decay_t<decltype(bases)>::value_type A;
-        typedef decltype(A().x) F;
-        constexpr uint32_t W = zkpairs::RUN_MAX - 2;
-        X.alt[query].assign((size_t)n_pairs * W, -1);
-        if (!W) return;
-        std::vector<uint32_t> js;
-        for (uint32_t j = 0; j < nv; j++)
-            if (qq[j] >= 0 && qq[pred[j]] >= 0) js.push_back(j);
-        std::vector<A> sums(js.size() * W, A::inf());
-        const unsigned nt = host_threads(js.size() / 64 + 1, 32);
-        auto work = [&](unsigned t) {
-            for (size_t k = js.size() * t / nt; k < js.size() * (t + 1) / nt; k++) {
-                const uint32_t j = js[k];
-                int32_t cur = pred[j];
-                auto acc = zkhost::padd(zkhost::Point<F>::from_affine(point(pos[j])), zkhost::Point<F>::from_affine(point(pos[cur])));
-                for (uint32_t l = 3; l <= zkpairs::RUN_MAX && qq[cur] >= 0; l++) {
-                    cur = pred[cur];
-                    acc = zkhost::padd(acc, zkhost::Point<F>::from_affine(point(pos[cur])));
-                    sums[k * W + (l - 3)] = zkhost::to_affine(acc);
-                }
-            }
-        };
-        run_threads(nt, work);
-        for (size_t k = 0; k < js.size(); k++)
-            for (uint32_t l = 3; l <= zkpairs::RUN_MAX; l++)
-                if (!sums[k * W + (l - 3)].is_inf()) {
-                    X.alt[query][(size_t)qq[js[k]] * W + (l - 3)] = (int32_t)bases.size();
-                    bases.push_back(sums[k * W + (l - 3)]);
-                    avail[js[k]] |= (int32_t)(1u << (8 * query + (l - 1)));
-                    X.xn[query][l - 3]++;
-                }
-    };
-    longer(0, X.n.a, pred_a, q, pa, [&](int32_t at) { return g1_at(P->enc_a, at); }, out.xa);
-    longer(1, X.n.b2, pred_b, q + nv, pb2, [&](int32_t at) { return g2_at(P->enc_b2, at); }, out.xb2);
-    longer(2, X.n.l, pred_l, q + 2 * (size_t)nv, pl, [&](int32_t at) { return set[at]; }, out.xl);
-    longer(3, X.n.b1, pred_b, q + 3 * (size_t)nv, pb1, [&](int32_t at) { return g1_at(P->enc_b1, at); }, out.xb1);
-    // what a proof is expected to merge, from the probes
-    uint64_t merged[4] = {0, 0, 0, 0};
-    for (const std::vector<Fr>& z : probes) {
-        merged[0] += zkpairs::count_merges(pred_a, pred_a + nv, q, avail, 0, z);
-        merged[1] += zkpairs::count_merges(pred_b, pred_b + nv, q + nv, avail, 1, z);
-        merged[2] += zkpairs::count_merges(pred_l, pred_l + nv, q + 2 * (size_t)nv, avail, 2, z);
-        merged[3] += zkpairs::count_merges(pred_b, pred_b + nv, q + 3 * (size_t)nv, avail, 3, z);
-    }
-    const uint64_t np = probes.size();
-    X.exp_a = (uint32_t)(merged[0] / np);
-    X.exp_b2 = (uint32_t)(merged[1] / np);
-    X.exp_l = (uint32_t)(merged[2] / np);
-    X.exp_b1 = (uint32_t)(merged[3] / np);
-    X.ready = X.n.any();
-}
-
-zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
-    if (P->drv.ready && P->drv.circuit == R->id) return ZK_OK;
-    const uint32_t n_in = R->n_in, n_aux = R->n_aux, nv = n_in + n_aux, n_con = R->n_con, n_rows = n_con + n_in, k = P->log_m;
-    const size_t m = P->m;
-    if (!P->g1.table.owned || R->h_row_ptr[2].size() != (size_t)n_con + 1 || n_in != P->n_ic || n_aux != P->n_l ||
-        (size_t)n_con + n_in > m || P->n_h + 1 != m)
-        return ZK_OK;
-    ZK_TRY(use_device(P->device));
-    const auto t0 = std::chrono::steady_clock::now();
-    typedef zkdev::XYZZ<zkdev::Fq> DP;
-    typedef zkdev::Affine<zkdev::Fq> DA;
-    P->drv.ready = false;
-    const DA* key = P->g1.table.as<DA>();
-    // C by columns, the coefficients in plain words
-    const std::vector<uint32_t>& rp = R->h_row_ptr[2];
-    const std::vector<uint32_t>& cl = R->h_col[2];
-    const uint32_t nnz = rp[n_con];
-    std::vector<uint32_t> ptr(nv + 1, 0), t_row(nnz ? nnz : 1), each(n_rows + 1);
-    std::vector<Fr> t_s(nnz ? nnz : 1);
-    for (uint32_t e = 0; e < nnz; e++) ptr[cl[e] + 1]++;
-    for (uint32_t i = 0; i < nv; i++) ptr[i + 1] += ptr[i];
-    {
-        std::vector<uint32_t> at(ptr.begin(), ptr.end() - 1);
-        for (uint32_t row = 0; row < n_con; row++)
-            for (uint32_t e = rp[row]; e < rp[row + 1]; e++) {
-                const uint32_t slot = at[cl[e]]++;
-                t_row[slot] = row;
-                t_s[slot] = R->h_coeff[2][e].from_mont();
-            }
-    }
-    for (uint32_t i = 0; i <= n_rows; i++) each[i] = i;   // (segments of one term: E_k = M_k + one point)
-    // H in bit-reversed order with the identity in the place of H_(m-1); the L query behind the (empty) inputs
-    std::vector<int32_t> idx(m + nv);
-    for (size_t pos = 0; pos < m; pos++) {
-        const uint32_t e = k ? (__builtin_bitreverse32((uint32_t)pos) >> (32 - k)) : 0;
-        idx[pos] = e < P->n_h ? (int32_t)(P->off_h + e) : -1;
-    }
-    for (uint32_t i = 0; i < nv; i++) idx[m + i] = i < n_in ? -1 : (int32_t)(P->off_l + (i - n_in));
-    const size_t rows = std::max<size_t>(m, nnz), n_set = 2 * (size_t)n_rows + nv;
-    DevBuf d_idx, d_ptr, d_each, d_row, d_s, d_tw, d_w, d_sl, d_sm, d_se, src, ping, pong, lam, mk, terms, tbl, all, stage;
-    for (DevBuf* b : {&d_idx, &d_ptr, &d_each, &d_row, &d_s, &d_tw, &d_w, &d_sl, &d_sm, &d_se, &src, &ping, &pong, &lam, &mk, &terms, &tbl, &all, &stage})
-        b->is_public = true;
-    ZK_TRY(d_idx.ensure(idx.size() * 4));
-    ZK_TRY(d_ptr.ensure(ptr.size() * 4));
-    ZK_TRY(d_each.ensure(each.size() * 4));
-    ZK_TRY(d_row.ensure(t_row.size() * 4));
-    ZK_TRY(d_s.ensure(t_s.size() * 32));
-    ZK_TRY(d_tw.ensure(m * 32));
-    ZK_TRY(d_w.ensure(5 * 32));
-    ZK_TRY(d_sl.ensure(m * 32));
-    ZK_TRY(d_sm.ensure(m * 32));
-    ZK_TRY(d_se.ensure((size_t)n_rows * 32));
-    ZK_TRY(src.ensure((m + nv) * sizeof(DP)));
-    ZK_TRY(ping.ensure(m * sizeof(DP)));
-    ZK_TRY(pong.ensure(m * sizeof(DP)));
-    ZK_TRY(lam.ensure(m * sizeof(DP)));
-    ZK_TRY(mk.ensure(m * sizeof(DP)));
-    ZK_TRY(terms.ensure(std::max<size_t>(nnz ? nnz : 1, n_rows) * sizeof(DP)));
-    ZK_TRY(tbl.ensure(15 * rows * sizeof(DP)));
-    ZK_TRY(all.ensure(n_set * sizeof(DP)));
-    HIP_TRY(hipMemcpy(d_idx.p, idx.data(), idx.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_ptr.p, ptr.data(), ptr.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_each.p, each.data(), each.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_row.p, t_row.data(), t_row.size() * 4, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d_s.p, t_s.data(), t_s.size() * 32, hipMemcpyHostToDevice));
-    const Fr ninv2 = P->ntt.n_inv * P->ntt.n_inv;
-    const Fr wv[5] = {P->ntt.w_inv, Fr::one(), ninv2, -ninv2, fr_from_u64((uint64_t)m) * P->ntt.z_inv};
-    HIP_TRY(hipMemcpy(d_w.p, wv, sizeof(wv), hipMemcpyHostToDevice));
-    const uint32_t* cw = d_w.as<uint32_t>();
-    auto table = [&](DevBuf& out, const uint32_t* base, const uint32_t* scale, uint32_t mode, size_t count) {
-        ZK_LAUNCH(zkdev::k_fr_pow_table, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, g_stream, out.as<uint32_t>(), base, scale,
-                  k, mode, 1u, (uint32_t)count);
-    };
-    // plain words: w^-e for e < m / 2; 1 / m^2 and - t / m^2 at the bit-reversed position of t; m / (g^m - 1) per live row
-    if (m > 1) table(d_tw, cw, cw + 8, 0, m / 2);
-    table(d_sl, cw + 8, cw + 16, 2, m);
-    table(d_sm, cw + 8, cw + 24, 3, m);
-    table(d_se, cw + 8, cw + 32, 2, n_rows);
-    zkcoop::basis_gather(key, d_idx.as<int32_t>(), src.as<DP>(), (uint32_t)(m + nv), g_stream);
-    // in: the scaled points in bit-reversed order; out: the transform in natural order
-    auto transform = [&](const uint32_t* scale, DP* out) -> zk_status {
-        DP *a = ping.as<DP>(), *b = pong.as<DP>();
-        zkcoop::basis_scale(src.as<DP>(), nullptr, scale, tbl.as<DP>(), k ? a : out, (uint32_t)m, g_stream);
-        for (uint32_t st = 0; st < k; st++) {
-            zkcoop::basis_dft_stage(a, st + 1 == k ? out : b, d_tw.as<uint32_t>(), tbl.as<DP>(), k, st, g_stream);
-            std::swap(a, b);
-        }
-        HIP_TRY(hipGetLastError());
-        return ZK_OK;
-    };
-    ZK_TRY(transform(d_sl.as<uint32_t>(), lam.as<DP>()));   // Lambda_j / m: the 1 / m of s_j rides in the base
-    ZK_TRY(transform(d_sm.as<uint32_t>(), mk.as<DP>()));    // M_k
-    DP* set = all.as<DP>();
-    HIP_TRY(hipMemcpyAsync(set, lam.p, (size_t)n_rows * sizeof(DP), hipMemcpyDeviceToDevice, g_stream));
-    // E_k = M_k + (m / (g^m - 1)) (Lambda_k / m)
-    zkcoop::basis_scale(lam.as<DP>(), nullptr, d_se.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), n_rows, g_stream);
-    zkcoop::basis_segment_sums(mk.as<DP>(), terms.as<DP>(), d_each.as<uint32_t>(), set + n_rows, n_rows, g_stream);
-    // D_i = sum_k C_ki M_k, behind L_i for an aux variable
-    if (nnz) zkcoop::basis_scale(mk.as<DP>(), d_row.as<uint32_t>(), d_s.as<uint32_t>(), tbl.as<DP>(), terms.as<DP>(), nnz, g_stream);
-    zkcoop::basis_segment_sums(src.as<DP>() + m, terms.as<DP>(), d_ptr.as<uint32_t>(), set + 2 * (size_t)n_rows, nv, g_stream);
-    HIP_TRY(hipGetLastError());
-    std::vector<HG1> host(n_set);
-    ZK_TRY(P->g1.normalize_to_host(set, n_set, host.data(), stage, g_stream));
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    std::vector<HG1A> pts(n_set);
-    P->drv.pos.assign(n_set, -1);
-    size_t live = 0;
-    for (size_t i = 0; i < n_set; i++) {
-        pts[i] = host[i].is_inf() ? HG1A::inf() : HG1A{host[i].x, host[i].y};
-        if (!host[i].is_inf()) {
-            P->drv.pos[i] = (int32_t)i;
-            if (i < n_rows || i >= 2 * (size_t)n_rows) live++;
-        }
-    }
-    // (the width of the set's own terms: the residuals are zero scalars unless a constraint fails)
-    // value pairs: [pairs of the L terms | of the B1 query | of the A query] behind the set, the B2 query's in a table of its own.
-    // A set expects fewer terms per proof with them (the mean over the probes), and its width follows that.
-    PairBases pb;
-    derived_pairs(P, R, pts, n_rows, pb);
-    zk_params::Pairs& X = P->prs;
-    X.base_l = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.l.begin(), pb.l.end());
-    X.base_b1 = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.b1.begin(), pb.b1.end());
-    X.base_a = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.a.begin(), pb.a.end());
-    X.base_b2 = P->n_b2 + 2;
-    // (the longer runs' bases behind every pair section: the pair sections stay where a set without them has them)
-    X.xbase[2] = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.xl.begin(), pb.xl.end());
-    X.xbase[3] = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.xb1.begin(), pb.xb1.end());
-    X.xbase[0] = (uint32_t)pts.size();
-    pts.insert(pts.end(), pb.xa.begin(), pb.xa.end());
-    X.xbase[1] = X.base_b2 + X.n.b2;
-#ifdef ZK_TEST_HOOKS
-    X.hook_g1.assign(pts.begin() + X.xbase[2], pts.end());
-    X.hook_d.assign(pts.begin() + 2 * (size_t)n_rows, pts.begin() + 2 * (size_t)n_rows + nv);
-#endif
-    const bool values = merge_values_on();   // (the widths of a run with the switch off stay those of a set without pairs)
-    const uint32_t c_set = pick_window(live + P->n_b1 - (values ? std::min<size_t>(X.exp_l + X.exp_b1, live) : 0), 1);
-    ZK_TRY(P->g1d.build_with_tail(pts, P->g1, P->off_a, P->g1.n_points - P->off_a, c_set));
-    P->g1d_lone.alias(P->g1d, P->g1_lone.c);
-    if (X.ready) {
-        P->g1da.alias(P->g1d, values ? pick_window(P->n_a - std::min(X.exp_a, P->n_a), 3) : P->g1a.c);
-        std::vector<HG2A> pts2(P->n_b2 + 2, HG2A::inf());
-        bool ok = P->vk_bytes.size() >= 864;
-        for (uint32_t i = 0; ok && i < P->n_b2; i++) ok = zkhost::g2_from_uncompressed(P->enc_b2.data() + (size_t)i * 192, &pts2[i]) == zkhost::DEC_OK;
-        ok = ok && zkhost::g2_from_uncompressed(P->vk_bytes.data() + 192, &pts2[P->n_b2]) == zkhost::DEC_OK &&
-             zkhost::g2_from_uncompressed(P->vk_bytes.data() + 672, &pts2[P->n_b2 + 1]) == zkhost::DEC_OK;
-        if (!ok) return fail(ZK_ERR_IO, "internal: the b_g2 query does not decode a second time");
-        pts2.insert(pts2.end(), pb.b2.begin(), pb.b2.end());
-        pts2.insert(pts2.end(), pb.xb2.begin(), pb.xb2.end());
-#ifdef ZK_TEST_HOOKS
-        X.hook_g2.assign(pts2.begin() + X.xbase[1], pts2.end());
-#endif
-        const uint32_t c2 = values ? pick_window(P->n_b2 - std::min(X.exp_b2, P->n_b2), 2) : P->g2.c;
-        ZK_TRY(P->g2p.build(pts2, c2, false, "pair bases (G2)"));
-        P->g2p_lone.alias(P->g2p, getenv("ZKAMD_WINDOW_BITS_G2") || c2 <= 10 ? c2 : 10u);
-    }
-    P->drv.n_rows = n_rows;
-    P->drv.off_a = (uint32_t)pts.size();
-    P->drv.off_b1 = P->drv.off_a + P->n_a + 2;
-    P->drv.circuit = R->id;
-    static std::atomic<uint32_t> serial{1};
-    P->drv.serial = serial++;
-    P->drv.bind_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    P->drv.ready = true;
-    if (getenv("ZKAMD_TRACE_HOST"))
-        fprintf(stderr, "[zkamd] derived bases: 2 x %u + %u points, %u entries of C, width %u, %.1f ms, table %.2f GB\n", n_rows, nv, nnz,
-                c_set, P->drv.bind_ms, (double)P->g1d.bytes / 1e9);
-    if (getenv("ZKAMD_TRACE_HOST") && X.ready)
-        fprintf(stderr, "[zkamd] value pairs: bases a %u, b_g2 %u, l %u, b_g1 %u; merges expected per proof %u, %u, %u, %u; widths "
-                        "C' %u, A %u, G2 %u; G2 table %.2f GB\n", X.n.a, X.n.b2, X.n.l, X.n.b1, X.exp_a, X.exp_b2, X.exp_l, X.exp_b1,
-                c_set, P->g1da.c, P->g2p.c, (double)P->g2p.bytes / 1e9);
-    if (getenv("ZKAMD_TRACE_HOST") && X.ready)
-        for (uint32_t l = 3; l <= zkpairs::RUN_MAX; l++)
-            fprintf(stderr, "[zkamd] value runs: bases of %u members: a %u, b_g2 %u, l %u, b_g1 %u\n", l, X.xn[0][l - 3], X.xn[1][l - 3],
-                    X.xn[2][l - 3], X.xn[3][l - 3]);
-    return ZK_OK;
-}
-
-// row evaluations + create_proof of the np assignments in R->z[slot] (Montgomery form)
+// row evaluations + create_proof of the np assignments in R->work.z[slot] (Montgomery form)
 // derived: the caller is one of the statement-to-proof entries, which take the four-transform form over the derived bases
 // of the pair (built here the first time); zk_prove_batch_witness keeps the key's own bases
 zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
-    const uint32_t nv = R->n_in + R->n_aux, n_rows = R->n_con + R->n_in;
+    const uint32_t nv = R->sys.n_in + R->sys.n_aux, n_rows = R->sys.n_con + R->sys.n_in;
     if (derived) {
         ZK_TRY(ensure_derived(P, R));
-        derived = P->drv.ready && P->drv.circuit == R->id;
+        derived = P->bind.drv.ready && P->bind.drv.circuit == R->sys.id;
     }
-    ZK_TRY(R->abc.ensure(3 * np * (size_t)n_rows * 32));
+    ZK_TRY(R->work.abc.ensure(3 * np * (size_t)n_rows * 32));
     zkdev::R1csMat mm[3];
     for (int m = 0; m < 3; m++)
-        mm[m] = zkdev::R1csMat{R->row_ptr[m].as<uint32_t>(), R->col[m].as<uint32_t>(), R->coeff[m].as<uint32_t>()};
+        mm[m] = zkdev::R1csMat{R->sys.row_ptr[m].as<uint32_t>(), R->sys.col[m].as<uint32_t>(), R->sys.coeff[m].as<uint32_t>()};
     {
         ProfScope ps("r1cs_eval");
         ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, 3, (unsigned)np), dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
-                  (const uint32_t*)R->z[slot].as<uint32_t>(), R->abc.as<uint32_t>(), R->n_con, R->n_in, nv, n_rows,
+                  (const uint32_t*)R->work.z[slot].as<uint32_t>(), R->work.abc.as<uint32_t>(), R->sys.n_con, R->sys.n_in, nv, n_rows,
                   np * (size_t)n_rows);
     }
     HIP_TRY(hipGetLastError());
     zk_batch_dev bt;
     bt.n_rows = n_rows;
-    bt.n_inputs = R->n_in;
-    bt.n_aux = R->n_aux;
+    bt.n_inputs = R->sys.n_in;
+    bt.n_aux = R->sys.n_aux;
     bt.flags = ZK_FR_MONTGOMERY;
-    bt.d_a = R->abc.as<uint32_t>();
-    bt.d_b = R->abc.as<uint32_t>() + np * (size_t)n_rows * 8;
-    bt.d_c = R->abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
-    bt.d_wit = R->z[slot].p;
-    bt.a_aux_density = R->a_aux_density.data();
-    bt.b_input_density = R->b_input_density.data();
-    bt.b_aux_density = R->b_aux_density.data();
+    bt.d_a = R->work.abc.as<uint32_t>();
+    bt.d_b = R->work.abc.as<uint32_t>() + np * (size_t)n_rows * 8;
+    bt.d_c = R->work.abc.as<uint32_t>() + 2 * np * (size_t)n_rows * 8;
+    bt.d_wit = R->work.z[slot].p;
+    bt.a_aux_density = R->sys.a_aux_density.data();
+    bt.b_input_density = R->sys.b_input_density.data();
+    bt.b_aux_density = R->sys.b_aux_density.data();
     return prove_batch_dev(P, np, &bt, rs, proofs_out, derived);
 }
 
@@ -1733,24 +554,24 @@ zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t*
                               uint8_t* proofs_out, bool derived) {
     if (!P || !R || !witness || !rs || !proofs_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
-    if (R->device != P->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
-    ZK_TRY(use_device(P->device));
-    const uint32_t nv = R->n_in + R->n_aux, n_rows = R->n_con + R->n_in;
-    if (n_rows > P->m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
+    if (R->sys.device != P->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+    ZK_TRY(use_device(P->key.device));
+    const uint32_t nv = R->sys.n_in + R->sys.n_aux, n_rows = R->sys.n_con + R->sys.n_in;
+    if (n_rows > P->key.m) return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     const size_t chunk = ProveTunables::read().batch_chunk;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
-        ZK_TRY(R->z[0].ensure(np * (size_t)nv * 32));
-        HIP_TRY(hipMemcpyAsync(R->z[0].p, witness + first * (size_t)nv * 32, np * (size_t)nv * 32, hipMemcpyHostToDevice, g_stream));
-        ZK_TRY(P->bad.ensure(8));
-        HIP_TRY(hipMemsetAsync(P->bad.as<uint32_t>() + 1, 0, 4, g_stream));
+        ZK_TRY(R->work.z[0].ensure(np * (size_t)nv * 32));
+        HIP_TRY(hipMemcpyAsync(R->work.z[0].p, witness + first * (size_t)nv * 32, np * (size_t)nv * 32, hipMemcpyHostToDevice, g_stream));
+        ZK_TRY(P->work.bad.ensure(8));
+        HIP_TRY(hipMemsetAsync(P->work.bad.as<uint32_t>() + 1, 0, 4, g_stream));
         if (!(flags & ZK_FR_MONTGOMERY)) {
             const size_t cnt = np * (size_t)nv;
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, R->z[0].as<uint32_t>(),
-                      (const uint32_t*)R->z[0].as<uint32_t>(), 0u, cnt, P->bad.as<uint32_t>() + 1);
+            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, R->work.z[0].as<uint32_t>(),
+                      (const uint32_t*)R->work.z[0].as<uint32_t>(), 0u, cnt, P->work.bad.as<uint32_t>() + 1);
         }
         ZK_TRY(prove_from_z(P, R, np, 0, rs + first * 64, proofs_out + first * 192, derived));
-        if (P->pin_bad.as<uint32_t>()[1] & zkdev::ZK_BAD_SCALAR)
+        if (P->work.pin_bad.as<uint32_t>()[1] & zkdev::ZK_BAD_SCALAR)
             return fail(ZK_ERR_INVALID_ARGUMENT, "a witness scalar is not a canonical field element (>= r)");
     }
     return ZK_OK;
@@ -2254,8 +1075,8 @@ zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const 
 }
 size_t lib_batch_chunk() { return ProveTunables::read().batch_chunk; }
 bool lib_witness_on_host(size_t n) { return witness_on_host(n); }
-int lib_params_device(const zk_params* P) { return P->device; }
-size_t lib_params_domain(const zk_params* P) { return P->m; }
+int lib_params_device(const zk_params* P) { return P->key.device; }
+size_t lib_params_domain(const zk_params* P) { return P->key.m; }
 }  // namespace zkrt
 
 // ------------------------------------------------------------------------------------------
@@ -2299,48 +1120,48 @@ zk_status zk_params_load(const uint8_t* pk_bytes, size_t len, int checked, int d
 } ZK_ABI_CATCH
 zk_status zk_params_get_info(const zk_params* p, zk_params_info* info) try {
     if (!p || !info) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    info->n_ic = p->n_ic;
-    info->n_h = p->n_h;
-    info->n_l = p->n_l;
-    info->n_a = p->n_a;
-    info->n_b_g1 = p->n_b1;
-    info->n_b_g2 = p->n_b2;
-    info->log_domain = p->log_m;
-    info->window_bits = p->g1.c;
+    info->n_ic = p->key.n_ic;
+    info->n_h = p->key.n_h;
+    info->n_l = p->key.n_l;
+    info->n_a = p->key.n_a;
+    info->n_b_g1 = p->key.n_b1;
+    info->n_b_g2 = p->key.n_b2;
+    info->log_domain = p->key.log_m;
+    info->window_bits = p->tab.g1.c;
     info->n_windows = zkdev::MSM_NPOS;
-    info->device = (uint32_t)p->device;
-    info->device_bytes = p->g1.bytes + p->g2.bytes + p->ntt.bytes;
+    info->device = (uint32_t)p->key.device;
+    info->device_bytes = p->tab.g1.bytes + p->tab.g2.bytes + p->tab.ntt.bytes;
     return ZK_OK;
 } ZK_ABI_CATCH
 zk_status zk_params_get_windows(const zk_params* p, uint32_t out[4]) try {
     if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    out[0] = p->g1.c;
-    out[1] = p->g1a.c;
-    out[2] = p->g1_lone.c;
-    out[3] = p->g2.c;
+    out[0] = p->tab.g1.c;
+    out[1] = p->tab.g1a.c;
+    out[2] = p->tab.g1_lone.c;
+    out[3] = p->tab.g2.c;
     return ZK_OK;
 } ZK_ABI_CATCH
 zk_status zk_params_get_merged(const zk_params* p, uint32_t out[3]) try {
     if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    out[0] = p->grp_a.merged();
-    out[1] = p->grp_b1.merged();
-    out[2] = p->grp_b2.merged();
+    out[0] = p->key.grp_a.merged();
+    out[1] = p->key.grp_b1.merged();
+    out[2] = p->key.grp_b2.merged();
     return ZK_OK;
 } ZK_ABI_CATCH
 zk_status zk_params_get_pairs(const zk_params* p, uint32_t out[8]) try {
     if (!p || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    const zk_params::Pairs& X = p->prs;
-    const uint32_t v[8] = {X.n.a, X.n.b1, X.n.b2, X.n.l, X.exp_a, X.exp_b1, X.exp_b2, X.exp_l};
-    for (int i = 0; i < 8; i++) out[i] = p->drv.ready && X.ready ? v[i] : 0u;
+    const zk_params::Binding::Pairs& X = p->bind.prs;
+    const uint32_t v[8] = {X.q[QA].n, X.q[QB1].n, X.q[QB2].n, X.q[QL].n, X.q[QA].expect, X.q[QB1].expect, X.q[QB2].expect, X.q[QL].expect};
+    for (int i = 0; i < 8; i++) out[i] = p->bind.drv.ready && X.ready ? v[i] : 0u;
     return ZK_OK;
 } ZK_ABI_CATCH
 void zk_params_free(zk_params* p) { delete p; }
 zk_status zk_params_write_vk(const zk_params* p, uint8_t* out, size_t cap, size_t* len) try {
     if (!p || !len) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    *len = p->vk_bytes.size();
+    *len = p->key.vk_bytes.size();
     if (out) {
-        if (cap < p->vk_bytes.size()) return fail(ZK_ERR_INVALID_ARGUMENT, "output buffer too small");
-        memcpy(out, p->vk_bytes.data(), p->vk_bytes.size());
+        if (cap < p->key.vk_bytes.size()) return fail(ZK_ERR_INVALID_ARGUMENT, "output buffer too small");
+        memcpy(out, p->key.vk_bytes.data(), p->key.vk_bytes.size());
     }
     return ZK_OK;
 } ZK_ABI_CATCH
@@ -2433,8 +1254,8 @@ zk_status zk_hook_prove_batch_witness_derived(zk_params* p, zk_r1cs* circuit, si
                                               const uint8_t* rs, uint8_t* proofs_out, uint32_t info[2]) try {
     const zk_status rc = prove_batch_witness(p, circuit, n, witness, flags, rs, proofs_out, true);
     if (info && p && circuit) {
-        info[0] = p->drv.ready && p->drv.circuit == circuit->id ? 1u : 0u;
-        info[1] = (uint32_t)std::count(p->drv.pos.begin(), p->drv.pos.end(), -1);
+        info[0] = p->bind.drv.ready && p->bind.drv.circuit == circuit->sys.id ? 1u : 0u;
+        info[1] = (uint32_t)std::count(p->bind.drv.pos.begin(), p->bind.drv.pos.end(), -1);
     }
     return rc;
 } ZK_ABI_CATCH
@@ -2444,14 +1265,14 @@ zk_status zk_hook_prove_batch_witness_derived(zk_params* p, zk_r1cs* circuit, si
 zk_status zk_hook_derived_layout(zk_params* p, zk_r1cs* circuit, uint32_t info[7]) try {
     if (!p || !circuit || !info) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     std::fill(info, info + 7, 0u);
-    const zk_params::Derived& D = p->drv;
-    if (!D.ready || D.circuit != circuit->id) return ZK_OK;
+    const zk_params::Binding::Derived& D = p->bind.drv;
+    if (!D.ready || D.circuit != circuit->sys.id) return ZK_OK;
     info[0] = 1;
     info[1] = info[2] = D.n_rows;
     info[3] = (uint32_t)D.pos.size() - 2 * D.n_rows;
     info[4] = D.off_a;
     info[5] = D.off_b1;
-    info[6] = p->g1d.c;
+    info[6] = p->bind.g1d.c;
     return ZK_OK;
 } ZK_ABI_CATCH
 // Test hook: the plan of a chunk of np proofs (prove_plan.h) under the environment of the call, no GPU involved: out[0 .. 32) =
@@ -2475,8 +1296,7 @@ zk_status zk_hook_prove_plan(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t 
 zk_status zk_hook_prove_plan_pairs(size_t np, uint32_t n_in, uint32_t n_aux, uint32_t n_rows, size_t m, uint32_t ga, uint32_t gb2,
                                    uint32_t gb1, int derived, const uint32_t counts[4], uint64_t* out, size_t out_words) try {
     if (!out || !counts || out_words < 44) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
-    PairCounts pc;
-    pc.a = counts[0]; pc.b2 = counts[1]; pc.l = counts[2]; pc.b1 = counts[3];
+    const PairCounts pc = PairCounts::of(counts);
     const ProveTunables tun = ProveTunables::read();
     const ProvePlan p = prove_plan(np, n_in, n_aux, n_rows, m, ga, gb2, gb1, derived != 0, tun, pc);
     const CJobLayout& L = p.layout;
@@ -2497,10 +1317,8 @@ zk_status zk_hook_pair_chains(int circuit, int32_t* out, size_t cap, uint32_t* n
     if (nv_out) *nv_out = nv;
     if (!out) return ZK_OK;
     if (cap < 8 * (size_t)nv) return fail(ZK_ERR_INVALID_ARGUMENT, "output too short");
-    std::vector<uint8_t> a_dense(nv, 0), b_dense(nv, 0);
-    for (uint32_t i = 0; i < sys.n_inputs; i++) a_dense[i] = 1;
-    for (uint32_t v : sys.m[0].col) a_dense[v] = 1;
-    for (uint32_t v : sys.m[1].col) b_dense[v] = 1;
+    std::vector<uint8_t> a_dense, b_dense;
+    system_densities(sys, a_dense, b_dense);
     const std::vector<int32_t> c = zkpairs::chains_of(zkpairs::circuit_probes((zkpairs::Circuit)circuit), sys.n_inputs, a_dense, b_dense);
     std::copy(c.begin(), c.end(), out);
     std::copy(a_dense.begin(), a_dense.end(), out + 6 * (size_t)nv);
@@ -2532,8 +1350,7 @@ static zk_status hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_
     if (!counts || !links || !ngroups || !groups || !wit || !r || !s || !layout || !n_in) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     ZK_TRY(use_device(0));
     const uint32_t nv = n_in + n_aux;
-    PairCounts pc;
-    pc.a = counts[0]; pc.b2 = counts[1]; pc.l = counts[2]; pc.b1 = counts[3];
+    const PairCounts pc = PairCounts::of(counts);
     for (size_t k = 0; k < 10 * (size_t)nv; k++) {
         const uint32_t bound = k < 6 * (size_t)nv ? nv : counts[k / nv - 6];
         if (links[k] < -1 || links[k] >= (int32_t)bound) return fail(ZK_ERR_INVALID_ARGUMENT, "link out of range");
@@ -2592,7 +1409,7 @@ static zk_status hook_build_scalars(uint32_t n_in, uint32_t n_aux, const uint32_
         for (uint32_t i = 0; i < nv; i++) memcpy(&z[i], wit + (size_t)i * 32, 32);   // (plain words: only compared)
         const int32_t* q = links + 6 * (size_t)nv;
         for (uint32_t k = 0; k < 4; k++) {
-            const int32_t* pred = links + 2 * (size_t)nv * (k == 0 ? 0 : k == 2 ? 2 : 1);
+            const int32_t* pred = links + 2 * (size_t)nv * zkpairs::chain_of((Query)k);
             merges[k] = zkpairs::count_merges(pred, pred + nv, q + k * (size_t)nv, avail, k, z, cap);
         }
     }
@@ -2625,16 +1442,16 @@ uint32_t zk_hook_run_max(void) { return zkpairs::RUN_MAX; }
 // uncompressed points the tables got from xbase l / xbase b_g2 on), d (nv uncompressed points: the D block of the derived set)
 zk_status zk_hook_value_runs(const zk_params* p, uint32_t info[12], int32_t* links, int32_t* alt, uint8_t* g1, uint8_t* g2, uint8_t* d) try {
     if (!p || !info) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    const zk_params::Pairs& X = p->prs;
-    if (!p->drv.ready || !X.ready) return fail(ZK_ERR_INVALID_ARGUMENT, "the key has no value pairs");
+    const zk_params::Binding::Pairs& X = p->bind.prs;
+    if (!p->bind.drv.ready || !X.ready) return fail(ZK_ERR_INVALID_ARGUMENT, "the key has no value pairs");
     const uint32_t nv = (uint32_t)(X.links.size() / 11);
-    const uint32_t f[12] = {zkpairs::RUN_MAX, nv, X.n.a, X.n.b2, X.n.l, X.n.b1, X.xbase[0], X.xbase[1], X.xbase[2], X.xbase[3],
+    const uint32_t f[12] = {zkpairs::RUN_MAX, nv, X.q[QA].n, X.q[QB2].n, X.q[QL].n, X.q[QB1].n, X.q[QA].xbase, X.q[QB2].xbase, X.q[QL].xbase, X.q[QB1].xbase,
                             (uint32_t)X.hook_g1.size(), (uint32_t)X.hook_g2.size()};
     std::copy(f, f + 12, info);
     if (!links) return ZK_OK;
     if (!alt || !g1 || !g2 || !d) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     std::copy(X.links.begin(), X.links.end(), links);
-    for (int k = 0; k < 4; k++) alt = std::copy(X.alt[k].begin(), X.alt[k].end(), alt);
+    for (const auto& Q : X.q) alt = std::copy(Q.alt.begin(), Q.alt.end(), alt);
     for (size_t i = 0; i < X.hook_g1.size(); i++) zkhost::g1_to_uncompressed(X.hook_g1[i], g1 + i * 96);
     for (size_t i = 0; i < X.hook_g2.size(); i++) zkhost::g2_to_uncompressed(X.hook_g2[i], g2 + i * 192);
     for (size_t i = 0; i < X.hook_d.size(); i++) zkhost::g1_to_uncompressed(X.hook_d[i], d + i * 96);
@@ -2687,15 +1504,15 @@ zk_status zk_anonymous_witness(const zk_anonymous_statement* st, size_t n, uint3
 zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, const zk_transfer_statement* st,
                                   const uint8_t* rs, uint8_t* proofs_out) try {
     if (!p || !circuit || !rs || !proofs_out || (!st && n)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->n_in != ZK_TRANSFER_N_INPUTS || circuit->n_aux != ZK_TRANSFER_N_AUX)
+    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->device != p->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+    if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
     if (n == 0) return ZK_OK;
     const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
     const size_t chunk = ProveTunables::read().batch_chunk;
-    zk_status rc = use_device(p->device);
+    zk_status rc = use_device(p->key.device);
     if (rc != ZK_OK) return rc;
-    if ((size_t)circuit->n_con + circuit->n_in > p->m)
+    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > p->key.m)
         return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     if (!witness_on_host(n)) {
         // witnesses on the GPU (witness_gpu.h), on the side stream of the copy engine: the kernels of chunk k + 1
@@ -2714,9 +1531,9 @@ zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, cons
     // a handful of statements, or ZKAMD_WITNESS=host: the host calculator (transfer_witness.h) on the host cores; two pinned
     // buffers, the witnesses of chunk k + 1 are computed while the GPU proves chunk k
     const size_t cap = std::min(chunk, n) * nv * 32;
-    rc = circuit->host_ensure(2 * cap);
+    rc = circuit->work.host_ensure(2 * cap);
     if (rc != ZK_OK) return rc;
-    uint8_t* buf[2] = {(uint8_t*)circuit->host_z, (uint8_t*)circuit->host_z + cap};
+    uint8_t* buf[2] = {(uint8_t*)circuit->work.host_z, (uint8_t*)circuit->work.host_z + cap};
     rc = transfer_witness(st, std::min(chunk, n), ZK_FR_MONTGOMERY, buf[0]);
     if (rc != ZK_OK) return rc;
     int cur = 0;
@@ -2748,17 +1565,17 @@ zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, cons
 zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, const zk_anonymous_statement* st, const uint8_t* rs,
                                    uint8_t* proofs_out) try {
     if (!p || !circuit || !rs || !proofs_out || (!st && n)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->n_in != ZK_ANONYMOUS_N_INPUTS || circuit->n_aux != ZK_ANONYMOUS_N_AUX)
+    if (circuit->sys.n_in != ZK_ANONYMOUS_N_INPUTS || circuit->sys.n_aux != ZK_ANONYMOUS_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the anonymous-transfer circuit's");
     if (n == 0) return ZK_OK;
-    ZK_TRY(use_device(p->device));
+    ZK_TRY(use_device(p->key.device));
     const size_t nv = ZK_ANONYMOUS_N_INPUTS + ZK_ANONYMOUS_N_AUX;
     size_t chunk = ProveTunables::read().batch_chunk;
     if (chunk > 512) chunk = 512;   // domain 2^16: half the proofs of a transfer chunk fill the same workspaces
     if (!witness_on_host(n)) {
         // witness generation on the GPU (witness_anon_gpu.h), statement in: 1.7 KB instead of 1.6 MB of witness vector; the
         // kernels of chunk k + 1 run beside the multiexps of chunk k (as zk_transfer_prove_batch)
-        if (circuit->device != p->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+        if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
         int slot = 0;
         zk_status rc = witness_anon_gpu_enqueue(circuit, st, std::min(chunk, n), slot, g_copy_stream);
         for (size_t first = 0; first < n && rc == ZK_OK; first += chunk) {
@@ -2776,8 +1593,8 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
         return rc;
     }
     const size_t cap = std::min(chunk, n) * nv * 32;
-    ZK_TRY(circuit->host_ensure(2 * cap));
-    uint8_t* buf[2] = {(uint8_t*)circuit->host_z, (uint8_t*)circuit->host_z + cap};
+    ZK_TRY(circuit->work.host_ensure(2 * cap));
+    uint8_t* buf[2] = {(uint8_t*)circuit->work.host_z, (uint8_t*)circuit->work.host_z + cap};
     auto witness = [&](size_t first, size_t np, uint8_t* out) -> zk_status {
         return witness_batch<zkwit::AnonStatement>(
             np, ZK_ANONYMOUS_N_INPUTS, ZK_ANONYMOUS_N_AUX, ZK_FR_MONTGOMERY, out,
@@ -2813,9 +1630,9 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
 // element against zk_anonymous_witness).  witness_out: n x (105 + 50429) x 32 bytes.
 zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
     if (!circuit || (n && (!st || !witness_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->n_in != ZK_ANONYMOUS_N_INPUTS || circuit->n_aux != ZK_ANONYMOUS_N_AUX)
+    if (circuit->sys.n_in != ZK_ANONYMOUS_N_INPUTS || circuit->sys.n_aux != ZK_ANONYMOUS_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the anonymous-transfer circuit's");
-    ZK_TRY(use_device(circuit->device));
+    ZK_TRY(use_device(circuit->sys.device));
     const size_t nv = ZK_ANONYMOUS_N_INPUTS + ZK_ANONYMOUS_N_AUX, chunk = 256;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
@@ -2823,12 +1640,12 @@ zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statemen
         ZK_TRY(witness_anon_gpu_finish(circuit, np, 0, first));
         if (!(flags & ZK_FR_MONTGOMERY)) {
             const size_t cnt = np * nv;
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->z[0].as<uint32_t>(),
-                      (const uint32_t*)circuit->z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
+            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->work.z[0].as<uint32_t>(),
+                      (const uint32_t*)circuit->work.z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->work.z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
     }
     return ZK_OK;
 } ZK_ABI_CATCH
@@ -2837,9 +1654,9 @@ zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statemen
 // host calculator (zk_transfer_witness) element by element.  witness_out: n x (23 + 19955) x 32 bytes.
 zk_status zk_transfer_witness_gpu(zk_r1cs* circuit, const zk_transfer_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
     if (!circuit || (n && (!st || !witness_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->n_in != ZK_TRANSFER_N_INPUTS || circuit->n_aux != ZK_TRANSFER_N_AUX)
+    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    ZK_TRY(use_device(circuit->device));
+    ZK_TRY(use_device(circuit->sys.device));
     const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, chunk = ProveTunables::read().batch_chunk;
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
@@ -2847,12 +1664,12 @@ zk_status zk_transfer_witness_gpu(zk_r1cs* circuit, const zk_transfer_statement*
         ZK_TRY(witness_gpu_finish(circuit, np, 0, first));
         if (!(flags & ZK_FR_MONTGOMERY)) {
             const size_t cnt = np * nv;
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->z[0].as<uint32_t>(),
-                      (const uint32_t*)circuit->z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
+            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->work.z[0].as<uint32_t>(),
+                      (const uint32_t*)circuit->work.z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
             HIP_TRY(hipGetLastError());
         }
         HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->work.z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
     }
     return ZK_OK;
 } ZK_ABI_CATCH
@@ -2936,7 +1753,7 @@ struct zk_pipeline {
         g_lane = lane;
         zk_params* Pw = lane ? Pl[lane] : P;   // this lane's handles: its own workspaces over the shared tables
         zk_r1cs* Rw = lane ? Rl[lane] : R;
-        if (use_device(Pw->device) != ZK_OK) {
+        if (use_device(Pw->key.device) != ZK_OK) {
             // no context on this lane (stream creation / out of memory): report it and keep DRAINING the queue, so
             // that wait() and free() never block on jobs nobody will take
             std::unique_lock<std::mutex> lk(mu);
@@ -3059,17 +1876,17 @@ extern "C" {
 zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) try {
     if (!p || !circuit || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (circuit->n_in != ZK_TRANSFER_N_INPUTS || circuit->n_aux != ZK_TRANSFER_N_AUX)
+    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
         return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->device != p->device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
-    ZK_TRY(use_device(p->device));
+    if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+    ZK_TRY(use_device(p->key.device));
     zk_pipeline* L = new (std::nothrow) zk_pipeline();
     if (!L) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
     L->P = p;
     L->R = circuit;
     L->nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
     L->chunk = ProveTunables::read().batch_chunk;
-    if ((size_t)circuit->n_con + circuit->n_in > p->m) {
+    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > p->key.m) {
         delete L;
         return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     }
@@ -3103,7 +1920,7 @@ zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) 
                     if (atoll(env) > 0) per_lane = (size_t)atoll(env);
                 const size_t reserve = (size_t)2 << 30;
                 const size_t avail = free_b > reserve ? free_b - reserve : 0;
-                const size_t lane0 = p->abc.p ? 0 : per_lane;       // nothing more to allocate once it has proved a chunk
+                const size_t lane0 = p->work.abc.p ? 0 : per_lane;       // nothing more to allocate once it has proved a chunk
                 const size_t fit = 1 + (avail > lane0 ? (avail - lane0) / per_lane : 0);
                 if ((size_t)lanes > fit) lanes = (int)fit;
             }
