@@ -65,6 +65,13 @@
  *                                   two scans above, keys.rs:250-261, elgamal.rs:85-108, crypto_components.rs:168-220)
  *   zk_balance_keys                 BalanceQuery::get_balance_from_decryption_key for the accounts of a key set in one call
  *                                   zface/src/utils/getter.rs:135-175 (Ciphertext::add, ::write, ::decrypt: elgamal.rs:85-158)
+ *   zk_hd_master                    ExtendedSpendingKey::master                   zface/src/derive/mod.rs:48-64
+ *   zk_hd_xpgk_from_xsk             From<&ExtendedSpendingKey> for ExtendedProofGenerationKey   zface/src/derive/mod.rs:136-146
+ *   zk_hd_derive                    ExtendedSpendingKey::derive_child, ExtendedProofGenerationKey::derive_child for the children of one
+ *                                   parent, with into_decryption_key / into_encryption_key of each
+ *                                   zface/src/derive/mod.rs:66-104, 164-197, components.rs:15-74, no_std_aliases/keys.rs:166-198
+ *   zk_scan_keys_create_hd          - (zk_scan_keys_create for the accounts of such children: zface/src/wallet/keyfile.rs:78-92 per account)
+ *   zk_jubjub_base_mul_dev          EncryptionKey::from_decryption_key, ProofGenerationKey::add on the device   no_std_aliases/keys.rs:200-203, 250-261
  *   zk_elgamal_ledger_apply        rollover, sub_enc_balance, add_pending_transfer of a block (Ciphertext::add / sub in order)
  *                                   modules/encrypted-balances/src/lib.rs:133-222, modules/encrypted-assets/src/lib.rs:266-350,
  *                                   modules/anonymous-balances/src/lib.rs:169-225, core/primitives/src/ciphertext.rs:90-100
@@ -872,6 +879,59 @@ typedef struct {
 typedef struct { uint32_t account, key; zk_balance_result r; } zk_balance_hit;   /* 80 bytes */
 zk_status zk_balance_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n_accounts, const zk_block_account* accounts,
                           uint64_t limit, zk_balance_hit* hits_out, size_t hits_cap, size_t* n_hits_out);
+
+/* ------------------------------------------------------------------------------------------
+ * Hierarchical key derivation (zface/src/derive/mod.rs, a ZIP32-style scheme): every account of a wallet is a child of one
+ * extended key, and the watch-only half - an extended proof generation key - derives the same non-hardened children without any
+ * spending key: what an exchange, a custodian or an auditor runs on the server that reads blocks.  All bytes are the reference's.
+ * An extended key is ZK_HD_XKEY_BYTES = 73 bytes: depth (1) | parent_enckey_tag (4) | child_index (u32 LE) | chain_code (32) |
+ *   key (32) - SpendingKey::write for an xsk (kind ZK_HD_XSK), ProofGenerationKey::write for an xpgk (ZK_HD_XPGK); mod.rs:125-134,
+ *   219-228.  Another kind is ZK_ERR_INVALID_ARGUMENT.
+ * zk_hd_master (mod.rs:48-64): I = BLAKE2b-512("Zerochain_Master", seed), the key SpendingKey::from_seed(I[0..32]), the chain code
+ *   I[32..64], depth 0, tag 00000000, index 0.
+ * zk_hd_xpgk_from_xsk (mod.rs:136-146): the same header with pgk = [sk] G, G = FixedGenerators::NoteCommitmentRandomness; the two
+ *   arrays may be the same.
+ * zk_hd_derive: the children indices[0 .. n) of ONE parent; an index of 2^31 or more is hardened (components.rs:57-74).
+ *   I = prf_expand_vec(chain_code, [0x11], sk, i LE) for a hardened child, (chain_code, [0x12], pgk, i LE) otherwise; f =
+ *   Fs::to_uniform(prf_expand(I[0..32], [0x13])); the child's chain code is I[32..64], its depth the parent's + 1, its tag the first
+ *   four bytes of BLAKE2b-256("ZerochainEFinger", the parent's pgk); its key sk + f (xsk) or [f] G + pgk (xpgk).  The child's
+ *   account (keys.rs:166-198): dec_key = BLAKE2s-256("zech_bdk", the child's pgk) with the top five bits of byte 31 cleared,
+ *   enc_key = [dec_key] G.  Each output may be NULL (not wanted): xkeys_out n x 73 bytes, children of the parent's kind; dec_keys_out
+ *   n x 32, little-endian; enc_keys_out n x 32, Point::write.  Repeated indices are allowed.  n == 0 is ZK_OK and touches nothing.
+ *   ZK_ERR_INVALID_ARGUMENT, with nothing written: a hardened index with ZK_HD_XPGK (the reference returns Err for that child,
+ *   mod.rs:166-169; the message names the first such position); a parent of depth 255 (depth + 1 overflows in the reference); an
+ *   xsk whose key is not a canonical Fs scalar (SpendingKey::read, keys.rs:67-74); an xpgk whose point does not decode or is outside
+ *   the prime-order subgroup (ProofGenerationKey::read, keys.rs:210-217); a NULL xkey or indices with n > 0.  No failure leaves a
+ *   partly written output: the outputs are written last, after everything that can fail.
+ *   The hashes run on the zk_set_host_threads pool.  The point work of n children - [f_i] G + pgk, [dec_key_i] G, two inversions and
+ *   two encodings each - runs on those threads for device < 0 or n <= ZKAMD_HD_HOST_MAX (read per call; 0 = always the kernel),
+ *   above that in one kernel on `device`, one lane per child (csrc/hd_keys.h); both forms write the same bytes.  Both kinds take the
+ *   same device route: the device receives f_i and the parent's pgk, never a spending key.  f_i and dec_key_i are key-derived: the
+ *   device buffers that held them are zeroed before the call returns (zk_memory_stats counts them), on failure too, and the host
+ *   copies are wiped.  The host form multiplies without branching on a scalar; the device form is NOT constant-time: a zero digit
+ *   of a lane's scalar skips that lane's addition.
+ * zk_scan_keys_create_hd: the handle zk_scan_keys_create would build from the decryption keys of those children in index order,
+ *   without deriving the encryption keys a second time; zk_scan_keys_get, both scans and zk_balance_keys work on it unchanged.  n
+ *   must be 1 .. 2^32 - 1; two equal indices fail with zk_scan_keys_create's "dec_key a and dec_key b are equal".
+ * zk_jubjub_base_mul_dev: n x [scalar_i] G, optionally + addend_i, ALWAYS in the kernel on `device` - the multiplier of the
+ *   entries above, reachable with chosen scalars.  Scalars as zk_jubjub_base_mul: canonical Fs, else ZK_ERR_INVALID_ARGUMENT
+ *   naming the index.  addends: n x 32 bytes or NULL; each is read as edwards::Point::read reads it, WITHOUT a subgroup test.  A
+ *   refused addend is a status, never an error: status_out[i] is 0 or ZK_INTO_XY_NOT_IN_FIELD / ZK_INTO_XY_NOT_ON_CURVE, and the
+ *   output point of a refused addend is 32 zero bytes.  status_out: n bytes, required with addends and not written without.  The
+ *   buffers are treated as zk_hd_derive's; not constant-time.
+ * ------------------------------------------------------------------------------------------ */
+#define ZK_HD_XKEY_BYTES 73
+#define ZK_HD_XSK 0u
+#define ZK_HD_XPGK 1u
+zk_status zk_hd_master(const uint8_t* seed, size_t len, uint8_t xsk_out[73]);
+zk_status zk_hd_xpgk_from_xsk(const uint8_t xsk[73], uint8_t xpgk_out[73]);
+zk_status zk_hd_derive(uint32_t kind, const uint8_t xkey[73], const uint32_t* indices, size_t n, int device, uint8_t* xkeys_out,
+                       uint8_t* dec_keys_out, uint8_t* enc_keys_out);
+zk_status zk_scan_keys_create_hd(uint32_t kind, const uint8_t xkey[73], const uint32_t* indices, size_t n, int device,
+                                 zk_scan_keys** out);
+zk_status zk_jubjub_base_mul_dev(const uint8_t* scalars, const uint8_t* addends, size_t n, int device, uint8_t* points_out,
+                                 uint8_t* status_out);
+
 /* GEpoch::group_hash (core/primitives/src/g_epoch.rs:102-110): the Jubjub group hash (core/jubjub/src/group_hash.rs:17-46,
  * find_group_hash curve/mod.rs:223-247) personalised "zcgepoch" over the four little-endian bytes of `epoch` and a counter byte
  * from 0 - the g_epoch every wallet and verifier entry takes.  Host only.  out: Point::write of the point. */

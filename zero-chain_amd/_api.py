@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "jubjub_base_mul_dev", "hd_master", "hd_xpgk", "hd_derive", "HD_XKEY_BYTES", "HD_XSK", "HD_XPGK", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -898,6 +898,80 @@ def jubjub_base_mul(scalars, lib=None):
     return [ob[i:i + 32] for i in range(0, len(ob), 32)]
 
 
+def jubjub_base_mul_dev(scalars, addends=None, device=0, lib=None):
+    """zk_jubjub_base_mul_dev: scalar * G, plus addends[i] (a 32-byte encoding, read without a subgroup test) where addends is
+    given, always in the kernel of the key derivation on `device`.  Returns the 32-byte encodings, or with addends
+    (encodings, statuses): a refused addend has its ZK_INTO_XY_* status and 32 zero bytes."""
+    lib = lib or _lib.load()
+    n = len(scalars)
+    if addends is not None and len(addends) != n:
+        raise ValueError("scalars and addends must have the same length")
+    sb = scalars_to_bytes(scalars)
+    ab = None if addends is None else _points(addends, n)
+    out, st = np.zeros(32 * n, dtype=np.uint8), np.zeros(max(n, 1), dtype=np.uint8)
+    try:
+        lib.check(lib.zk_jubjub_base_mul_dev(_ptr(sb) if n else None, _ptr(ab) if ab is not None and n else None, n, int(device),
+                                             _ptr(out) if n else None, _ptr(st) if ab is not None else None))
+    finally:
+        sb[:] = 0
+    ob = out.tobytes()
+    pts = [ob[i:i + 32] for i in range(0, len(ob), 32)]
+    return pts if addends is None else (pts, [int(v) for v in st[:n]])
+
+
+HD_XKEY_BYTES, HD_XSK, HD_XPGK = 73, 0, 1
+
+
+def hd_master(seed, lib=None):
+    """ExtendedSpendingKey::master (zface/src/derive/mod.rs:48-64): the 73 bytes of the master xsk of `seed` (zk_hd_master)."""
+    lib = lib or _lib.load()
+    buf = _u8(bytes(seed))
+    out = np.zeros(HD_XKEY_BYTES, dtype=np.uint8)
+    lib.check(lib.zk_hd_master(_ptr(buf) if buf.size else None, buf.size, _ptr(out)))
+    return out.tobytes()
+
+
+def hd_xpgk(xsk, lib=None):
+    """ExtendedProofGenerationKey::from(&xsk) (mod.rs:136-146): the watch-only half of an extended spending key (zk_hd_xpgk_from_xsk)."""
+    lib = lib or _lib.load()
+    buf = _u8(bytes(xsk), HD_XKEY_BYTES).copy()
+    out = np.zeros(HD_XKEY_BYTES, dtype=np.uint8)
+    try:
+        lib.check(lib.zk_hd_xpgk_from_xsk(_ptr(buf), _ptr(out)))
+    finally:
+        buf[:] = 0
+    return out.tobytes()
+
+
+def hd_derive(xkey, indices, kind=HD_XSK, device=0, want=("xkeys", "dec_keys", "enc_keys"), lib=None):
+    """zk_hd_derive: the children `indices` (u32; 2^31 and above hardened) of the extended key `xkey` of `kind`.  Returns
+    (xkeys, dec_keys, enc_keys): the 73-byte children of the parent's kind, the decryption keys as integers and the 32-byte
+    encryption keys of their accounts; an output not named in `want` is None (and not computed)."""
+    lib = lib or _lib.load()
+    n = len(indices)
+    buf = _u8(bytes(xkey), HD_XKEY_BYTES).copy()
+    ib = np.asarray([int(i) for i in indices], dtype=np.uint32)
+    outs = {"xkeys": HD_XKEY_BYTES, "dec_keys": 32, "enc_keys": 32}
+    arr = {k: (np.zeros(max(w * n, 1), dtype=np.uint8) if k in want else None) for k, w in outs.items()}
+    try:
+        lib.check(lib.zk_hd_derive(int(kind), _ptr(buf), _ptr(ib) if n else None, n, int(device),
+                                   *[_ptr(arr[k]) if arr[k] is not None else None for k in ("xkeys", "dec_keys", "enc_keys")]))
+        res = []
+        for k, w in outs.items():
+            if arr[k] is None:
+                res.append(None)
+                continue
+            b = arr[k].tobytes()
+            rows = [b[i:i + w] for i in range(0, w * n, w)]
+            res.append([int.from_bytes(r, "little") for r in rows] if k == "dec_keys" else rows)
+        return tuple(res)
+    finally:
+        buf[:] = 0
+        for a in arr.values():
+            if a is not None:
+                a[:] = 0
+
+
 def elgamal_encrypt(values, randomness, enc_keys, lib=None):
     """elgamal::Ciphertext::encrypt (elgamal.rs:46-63) for lists of u32 values, Fs randomness and 32-byte encryption
     keys (zk_elgamal_encrypt).  Returns (left encodings, right encodings)."""
@@ -989,6 +1063,24 @@ class ScanKeys:
         finally:
             kb[:] = 0   # (the caller's copy of the keys is the caller's)
         self._h = h
+
+    @classmethod
+    def from_hd(cls, xkey, indices, kind=HD_XSK, device=0, lib=None):
+        """zk_scan_keys_create_hd: the key set of the accounts of the children `indices` of the extended key `xkey` (hd_derive's
+        arguments), in index order; the encryption keys are those the derivation computed"""
+        self = cls.__new__(cls)
+        self._lib = lib or _lib.load()
+        self._h = None
+        self._n = len(indices)
+        buf = _u8(bytes(xkey), HD_XKEY_BYTES).copy()
+        ib = np.asarray([int(i) for i in indices], dtype=np.uint32)
+        h = C.c_void_p()
+        try:
+            self._lib.check(self._lib.zk_scan_keys_create_hd(int(kind), _ptr(buf), _ptr(ib) if self._n else None, self._n, int(device), C.byref(h)))
+        finally:
+            buf[:] = 0
+        self._h = h
+        return self
 
     def __len__(self):
         return self._n

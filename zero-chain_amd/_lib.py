@@ -193,6 +193,11 @@ _PROTOS = {
                                            C.POINTER(AnonymousScanHit), C.c_size_t, C.POINTER(C.c_size_t)]),
     "zk_balance_keys": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(BlockAccount), C.c_uint64, C.POINTER(BalanceHit), C.c_size_t,
                                     C.POINTER(C.c_size_t)]),
+    "zk_hd_master": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "zk_hd_xpgk_from_xsk": (C.c_int32, [C.c_void_p, C.c_void_p]),
+    "zk_hd_derive": (C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "zk_scan_keys_create_hd": (C.c_int32, [C.c_uint32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.POINTER(C.c_void_p)]),
+    "zk_jubjub_base_mul_dev": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p, C.c_void_p]),
     "zk_elgamal_ledger_apply": (C.c_int32, [C.c_size_t, C.c_void_p, C.c_size_t, C.POINTER(LedgerOp), C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "zk_transfer_derive": (C.c_int32, [C.POINTER(TransferRequest), C.c_size_t, C.POINTER(TransferStatement), C.c_void_p]),

@@ -25,10 +25,9 @@ struct zk_scan_keys {
 
 namespace zkscan {
 
-inline zk_status keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_keys** out) {
-    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    if (!dec_keys) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+// The two halves of a key set's construction, shared by zk_scan_keys_create and zk_scan_keys_create_hd (hd_keys.h), which differ in
+// where the encryption keys come from.  keys_load: the handle with its n_keys canonical scalars and room for their encryption keys.
+inline zk_status keys_load(const uint8_t* dec_keys, size_t n_keys, std::unique_ptr<zk_scan_keys>* out) {
     if (n_keys == 0 || n_keys > 0xffffffffull) return fail(ZK_ERR_INVALID_ARGUMENT, "n_keys must be 1 .. 2^32 - 1");
     std::unique_ptr<zk_scan_keys> k(new zk_scan_keys());
     k->dk.resize(n_keys * 4);
@@ -37,12 +36,12 @@ inline zk_status keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_key
         zkrt::load_scalar_le(dec_keys + 32 * i, &k->dk[4 * i]);
         if (!fs_lt_mod(&k->dk[4 * i])) return fail(ZK_ERR_INVALID_ARGUMENT, "dec_key " + std::to_string(i) + " is not a canonical Fs scalar");
     }
-    (void)zkwit::tables();
-    ZK_TRY(zkrt::for_each_status(n_keys, 64, [&](size_t i) -> zk_status {
-        const zkwit::JPoint pk = jubjub_fixed_mul(&k->dk[4 * i]);   // EncryptionKey::from_decryption_key
-        jubjub_encode(pk.x, pk.y, &k->enc[32 * i]);
-        return ZK_OK;
-    }));
+    *out = std::move(k);
+    return ZK_OK;
+}
+// keys_index: with k->enc filled, the sort by those bytes, the duplicate check and the handle's release to the caller
+inline zk_status keys_index(std::unique_ptr<zk_scan_keys> k, zk_scan_keys** out) {
+    const size_t n_keys = k->enc.size() / 32;
     k->order.resize(n_keys);
     for (size_t i = 0; i < n_keys; i++) k->order[i] = (uint32_t)i;
     const uint8_t* enc = k->enc.data();
@@ -56,6 +55,20 @@ inline zk_status keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_key
             return fail(ZK_ERR_INVALID_ARGUMENT, "dec_key " + std::to_string(k->order[i]) + " and dec_key " + std::to_string(k->order[i + 1]) + " are equal");
     *out = k.release();
     return ZK_OK;
+}
+inline zk_status keys_create(const uint8_t* dec_keys, size_t n_keys, zk_scan_keys** out) {
+    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    *out = nullptr;
+    if (!dec_keys) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    std::unique_ptr<zk_scan_keys> k;
+    ZK_TRY(keys_load(dec_keys, n_keys, &k));
+    (void)zkwit::tables();
+    ZK_TRY(zkrt::for_each_status(n_keys, 64, [&](size_t i) -> zk_status {
+        const zkwit::JPoint pk = jubjub_fixed_mul(&k->dk[4 * i]);   // EncryptionKey::from_decryption_key
+        jubjub_encode(pk.x, pk.y, &k->enc[32 * i]);
+        return ZK_OK;
+    }));
+    return keys_index(std::move(k), out);
 }
 
 inline zk_status keys_get(const zk_scan_keys* k, size_t first, size_t count, uint8_t* enc_keys_out) {

@@ -10,9 +10,10 @@
 //   redjubjub PrivateKey::sign / PublicKey::verify       core/jubjub/src/redjubjub.rs:73-103, 127-155 (redjubjub.h)
 //   a block read with one decryption key                 - (elgamal.rs:85-108 per value, crypto_components.rs:168-220; elgamal_scan.h)
 //   BalanceQuery::get_balance_from_decryption_key        zface/src/utils/getter.rs:135-175, for the accounts of a key set (balance_keys.h)
+//   ExtendedSpendingKey / ExtendedProofGenerationKey     zface/src/derive/mod.rs:48-228 (master, derive_child, read / write; hd_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
-// the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h) and
-// its two combines (elgamal_scan.h, balance_keys.h).
+// the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h),
+// its two combines (elgamal_scan.h, balance_keys.h) and the two of the key derivation's fixed-base multiplier (hd_keys.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -96,7 +97,7 @@ static inline zkhost::Fr ct_pick(uint64_t mask, const zkhost::Fr& a, const zkhos
     return r;
 }
 // k * G for the fixed generator, from its 3-bit window tables (k < 2^252)
-zkwit::JPoint jubjub_fixed_mul(const uint64_t k[4]) {
+zkwit::EPoint jubjub_fixed_mul_ext(const uint64_t k[4]) {   // (projective: for callers that bring many to affine form at once)
     const zkwit::Tables& t = zkwit::tables();
     zkwit::EPoint acc = zkwit::ext_zero();
     for (int w = 0; w < 84; w++) {
@@ -110,6 +111,10 @@ zkwit::JPoint jubjub_fixed_mul(const uint64_t k[4]) {
         }
         acc = zkwit::ext_add(acc, zkwit::to_ext(e));
     }
+    return acc;
+}
+zkwit::JPoint jubjub_fixed_mul(const uint64_t k[4]) {
+    const zkwit::EPoint acc = jubjub_fixed_mul_ext(k);
     zkwit::JPoint out;
     zkwit::batch_to_affine(&acc, &out, 1);
     return out;
@@ -233,6 +238,7 @@ zk_status transfer_derive(const zk_transfer_request* rq, size_t n, zk_transfer_s
 #include "elgamal_scan.h"   // (the scan decodes, multiplies and wipes with the helpers above)
 #include "scan_keys.h"      // (the same scan for a set of keys: a scalar per hit)
 #include "balance_keys.h"   // (the balances of such a set's accounts: the same point kernel, a combine of its own)
+#include "hd_keys.h"        // (the children of an extended key and their accounts: a fixed-base multiplier of its own, two kernels)
 
 extern "C" {
 
@@ -408,6 +414,30 @@ zk_status zk_anonymous_scan_keys(zk_elgamal_table* t, const zk_scan_keys* keys, 
 zk_status zk_balance_keys(zk_elgamal_table* t, const zk_scan_keys* keys, size_t n_accounts, const zk_block_account* accounts, uint64_t limit,
                           zk_balance_hit* hits_out, size_t hits_cap, size_t* n_hits_out) try {
     return zkscan::balance_keys(t, keys, n_accounts, accounts, limit, hits_out, hits_cap, n_hits_out);
+} ZK_ABI_CATCH
+
+zk_status zk_hd_master(const uint8_t* seed, size_t len, uint8_t xsk_out[73]) try {
+    if ((!seed && len) || !xsk_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    return zkhd::master(seed, len, xsk_out);
+} ZK_ABI_CATCH
+
+zk_status zk_hd_xpgk_from_xsk(const uint8_t xsk[73], uint8_t xpgk_out[73]) try {
+    if (!xsk || !xpgk_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    return zkhd::xpgk_from_xsk(xsk, xpgk_out);
+} ZK_ABI_CATCH
+
+zk_status zk_hd_derive(uint32_t kind, const uint8_t xkey[73], const uint32_t* indices, size_t n, int device, uint8_t* xkeys_out,
+                       uint8_t* dec_keys_out, uint8_t* enc_keys_out) try {
+    return zkhd::derive(kind, xkey, indices, n, device, xkeys_out, dec_keys_out, enc_keys_out);
+} ZK_ABI_CATCH
+
+zk_status zk_scan_keys_create_hd(uint32_t kind, const uint8_t xkey[73], const uint32_t* indices, size_t n, int device, zk_scan_keys** out) try {
+    return zkhd::scan_keys_create(kind, xkey, indices, n, device, out);
+} ZK_ABI_CATCH
+
+zk_status zk_jubjub_base_mul_dev(const uint8_t* scalars, const uint8_t* addends, size_t n, int device, uint8_t* points_out,
+                                 uint8_t* status_out) try {
+    return zkhd::base_mul_dev(scalars, addends, n, device, points_out, status_out);
 } ZK_ABI_CATCH
 
 zk_status zk_elgamal_add(const uint8_t* left_a, const uint8_t* right_a, const uint8_t* left_b, const uint8_t* right_b, size_t n,
