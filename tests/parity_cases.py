@@ -866,8 +866,10 @@ def verifier_pvk_fixtures(lib):
             pvk.close()
 
 
-def empty_batches(lib):
-    """n = 0 through every batch entry of the boundary: nothing to do is not an error and touches no buffer."""
+def empty_batches(lib, statement_routes=False):
+    """n = 0 through every batch entry of the boundary: nothing to do is not an error and touches no buffer.
+    statement_routes: the two statement-to-proof entries too, over the natively emitted matrices and a key of each circuit's
+    shape (the GPU form alone: the emulation build cannot afford a key of 2^15 / 2^16 rows)."""
     r1, asg, P, pk = helpers.small_case(2, 2, 6, 7)
     params = zk.Parameters.read(pk, checked=False, lib=lib)
     mats = zk.ConstraintMatrices(r1.n_in, r1.n_aux, r1.constraints, lib=lib)
@@ -894,6 +896,17 @@ def empty_batches(lib):
         pvk.close()
         mats.close()
         params.close()
+    if not statement_routes:
+        return
+    for case, circuit, pack, prove in ((helpers.transfer_case(1), zk.ConstraintMatrices.transfer_circuit, zk.transfer_statements, zk.transfer_prove_batch),
+                                       (helpers.anonymous_case(2), zk.ConstraintMatrices.anonymous_circuit, zk.anonymous_statements, zk.anonymous_prove_batch)):
+        params_c = zk.Parameters.read(case[3], checked=False, lib=lib)
+        mats_c = circuit(lib=lib)
+        try:
+            assert prove(mats_c, params_c, pack([]), []) == []
+        finally:
+            mats_c.close()
+            params_c.close()
 
 
 def parsers_survive_mutations(lib, rounds=24):
@@ -1544,6 +1557,43 @@ def anonymous_witness_gpu_matches_host(lib, n=3):
                 assert e.value.variant == "InvalidArgument" and what in str(e.value), (what, str(e.value))
     finally:
         mats.close()
+
+
+def statement_routes_report_the_absolute_index(lib, circuit, engine, monkeypatch):
+    """zk_transfer_prove_batch / zk_anonymous_prove_batch over two chunks (2 + 1 statements) with a malformed statement at
+    index 2 - relative index 0 of the second chunk: both witness engines report it with its index in the BATCH, in the host
+    calculator's words; the same handles then prove the three good statements (nothing of the failed call is left behind),
+    with the proofs zk_prove_batch_witness gives for the host calculator's assignments and the same (r, s)."""
+    from oracle import anonymous_circuit as ac
+    from oracle import transfer_circuit as tc
+    monkeypatch.setenv("ZKAMD_BATCH_CHUNK", "2")
+    monkeypatch.setenv("ZKAMD_WITNESS", engine)
+    if circuit == "transfer":
+        r1, asgs, P, pk = helpers.transfer_case(1)
+        items = [tc.statement_dict(tc.make_witness(40 + i, amount=5 + i, fee=i & 1, balance=77 + i)) for i in range(3)]
+        pack, prove, witness = zk.transfer_statements, zk.transfer_prove_batch, zk.transfer_witness
+    else:
+        r1, asgs, P, pk = helpers.anonymous_case(2)
+        items = [ac.statement_dict(ac.make_witness(1 + i, amount=10 + i, balance=100 + 3 * i)) for i in range(3)]
+        pack, prove, witness = zk.anonymous_statements, zk.anonymous_prove_batch, zk.anonymous_witness
+    params = zk.Parameters.read(pk, checked=False, lib=lib)
+    mats = zk.ConstraintMatrices(r1.n_in, r1.n_aux, r1.constraints, lib=lib)
+    try:
+        rs = [(3 + i, 5 + 11 * i) for i in range(3)]
+        batches = [(items[:2] + [dict(items[2], g_epoch=bytes([2]) + bytes(31))], ("statement 2", "g_epoch"))]
+        if circuit == "anonymous":
+            batches.append(([items[0], items[1], dict(items[2], s_index=12)], ("statement 2: member index",)))
+        for batch, words in batches:
+            with pytest.raises(zk.ZkError) as e:
+                prove(mats, params, pack(batch), rs)
+            assert e.value.variant == "InvalidArgument" and all(w in str(e.value) for w in words), str(e.value)
+        sts = pack(items)
+        want = zk.create_proofs_from_witness(mats, params, witness(sts, lib=lib), rs)
+        got = prove(mats, params, sts, rs)
+        assert [p.write() for p in got] == [p.write() for p in want]
+    finally:
+        mats.close()
+        params.close()
 
 
 def setup_matches_oracle(lib, seed=21, n_in=3, n_aux=17, n_con=20):

@@ -198,7 +198,7 @@ def test_anonymous_circuit_from_witness(gpu_lib, monkeypatch):
         params.close()
 
 
-# The assignment of a handful of statements is computed on the host cores by default (zkamd.cpp witness_on_host: a transaction
+# The assignment of a handful of statements is computed on the host cores by default (statement_route.h witness_on_host: a transaction
 # proved alone is 4.6 instead of 11.5 ms), of a batch by the witness kernels: the statement -> proof tests run under both.
 WITNESS_ENGINES = ("gpu", "host")
 
@@ -354,7 +354,7 @@ def test_verifier_golden_multiples(gpu_lib):
 
 
 def test_empty_batches(gpu_lib):
-    pc.empty_batches(gpu_lib)
+    pc.empty_batches(gpu_lib, statement_routes=True)
 
 
 def test_parsers_survive_mutations(gpu_lib):
@@ -501,6 +501,12 @@ def test_witness_gpu_matches_host(gpu_lib):
 
 def test_anonymous_witness_gpu_matches_host(gpu_lib):
     pc.anonymous_witness_gpu_matches_host(gpu_lib, n=5)
+
+
+@pytest.mark.parametrize("engine", WITNESS_ENGINES)
+@pytest.mark.parametrize("circuit", ("transfer", "anonymous"))
+def test_statement_routes_report_the_absolute_index(gpu_lib, monkeypatch, circuit, engine):
+    pc.statement_routes_report_the_absolute_index(gpu_lib, circuit, engine, monkeypatch)
 
 
 def test_setup_matches_oracle(gpu_lib):

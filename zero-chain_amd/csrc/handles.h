@@ -85,8 +85,7 @@ zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_
                               bool typed_inputs = false);
 zk_status witness_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base);
 // ... and of the anonymous-transfer circuit (witness_anon_gpu.h)
-zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st, size_t np, int slot, hipStream_t stream,
-                                   size_t index_base = 0);
+zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st, size_t np, int slot, hipStream_t stream);
 zk_status witness_anon_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base);
 
 // ------------------------------------------------------------------------------------------
@@ -123,12 +122,14 @@ zk_status elgamal_dlog_search_resident(zk_elgamal_table* T, size_t nb, uint64_t 
 // proofs are this library's own fresh results (gen_proof's self-check) - decoded without the r-torsion test.
 namespace zkrt {
 // what wallet.cpp (gen_proof, the Jubjub host side) needs of zkamd.cpp: one chunk of proofs from the assignment the witness
-// kernels left in R->work.z[slot]; proofs per launch set; the key's device and evaluation domain
+// kernels left in R->work.z[slot]; proofs per launch set
 zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out);
 size_t lib_batch_chunk();
-bool lib_witness_on_host(size_t n);   // a handful of statements: the assignment on the host cores (zkamd.cpp witness_on_host)
-int lib_params_device(const zk_params* P);
-size_t lib_params_domain(const zk_params* P);
+bool lib_witness_on_host(size_t n);   // a handful of statements: the assignment on the host cores (statement_route.h witness_on_host)
+// what every statement entry refuses of a (key, circuit) pair (statement_route.h): circuit = 0 the transfer circuit, 1 the
+// anonymous one (zkpairs::Circuit); P = null: the circuit alone; n = 0: the checks of an empty batch, which come before the
+// device is made current and the key's evaluation domain is compared
+zk_status route_check(zk_params* P, zk_r1cs* R, int circuit, size_t n = 1);
 zk_status verify_batch(zk_vk* vk, size_t n, const uint8_t* proofs, const uint8_t* public_inputs, size_t n_inputs, uint8_t* ok_out,
                        bool own_proofs, int form = VERIFY_AUTO, const uint8_t* own_affine = nullptr);
 }

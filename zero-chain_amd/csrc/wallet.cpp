@@ -474,13 +474,8 @@ extern "C" {
 zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk, size_t n, const zk_transfer_request* req,
                                       const uint8_t* rs, zk_confidential_xt* out) try {
     if (!p || !circuit || !vk || (n && (!req || !rs || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->sys.device != lib_params_device(p)) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
+    ZK_TRY(route_check(p, circuit, 0, n));
     if (n == 0) return ZK_OK;
-    ZK_TRY(use_device(lib_params_device(p)));
-    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > lib_params_domain(p))
-        return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
     std::vector<zk_transfer_statement> st(n);
     std::vector<uint8_t> rsk(n * 32), proofs(n * 192), ok(n);
     WipeOnExit wipe_st{st.data(), n * sizeof(zk_transfer_statement)}, wipe_rsk{rsk.data(), rsk.size()};
@@ -489,7 +484,7 @@ zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk,
     const auto t_start = std::chrono::steady_clock::now();
     auto since = [&] { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count(); };
     // A handful of requests (one transaction at a time is the reference's call pattern): the assignment on the host cores,
-    // 1.4 ms per statement, instead of the witness kernels' 8.4 ms of serial chains (zkamd.cpp witness_on_host); the typed
+    // 1.4 ms per statement, instead of the witness kernels' 8.4 ms of serial chains (statement_route.h witness_on_host); the typed
     // inputs are then checked here, otherwise by the witness kernels of the chunk.
     const bool host_wit = lib_witness_on_host(n);
     ZK_TRY(transfer_derive(req, n, st.data(), rsk.data(), host_wit));

@@ -1,6 +1,7 @@
-// libzkamd, witness half: the GPU witness generator of the confidential-transfer circuit behind
-// zk_transfer_prove_batch / zk_pipeline / zk_transfer_witness_gpu (kernels: witness_gpu.h), and the discrete-log search of
-// zk_elgamal_decrypt (kernels: elgamal_dlog.h; its C entries are wallet.cpp's).
+// libzkamd, witness half: the GPU witness generators of the two built-in circuits - the confidential transfer (kernels:
+// witness_gpu.h) and the anonymous transfer (witness_anon_gpu.h) - as the statement route (statement_route.h), zk_pipeline and
+// gen_proof drive them: one slot prologue and epilogue, each circuit's launches between them, each circuit's finish; and the
+// discrete-log search of zk_elgamal_decrypt (kernels: elgamal_dlog.h; its C entries are wallet.cpp's).
 #include <algorithm>
 #include "handles.h"
 #include "transfer_witness.h"
@@ -26,28 +27,53 @@ static zk_status witness_gpu_init(zk_r1cs* R) {
     R->work.wit_ready = true;
     return ZK_OK;
 }
-zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_t np, int slot, hipStream_t stream, bool typed_inputs) {
+// What the witness kernels of a circuit need of a slot beside its statements: variables per statement, bytes of a statement,
+// points that travel between the levels, roles of the chain scratch
+struct SlotSizes {
+    size_t nv, st_size, points, scratch_roles;
+};
+// The prologue both circuits share, in two steps.  stage: the buffers of the slot, and the np statements copied into its pinned
+// half, where the caller may still touch them.  begin: their upload, wit_bad filled with the circuit's "nothing found", and the
+// Ctx of the slot, all but its statements.
+static zk_status witness_slot_stage(zk_r1cs* R, const SlotSizes& S, const void* st, size_t np, int slot) {
     ZK_TRY(witness_gpu_init(R));
-    const size_t nv = zkwitdev::NV;
-    ZK_TRY(R->work.z[slot].ensure(np * nv * 32));
-    ZK_TRY(R->work.wit_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
+    ZK_TRY(R->work.z[slot].ensure(np * S.nv * 32));
+    ZK_TRY(R->work.wit_st[slot].ensure(np * S.st_size));
     ZK_TRY(R->work.wit_bad[slot].ensure(np * 4));
-    ZK_TRY(R->work.pin_st[slot].ensure(np * sizeof(zkwitdev::Stmt)));
+    ZK_TRY(R->work.pin_st[slot].ensure(np * S.st_size));
     ZK_TRY(R->work.pin_bad[slot].ensure(np * 4));
-    ZK_TRY(R->work.wit_pts.ensure(np * (size_t)zkwitdev::P_COUNT * 64));
-    ZK_TRY(R->work.wit_scratch.ensure((size_t)zkwitdev::L1_SCRATCH_ROLES * zkwitdev::SCRATCH_SLOTS * np * 32));
-    memcpy(R->work.pin_st[slot].p, st, np * sizeof(zkwitdev::Stmt));
-    HIP_TRY(hipMemcpyAsync(R->work.wit_st[slot].p, R->work.pin_st[slot].p, np * sizeof(zkwitdev::Stmt), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(R->work.wit_bad[slot].p, 0, np * 4, stream));
+    ZK_TRY(R->work.wit_pts.ensure(np * S.points * 64));
+    ZK_TRY(R->work.wit_scratch.ensure(S.scratch_roles * zkwitdev::SCRATCH_SLOTS * np * 32));
+    memcpy(R->work.pin_st[slot].p, st, np * S.st_size);
+    return ZK_OK;
+}
+static zk_status witness_slot_begin(zk_r1cs* R, const SlotSizes& S, size_t np, int slot, hipStream_t stream, int bad_fill, zkwitdev::Ctx* c) {
+    HIP_TRY(hipMemcpyAsync(R->work.wit_st[slot].p, R->work.pin_st[slot].p, np * S.st_size, hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(R->work.wit_bad[slot].p, bad_fill, np * 4, stream));
+    c->z = R->work.z[slot].as<uint32_t>();
+    c->st = nullptr;
+    c->pts = R->work.wit_pts.as<uint32_t>();
+    c->table = R->work.wit_table.as<uint32_t>();
+    c->consts = R->work.wit_consts.as<uint32_t>();
+    c->scratch = R->work.wit_scratch.as<uint32_t>();
+    c->bad = R->work.wit_bad[slot].as<uint32_t>();
+    c->n = (uint32_t)np;
+    return ZK_OK;
+}
+// ... and the epilogue, behind the circuit's launches: what they found on its way to the pinned half, the event finish() waits for
+static zk_status witness_slot_end(zk_r1cs* R, size_t np, int slot, hipStream_t stream) {
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(R->work.pin_bad[slot].p, R->work.wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipEventRecord(R->work.wit_done[slot], stream));
+    return ZK_OK;
+}
+
+zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_t np, int slot, hipStream_t stream, bool typed_inputs) {
+    const SlotSizes S = {zkwitdev::NV, sizeof(zkwitdev::Stmt), zkwitdev::P_COUNT, zkwitdev::L1_SCRATCH_ROLES};
+    ZK_TRY(witness_slot_stage(R, S, st, np, slot));
     zkwitdev::Ctx c;
-    c.z = R->work.z[slot].as<uint32_t>();
+    ZK_TRY(witness_slot_begin(R, S, np, slot, stream, 0, &c));
     c.st = R->work.wit_st[slot].as<zkwitdev::Stmt>();
-    c.pts = R->work.wit_pts.as<uint32_t>();
-    c.table = R->work.wit_table.as<uint32_t>();
-    c.consts = R->work.wit_consts.as<uint32_t>();
-    c.scratch = R->work.wit_scratch.as<uint32_t>();
-    c.bad = R->work.wit_bad[slot].as<uint32_t>();
-    c.n = (uint32_t)np;
     const unsigned b64 = (unsigned)((np + 63) / 64);
     {
         ProfScope ps("witness_gpu", stream);
@@ -57,10 +83,7 @@ zk_status witness_gpu_enqueue(zk_r1cs* R, const zk_transfer_statement* st, size_
         ZK_LAUNCH(zkwitdev::k_wit_mul_fill, dim3(b64, zkwitdev::N_MULS * zkwitdev::MUL_FILL_CHUNKS), dim3(64), 0, stream, c);
         ZK_LAUNCH(zkwitdev::k_wit_level2, dim3(b64, zkwitdev::L2_ROLES), dim3(64), 0, stream, c);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(R->work.pin_bad[slot].p, R->work.wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(R->work.wit_done[slot], stream));
-    return ZK_OK;
+    return witness_slot_end(R, np, slot, stream);
 }
 // waits for the witness kernels of `slot`; a malformed statement is reported with its absolute index
 zk_status witness_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base) {
@@ -87,43 +110,25 @@ zk_status witness_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base)
 
 // ---- the anonymous-transfer circuit (witness_anon_gpu.h): np statements -> R->work.z[slot], enqueued on `stream`.  The
 // handle's witness buffers are shared with the transfer generator (a zk_r1cs holds ONE circuit).
-zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st, size_t np, int slot, hipStream_t stream, size_t index_base) {
+zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st, size_t np, int slot, hipStream_t stream) {
     using namespace zkwitdev;
-    ZK_TRY(witness_gpu_init(R));
     static_assert(sizeof(AStmt) == sizeof(zk_anonymous_statement), "statement layout");
-    ZK_TRY(R->work.z[slot].ensure(np * (size_t)A_NV * 32));
-    ZK_TRY(R->work.wit_st[slot].ensure(np * sizeof(AStmt)));
-    ZK_TRY(R->work.wit_bad[slot].ensure(np * 4));
-    ZK_TRY(R->work.pin_st[slot].ensure(np * sizeof(AStmt)));
-    ZK_TRY(R->work.pin_bad[slot].ensure(np * 4));
-    ZK_TRY(R->work.wit_pts.ensure(np * (size_t)AP_COUNT * 64));
-    ZK_TRY(R->work.wit_scratch.ensure((size_t)A1_ROLES * SCRATCH_SLOTS * np * 32));
-    memcpy(R->work.pin_st[slot].p, st, np * sizeof(AStmt));
+    const SlotSizes S = {A_NV, sizeof(AStmt), AP_COUNT, A1_ROLES};
+    ZK_TRY(witness_slot_stage(R, S, st, np, slot));
     // A member index out of range is reported by witness_anon_gpu_finish, in statement order with everything else the
-    // kernels find - exactly where the host calculator reports it (zkamd.cpp anonymous_decode; ADVICE r4: refused here, a
-    // bad index in chunk k + 1 was reported before chunk k had been proved).  The kernels see the index clamped.
+    // kernels find - exactly where the host calculator reports it (statement_route.h anonymous_decode; ADVICE r4: refused
+    // here, a bad index in chunk k + 1 was reported before chunk k had been proved).  The kernels see the index clamped.
     R->work.anon_index_bad[slot] = (size_t)-1;
-    {
-        zk_anonymous_statement* ps = (zk_anonymous_statement*)R->work.pin_st[slot].p;
-        for (size_t i = 0; i < np; i++)
-            if (ps[i].s_index >= ZK_ANONYMOUS_SIZE || ps[i].t_index >= ZK_ANONYMOUS_SIZE) {
-                if (R->work.anon_index_bad[slot] == (size_t)-1) R->work.anon_index_bad[slot] = i;
-                ps[i].s_index = 0;
-                ps[i].t_index = 1;
-            }
-    }
-    HIP_TRY(hipMemcpyAsync(R->work.wit_st[slot].p, R->work.pin_st[slot].p, np * sizeof(AStmt), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(R->work.wit_bad[slot].p, 0xff, np * 4, stream));   // A_BAD_NONE
+    zk_anonymous_statement* ps = (zk_anonymous_statement*)R->work.pin_st[slot].p;
+    for (size_t i = 0; i < np; i++)
+        if (ps[i].s_index >= ZK_ANONYMOUS_SIZE || ps[i].t_index >= ZK_ANONYMOUS_SIZE) {
+            if (R->work.anon_index_bad[slot] == (size_t)-1) R->work.anon_index_bad[slot] = i;
+            ps[i].s_index = 0;
+            ps[i].t_index = 1;
+        }
     ACtx c;
-    c.z = R->work.z[slot].as<uint32_t>();
-    c.st = nullptr;
+    ZK_TRY(witness_slot_begin(R, S, np, slot, stream, 0xff, &c));   // A_BAD_NONE
     c.ast = R->work.wit_st[slot].as<AStmt>();
-    c.pts = R->work.wit_pts.as<uint32_t>();
-    c.table = R->work.wit_table.as<uint32_t>();
-    c.consts = R->work.wit_consts.as<uint32_t>();
-    c.scratch = R->work.wit_scratch.as<uint32_t>();
-    c.bad = R->work.wit_bad[slot].as<uint32_t>();
-    c.n = (uint32_t)np;
     const unsigned b64 = (unsigned)((np + 63) / 64);
     {
         ProfScope ps("witness_gpu", stream);
@@ -137,13 +142,10 @@ zk_status witness_anon_gpu_enqueue(zk_r1cs* R, const zk_anonymous_statement* st,
         ZK_LAUNCH(k_awit_mul_fill, dim3(b64, MUL_FILL_CHUNKS), dim3(64), 0, stream, c, A_MUL_CRD_SK);
         ZK_LAUNCH(k_awit_level4, dim3(b64), dim3(64), 0, stream, c);
     }
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(R->work.pin_bad[slot].p, R->work.wit_bad[slot].p, np * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipEventRecord(R->work.wit_done[slot], stream));
-    return ZK_OK;
+    return witness_slot_end(R, np, slot, stream);
 }
 // waits for the witness kernels of `slot`; a malformed statement is reported with its absolute index, in the words and the
-// order of the host calculator (zkamd.cpp anonymous_decode)
+// order of the host calculator (statement_route.h anonymous_decode)
 zk_status witness_anon_gpu_finish(zk_r1cs* R, size_t np, int slot, size_t index_base) {
     using namespace zkwitdev;
     HIP_TRY(hipEventSynchronize(R->work.wit_done[slot]));

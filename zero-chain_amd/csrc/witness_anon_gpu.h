@@ -100,7 +100,7 @@ struct AStmt {
 enum { AP_PGK = 0, AP_GEPOCH = 1, AP_KEYS = 2, AP_LEFT = AP_KEYS + ANON, AP_BALL = AP_LEFT + ANON, AP_BALR = AP_BALL + ANON,
        AP_KMR = AP_BALR + ANON, AP_ADDED = AP_KMR + ANON, AP_AMOUNT_G = AP_ADDED + ANON, AP_REMAINING_G, AP_RIGHT, AP_ALPHA_G,
        AP_RIGHT_FOLD, AP_FOLD_T, AP_CRD, AP_CRD_SK, AP_COUNT };
-// error codes in wit_bad (the smallest one wins: the order the host calculator checks in, zkamd.cpp anonymous_decode)
+// error codes in wit_bad (the smallest one wins: the order the host calculator checks in, statement_route.h anonymous_decode)
 constexpr uint32_t A_BAD_NONE = 0xffffffffu;
 enum { A_BAD_RANDOMNESS = 0, A_BAD_ALPHA, A_BAD_DEC_KEY, A_BAD_PGK, A_BAD_GEPOCH, A_BAD_SET = 5 /* + 4 k + {key, left, ball, balr} */ };
 

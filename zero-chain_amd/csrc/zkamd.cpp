@@ -579,162 +579,7 @@ zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t*
 
 }  // namespace
 
-// ------------------------------------------------------------------------------------------
-// transfer-circuit witness calculator (transfer_witness.h) behind the C ABI
-// ------------------------------------------------------------------------------------------
-namespace {
-
-zk_status transfer_decode(const zk_transfer_statement& in, size_t index, zkwit::Statement* out) {
-    static const uint64_t FS[4] = ZK_JUBJUB_FS_MODULUS_64;
-    auto scalar = [&](const uint8_t* b, uint64_t (&v)[4], const char* what) -> zk_status {
-        load_scalar_le(b, v);
-        for (int i = 3; i >= 0; i--) {
-            if (v[i] < FS[i]) return ZK_OK;
-            if (v[i] > FS[i]) break;
-        }
-        return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index) + ": " + what + " is not a canonical Fs scalar");
-    };
-    auto point = [&](const uint8_t* b, zkwit::JPoint* p, const char* what) -> zk_status {
-        if (!zkwit::decode_point(b, p))
-            return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index) + ": " + what + " is not a Jubjub point");
-        return ZK_OK;
-    };
-    out->amount = in.amount;
-    out->remaining_balance = in.remaining_balance;
-    out->fee = in.fee;
-    ZK_TRY(scalar(in.randomness, out->randomness, "randomness"));
-    ZK_TRY(scalar(in.alpha, out->alpha, "alpha"));
-    ZK_TRY(scalar(in.dec_key_sender, out->dec_key, "dec_key_sender"));
-    ZK_TRY(point(in.proof_generation_key, &out->pgk, "proof_generation_key"));
-    ZK_TRY(point(in.enc_key_recipient, &out->enc_key_recipient, "enc_key_recipient"));
-    ZK_TRY(point(in.enc_balance_left, &out->enc_balance_left, "enc_balance_left"));
-    ZK_TRY(point(in.enc_balance_right, &out->enc_balance_right, "enc_balance_right"));
-    ZK_TRY(point(in.g_epoch, &out->g_epoch, "g_epoch"));
-    return ZK_OK;
-}
-
-// n statements -> n variable assignments on the host cores.  decode(i, &statement) / synth(statement, wit).
-template <class Stmt, class Decode, class Synth>
-zk_status witness_batch(size_t n, size_t n_inputs, size_t n_aux, uint32_t flags, uint8_t* out, Decode&& decode, Synth&& synth) {
-    // decode(i, ...) reports the ABSOLUTE statement index (the callers add their batch offset); threads own
-    // increasing index ranges and stop at their first failure, so the first failing thread holds the
-    // lowest failing statement
-    if (n == 0) return ZK_OK;
-    (void)zkwit::tables();   // build the window tables before the threads start
-    const size_t nv = n_inputs + n_aux;
-    const unsigned nthreads = host_threads(n, 64);
-    std::vector<zk_status> sts(nthreads, ZK_OK);
-    std::vector<std::string> msgs(nthreads);
-    const bool mont = (flags & ZK_FR_MONTGOMERY) != 0;
-    auto work = [&](unsigned t) {
-        for (size_t i = n * t / nthreads; i < n * (t + 1) / nthreads; i++) {
-            Stmt s;
-            zk_status rc = decode(i, &s);
-            if (rc != ZK_OK) {
-                sts[t] = rc;
-                msgs[t] = g_err;
-                return;
-            }
-            zkwit::Wit w;
-            synth(s, w);
-            if (w.inputs.size() != n_inputs || w.aux.size() != n_aux) {
-                sts[t] = ZK_ERR_INVALID_ARGUMENT;
-                msgs[t] = "internal: witness size mismatch";
-                return;
-            }
-            uint64_t* dst = reinterpret_cast<uint64_t*>(out + i * nv * 32);
-            size_t k = 0;
-            for (const auto* vec : {&w.inputs, &w.aux})
-                for (const zkhost::Fr& v : *vec) {
-                    zkhost::Fr x = mont ? v : v.from_mont();
-                    memcpy(dst + 4 * k, x.l, 32);
-                    k++;
-                }
-        }
-    };
-    run_threads(nthreads, work);
-    for (unsigned t = 0; t < nthreads; t++)
-        if (sts[t] != ZK_OK) return fail(sts[t], msgs[t]);
-    return ZK_OK;
-}
-
-zk_status transfer_witness(const zk_transfer_statement* st, size_t n, uint32_t flags, uint8_t* out, size_t index_base = 0) {
-    if ((!st || !out) && n) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    return witness_batch<zkwit::Statement>(
-        n, ZK_TRANSFER_N_INPUTS, ZK_TRANSFER_N_AUX, flags, out,
-        [&](size_t i, zkwit::Statement* s) { return transfer_decode(st[i], index_base + i, s); },
-        [n](const zkwit::Statement& s, zkwit::Wit& w) {
-            // fewer statements than a fifth of the host threads: each statement's five 252-bit multiplications side by side
-            // (transfer_witness.h synthesize_parallel) - one transaction 1.2 -> 0.35 ms; a batch keeps one thread per statement
-            if (n * 5 <= (size_t)host_threads(64, 64)) zkwit::synthesize_parallel(s, w);
-            else zkwit::synthesize(s, w);
-        });
-}
-
-// Which engine computes the variable assignment of n statements.  ZKAMD_WITNESS = host | gpu forces one.  Default: the GPU
-// generator (witness_gpu.h) - except for a handful of statements: its kernels are serial chains (point decompression 2.0 ms,
-// the 252-bit in-circuit multiplications 5.1 + 0.7 ms, the rest 0.7) that take 8.4 ms whatever the batch holds, while the
-// native host calculator (transfer_witness.h) needs 1.4 ms per statement and host thread.  A transaction proved ALONE - the
-// reference's call pattern, one gen_proof per transfer - is 11.5 ms through the kernels and 4.6 ms with its assignment
-// computed on a host core, as the reference's own synthesize is (profiles/r05_experiments.txt r05k / r05l).  The proof itself
-// (create_proof) is on the GPU either way.  n = SIZE_MAX: a stream of batches (zk_pipeline) - the GPU generator.
-bool witness_on_host(size_t n = (size_t)-1) {
-    if (const char* env = getenv("ZKAMD_WITNESS")) {
-        if (!strcmp(env, "host")) return true;
-        if (!strcmp(env, "gpu")) return false;
-    }
-    // (the crossover, measured with 16 host threads: 64 statements 34.0 against 39.3 ms per call, 128: 51.9 / 53.9, 192: 68.2 / 69.3,
-    //  256: 87.6 / 85.3 - tools/witness_engine_probe.py, profiles/r05end_witness_engine_probe.txt)
-    return n != (size_t)-1 && n <= 8 * (size_t)host_threads(n, 64);
-}
-
-zk_status decode_fs(const uint8_t* b, uint64_t (&v)[4], size_t index, const char* what) {
-    static const uint64_t FS[4] = ZK_JUBJUB_FS_MODULUS_64;
-    load_scalar_le(b, v);
-    for (int i = 3; i >= 0; i--) {
-        if (v[i] < FS[i]) return ZK_OK;
-        if (v[i] > FS[i]) break;
-    }
-    return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index) + ": " + what + " is not a canonical Fs scalar");
-}
-zk_status decode_jubjub(const uint8_t* b, zkwit::JPoint* p, size_t index, const std::string& what) {
-    if (!zkwit::decode_point(b, p))
-        return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index) + ": " + what + " is not a Jubjub point");
-    return ZK_OK;
-}
-
-zk_status anonymous_decode(const zk_anonymous_statement& in, size_t index, zkwit::AnonStatement* out) {
-    if (in.s_index >= ZK_ANONYMOUS_SIZE || in.t_index >= ZK_ANONYMOUS_SIZE)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "statement " + std::to_string(index) + ": member index out of range");
-    out->amount = in.amount;
-    out->remaining_balance = in.remaining_balance;
-    out->s_index = in.s_index;
-    out->t_index = in.t_index;
-    ZK_TRY(decode_fs(in.randomness, out->randomness, index, "randomness"));
-    ZK_TRY(decode_fs(in.alpha, out->alpha, index, "alpha"));
-    ZK_TRY(decode_fs(in.dec_key, out->dec_key, index, "dec_key"));
-    ZK_TRY(decode_jubjub(in.proof_generation_key, &out->pgk, index, "proof_generation_key"));
-    ZK_TRY(decode_jubjub(in.g_epoch, &out->g_epoch, index, "g_epoch"));
-    for (size_t k = 0; k < ZK_ANONYMOUS_SIZE; k++) {
-        const std::string m = "[" + std::to_string(k) + "]";
-        ZK_TRY(decode_jubjub(in.enc_keys[k], &out->enc_keys[k], index, "enc_keys" + m));
-        ZK_TRY(decode_jubjub(in.left_ciphertexts[k], &out->left_ciphertexts[k], index, "left_ciphertexts" + m));
-        ZK_TRY(decode_jubjub(in.enc_balances_left[k], &out->balance_left[k], index, "enc_balances_left" + m));
-        ZK_TRY(decode_jubjub(in.enc_balances_right[k], &out->balance_right[k], index, "enc_balances_right" + m));
-    }
-    return ZK_OK;
-}
-
-zk_status anonymous_witness(const zk_anonymous_statement* st, size_t n, uint32_t flags, uint8_t* out) {
-    if ((!st || !out) && n) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    static_assert(zkwit::ANON_SIZE == ZK_ANONYMOUS_SIZE, "anonymity set size");
-    return witness_batch<zkwit::AnonStatement>(
-        n, ZK_ANONYMOUS_N_INPUTS, ZK_ANONYMOUS_N_AUX, flags, out,
-        [&](size_t i, zkwit::AnonStatement* s) { return anonymous_decode(st[i], i, s); },
-        [](const zkwit::AnonStatement& s, zkwit::Wit& w) { zkwit::synthesize_anonymous(s, w); });
-}
-
-}  // namespace
+#include "statement_route.h"   // (the statement route: host witness calculators, route_check, prove_statements, ...)
 
 // ------------------------------------------------------------------------------------------
 // stand-alone MSM / NTT handles
@@ -1075,8 +920,6 @@ zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const 
 }
 size_t lib_batch_chunk() { return ProveTunables::read().batch_chunk; }
 bool lib_witness_on_host(size_t n) { return witness_on_host(n); }
-int lib_params_device(const zk_params* P) { return P->key.device; }
-size_t lib_params_domain(const zk_params* P) { return P->key.m; }
 }  // namespace zkrt
 
 // ------------------------------------------------------------------------------------------
@@ -1189,58 +1032,18 @@ zk_status zk_r1cs_load(uint32_t n_inputs, uint32_t n_aux, uint32_t n_constraints
 } ZK_ABI_CATCH
 void zk_r1cs_free(zk_r1cs* r) { delete r; }
 
-// the natively emitted constraint system of the transfer circuit (transfer_r1cs.h), built once per process
-static const zkr1cs::System& transfer_system_cached() { return builtin_system(zkpairs::TRANSFER); }
+// the natively emitted constraint systems of the two circuits (statement_route.h)
 zk_status zk_transfer_r1cs_fingerprint(uint8_t hash_out[32], uint32_t* n_inputs, uint32_t* n_aux, uint32_t* n_constraints) try {
-    const zkr1cs::System& sys = transfer_system_cached();
-    if (hash_out) sys.fingerprint(hash_out);
-    if (n_inputs) *n_inputs = sys.n_inputs;
-    if (n_aux) *n_aux = sys.n_aux;
-    if (n_constraints) *n_constraints = sys.n_constraints;
-    return ZK_OK;
+    return system_fingerprint(zkpairs::TRANSFER, hash_out, n_inputs, n_aux, n_constraints);
 } ZK_ABI_CATCH
-static zk_status system_load(const zkr1cs::System& sys, int device, zk_r1cs** out) {
-    std::vector<uint8_t> coeff[3];
-    zk_csr mats[3];
-    for (int m = 0; m < 3; m++) {
-        const zkr1cs::Csr& M = sys.m[m];
-        coeff[m].resize(M.coeff.size() * 32 + 32);
-        for (size_t k = 0; k < M.coeff.size(); k++) {
-            const zkhost::Fr p = M.coeff[k].from_mont();
-            memcpy(&coeff[m][k * 32], p.l, 32);
-        }
-        mats[m].row_ptr = M.row_ptr.data();
-        mats[m].col = M.col.data();
-        mats[m].coeff = coeff[m].data();
-    }
-    const zk_csr* ptrs[3] = {&mats[0], &mats[1], &mats[2]};
-    return r1cs_load(sys.n_inputs, sys.n_aux, sys.n_constraints, ptrs, device, out);
-}
 zk_status zk_transfer_r1cs_load(int device, zk_r1cs** out) try {
-    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    const zkr1cs::System& sys = transfer_system_cached();
-    if (sys.n_inputs != ZK_TRANSFER_N_INPUTS || sys.n_aux != ZK_TRANSFER_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "internal: emitted system has the wrong shape");
-    return system_load(sys, device, out);
+    return system_load(zkpairs::TRANSFER, device, out);
 } ZK_ABI_CATCH
-// the anonymous-transfer circuit, emitted the same way
-static const zkr1cs::System& anonymous_system_cached() { return builtin_system(zkpairs::ANONYMOUS); }
 zk_status zk_anonymous_r1cs_fingerprint(uint8_t hash_out[32], uint32_t* n_inputs, uint32_t* n_aux, uint32_t* n_constraints) try {
-    const zkr1cs::System& sys = anonymous_system_cached();
-    if (hash_out) sys.fingerprint(hash_out);
-    if (n_inputs) *n_inputs = sys.n_inputs;
-    if (n_aux) *n_aux = sys.n_aux;
-    if (n_constraints) *n_constraints = sys.n_constraints;
-    return ZK_OK;
+    return system_fingerprint(zkpairs::ANONYMOUS, hash_out, n_inputs, n_aux, n_constraints);
 } ZK_ABI_CATCH
 zk_status zk_anonymous_r1cs_load(int device, zk_r1cs** out) try {
-    if (!out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    *out = nullptr;
-    const zkr1cs::System& sys = anonymous_system_cached();
-    if (sys.n_inputs != ZK_ANONYMOUS_N_INPUTS || sys.n_aux != ZK_ANONYMOUS_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "internal: emitted system has the wrong shape");
-    return system_load(sys, device, out);
+    return system_load(zkpairs::ANONYMOUS, device, out);
 } ZK_ABI_CATCH
 zk_status zk_prove_batch_witness(zk_params* p, zk_r1cs* circuit, size_t n, const uint8_t* witness, uint32_t flags,
                                  const uint8_t* rs, uint8_t* proofs_out) try {
@@ -1312,7 +1115,7 @@ zk_status zk_hook_prove_plan_pairs(size_t np, uint32_t n_in, uint32_t n_aux, uin
 // emitted system, out = [pred A | succ A | pred B | succ B | pred L | succ L | A-dense | B-dense], 8 nv words
 zk_status zk_hook_pair_chains(int circuit, int32_t* out, size_t cap, uint32_t* nv_out) try {
     if (circuit != 0 && circuit != 1) return fail(ZK_ERR_INVALID_ARGUMENT, "no such circuit");
-    const zkr1cs::System& sys = circuit ? anonymous_system_cached() : transfer_system_cached();
+    const zkr1cs::System& sys = builtin_system((zkpairs::Circuit)circuit);
     const uint32_t nv = sys.n_inputs + sys.n_aux;
     if (nv_out) *nv_out = nv;
     if (!out) return ZK_OK;
@@ -1501,177 +1304,30 @@ zk_status zk_transfer_witness(const zk_transfer_statement* st, size_t n, uint32_
 zk_status zk_anonymous_witness(const zk_anonymous_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
     return anonymous_witness(st, n, flags, witness_out);
 } ZK_ABI_CATCH
+// Statement -> proof (statement_route.h prove_statements): the witnesses of chunk k + 1 - the witness kernels on the side
+// stream, or the native host calculator on the host cores (witness_on_host) - beside the proving of chunk k.  Both engines
+// prove every chunk before the first malformed statement's and report that statement in the same words.
 zk_status zk_transfer_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, const zk_transfer_statement* st,
                                   const uint8_t* rs, uint8_t* proofs_out) try {
     if (!p || !circuit || !rs || !proofs_out || (!st && n)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
-    if (n == 0) return ZK_OK;
-    const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
-    const size_t chunk = ProveTunables::read().batch_chunk;
-    zk_status rc = use_device(p->key.device);
-    if (rc != ZK_OK) return rc;
-    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > p->key.m)
-        return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
-    if (!witness_on_host(n)) {
-        // witnesses on the GPU (witness_gpu.h), on the side stream of the copy engine: the kernels of chunk k + 1
-        // are latency-bound chains for a few hundred waves and run beside the multiexps of chunk k
-        int slot = 0;
-        ZK_TRY(witness_gpu_enqueue(circuit, st, std::min(chunk, n), slot, g_copy_stream));
-        for (size_t first = 0; first < n; first += chunk) {
-            const size_t np = std::min(chunk, n - first), next = first + chunk;
-            ZK_TRY(witness_gpu_finish(circuit, np, slot, first));
-            if (next < n) ZK_TRY(witness_gpu_enqueue(circuit, st + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream));
-            ZK_TRY(prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192, true));
-            slot ^= 1;
-        }
-        return ZK_OK;
-    }
-    // a handful of statements, or ZKAMD_WITNESS=host: the host calculator (transfer_witness.h) on the host cores; two pinned
-    // buffers, the witnesses of chunk k + 1 are computed while the GPU proves chunk k
-    const size_t cap = std::min(chunk, n) * nv * 32;
-    rc = circuit->work.host_ensure(2 * cap);
-    if (rc != ZK_OK) return rc;
-    uint8_t* buf[2] = {(uint8_t*)circuit->work.host_z, (uint8_t*)circuit->work.host_z + cap};
-    rc = transfer_witness(st, std::min(chunk, n), ZK_FR_MONTGOMERY, buf[0]);
-    if (rc != ZK_OK) return rc;
-    int cur = 0;
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t np = std::min(chunk, n - first);
-        const size_t next = first + chunk;
-        zk_status next_rc = ZK_OK;
-        std::string next_err;
-        SideThread producer;
-        if (next < n)
-            producer.start([&, next] {
-                next_rc = transfer_witness(st + next, std::min(chunk, n - next), ZK_FR_MONTGOMERY, buf[cur ^ 1], next);
-                if (next_rc != ZK_OK) next_err = g_err;   // g_err is thread-local
-            });
-        rc = prove_batch_witness(p, circuit, np, buf[cur], ZK_FR_MONTGOMERY, rs + first * 64, proofs_out + first * 192, true);
-        producer.join();
-        if (rc != ZK_OK) return rc;
-        if (next_rc != ZK_OK) return fail(next_rc, next_err);
-        cur ^= 1;
-    }
-    return ZK_OK;
+    ZK_TRY(route_check(p, circuit, zkpairs::TRANSFER, n));
+    return n ? prove_statements(p, circuit, zkpairs::TRANSFER, st, n, rs, proofs_out) : ZK_OK;
 } ZK_ABI_CATCH
-
-// Statement -> proof for the anonymous-transfer circuit (core/proofs/src/anonymous.rs:165: create_random_proof of
-// AnonymousTransfer): witness generation on the GPU (witness_anon_gpu.h, round 4), the kernels of chunk k + 1 beside the
-// proving of chunk k; ZKAMD_WITNESS=host keeps the native host calculator (transfer_witness.h: synthesize_anonymous) on
-// the host cores.  Both paths prove every chunk before the first malformed statement's and report that statement in the
-// same words.
+// ... for the anonymous-transfer circuit (core/proofs/src/anonymous.rs:165: create_random_proof of AnonymousTransfer)
 zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, const zk_anonymous_statement* st, const uint8_t* rs,
                                    uint8_t* proofs_out) try {
     if (!p || !circuit || !rs || !proofs_out || (!st && n)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->sys.n_in != ZK_ANONYMOUS_N_INPUTS || circuit->sys.n_aux != ZK_ANONYMOUS_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the anonymous-transfer circuit's");
-    if (n == 0) return ZK_OK;
-    ZK_TRY(use_device(p->key.device));
-    const size_t nv = ZK_ANONYMOUS_N_INPUTS + ZK_ANONYMOUS_N_AUX;
-    size_t chunk = ProveTunables::read().batch_chunk;
-    if (chunk > 512) chunk = 512;   // domain 2^16: half the proofs of a transfer chunk fill the same workspaces
-    if (!witness_on_host(n)) {
-        // witness generation on the GPU (witness_anon_gpu.h), statement in: 1.7 KB instead of 1.6 MB of witness vector; the
-        // kernels of chunk k + 1 run beside the multiexps of chunk k (as zk_transfer_prove_batch)
-        if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
-        int slot = 0;
-        zk_status rc = witness_anon_gpu_enqueue(circuit, st, std::min(chunk, n), slot, g_copy_stream);
-        for (size_t first = 0; first < n && rc == ZK_OK; first += chunk) {
-            const size_t np = std::min(chunk, n - first), next = first + chunk;
-            rc = witness_anon_gpu_finish(circuit, np, slot, first);
-            if (rc == ZK_OK && next < n) rc = witness_anon_gpu_enqueue(circuit, st + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream, next);
-            if (rc == ZK_OK) rc = prove_from_z(p, circuit, np, slot, rs + first * 64, proofs_out + first * 192, true);
-            slot ^= 1;
-        }
-        if (rc != ZK_OK) {
-            const std::string why = g_err;
-            (void)hipStreamSynchronize(g_copy_stream);   // no witness kernel of a later chunk stays in flight behind an error
-            g_err = why;
-        }
-        return rc;
-    }
-    const size_t cap = std::min(chunk, n) * nv * 32;
-    ZK_TRY(circuit->work.host_ensure(2 * cap));
-    uint8_t* buf[2] = {(uint8_t*)circuit->work.host_z, (uint8_t*)circuit->work.host_z + cap};
-    auto witness = [&](size_t first, size_t np, uint8_t* out) -> zk_status {
-        return witness_batch<zkwit::AnonStatement>(
-            np, ZK_ANONYMOUS_N_INPUTS, ZK_ANONYMOUS_N_AUX, ZK_FR_MONTGOMERY, out,
-            [&](size_t i, zkwit::AnonStatement* s) { return anonymous_decode(st[first + i], first + i, s); },
-            [](const zkwit::AnonStatement& s, zkwit::Wit& w) { zkwit::synthesize_anonymous(s, w); });
-    };
-    ZK_TRY(witness(0, std::min(chunk, n), buf[0]));
-    int cur = 0;
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t np = std::min(chunk, n - first), next = first + chunk;
-        zk_status next_rc = ZK_OK;
-        std::string next_err;
-        SideThread producer;
-        if (next < n)
-            producer.start([&, next] {
-                next_rc = witness(next, std::min(chunk, n - next), buf[cur ^ 1]);
-                if (next_rc != ZK_OK) next_err = g_err;
-            });
-        // prove_batch_witness cuts at its own chunk size: keep the two equal for this call
-        zk_status rc = ZK_OK;
-        for (size_t off = 0; off < np && rc == ZK_OK; off += chunk)
-            rc = prove_batch_witness(p, circuit, std::min(chunk, np - off), buf[cur] + off * nv * 32, ZK_FR_MONTGOMERY,
-                                     rs + (first + off) * 64, proofs_out + (first + off) * 192, true);
-        producer.join();
-        if (rc != ZK_OK) return rc;
-        if (next_rc != ZK_OK) return fail(next_rc, next_err);
-        cur ^= 1;
-    }
-    return ZK_OK;
+    ZK_TRY(route_check(p, circuit, zkpairs::ANONYMOUS, n));
+    return n ? prove_statements(p, circuit, zkpairs::ANONYMOUS, st, n, rs, proofs_out) : ZK_OK;
 } ZK_ABI_CATCH
 
-// The witness vectors the GPU generator of the anonymous circuit produces, copied back to the host (tests: element by
-// element against zk_anonymous_witness).  witness_out: n x (105 + 50429) x 32 bytes.
-zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
-    if (!circuit || (n && (!st || !witness_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->sys.n_in != ZK_ANONYMOUS_N_INPUTS || circuit->sys.n_aux != ZK_ANONYMOUS_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the anonymous-transfer circuit's");
-    ZK_TRY(use_device(circuit->sys.device));
-    const size_t nv = ZK_ANONYMOUS_N_INPUTS + ZK_ANONYMOUS_N_AUX, chunk = 256;
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t np = std::min(chunk, n - first);
-        ZK_TRY(witness_anon_gpu_enqueue(circuit, st + first, np, 0, g_stream, first));
-        ZK_TRY(witness_anon_gpu_finish(circuit, np, 0, first));
-        if (!(flags & ZK_FR_MONTGOMERY)) {
-            const size_t cnt = np * nv;
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->work.z[0].as<uint32_t>(),
-                      (const uint32_t*)circuit->work.z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->work.z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
-    }
-    return ZK_OK;
-} ZK_ABI_CATCH
-
-// The witness vectors the GPU generator produces, copied back to the host: lets the tests compare it with the
-// host calculator (zk_transfer_witness) element by element.  witness_out: n x (23 + 19955) x 32 bytes.
+// The witness vectors the GPU generators produce, copied back to the host (tests: element by element against zk_transfer_witness
+// / zk_anonymous_witness).  witness_out: n x (23 + 19955) x 32 bytes / n x (105 + 50429) x 32 bytes.
 zk_status zk_transfer_witness_gpu(zk_r1cs* circuit, const zk_transfer_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
-    if (!circuit || (n && (!st || !witness_out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    ZK_TRY(use_device(circuit->sys.device));
-    const size_t nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, chunk = ProveTunables::read().batch_chunk;
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t np = std::min(chunk, n - first);
-        ZK_TRY(witness_gpu_enqueue(circuit, st + first, np, 0, g_stream));
-        ZK_TRY(witness_gpu_finish(circuit, np, 0, first));
-        if (!(flags & ZK_FR_MONTGOMERY)) {
-            const size_t cnt = np * nv;
-            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, circuit->work.z[0].as<uint32_t>(),
-                      (const uint32_t*)circuit->work.z[0].as<uint32_t>(), 1u, cnt, (uint32_t*)nullptr);
-            HIP_TRY(hipGetLastError());
-        }
-        HIP_TRY(hipStreamSynchronize(g_stream));
-        HIP_TRY(hipMemcpy(witness_out + first * nv * 32, circuit->work.z[0].p, np * nv * 32, hipMemcpyDeviceToHost));
-    }
-    return ZK_OK;
+    return witness_readback(circuit, zkpairs::TRANSFER, st, n, flags, witness_out);
+} ZK_ABI_CATCH
+zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statement* st, size_t n, uint32_t flags, uint8_t* witness_out) try {
+    return witness_readback(circuit, zkpairs::ANONYMOUS, st, n, flags, witness_out);
 } ZK_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------
@@ -1876,20 +1532,13 @@ extern "C" {
 zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) try {
     if (!p || !circuit || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
-    if (circuit->sys.n_in != ZK_TRANSFER_N_INPUTS || circuit->sys.n_aux != ZK_TRANSFER_N_AUX)
-        return fail(ZK_ERR_INVALID_ARGUMENT, "the loaded constraint matrices are not the transfer circuit's");
-    if (circuit->sys.device != p->key.device) return fail(ZK_ERR_INVALID_ARGUMENT, "parameters and circuit live on different devices");
-    ZK_TRY(use_device(p->key.device));
+    ZK_TRY(route_check(p, circuit, zkpairs::TRANSFER));
     zk_pipeline* L = new (std::nothrow) zk_pipeline();
     if (!L) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
     L->P = p;
     L->R = circuit;
     L->nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
     L->chunk = ProveTunables::read().batch_chunk;
-    if ((size_t)circuit->sys.n_con + circuit->sys.n_in > p->key.m) {
-        delete L;
-        return fail(ZK_ERR_POLYNOMIAL_DEGREE_TOO_LARGE, "more rows than the key's evaluation domain");
-    }
     (void)zkwit::tables();
     {
         // the derived bases of the pair before the lanes borrow the key's tables: every lane binds to the same set
