@@ -82,6 +82,10 @@
  *   zk_anonymous_witness, zk_anonymous_witness_gpu   value half of AnonymousTransfer::synthesize          circuit/anonymous_transfer.rs:40-54, 56-337
  *   zk_anonymous_prove_batch        synthesize + create_random_proof              anonymous.rs:147-165
  *   zk_anonymous_derive             the derivations at the head of gen_proof      anonymous.rs:97-146
+ *   zk_r1cs_check_batch, zk_transfer_check_batch, zk_anonymous_check_batch
+ *                                   TestConstraintSystem::which_is_unsatisfied / is_satisfied   core/proofs/src/circuit/test.rs:253-272
+ *   zk_r1cs_stage                   - (the namespace half of which_is_unsatisfied's answer, circuit/test.rs:253-272: the part of a
+ *                                   built-in circuit a constraint index lies in, in this library's own words)
  *   zk_anonymous_gen_proof_batch    ProofBuilder::gen_proof (Anonymous)           anonymous.rs:97-183, check_proof :213-264
  *   zk_generate_parameters          generate_random_parameters                    core/proofs/src/setup.rs:28-31, 59-62
  *   zk_vk_prepare                   prepare_verifying_key                         core/bellman-verifier/src/verifier.rs:15-30
@@ -499,6 +503,39 @@ zk_status zk_anonymous_prove_batch(zk_params* p, zk_r1cs* circuit, size_t n, con
  * source beside them, which has 50 514 constraints. */
 zk_status zk_anonymous_r1cs_load(int device, zk_r1cs** out);
 zk_status zk_anonymous_r1cs_fingerprint(uint8_t hash_out[32], uint32_t* n_inputs, uint32_t* n_aux, uint32_t* n_constraints);
+
+/* ------------------------------------------------------------------------------------------
+ * Which constraint an assignment breaks, checked on the GPU before anything is proved.
+ * replaces: TestConstraintSystem::which_is_unsatisfied / is_satisfied (core/proofs/src/circuit/test.rs:253-272).
+ * The proving entries turn an assignment that satisfies nothing into 192 bytes that do not verify; these entries say
+ * beforehand, per assignment, whether a_j * b_j = c_j holds for every constraint j of the loaded matrices, and where it
+ * does not - with no key, no transform and no multiexp (csrc/r1cs_check.h).
+ *   first_bad  the lowest j with a_j * b_j != c_j, or ZK_R1CS_SATISFIED
+ *   n_bad      how many such j
+ *   flags      ZK_R1CS_ONE_IS_NOT_ONE: input 0 of the assignment is not 1 (such a vector may satisfy every row and
+ *              still does not verify: ONE is an input like any other)
+ * A verdict is not an error: an unsatisfied assignment returns ZK_OK with its verdict filled in.  n = 0 writes nothing.
+ * zk_r1cs_check_batch: any loaded system; witness as for zk_prove_batch_witness (n x (n_inputs + n_aux) x 32 bytes, plain
+ * or ZK_FR_MONTGOMERY; a scalar >= r is ZK_ERR_INVALID_ARGUMENT), in the same chunks.  zk_transfer_check_batch /
+ * zk_anonymous_check_batch: the statements of the built-in circuits, through the witness engine the prove entries would
+ * pick (ZKAMD_WITNESS) and with their refusals of a malformed statement.  out: n verdicts.
+ * zk_r1cs_stage names the part of a built-in circuit a constraint lies in ("range: amount", "balance equation", ...):
+ * *stage_out = its number in the circuit's order, [*first_out, *first_out + *count_out) its constraints, name_out its
+ * name (cut to name_cap - 1 characters, always terminated); every out pointer may be null.  Matrices loaded with
+ * zk_r1cs_load carry no table: *stage_out = 0xFFFFFFFF, the whole system as the range and an empty name.  A constraint
+ * >= n_constraints is ZK_ERR_INVALID_ARGUMENT.
+ * ------------------------------------------------------------------------------------------ */
+#define ZK_R1CS_SATISFIED 0xFFFFFFFFu
+#define ZK_R1CS_ONE_IS_NOT_ONE 1u
+typedef struct {
+    uint32_t first_bad, n_bad, flags, reserved;
+} zk_r1cs_verdict;
+zk_status zk_r1cs_check_batch(zk_r1cs* circuit, size_t n, const uint8_t* witness, uint32_t flags, zk_r1cs_verdict* out);
+zk_status zk_transfer_check_batch(zk_r1cs* circuit, size_t n, const zk_transfer_statement* st, zk_r1cs_verdict* out);
+zk_status zk_anonymous_check_batch(zk_r1cs* circuit, size_t n, const zk_anonymous_statement* st, zk_r1cs_verdict* out);
+zk_status zk_r1cs_stage(const zk_r1cs* circuit, uint32_t constraint, uint32_t* stage_out, uint32_t* first_out,
+                        uint32_t* count_out, char* name_out, size_t name_cap);
+
 /* gen_proof of the anonymous transfer (ProofBuilder::gen_proof, core/proofs/src/anonymous.rs:97-183): the key
  * derivations of the confidential entry, the anonymity set assembled with the sender at s_index, the recipient at
  * t_index and the ten decoys in their order elsewhere (:117-126), MultiCiphertexts::<Anonymous>::encrypt

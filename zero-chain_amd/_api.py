@@ -23,7 +23,7 @@ from ._shard import shard_bounds, gather_proofs, prove_sharded
 from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSET, ZK_NTT_IN_BITREV,
                    ZK_NTT_OUT_BITREV)
 
-__all__ = ["Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
+__all__ = ["transfer_check", "anonymous_check", "Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "jubjub_base_mul_dev", "hd_master", "hd_xpgk", "hd_derive", "HD_XKEY_BYTES", "HD_XSK", "HD_XPGK", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
@@ -784,6 +784,30 @@ class ConstraintMatrices:
                                                C.byref(structs[2]), device, C.byref(h)))
         self._h = h
 
+    def check(self, witnesses, montgomery=False):
+        """zk_r1cs_check_batch: which constraint each assignment breaks, checked on the GPU with no key.  witnesses as for
+        `create_proofs_from_witness` (with montgomery=True: raw Montgomery limbs).  One (first_bad or None, n_bad, one_ok)
+        per assignment: the lowest unsatisfied constraint, how many there are, and whether input 0 is ONE = 1."""
+        nv = self.n_inputs + self.n_aux
+        if isinstance(witnesses, np.ndarray):
+            w = _u8(witnesses)
+            n = w.size // (nv * 32)
+            w = _u8(w, n * nv * 32)
+        else:
+            n = len(witnesses)
+            w = scalars_to_bytes([x for z in witnesses for x in z]) if n else np.zeros(0, dtype=np.uint8)
+        out = (_lib.R1csVerdict * max(n, 1))()
+        self._lib.check(self._lib.zk_r1cs_check_batch(self._h, n, _ptr(w) if n else None, ZK_FR_MONTGOMERY if montgomery else 0, out))
+        return _verdicts(out, n)
+
+    def stage(self, constraint):
+        """zk_r1cs_stage: (stage number or None, first constraint, count, name) of the part of a built-in circuit the
+        constraint lies in; a system built from a constraint list has no table: (None, 0, n_constraints, "")."""
+        stage, first, count = C.c_uint32(0), C.c_uint32(0), C.c_uint32(0)
+        name = C.create_string_buffer(128)
+        self._lib.check(self._lib.zk_r1cs_stage(self._h, constraint, C.byref(stage), C.byref(first), C.byref(count), name, len(name)))
+        return (None if stage.value == 0xFFFFFFFF else stage.value), first.value, count.value, name.value.decode()
+
     def close(self):
         if self._h:
             self._lib.zk_r1cs_free(self._h)
@@ -794,6 +818,30 @@ class ConstraintMatrices:
             self.close()
         except Exception:
             pass
+
+
+def _verdicts(out, n):
+    return [(None if v.first_bad == _lib.ZK_R1CS_SATISFIED else v.first_bad, v.n_bad, not (v.flags & _lib.ZK_R1CS_ONE_IS_NOT_ONE))
+            for v in out[:n]]
+
+
+def transfer_check(matrices, statements):
+    """zk_transfer_check_batch: statements of the transfer circuit -> [(first_bad or None, n_bad, one_ok)], through the
+    witness engine zk_transfer_prove_batch would pick and no key: what a prover service asks before it pays for a proof."""
+    lib = matrices._lib
+    n = len(statements)
+    out = (_lib.R1csVerdict * max(n, 1))()
+    lib.check(lib.zk_transfer_check_batch(matrices._h, n, statements, out))
+    return _verdicts(out, n)
+
+
+def anonymous_check(matrices, statements):
+    """zk_anonymous_check_batch: the same for statements of the anonymous-transfer circuit."""
+    lib = matrices._lib
+    n = len(statements)
+    out = (_lib.R1csVerdict * max(n, 1))()
+    lib.check(lib.zk_anonymous_check_batch(matrices._h, n, statements, out))
+    return _verdicts(out, n)
 
 
 def create_proofs_from_witness(matrices, params, witnesses, rs, montgomery=False):

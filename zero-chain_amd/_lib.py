@@ -15,6 +15,7 @@ HOOKS_LIB_PATH = os.path.join(HERE, "libzkamd_hooks.so")
 
 ZK_OK = 0
 ZK_FR_MONTGOMERY = 1
+ZK_R1CS_SATISFIED, ZK_R1CS_ONE_IS_NOT_ONE = 0xFFFFFFFF, 1
 ZK_NTT_INVERSE, ZK_NTT_COSET, ZK_NTT_IN_BITREV, ZK_NTT_OUT_BITREV = 1, 2, 4, 8
 
 STATUS_NAMES = {
@@ -132,6 +133,10 @@ class BalanceHit(C.Structure):
     _fields_ = [("account", C.c_uint32), ("key", C.c_uint32), ("r", BalanceResult)]
 
 
+class R1csVerdict(C.Structure):
+    _fields_ = [(n, C.c_uint32) for n in ("first_bad", "n_bad", "flags", "reserved")]
+
+
 class BatchDev(C.Structure):
     _fields_ = [("n_rows", C.c_uint32), ("n_inputs", C.c_uint32), ("n_aux", C.c_uint32), ("flags", C.c_uint32),
                 ("d_a", C.c_void_p), ("d_b", C.c_void_p), ("d_c", C.c_void_p), ("d_wit", C.c_void_p),
@@ -163,6 +168,11 @@ _PROTOS = {
     "zk_anonymous_gen_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousRequest), C.c_void_p,
                                                  C.POINTER(AnonymousXt)]),
     "zk_anonymous_r1cs_fingerprint": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
+    "zk_r1cs_check_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.POINTER(R1csVerdict)]),
+    "zk_transfer_check_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(TransferStatement), C.POINTER(R1csVerdict)]),
+    "zk_anonymous_check_batch": (C.c_int32, [C.c_void_p, C.c_size_t, C.POINTER(AnonymousStatement), C.POINTER(R1csVerdict)]),
+    "zk_r1cs_stage": (C.c_int32, [C.c_void_p, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.c_char_p,
+                                  C.c_size_t]),
     "zk_prove_batch_witness": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "zk_transfer_witness": (C.c_int32, [C.POINTER(TransferStatement), C.c_size_t, C.c_uint32, C.c_void_p]),
     "zk_transfer_witness_gpu": (C.c_int32, [C.c_void_p, C.POINTER(TransferStatement), C.c_size_t, C.c_uint32, C.c_void_p]),

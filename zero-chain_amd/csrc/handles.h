@@ -18,6 +18,10 @@ struct zk_r1cs {
         // host copy of the matrices (the parameter generator transposes them): CSR, Montgomery coefficients
         std::vector<uint32_t> h_row_ptr[3], h_col[3];
         std::vector<zkhost::Fr> h_coeff[3];
+        // the parts of a built-in circuit (transfer_r1cs.h System::mark), ascending: stage k is the constraints
+        // [stage_first[k], stage_first[k + 1]) - the last one ends at n_con.  Empty for matrices a caller loaded.
+        std::vector<uint32_t> stage_first;
+        std::vector<std::string> stage_name;
         // The matrices on the GPU borrowed, the shape and the densities copied; o must outlive this one.  The host copy stays
         // with o alone: a key is bound to the circuit through the handle that loaded it (ensure_derived does nothing without).
         void share(const System& o) {
@@ -32,6 +36,8 @@ struct zk_r1cs {
             a_aux_density = o.a_aux_density;
             b_input_density = o.b_input_density;
             b_aux_density = o.b_aux_density;
+            stage_first = o.stage_first;
+            stage_name = o.stage_name;
         }
     } sys;
     // What the proving calls on this handle fill.  Every handle has its own: a lane's clone starts with none.
@@ -39,6 +45,8 @@ struct zk_r1cs {
         // per-chunk workspaces: Montgomery assignment (two: the witness kernels fill one while the prover reads the
         // other), row evaluations
         zkrt::DevBuf z[2], abc;
+        // the constraint check (r1cs_check.h): 16 bytes of flags over the caller's scalars | one verdict per assignment
+        zkrt::DevBuf verdict;
         // GPU witness generator of the transfer circuit (witness_gpu.h)
         zkrt::DevBuf wit_st[2], wit_bad[2], wit_pts, wit_table, wit_consts, wit_scratch;
         zkrt::PinBuf pin_st[2], pin_bad[2];
@@ -48,7 +56,7 @@ struct zk_r1cs {
         // pinned host buffer of zk_transfer_prove_batch in host-witness mode (witness vectors of one chunk)
         void* host_z = nullptr;
         size_t host_z_cap = 0;
-        Work() {}
+        Work() { verdict.is_public = true; }
         Work(const Work&) = delete;
         Work& operator=(const Work&) = delete;
         ~Work() {

@@ -199,13 +199,16 @@ zk_status zkrt::route_check(zk_params* P, zk_r1cs* R, int circuit, size_t n) {
 
 namespace {
 
-// Statements -> proofs, n > 0 of them behind route_check, in chunks of the circuit's launch set over two slots: the witnesses of
-// chunk k + 1 are made while the GPU proves chunk k, and a malformed statement among them is reported once chunk k is proved.
+// The chunk loop of the statement entries, n > 0 statements behind route_check, in chunks of the circuit's launch set over two
+// slots: the witnesses of chunk k + 1 are made while step(first, np, slot, host_z) works on chunk k, and a malformed
+// statement among them is reported once chunk k is done.  host_z: the chunk's assignments where the host engine made them
+// (Montgomery form), null where the witness kernels left them in R->work.z[slot].
 //   the witness kernels (witness_gpu.h / witness_anon_gpu.h), on the side stream of the copy engine: latency-bound chains for a
 //     few hundred waves beside the multiexps; a slot is R->work.z[slot];
 //   a handful of statements, or ZKAMD_WITNESS=host (witness_on_host): the host calculator on the host cores, in a thread beside
 //     the caller; a slot is one half of the pinned R->work.host_z.
-zk_status prove_statements(zk_params* P, zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, const uint8_t* rs, uint8_t* out) {
+template <class Step>
+zk_status statement_chunks(zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, Step&& step) {
     const StatementRoute& T = STATEMENT_ROUTES[circuit];
     const size_t chunk = T.chunk(), half = std::min(chunk, n) * T.nv() * 32;
     const bool host = witness_on_host(n);
@@ -235,9 +238,7 @@ zk_status prove_statements(zk_params* P, zk_r1cs* R, zkpairs::Circuit circuit, c
         const size_t np = std::min(chunk, n - first), next = first + chunk;
         rc = ready(first, np, slot);
         if (rc == ZK_OK && next < n) rc = start(next, slot ^ 1);
-        if (rc == ZK_OK)
-            rc = host ? prove_batch_witness(P, R, np, host_z + slot * half, ZK_FR_MONTGOMERY, rs + first * 64, out + first * 192, true)
-                      : prove_from_z(P, R, np, slot, rs + first * 64, out + first * 192, true);
+        if (rc == ZK_OK) rc = step(first, np, slot, host ? host_z + slot * half : (const uint8_t*)nullptr);
     }
     if (rc != ZK_OK) {   // no witness kernel of a later chunk stays in flight behind an error (nor its thread: joined as `side` goes)
         const std::string why = g_err;
@@ -245,6 +246,22 @@ zk_status prove_statements(zk_params* P, zk_r1cs* R, zkpairs::Circuit circuit, c
         g_err = why;
     }
     return rc;
+}
+
+// Statements -> proofs: a chunk's step is row evaluations + create_proof over the derived bases of the pair
+zk_status prove_statements(zk_params* P, zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, const uint8_t* rs, uint8_t* out) {
+    return statement_chunks(R, circuit, st, n, [&](size_t first, size_t np, int slot, const uint8_t* host_z) {
+        return host_z ? prove_batch_witness(P, R, np, host_z, ZK_FR_MONTGOMERY, rs + first * 64, out + first * 192, true)
+                      : prove_from_z(P, R, np, slot, rs + first * 64, out + first * 192, true);
+    });
+}
+
+// Statements -> verdicts: a chunk's step is the constraint check (r1cs_check.h) of its assignments - the host engine's uploaded
+// into R->work.z[0] first, the same kernel over either
+zk_status check_statements(zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, zk_r1cs_verdict* out) {
+    return statement_chunks(R, circuit, st, n, [&](size_t first, size_t np, int slot, const uint8_t* host_z) {
+        return host_z ? check_batch_witness(R, np, host_z, ZK_FR_MONTGOMERY, out + first, true) : check_from_z(R, np, slot, out + first);
+    });
 }
 
 // The witness vectors the GPU generator of a circuit produces, copied back to the host: lets the tests compare it with the
@@ -299,7 +316,16 @@ zk_status system_load(zkpairs::Circuit circuit, int device, zk_r1cs** out) {
         mats[m].coeff = coeff[m].data();
     }
     const zk_csr* ptrs[3] = {&mats[0], &mats[1], &mats[2]};
-    return r1cs_load(sys.n_inputs, sys.n_aux, sys.n_constraints, ptrs, device, out);
+    std::vector<uint32_t> stage_first;   // the parts of the circuit, for zk_r1cs_stage
+    std::vector<std::string> stage_name;
+    for (const auto& mk : sys.marks) {
+        stage_first.push_back(mk.first);
+        stage_name.push_back(mk.second);
+    }
+    ZK_TRY(r1cs_load(sys.n_inputs, sys.n_aux, sys.n_constraints, ptrs, device, out));
+    (*out)->sys.stage_first.swap(stage_first);
+    (*out)->sys.stage_name.swap(stage_name);
+    return ZK_OK;
 }
 
 }  // namespace

@@ -15,6 +15,8 @@
 #pragma once
 #include <array>
 #include <map>
+#include <string>
+#include <utility>
 #include <vector>
 #include "blake2s.h"
 #include "transfer_witness.h"
@@ -72,6 +74,14 @@ struct System {
     std::array<Csr, 3> m;
     // rows are normalised against the FINAL number of inputs, so the raw rows are kept until finish()
     std::vector<std::array<std::vector<Term>, 3>> raw;
+
+    // the parts of the circuit (zk_r1cs_stage): the constraints from a mark up to the next one carry its name.  A mark emits
+    // nothing; one placed where the last one stands (a part without rows of its own) takes its place.
+    std::vector<std::pair<uint32_t, std::string>> marks;
+    void mark(const char* name) {
+        if (!marks.empty() && marks.back().first == n_constraints) marks.pop_back();
+        marks.emplace_back(n_constraints, name);
+    }
 
     Var alloc() { return AUX | n_aux++; }
     Var alloc_input() { return n_inputs++; }
@@ -337,54 +347,82 @@ inline Pt fixed_base_multiplication(System& cs, const Bits& by) {
 // confidential_transfer.rs:61-305
 inline System transfer_system() {
     System cs;
+    cs.mark("range: amount");
     const Bits amount_bits = u32_into_bit_vec_le(cs);
+    cs.mark("range: remaining balance");
     const Bits remaining_bits = u32_into_bit_vec_le(cs);
+    cs.mark("range: fee");
     const Bits fee_bits = u32_into_bit_vec_le(cs);
+    cs.mark("decryption key bits");
     const Bits dec_key_bits = field_into_boolean_vec_le(cs);
+    cs.mark("fixed-base: sender's encryption key");
     const Pt enc_key_sender = fixed_base_multiplication(cs, dec_key_bits);
     pt_inputize(cs, enc_key_sender);
+    cs.mark("fixed-base: amount");
     const Pt amount_g = fixed_base_multiplication(cs, amount_bits);
+    cs.mark("fixed-base: fee");
     const Pt fee_g = fixed_base_multiplication(cs, fee_bits);
+    cs.mark("randomness bits");
     const Bits randomness_bits = field_into_boolean_vec_le(cs);
+    cs.mark("variable-base: randomness x sender's key");
     const Pt val_rls = pt_mul(cs, enc_key_sender, randomness_bits);
+    cs.mark("small order: recipient's encryption key");
     const Pt enc_key_recipient = pt_witness(cs);
     pt_assert_not_small_order(cs, enc_key_recipient);
+    cs.mark("variable-base: randomness x recipient's key");
     const Pt val_rlr = pt_mul(cs, enc_key_recipient, randomness_bits);
     pt_inputize(cs, enc_key_recipient);
+    cs.mark("ciphertexts: left parts");
     const Pt c_left_sender = pt_add(cs, amount_g, val_rls);
     const Pt c_left_recipient = pt_add(cs, amount_g, val_rlr);
+    cs.mark("fixed-base: randomness");
     const Pt c_right = fixed_base_multiplication(cs, randomness_bits);
+    cs.mark("ciphertexts: fee and public inputs");
     const Pt f_left_sender = pt_add(cs, fee_g, val_rls);
     pt_inputize(cs, c_left_sender);
     pt_inputize(cs, c_left_recipient);
     pt_inputize(cs, c_right);
     pt_inputize(cs, f_left_sender);
+    cs.mark("small order: encrypted balance, left");
     const Pt bal_left = pt_witness(cs);
     const Pt bal_right = pt_witness(cs);
     pt_assert_not_small_order(cs, bal_left);
+    cs.mark("small order: encrypted balance, right");
     pt_assert_not_small_order(cs, bal_right);
+    cs.mark("variable-base: decryption key x right ciphertext");
     const Pt dksr = pt_mul(cs, c_right, dec_key_bits);
+    cs.mark("balance: left side");
     const Pt bal_dksr = pt_add(cs, bal_left, dksr);
     const Pt bi_left = pt_add(cs, bal_dksr, dksr);
+    cs.mark("variable-base: decryption key x encrypted balance, right");
     const Pt dkspr = pt_mul(cs, bal_right, dec_key_bits);
+    cs.mark("fixed-base: remaining balance");
     const Pt rem_bal_g = fixed_base_multiplication(cs, remaining_bits);
+    cs.mark("balance: right side");
     const Pt val_rem_bal = pt_add(cs, c_left_sender, rem_bal_g);
     const Pt val_rem_bal_balr = pt_add(cs, val_rem_bal, dkspr);
     const Pt bi_right = pt_add(cs, f_left_sender, val_rem_bal_balr);
     // eq_edwards_points (utils.rs:10-37)
+    cs.mark("balance equation");
     cs.enforce(lc(bi_left.x), lc(ONE), lc(bi_right.x));
     cs.enforce(lc(bi_left.y), lc(ONE), lc(bi_right.y));
+    cs.mark("encrypted balance as public input");
     pt_inputize(cs, bal_left);
     pt_inputize(cs, bal_right);
     // rvk_inputize (utils.rs:71-123)
+    cs.mark("rvk: small order of the proof generation key");
     const Pt pgk = pt_witness(cs);
     pt_assert_not_small_order(cs, pgk);
+    cs.mark("rvk: alpha bits");
     const Bits alpha_bits = field_into_boolean_vec_le(cs);
+    cs.mark("rvk: fixed-base alpha");
     const Pt alpha_g = fixed_base_multiplication(cs, alpha_bits);
+    cs.mark("rvk: sum and its small order");
     const Pt rvk = pt_add(cs, pgk, alpha_g);
     pt_assert_not_small_order(cs, rvk);
     pt_inputize(cs, rvk);
     // g_epoch_nonce_inputize (utils.rs:125-154)
+    cs.mark("nonce: variable-base decryption key x g_epoch");
     const Pt g_epoch = pt_witness(cs);
     const Pt nonce = pt_mul(cs, g_epoch, dec_key_bits);
     pt_inputize(cs, g_epoch);
@@ -432,34 +470,53 @@ inline std::vector<Pt> pt_witness_set(System& cs) {
 
 inline System anonymous_system() {
     System cs;
+    cs.mark("zero point");
     const Pt zero_p = pt_witness(cs);
+    cs.mark("range: amount");
     const Bits amount_bits = u32_into_bit_vec_le(cs);
+    cs.mark("fixed-base: amount");
     const Pt amount_g = fixed_base_multiplication(cs, amount_bits);
+    cs.mark("range: remaining balance");
     const Bits remaining_bits = u32_into_bit_vec_le(cs);
+    cs.mark("fixed-base: remaining balance");
     const Pt remaining_g = fixed_base_multiplication(cs, remaining_bits);
+    cs.mark("decryption key bits");
     const Bits dec_key_bits = field_into_boolean_vec_le(cs);
+    cs.mark("member selectors s and t");
     const Bits s_bins = binary(cs);
     const Bits t_bins = binary(cs);
+    cs.mark("sender's key: fold of the set over s");
     const std::vector<Pt> enc_key_set = pt_witness_set(cs);
     const Pt expected_enc_key_sender = add_fold(cs, s_bins, enc_key_set, zero_p);
+    cs.mark("fixed-base: sender's encryption key");
     const Pt enc_key_sender = fixed_base_multiplication(cs, dec_key_bits);
+    cs.mark("sender's key equation");
     eq_points(cs, expected_enc_key_sender, enc_key_sender);                 // sk * G = sum s_i y_i
     // EncKeySet::gen_enc_keys_mul_random (anonimity_set.rs:230-256)
+    cs.mark("randomness bits");
     const Bits randomness_bits = field_into_boolean_vec_le(cs);
     std::vector<Pt> enc_keys_mul_random;
-    for (const Pt& y : enc_key_set) enc_keys_mul_random.push_back(pt_mul(cs, y, randomness_bits));
+    for (const Pt& y : enc_key_set) {
+        cs.mark("variable-base: randomness x a member's key");
+        enc_keys_mul_random.push_back(pt_mul(cs, y, randomness_bits));
+    }
+    cs.mark("recipient's ciphertext: folds over t");
     const std::vector<Pt> left_set = pt_witness_set(cs);
     // sum t_i C_i = b_1 G + sum t_i r y_i
     const Pt fold_t = add_fold(cs, t_bins, enc_keys_mul_random, zero_p);
     const Pt expected_left_t = pt_add(cs, fold_t, amount_g);
     const Pt left_t = add_fold(cs, t_bins, left_set, zero_p);
+    cs.mark("recipient's ciphertext equation");
     eq_points(cs, expected_left_t, left_t);
+    cs.mark("sender and recipient: folds over s xor t");
     // sum (s_i xor t_i) C_i = sum (s_i xor t_i) r y_i
     Bits xor_st;
     for (size_t i = 0; i < ANONIMITY_SIZE; i++) xor_st.push_back(xor_allocated(cs, s_bins[i], t_bins[i]));
     const Pt fold_keys_xor = add_fold(cs, xor_st, enc_keys_mul_random, zero_p);
     const Pt fold_left_xor = add_fold(cs, xor_st, left_set, zero_p);
+    cs.mark("sender and recipient equation");
     eq_points(cs, fold_left_xor, fold_keys_xor);
+    cs.mark("decoys: zero ciphertexts");
     // (1 - s_i)(1 - t_i) C_i = (1 - s_i)(1 - t_i) r y_i   (Binary::nor, conditionally_equals)
     Bits nor_st;
     for (size_t i = 0; i < ANONIMITY_SIZE; i++) nor_st.push_back(and_(cs, s_bins[i].negated(), t_bins[i].negated()));
@@ -471,30 +528,41 @@ inline System anonymous_system() {
     for (const Pt& q : enc_key_set) pt_inputize(cs, q);
     for (const Pt& q : left_set) pt_inputize(cs, q);
     // balance integrity: sum s_i (C_li + C_i) = b_2 G + sk (sum s_i C_ri + D)
+    cs.mark("balance: folds over s");
     const std::vector<Pt> left_balance = pt_witness_set(cs);
     std::vector<Pt> added_lefts;
     for (size_t i = 0; i < ANONIMITY_SIZE; i++) added_lefts.push_back(pt_add(cs, left_balance[i], left_set[i]));
     const Pt lh_c = add_fold(cs, s_bins, added_lefts, zero_p);
     const std::vector<Pt> right_balance = pt_witness_set(cs);
     const Pt right_fold = add_fold(cs, s_bins, right_balance, zero_p);
+    cs.mark("randomness bits, second allocation");
     const Bits randomness_bits2 = field_into_boolean_vec_le(cs);              // allocated a second time
+    cs.mark("fixed-base: randomness");
     const Pt right_ciphertext = fixed_base_multiplication(cs, randomness_bits2);
+    cs.mark("variable-base: decryption key x right side");
     const Pt cr_d = pt_add(cs, right_fold, right_ciphertext);
     const Pt cr_d_mul_sk = pt_mul(cs, cr_d, dec_key_bits);
     const Pt rh_c = pt_add(cs, remaining_g, cr_d_mul_sk);
+    cs.mark("balance equation");
     eq_points(cs, lh_c, rh_c);
+    cs.mark("encrypted balances as public inputs");
     for (const Pt& q : left_balance) pt_inputize(cs, q);
     for (const Pt& q : right_balance) pt_inputize(cs, q);
     pt_inputize(cs, right_ciphertext);
     // rvk_inputize (utils.rs:71-123)
+    cs.mark("rvk: small order of the proof generation key");
     const Pt pgk = pt_witness(cs);
     pt_assert_not_small_order(cs, pgk);
+    cs.mark("rvk: alpha bits");
     const Bits alpha_bits = field_into_boolean_vec_le(cs);
+    cs.mark("rvk: fixed-base alpha");
     const Pt alpha_g = fixed_base_multiplication(cs, alpha_bits);
+    cs.mark("rvk: sum and its small order");
     const Pt rvk = pt_add(cs, pgk, alpha_g);
     pt_assert_not_small_order(cs, rvk);
     pt_inputize(cs, rvk);
     // g_epoch_nonce_inputize (utils.rs:125-154)
+    cs.mark("nonce: variable-base decryption key x g_epoch");
     const Pt g_epoch = pt_witness(cs);
     const Pt nonce = pt_mul(cs, g_epoch, dec_key_bits);
     pt_inputize(cs, g_epoch);

@@ -30,6 +30,7 @@
 #include "host_common.h"
 #include "host_math.h"
 #include "ntt.h"
+#include "r1cs_check.h"
 #include "ntt_plan.h"
 #include "msm_group.h"
 #include "prove_plan.h"
@@ -577,6 +578,82 @@ zk_status prove_batch_witness(zk_params* P, zk_r1cs* R, size_t n, const uint8_t*
     return ZK_OK;
 }
 
+// ------------------------------------------------------------------------------------------
+// the constraint check (r1cs_check.h): which row an assignment breaks, with no key and no proof
+// ------------------------------------------------------------------------------------------
+static_assert(sizeof(zk_r1cs_verdict) == zkdev::R1CS_V_WORDS * 4 && ZK_R1CS_SATISFIED == zkdev::R1CS_SATISFIED &&
+                  ZK_R1CS_ONE_IS_NOT_ONE == zkdev::R1CS_ONE_IS_NOT_ONE, "zk_r1cs_verdict as the kernel writes it");
+// From this many assignments on the lanes of a wave run across proofs.  Transfer assignments, k_r1cs_check by rows / by proofs
+// (profiles/r26_r1cs_check.json): 64: 0.146 / 0.205 ms, 128: 0.243 / 0.272, 256: 0.429 / 0.376, 512: 0.796 / 0.653, 1024:
+// 1.643 / 1.402 - a wave per 32 rows of 64 proofs is too few waves for the device below four such groups.
+constexpr size_t R1CS_CHECK_LANE_MIN = 256;
+#ifdef ZK_TEST_HOOKS
+int g_r1cs_check_mapping = -1;   // tools/r1cs_check_probe.py: 0 / 1 force a mapping, -1 the rule above
+#endif
+
+// R->work.verdict = [16 bytes: the flags k_fr_convert raises over a caller's scalars | one verdict per assignment]
+zk_status verdict_ensure(zk_r1cs* R, size_t np) { return R->work.verdict.ensure((np + 1) * sizeof(zk_r1cs_verdict)); }
+
+// the verdicts of the np assignments in R->work.z[slot] (Montgomery form), on the host when this returns
+zk_status check_from_z(zk_r1cs* R, size_t np, int slot, zk_r1cs_verdict* out) {
+    const uint32_t nv = R->sys.n_in + R->sys.n_aux, n_con = R->sys.n_con;
+    ZK_TRY(verdict_ensure(R, np));
+    uint32_t* const verdict = R->work.verdict.as<uint32_t>() + zkdev::R1CS_V_WORDS;
+    const uint32_t* z = R->work.z[slot].as<uint32_t>();
+    zkdev::R1csMat mm[3];
+    for (int m = 0; m < 3; m++)
+        mm[m] = zkdev::R1csMat{R->sys.row_ptr[m].as<uint32_t>(), R->sys.col[m].as<uint32_t>(), R->sys.coeff[m].as<uint32_t>()};
+    ZK_LAUNCH(zkdev::k_r1cs_check_begin, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, g_stream, z, nv, (uint32_t)np, verdict);
+    bool lanes = np >= R1CS_CHECK_LANE_MIN;
+#ifdef ZK_TEST_HOOKS
+    if (g_r1cs_check_mapping >= 0) lanes = g_r1cs_check_mapping != 0;
+#endif
+    if (n_con) {
+        ProfScope ps("r1cs_check");
+        if (lanes)
+            ZK_LAUNCH(zkdev::k_r1cs_check<true>, dim3((n_con + zkdev::R1CS_CHECK_ROWS - 1) / zkdev::R1CS_CHECK_ROWS,
+                                                      (unsigned)((np + zkdev::R1CS_CHECK_WAVE - 1) / zkdev::R1CS_CHECK_WAVE)),
+                      dim3(zkdev::R1CS_CHECK_WAVE), 0, g_stream, mm[0], mm[1], mm[2], z, verdict, n_con, nv, (uint32_t)np);
+        else
+            ZK_LAUNCH(zkdev::k_r1cs_check<false>, dim3((n_con + 255) / 256, (unsigned)np), dim3(256), 0, g_stream, mm[0], mm[1], mm[2], z,
+                      verdict, n_con, nv, (uint32_t)np);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(hipMemcpy(out, verdict, np * sizeof(zk_r1cs_verdict), hipMemcpyDeviceToHost));
+    return ZK_OK;
+}
+
+// zk_r1cs_check_batch: prove_batch_witness with check_from_z in the place of prove_from_z - the same chunks, R->work.z[0], the
+// same refusal of a scalar >= r (own: the host calculator's vectors, canonical by construction, as prove_statements hands them on)
+zk_status check_batch_witness(zk_r1cs* R, size_t n, const uint8_t* witness, uint32_t flags, zk_r1cs_verdict* out, bool own) {
+    if (!R || (n && (!witness || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    ZK_TRY(use_device(R->sys.device));
+    const uint32_t nv = R->sys.n_in + R->sys.n_aux;
+    const size_t chunk = ProveTunables::read().batch_chunk;
+    for (size_t first = 0; first < n; first += chunk) {
+        const size_t np = std::min(chunk, n - first), cnt = np * (size_t)nv;
+        ZK_TRY(R->work.z[0].ensure(cnt * 32));
+        ZK_TRY(verdict_ensure(R, np));
+        uint32_t* const bad = R->work.verdict.as<uint32_t>();
+        HIP_TRY(hipMemcpyAsync(R->work.z[0].p, witness + first * (size_t)nv * 32, cnt * 32, hipMemcpyHostToDevice, g_stream));
+        HIP_TRY(hipMemsetAsync(bad, 0, 4, g_stream));
+        if (!(flags & ZK_FR_MONTGOMERY))
+            ZK_LAUNCH(zkdev::k_fr_convert, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream, R->work.z[0].as<uint32_t>(),
+                      (const uint32_t*)R->work.z[0].as<uint32_t>(), 0u, cnt, bad);
+        else if (!own)
+            ZK_LAUNCH(zkdev::k_fr_flag_noncanonical, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, g_stream,
+                      (const uint32_t*)R->work.z[0].as<uint32_t>(), cnt, bad);
+        ZK_TRY(check_from_z(R, np, 0, out + first));
+        uint32_t raised = 0;
+        HIP_TRY(hipMemcpy(&raised, bad, 4, hipMemcpyDeviceToHost));
+        if (raised & zkdev::ZK_BAD_SCALAR)
+            return fail(ZK_ERR_INVALID_ARGUMENT, "a witness scalar is not a canonical field element (>= r)");
+    }
+    return ZK_OK;
+}
+
 }  // namespace
 
 #include "statement_route.h"   // (the statement route: host witness calculators, route_check, prove_statements, ...)
@@ -1049,7 +1126,79 @@ zk_status zk_prove_batch_witness(zk_params* p, zk_r1cs* circuit, size_t n, const
                                  const uint8_t* rs, uint8_t* proofs_out) try {
     return prove_batch_witness(p, circuit, n, witness, flags, rs, proofs_out, false);   // (a caller's witness: the key's own bases)
 } ZK_ABI_CATCH
+// Which constraint an assignment breaks (r1cs_check.h; statement_route.h check_statements).  A verdict is not an error.
+zk_status zk_r1cs_check_batch(zk_r1cs* circuit, size_t n, const uint8_t* witness, uint32_t flags, zk_r1cs_verdict* out) try {
+    return check_batch_witness(circuit, n, witness, flags, out, false);
+} ZK_ABI_CATCH
+zk_status zk_transfer_check_batch(zk_r1cs* circuit, size_t n, const zk_transfer_statement* st, zk_r1cs_verdict* out) try {
+    if (!circuit || (n && (!st || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    ZK_TRY(route_check(nullptr, circuit, zkpairs::TRANSFER, n));
+    return n ? check_statements(circuit, zkpairs::TRANSFER, st, n, out) : ZK_OK;
+} ZK_ABI_CATCH
+zk_status zk_anonymous_check_batch(zk_r1cs* circuit, size_t n, const zk_anonymous_statement* st, zk_r1cs_verdict* out) try {
+    if (!circuit || (n && (!st || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    ZK_TRY(route_check(nullptr, circuit, zkpairs::ANONYMOUS, n));
+    return n ? check_statements(circuit, zkpairs::ANONYMOUS, st, n, out) : ZK_OK;
+} ZK_ABI_CATCH
+// the part of a built-in circuit a constraint belongs to (transfer_r1cs.h System::mark; system_load hands the table on)
+zk_status zk_r1cs_stage(const zk_r1cs* circuit, uint32_t constraint, uint32_t* stage_out, uint32_t* first_out, uint32_t* count_out,
+                        char* name_out, size_t name_cap) try {
+    if (!circuit) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    const zk_r1cs::System& S = circuit->sys;
+    if (constraint >= S.n_con)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "constraint " + std::to_string(constraint) + " of " + std::to_string(S.n_con));
+    uint32_t stage = 0xFFFFFFFFu, first = 0, count = S.n_con;
+    const char* name = "";
+    if (!S.stage_first.empty()) {
+        stage = (uint32_t)(std::upper_bound(S.stage_first.begin(), S.stage_first.end(), constraint) - S.stage_first.begin()) - 1;
+        first = S.stage_first[stage];
+        count = (stage + 1 < S.stage_first.size() ? S.stage_first[stage + 1] : S.n_con) - first;
+        name = S.stage_name[stage].c_str();
+    }
+    if (stage_out) *stage_out = stage;
+    if (first_out) *first_out = first;
+    if (count_out) *count_out = count;
+    if (name_out && name_cap) {
+        strncpy(name_out, name, name_cap - 1);
+        name_out[name_cap - 1] = 0;
+    }
+    return ZK_OK;
+} ZK_ABI_CATCH
 #ifdef ZK_TEST_HOOKS
+// Test hooks of tools/r1cs_check_probe.py, NOT part of the ABI: the lane mapping of the check forced (0 rows, 1 proofs, -1 the
+// library's rule); the check, and the row evaluations of the prover, on the np assignments a call left in R->work.z[0] -
+// each under its zk_profile name ("r1cs_check", "r1cs_eval").
+zk_status zk_hook_r1cs_check_mapping(int mapping) try {
+    g_r1cs_check_mapping = mapping;
+    return ZK_OK;
+} ZK_ABI_CATCH
+zk_status zk_hook_r1cs_check_resident(zk_r1cs* circuit, size_t np, zk_r1cs_verdict* out) try {
+    if (!circuit || !out || !np) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    ZK_TRY(use_device(circuit->sys.device));
+    if (circuit->work.z[0].cap < np * (size_t)(circuit->sys.n_in + circuit->sys.n_aux) * 32)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "fewer assignments are resident");
+    return check_from_z(circuit, np, 0, out);
+} ZK_ABI_CATCH
+zk_status zk_hook_r1cs_eval_resident(zk_r1cs* circuit, size_t np) try {
+    if (!circuit || !np) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    zk_r1cs* R = circuit;
+    ZK_TRY(use_device(R->sys.device));
+    const uint32_t nv = R->sys.n_in + R->sys.n_aux, n_rows = R->sys.n_con + R->sys.n_in;
+    if (R->work.z[0].cap < np * (size_t)nv * 32) return fail(ZK_ERR_INVALID_ARGUMENT, "fewer assignments are resident");
+    ZK_TRY(R->work.abc.ensure(3 * np * (size_t)n_rows * 32));
+    zkdev::R1csMat mm[3];
+    for (int m = 0; m < 3; m++)
+        mm[m] = zkdev::R1csMat{R->sys.row_ptr[m].as<uint32_t>(), R->sys.col[m].as<uint32_t>(), R->sys.coeff[m].as<uint32_t>()};
+    {
+        ProfScope ps("r1cs_eval");
+        ZK_LAUNCH(zkdev::k_r1cs_eval, dim3((n_rows + 255) / 256, 3, (unsigned)np), dim3(256), 0, g_stream, mm[0], mm[1], mm[2],
+                  (const uint32_t*)R->work.z[0].as<uint32_t>(), R->work.abc.as<uint32_t>(), R->sys.n_con, R->sys.n_in, nv, n_rows,
+                  np * (size_t)n_rows);
+    }
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return ZK_OK;
+} ZK_ABI_CATCH
 // Test hook, NOT part of the ABI (absent from libzkamd.so): zk_prove_batch_witness on the route of the statement-to-proof
 // entries - the four-transform form over the derived bases of (p, circuit) - for circuits that have no statement form.
 // info[0] = whether the pair has a derived set after the call, info[1] = how many of its bases are the identity (mapped out).
