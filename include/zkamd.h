@@ -314,7 +314,8 @@ zk_status zk_transfer_witness_gpu(zk_r1cs* circuit, const zk_transfer_statement*
 
 /* A stream of statement batches: submit() queues a batch and returns at once; worker threads (one per lane, two lanes
  * by default) enqueue the witness kernels of a chunk beside the proving of the chunk before it, so two chunks are in flight
- * (ZKAMD_WITNESS=host: a producer thread computes the witnesses on the host cores, zk_set_host_threads, instead);
+ * (ZKAMD_WITNESS=host: one lane, whose helper thread computes the witnesses of the next chunk on the host cores,
+ * zk_set_host_threads, into the circuit handle's page-locked buffer while the lane proves the current one);
  * wait() blocks until everything submitted so far is proved and returns the first failure, if any (the
  * statement index in its message is relative to the failing submit).  The caller's buffers (statements, rs,
  * proofs_out) must stay valid until wait() returns, and `p` / `circuit` must not be used by other calls

@@ -212,7 +212,7 @@ def test_transfer_prove_from_statements(gpu_lib, monkeypatch, engine):
     from oracle import transfer_circuit as tc
     if engine != "default":
         monkeypatch.setenv("ZKAMD_WITNESS", engine)
-    monkeypatch.setenv("ZKAMD_BATCH_CHUNK", "3")   # two chunks: the witness producer thread runs beside the GPU
+    monkeypatch.setenv("ZKAMD_BATCH_CHUNK", "3")   # two chunks: the host engine's helper thread runs beside the GPU
     r1, asgs, P, pk = helpers.transfer_case(1)
     E = g.Bls12Engine()
     ws = [tc.make_witness(40 + i, amount=5 + i, fee=i & 1, balance=77 + i) for i in range(4)]
@@ -473,6 +473,40 @@ def test_pipeline_lane_retires_when_its_workspaces_do_not_fit(gpu_hooks_lib, mon
         monkeypatch.delenv("ZKAMD_INJECT_LANE_OOM")
         serial = zk.transfer_prove_batch(mats, params, sts, rs)
         assert b"".join(p.write() for p in serial) == out.tobytes()
+    finally:
+        pipe.close()
+        mats.close()
+        params.close()
+
+
+@pytest.mark.parametrize("lanes", (1, 2))
+@pytest.mark.parametrize("engine", WITNESS_ENGINES)
+def test_pipeline_reports_a_malformed_statement_of_a_later_chunk(gpu_lib, monkeypatch, engine, lanes):
+    """One submit of five statements in chunks of two, the second statement of the second chunk malformed: wait() names it by
+    its place in the submit whichever lane and witness engine met it, and the same pipeline then proves the five good
+    statements to the bytes of one zk_transfer_prove_batch call."""
+    import zero_chain_amd as zk
+    from oracle import transfer_circuit as tc
+    monkeypatch.setenv("ZKAMD_WITNESS", engine)
+    monkeypatch.setenv("ZKAMD_PIPELINE_LANES", str(lanes))
+    monkeypatch.setenv("ZKAMD_BATCH_CHUNK", "2")
+    r1, asgs, P, pk = helpers.transfer_case(1)
+    good = [tc.statement_dict(tc.make_witness(2300 + i, amount=2 + i, fee=i & 1, balance=60 + i)) for i in range(5)]
+    bad = [dict(s) for s in good]
+    bad[3]["g_epoch"] = bytes([2]) + bytes(31)
+    rs = [(7 + i, 9 + 5 * i) for i in range(5)]
+    params = zk.Parameters.read(pk, checked=False, lib=gpu_lib)
+    mats = zk.ConstraintMatrices.transfer_circuit(lib=gpu_lib)
+    pipe = zk.TransferPipeline(mats, params)
+    try:
+        pipe.submit(zk.transfer_statements(bad), rs)
+        with pytest.raises(zk.ZkError) as e:
+            pipe.wait()
+        assert e.value.variant == "InvalidArgument" and "statement 3" in str(e.value)
+        pipe.submit(zk.transfer_statements(good), rs)
+        streamed = pipe.wait()
+        serial = zk.transfer_prove_batch(mats, params, zk.transfer_statements(good), rs)
+        assert [p.write() for p in streamed] == [p.write() for p in serial]
     finally:
         pipe.close()
         mats.close()

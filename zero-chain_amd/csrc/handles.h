@@ -1,5 +1,7 @@
 // Handle types shared by the translation units of libzkamd.
 #pragma once
+#include <chrono>
+#include <functional>
 #include <vector>
 #include "host_common.h"
 #include "host_math.h"
@@ -129,10 +131,12 @@ zk_status elgamal_dlog_search_resident(zk_elgamal_table* T, size_t nb, uint64_t 
 // Groth16 verification of a batch (verify.cpp; zk_verify_batch is this with own_proofs = false).  own_proofs: the
 // proofs are this library's own fresh results (gen_proof's self-check) - decoded without the r-torsion test.
 namespace zkrt {
-// what wallet.cpp (gen_proof, the Jubjub host side) needs of zkamd.cpp: one chunk of proofs from the assignment the witness
-// kernels left in R->work.z[slot]; proofs per launch set
-zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out);
-size_t lib_batch_chunk();
+// what wallet.cpp (gen_proof, the Jubjub host side) needs of zkamd.cpp: the proofs of n > 0 transfer statements behind route_check,
+// chunk by chunk (statement_route.h statement_chunks); packed(first, np, heads, head_stride) after each chunk is proved: the 23
+// public inputs of its statement i at heads + i * head_stride, Montgomery form.  since: the ZKAMD_DEBUG_TIMING prints' zero, or null
+using TransferChunkPacked = std::function<zk_status(size_t first, size_t np, const uint8_t* heads, size_t head_stride)>;
+zk_status lib_transfer_chunks(zk_params* P, zk_r1cs* R, size_t n, const zk_transfer_statement* st, const uint8_t* rs, uint8_t* proofs_out,
+                              const TransferChunkPacked& packed, const std::chrono::steady_clock::time_point* since);
 bool lib_witness_on_host(size_t n);   // a handful of statements: the assignment on the host cores (statement_route.h witness_on_host)
 // what every statement entry refuses of a (key, circuit) pair (statement_route.h): circuit = 0 the transfer circuit, 1 the
 // anonymous one (zkpairs::Circuit); P = null: the circuit alone; n = 0: the checks of an empty batch, which come before the

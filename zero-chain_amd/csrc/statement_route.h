@@ -5,6 +5,7 @@
 // behind prove_from_z and prove_batch_witness).
 #pragma once
 #include "prover_binding.h"
+#include "pipeline_lanes.h"   // (SlotThread: the helper thread of the host engine)
 
 // ------------------------------------------------------------------------------------------
 // the witness calculators of the two circuits (transfer_witness.h) behind the C ABI
@@ -155,8 +156,9 @@ struct StatementRoute {
     size_t st_size;      // sizeof the statement of the C ABI
     const char* name;    // as the refusal of other matrices names the circuit
     size_t chunk_cap;    // proofs per launch set at the most (0: ProveTunables' alone)
-    // the witness kernels of np statements into R->work.z[slot], enqueued on `stream` / awaited (witness.cpp)
-    zk_status (*gpu_enqueue)(zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t stream);
+    // the witness kernels of np statements into R->work.z[slot], enqueued on `stream` / awaited (witness.cpp).  typed_inputs: a
+    // wallet-level request's points are tested for prime order too (the anonymous entry checks them on the host: ignored)
+    zk_status (*gpu_enqueue)(zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t stream, bool typed_inputs);
     zk_status (*gpu_finish)(zk_r1cs* R, size_t np, int slot, size_t index_base);
     // the host calculator above
     zk_status (*host_witness)(const void* st, size_t n, uint32_t flags, uint8_t* out, size_t index_base);
@@ -170,12 +172,12 @@ struct StatementRoute {
 static_assert(zkpairs::TRANSFER == 0 && zkpairs::ANONYMOUS == 1, "the order of the descriptions");
 const StatementRoute STATEMENT_ROUTES[2] = {
     {ZK_TRANSFER_N_INPUTS, ZK_TRANSFER_N_AUX, sizeof(zk_transfer_statement), "transfer", 0,
-     [](zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t s) { return witness_gpu_enqueue(R, (const zk_transfer_statement*)st, np, slot, s); },
+     [](zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t s, bool typed) { return witness_gpu_enqueue(R, (const zk_transfer_statement*)st, np, slot, s, typed); },
      witness_gpu_finish,
      [](const void* st, size_t n, uint32_t f, uint8_t* out, size_t base) { return transfer_witness((const zk_transfer_statement*)st, n, f, out, base); }},
     // (domain 2^16: half the proofs of a transfer chunk fill the same workspaces)
     {ZK_ANONYMOUS_N_INPUTS, ZK_ANONYMOUS_N_AUX, sizeof(zk_anonymous_statement), "anonymous-transfer", 512,
-     [](zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t s) { return witness_anon_gpu_enqueue(R, (const zk_anonymous_statement*)st, np, slot, s); },
+     [](zk_r1cs* R, const void* st, size_t np, int slot, hipStream_t s, bool) { return witness_anon_gpu_enqueue(R, (const zk_anonymous_statement*)st, np, slot, s); },
      witness_anon_gpu_finish,
      [](const void* st, size_t n, uint32_t f, uint8_t* out, size_t base) { return anonymous_witness((const zk_anonymous_statement*)st, n, f, out, base); }},
 };
@@ -199,52 +201,71 @@ zk_status zkrt::route_check(zk_params* P, zk_r1cs* R, int circuit, size_t n) {
 
 namespace {
 
-// The chunk loop of the statement entries, n > 0 statements behind route_check, in chunks of the circuit's launch set over two
-// slots: the witnesses of chunk k + 1 are made while step(first, np, slot, host_z) works on chunk k, and a malformed
-// statement among them is reported once chunk k is done.  host_z: the chunk's assignments where the host engine made them
-// (Montgomery form), null where the witness kernels left them in R->work.z[slot].
+// The witnesses of a run of chunks over two slots, by either engine, so that chunk k + 1 is made while the GPU works on chunk k:
 //   the witness kernels (witness_gpu.h / witness_anon_gpu.h), on the side stream of the copy engine: latency-bound chains for a
 //     few hundred waves beside the multiexps; a slot is R->work.z[slot];
 //   a handful of statements, or ZKAMD_WITNESS=host (witness_on_host): the host calculator on the host cores, in a thread beside
-//     the caller; a slot is one half of the pinned R->work.host_z.
-template <class Step>
-zk_status statement_chunks(zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, Step&& step) {
-    const StatementRoute& T = STATEMENT_ROUTES[circuit];
-    const size_t chunk = T.chunk(), half = std::min(chunk, n) * T.nv() * 32;
-    const bool host = witness_on_host(n);
-    if (host) ZK_TRY(R->work.host_ensure(2 * half));
-    uint8_t* const host_z = (uint8_t*)R->work.host_z;
-    zk_status side_rc = ZK_OK;
-    std::string side_err;
-    SideThread side;   // (behind what it writes: joined first on every way out)
-    auto start = [&](size_t first, int slot) -> zk_status {
-        const size_t np = std::min(chunk, n - first);
-        const uint8_t* s = (const uint8_t*)st + first * T.st_size;
-        if (!host) return T.gpu_enqueue(R, s, np, slot, g_copy_stream);
-        side.start([&, s, np, slot, first] {
-            side_rc = T.host_witness(s, np, ZK_FR_MONTGOMERY, host_z + slot * half, first);
-            if (side_rc != ZK_OK) side_err = g_err;   // g_err is thread-local
+//     the caller; a slot is one half (chunk_capacity assignments) of the pinned R->work.host_z.
+// start() may come before ready() of the chunk before it (zk_pipeline) or after it (statement_chunks): start() waits for the one
+// helper thread, whose result is kept per slot, and ready() waits only while the thread is still on the slot asked for - so the
+// next chunk's witnesses are made beside the current chunk's proving in either order.
+struct ChunkWitness {
+    zk_r1cs* const R;
+    const StatementRoute& T;
+    const bool host, typed_inputs;
+    const size_t half;
+    zk_status side_rc[2] = {ZK_OK, ZK_OK};   // what the helper thread made of a slot, with its message (g_err is thread-local)
+    std::string side_err[2];
+    zkpipe::SlotThread side;   // (behind what it writes: joined first as this goes)
+    ChunkWitness(zk_r1cs* R, const StatementRoute& T, bool host, size_t chunk_capacity, bool typed_inputs)
+        : R(R), T(T), host(host), typed_inputs(typed_inputs), half(chunk_capacity * T.nv() * 32) {}
+    // index_base: the place of st[0] in the caller's batch (a malformed statement is reported with its absolute index)
+    zk_status start(const void* st, size_t np, int slot, size_t index_base) {
+        if (!host) return T.gpu_enqueue(R, st, np, slot, g_copy_stream, typed_inputs);
+        side.join();   // (before the buffer may move)
+        // (never cached: another entry on this handle may have regrown the buffer since; it only grows, so not under a half in use)
+        ZK_TRY(R->work.host_ensure(2 * half));
+        uint8_t* const out = (uint8_t*)R->work.host_z + slot * half;
+        side.start(slot, [this, st, np, slot, index_base, out] {
+            side_rc[slot] = guarded([&] { return T.host_witness(st, np, ZK_FR_MONTGOMERY, out, index_base); });
+            if (side_rc[slot] != ZK_OK) side_err[slot] = g_err;
         });
         return ZK_OK;
-    };
-    auto ready = [&](size_t first, size_t np, int slot) -> zk_status {
-        if (!host) return T.gpu_finish(R, np, slot, first);
-        side.join();
-        return side_rc == ZK_OK ? ZK_OK : fail(side_rc, side_err);
-    };
-    zk_status rc = start(0, 0);
-    int slot = 0;
-    for (size_t first = 0; first < n && rc == ZK_OK; first += chunk, slot ^= 1) {
-        const size_t np = std::min(chunk, n - first), next = first + chunk;
-        rc = ready(first, np, slot);
-        if (rc == ZK_OK && next < n) rc = start(next, slot ^ 1);
-        if (rc == ZK_OK) rc = step(first, np, slot, host ? host_z + slot * half : (const uint8_t*)nullptr);
     }
-    if (rc != ZK_OK) {   // no witness kernel of a later chunk stays in flight behind an error (nor its thread: joined as `side` goes)
+    zk_status ready(size_t np, int slot, size_t index_base) {
+        if (!host) return T.gpu_finish(R, np, slot, index_base);
+        side.join_slot(slot);
+        return side_rc[slot] == ZK_OK ? ZK_OK : fail(side_rc[slot], side_err[slot]);
+    }
+    // the slot's assignments where the host engine made them (Montgomery form), null where the kernels left them in R->work.z[slot]
+    const uint8_t* host_z(int slot) const { return host ? (const uint8_t*)R->work.host_z + slot * half : nullptr; }
+    // behind an error: no witness kernel of a later chunk stays in flight, nor its thread
+    void drain() {
+        side.join();
         const std::string why = g_err;
         (void)hipStreamSynchronize(g_copy_stream);
         g_err = why;
     }
+};
+
+// The chunk loop of the statement entries, n > 0 statements behind route_check, in chunks of the circuit's launch set: the
+// witnesses of chunk k + 1 are made while step(first, np, slot, host_z) works on chunk k, and a malformed statement among them
+// is reported once chunk k is done.  host_z: ChunkWitness::host_z of the slot.
+template <class Step>
+zk_status statement_chunks(zk_r1cs* R, zkpairs::Circuit circuit, const void* st, size_t n, Step&& step, bool typed_inputs = false) {
+    const StatementRoute& T = STATEMENT_ROUTES[circuit];
+    const size_t chunk = T.chunk();
+    ChunkWitness W(R, T, witness_on_host(n), std::min(chunk, n), typed_inputs);
+    auto at = [&](size_t first) { return (const uint8_t*)st + first * T.st_size; };
+    zk_status rc = W.start(at(0), std::min(chunk, n), 0, 0);
+    int slot = 0;
+    for (size_t first = 0; first < n && rc == ZK_OK; first += chunk, slot ^= 1) {
+        const size_t np = std::min(chunk, n - first), next = first + chunk;
+        rc = W.ready(np, slot, first);
+        if (rc == ZK_OK && next < n) rc = W.start(at(next), std::min(chunk, n - next), slot ^ 1, next);
+        if (rc == ZK_OK) rc = step(first, np, slot, W.host_z(slot));
+    }
+    if (rc != ZK_OK) W.drain();
     return rc;
 }
 
@@ -273,7 +294,7 @@ zk_status witness_readback(zk_r1cs* R, zkpairs::Circuit circuit, const void* st,
     const size_t nv = T.nv(), chunk = std::min(T.chunk(), (size_t)256);
     for (size_t first = 0; first < n; first += chunk) {
         const size_t np = std::min(chunk, n - first);
-        ZK_TRY(T.gpu_enqueue(R, (const uint8_t*)st + first * T.st_size, np, 0, g_stream));
+        ZK_TRY(T.gpu_enqueue(R, (const uint8_t*)st + first * T.st_size, np, 0, g_stream, false));
         ZK_TRY(T.gpu_finish(R, np, 0, first));
         if (!(flags & ZK_FR_MONTGOMERY)) {
             const size_t cnt = np * nv;

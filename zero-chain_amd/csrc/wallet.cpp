@@ -489,45 +489,17 @@ zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk,
     const bool host_wit = lib_witness_on_host(n);
     ZK_TRY(transfer_derive(req, n, st.data(), rsk.data(), host_wit));
     if (timing) fprintf(stderr, "[gen_proof] derive done %.1f ms\n", since());
-    const size_t chunk = lib_batch_chunk(), nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, n_pub = ZK_TRANSFER_N_INPUTS - 1;
-    PinBuf pin_in;
-    std::vector<uint8_t> inputs(n * n_pub * 32), host_w;
+    const size_t n_pub = ZK_TRANSFER_N_INPUTS - 1;
+    std::vector<uint8_t> inputs(n * n_pub * 32);
     // the prover leaves the affine A, B, C of every proof here for the self-check below (host_common.h g_own_affine_sink)
     std::vector<uint8_t> own_aff(n * OWN_AFFINE_BYTES);
     OwnAffineSink sink(own_aff.data());
-    WipeOnExit wipe_w{nullptr, 0};   // (the assignment holds the bits of the keys)
-    int slot = 0;
-    if (host_wit) {
-        host_w.resize(n * nv * 32);
-        wipe_w.p = host_w.data();
-        wipe_w.n = host_w.size();
-        ZK_TRY(zk_transfer_witness(st.data(), n, ZK_FR_MONTGOMERY, host_w.data()));
-    } else {
-        ZK_TRY(pin_in.ensure(std::min(chunk, n) * ZK_TRANSFER_N_INPUTS * 32));
-        ZK_TRY(witness_gpu_enqueue(circuit, st.data(), std::min(chunk, n), slot, g_copy_stream, true));
-    }
-    for (size_t first = 0; first < n; first += chunk) {
-        const size_t np = std::min(chunk, n - first), next = first + chunk;
-        // the 23 public inputs of every statement (the head of its assignment), for check_proof and the packing
-        const uint8_t* heads = nullptr;
-        size_t head_stride = 0;
-        if (host_wit) {
-            ZK_TRY(zk_prove_batch_witness(p, circuit, np, host_w.data() + first * nv * 32, ZK_FR_MONTGOMERY, rs + first * 64,
-                                          proofs.data() + first * 192));
-            heads = host_w.data() + first * nv * 32;
-            head_stride = nv * 32;
-        } else {
-            ZK_TRY(witness_gpu_finish(circuit, np, slot, first));
-            if (next < n) ZK_TRY(witness_gpu_enqueue(circuit, st.data() + next, std::min(chunk, n - next), slot ^ 1, g_copy_stream, true));
-            HIP_TRY(hipMemcpy2DAsync(pin_in.p, ZK_TRANSFER_N_INPUTS * 32, circuit->work.z[slot].p, nv * 32, ZK_TRANSFER_N_INPUTS * 32, np,
-                                     hipMemcpyDeviceToHost, g_stream));
-            if (timing) fprintf(stderr, "[gen_proof] chunk %zu witness ready %.1f ms\n", first / chunk, since());
-            ZK_TRY(lib_prove_from_z(p, circuit, np, slot, rs + first * 64, proofs.data() + first * 192));
-            HIP_TRY(hipStreamSynchronize(g_stream));
-            heads = pin_in.as<uint8_t>();
-            head_stride = ZK_TRANSFER_N_INPUTS * 32;
-        }
-        if (timing) fprintf(stderr, "[gen_proof] chunk %zu proved %.1f ms\n", first / chunk, since());
+    size_t n_chunks = 0;
+    // the proofs chunk by chunk, the witnesses of the next chunk beside the proving of this one (zkamd.cpp lib_transfer_chunks); as
+    // each is proved, its statements' 23 public inputs (heads) are packed with the proofs
+    ZK_TRY(lib_transfer_chunks(p, circuit, n, st.data(), rs, proofs.data(), [&](size_t first, size_t np, const uint8_t* heads, size_t head_stride) {
+        if (timing) fprintf(stderr, "[gen_proof] chunk %zu proved %.1f ms\n", n_chunks, since());
+        n_chunks++;
         for (size_t i = 0; i < np; i++) {
             const zkhost::Fr* z = reinterpret_cast<const zkhost::Fr*>(heads + i * head_stride);
             zk_confidential_xt& x = out[first + i];
@@ -549,8 +521,8 @@ zk_status zk_transfer_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk,
             jubjub_encode(z[21], z[22], x.nonce);
             memcpy(x.rsk, rsk.data() + (first + i) * 32, 32);
         }
-        slot ^= 1;
-    }
+        return ZK_OK;
+    }, timing ? &t_start : nullptr));
     // check_proof of every proof of the call, in ONE set of launches at the end: a verification is a bundle of serial
     // chains (a few hundred waves on the whole GPU) whose duration hardly depends on how many proofs it holds - 8.0 ms for
     // 1024, 9.2 for 2048 (round 2: 45 ms).  Run beside the proving of the next chunk, as rounds 2 and 3 first did, it is

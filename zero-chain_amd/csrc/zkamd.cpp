@@ -19,8 +19,6 @@
 #include <new>
 #include <memory>
 #include <mutex>
-#include <condition_variable>
-#include <deque>
 #if defined(__linux__)
 #include <sched.h>
 #endif
@@ -657,6 +655,7 @@ zk_status check_batch_witness(zk_r1cs* R, size_t n, const uint8_t* witness, uint
 }  // namespace
 
 #include "statement_route.h"   // (the statement route: host witness calculators, route_check, prove_statements, ...)
+#include "pipeline.h"          // (zk_pipeline: its lanes over the route's witness engines)
 
 // ------------------------------------------------------------------------------------------
 // stand-alone MSM / NTT handles
@@ -992,10 +991,37 @@ zk_status ntt_run_dev(zk_ntt* T, void* d_data, uint32_t batch, uint32_t flags) {
 
 // what the wallet-level entries (wallet.cpp: gen_proof, the Jubjub host side) need of this translation unit
 namespace zkrt {
-zk_status lib_prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out) {
-    return prove_from_z(P, R, np, slot, rs, proofs_out, true);
+// gen_proof's chunks: statement_chunks over the transfer circuit with the typed inputs tested by the witness kernels; after each
+// chunk is proved, packed(first, np, heads, head_stride) gets the 23 public inputs of every statement of it (the head of its
+// assignment, Montgomery form), for check_proof and the packing.  since: where ZKAMD_DEBUG_TIMING counts from (null: no prints).
+zk_status lib_transfer_chunks(zk_params* P, zk_r1cs* R, size_t n, const zk_transfer_statement* st, const uint8_t* rs, uint8_t* proofs_out,
+                              const TransferChunkPacked& packed, const std::chrono::steady_clock::time_point* since) {
+    const size_t chunk = ProveTunables::read().batch_chunk, nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX, head = ZK_TRANSFER_N_INPUTS * 32;
+    PinBuf pin_in;
+    struct WipeHalves {   // (the assignments hold the bits of the keys: both halves of the host engine, on every way out)
+        zk_r1cs* R;
+        size_t bytes;
+        ~WipeHalves() {
+            if (R->work.host_z) explicit_bzero(R->work.host_z, std::min(bytes, R->work.host_z_cap));
+        }
+    } wipe{R, witness_on_host(n) ? 2 * std::min(chunk, n) * nv * 32 : 0};
+    return statement_chunks(R, zkpairs::TRANSFER, st, n, [&](size_t first, size_t np, int slot, const uint8_t* host_z) -> zk_status {
+        if (host_z) {
+            // derived = false, the key's own bases: a lone transaction must not pay the binding of the derived bases
+            // (ensure_derived) on its first call
+            ZK_TRY(prove_batch_witness(P, R, np, host_z, ZK_FR_MONTGOMERY, rs + first * 64, proofs_out + first * 192, false));
+            return packed(first, np, host_z, nv * 32);
+        }
+        ZK_TRY(pin_in.ensure(std::min(chunk, n) * head));
+        HIP_TRY(hipMemcpy2DAsync(pin_in.p, head, R->work.z[slot].p, nv * 32, head, np, hipMemcpyDeviceToHost, g_stream));
+        if (since)
+            fprintf(stderr, "[gen_proof] chunk %zu witness ready %.1f ms\n", first / chunk,
+                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - *since).count());
+        ZK_TRY(prove_from_z(P, R, np, slot, rs + first * 64, proofs_out + first * 192, true));
+        HIP_TRY(hipStreamSynchronize(g_stream));
+        return packed(first, np, pin_in.as<uint8_t>(), head);
+    }, true);
 }
-size_t lib_batch_chunk() { return ProveTunables::read().batch_chunk; }
 bool lib_witness_on_host(size_t n) { return witness_on_host(n); }
 }  // namespace zkrt
 
@@ -1480,225 +1506,24 @@ zk_status zk_anonymous_witness_gpu(zk_r1cs* circuit, const zk_anonymous_statemen
 } ZK_ABI_CATCH
 
 // ------------------------------------------------------------------------------------------
-// zk_pipeline: a stream of statement batches.  zk_transfer_prove_batch overlaps the witnesses of
-// chunk k + 1 with the GPU work of chunk k INSIDE one call; a service that proves batch after batch
-// wants the same overlap ACROSS calls.  submit() queues a batch and returns; a producer thread computes
-// its witnesses (host cores) into one of two page-locked buffers while the GPU thread proves the batch
-// before it; wait() returns when everything submitted so far is proved.
+// zk_pipeline: a stream of statement batches (pipeline.h)
 // ------------------------------------------------------------------------------------------
-}  // extern "C"
-
-struct zk_pipeline {
-    struct Job {
-        const zk_transfer_statement* st;
-        const uint8_t* rs;
-        uint8_t* out;
-        size_t n, index_base;
-        int slot;
-    };
-    zk_params* P = nullptr;
-    zk_r1cs* R = nullptr;
-    // lanes 1 .. (ZKAMD_PIPELINE_LANES, default 2): further workers with their own workspaces and streams over the
-    // same tables - several chunks in flight, the sort / reduction / fold / witness phases of one beside the
-    // accumulation of another
-    static constexpr int MAX_LANES = 4;
-    zk_params* Pl[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    zk_r1cs* Rl[MAX_LANES] = {nullptr, nullptr, nullptr, nullptr};
-    std::thread t_lane[MAX_LANES];
-    int n_lanes = 1;      // lanes started at create
-    int live_lanes = 1;   // ... minus the ones that retired when their workspaces did not fit (mu held)
-    size_t chunk = 0, nv = 0;   // (proofs per launch set: ProveTunables, at zk_pipeline_create)
-    PinBuf buf[2];
-    std::mutex mu;
-    std::condition_variable cv;
-    std::deque<Job> q_wit, q_gpu;
-    bool slot_free[2] = {true, true};
-    size_t in_flight = 0;
-    zk_status err = ZK_OK;
-    std::string err_msg;
-    bool stop = false;
-    std::thread t_wit, t_gpu;
-
-    void fail_with(zk_status st, const std::string& msg) {   // mu held
-        if (err == ZK_OK) {
-            err = st;
-            err_msg = msg;
-        }
-    }
-    void run_wit() {
-        for (;;) {
-            Job j;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || (!q_wit.empty() && (slot_free[0] || slot_free[1])); });
-                if (stop) return;
-                j = q_wit.front();
-                q_wit.pop_front();
-                j.slot = slot_free[0] ? 0 : 1;
-                slot_free[j.slot] = false;
-                if (err != ZK_OK) {   // a failed stream drains without doing work
-                    q_gpu.push_back(j);
-                    cv.notify_all();
-                    continue;
-                }
-            }
-            zk_status rc = guarded([&] { return transfer_witness(j.st, j.n, ZK_FR_MONTGOMERY, buf[j.slot].as<uint8_t>(), j.index_base); });
-            std::lock_guard<std::mutex> lk(mu);
-            if (rc != ZK_OK) fail_with(rc, g_err);
-            q_gpu.push_back(j);
-            cv.notify_all();
-        }
-    }
-    // GPU-witness mode: one thread.  The witness kernels of the job behind the current one are enqueued (side
-    // stream, other assignment buffer) before the current job is proved, so they run beside its multiexps.
-    void run_gpu_witness(int lane) {
-        Job cur{}, nxt{};
-        bool have_cur = false;
-        int slot = 0;
-        g_lane = lane;
-        zk_params* Pw = lane ? Pl[lane] : P;   // this lane's handles: its own workspaces over the shared tables
-        zk_r1cs* Rw = lane ? Rl[lane] : R;
-        if (use_device(Pw->key.device) != ZK_OK) {
-            // no context on this lane (stream creation / out of memory): report it and keep DRAINING the queue, so
-            // that wait() and free() never block on jobs nobody will take
-            std::unique_lock<std::mutex> lk(mu);
-            fail_with(ZK_ERR_DEVICE, g_err);
-            for (;;) {
-                cv.wait(lk, [&] { return stop || !q_wit.empty(); });
-                if (stop) return;
-                q_wit.pop_front();
-                in_flight--;
-                cv.notify_all();
-            }
-        }
-        const hipStream_t wstream = g_copy_stream;
-        auto start = [&](Job& j, int s) -> zk_status {
-            j.slot = s;
-            return guarded([&] { return witness_gpu_enqueue(Rw, j.st, j.n, s, wstream); });
-        };
-        for (;;) {
-            zk_status rc = ZK_OK;
-            if (!have_cur) {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || !q_wit.empty(); });
-                if (stop) return;
-                cur = q_wit.front();
-                q_wit.pop_front();
-                const bool skip = err != ZK_OK;
-                lk.unlock();
-                cur.slot = slot;
-                if (!skip) rc = start(cur, slot);
-                // test hook: a lane beyond the first behaves as if its workspaces did not fit (tests/test_gpu_parity.py)
-                if (!skip && lane > 0 && hook_env("ZKAMD_INJECT_LANE_OOM")) rc = fail(ZK_ERR_OUT_OF_MEMORY, "injected: lane workspaces do not fit");
-            }
-            bool have_nxt = false;
-            {
-                // (with several lanes a job is only taken ahead of time if the other lanes still find one each)
-                std::lock_guard<std::mutex> lk(mu);
-                if (q_wit.size() >= (size_t)live_lanes) {
-                    nxt = q_wit.front();
-                    q_wit.pop_front();
-                    have_nxt = true;
-                }
-            }
-            bool skip;
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                skip = err != ZK_OK;
-            }
-            zk_status rc_next = ZK_OK;
-            if (have_nxt && !skip && rc == ZK_OK) rc_next = start(nxt, cur.slot ^ 1);
-            if (!skip && rc == ZK_OK) rc = guarded([&] { return witness_gpu_finish(Rw, cur.n, cur.slot, cur.index_base); });
-            if (!skip && rc == ZK_OK) rc = guarded([&] { return prove_from_z(Pw, Rw, cur.n, cur.slot, cur.rs, cur.out, true); });
-            // nothing of a failed job stays in flight when wait() returns: drain the device BEFORE the job is counted done
-            if (rc != ZK_OK || rc_next != ZK_OK) (void)hipDeviceSynchronize();
-            if (lane > 0 && (rc == ZK_ERR_OUT_OF_MEMORY || rc_next == ZK_ERR_OUT_OF_MEMORY)) {
-                // The workspaces of a lane are allocated when it proves its first chunk; the free-memory estimate at
-                // create is only a hint (two ranks on one GPU see the same free bytes - ADVICE r3).  A lane beyond the
-                // first that does not get its memory hands its jobs back, releases what it holds and retires: the
-                // pipeline degrades to fewer lanes instead of failing in the middle of a batch.
-                std::unique_lock<std::mutex> lk(mu);
-                if (have_nxt) q_wit.push_front(nxt);
-                // (only the job that did NOT get proved goes back: when starting the NEXT job is what ran out of memory, the
-                //  current one is finished and counted - ADVICE r4)
-                if (rc == ZK_OK && !skip) in_flight--;
-                else q_wit.push_front(cur);
-                live_lanes--;
-                zk_params* mine = Pl[lane];
-                zk_r1cs* mine_r = Rl[lane];
-                Pl[lane] = nullptr;
-                Rl[lane] = nullptr;
-                lk.unlock();
-                delete mine;      // borrowed tables stay with the original, the lane's own buffers are freed
-                delete mine_r;
-                std::lock_guard<std::mutex> lk2(mu);
-                cv.notify_all();
-                return;
-            }
-            {
-                std::lock_guard<std::mutex> lk(mu);
-                if (rc != ZK_OK) fail_with(rc, g_err);
-                else if (rc_next != ZK_OK) fail_with(rc_next, g_err);
-                in_flight--;
-                cv.notify_all();
-            }
-            if (have_nxt) {
-                nxt.slot = cur.slot ^ 1;
-                cur = nxt;
-                have_cur = true;
-                slot = cur.slot;
-            } else {
-                have_cur = false;
-                slot = cur.slot ^ 1;
-            }
-        }
-    }
-    void run_gpu() {
-        for (;;) {
-            Job j;
-            bool skip;
-            {
-                std::unique_lock<std::mutex> lk(mu);
-                cv.wait(lk, [&] { return stop || !q_gpu.empty(); });
-                if (stop) return;
-                j = q_gpu.front();
-                q_gpu.pop_front();
-                skip = err != ZK_OK;
-            }
-            zk_status rc = ZK_OK;
-            if (!skip) rc = guarded([&] { return prove_batch_witness(P, R, j.n, buf[j.slot].as<uint8_t>(), ZK_FR_MONTGOMERY, j.rs, j.out, true); });
-            std::lock_guard<std::mutex> lk(mu);
-            if (rc != ZK_OK) fail_with(rc, g_err);
-            slot_free[j.slot] = true;
-            in_flight--;
-            cv.notify_all();
-        }
-    }
-};
-
-extern "C" {
-
 zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) try {
     if (!p || !circuit || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     *out = nullptr;
     ZK_TRY(route_check(p, circuit, zkpairs::TRANSFER));
+    (void)zkwit::tables();
+    // the derived bases of the pair before the lanes borrow the key's tables: every lane binds to the same set
+    ZK_TRY(ensure_derived(p, circuit));
     zk_pipeline* L = new (std::nothrow) zk_pipeline();
     if (!L) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
-    L->P = p;
-    L->R = circuit;
-    L->nv = ZK_TRANSFER_N_INPUTS + ZK_TRANSFER_N_AUX;
+    L->Pl[0] = p;
+    L->Rl[0] = circuit;
     L->chunk = ProveTunables::read().batch_chunk;
-    (void)zkwit::tables();
-    {
-        // the derived bases of the pair before the lanes borrow the key's tables: every lane binds to the same set
-        const zk_status rc = ensure_derived(p, circuit);
-        if (rc != ZK_OK) {
-            delete L;
-            return rc;
-        }
-    }
-    if (!witness_on_host()) {
-        int lanes = 2;
+    L->host = witness_on_host();
+    int lanes = 1;   // (the host calculator: lane 0 alone)
+    if (!L->host) {
+        lanes = 2;
         if (const char* env = getenv("ZKAMD_PIPELINE_LANES")) lanes = atoi(env);
 #ifdef ZK_EMU
         lanes = 1;   // the test-only emulation runs one launch at a time
@@ -1708,106 +1533,71 @@ zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) 
         // 35 GB at 1024).  The free memory seen here only caps the number of lanes STARTED (a hint: it is check-then-
         // allocate, and another process may take the memory in between); it never refuses the pipeline - lane 0 lets the
         // real allocation report OutOfMemory, and a further lane whose allocation fails later hands its jobs back and
-        // retires (run_gpu_witness).  A zk_params that has proved before already holds lane 0's workspaces.
+        // retires (pipeline_lanes.h lane_run).  A zk_params that has proved before already holds lane 0's workspaces.
 #ifndef ZK_EMU
-        {
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                size_t per_lane = L->chunk * ((size_t)36 << 20);
-                if (const char* env = getenv("ZKAMD_LANE_BYTES"))
-                    if (atoll(env) > 0) per_lane = (size_t)atoll(env);
-                const size_t reserve = (size_t)2 << 30;
-                const size_t avail = free_b > reserve ? free_b - reserve : 0;
-                const size_t lane0 = p->work.abc.p ? 0 : per_lane;       // nothing more to allocate once it has proved a chunk
-                const size_t fit = 1 + (avail > lane0 ? (avail - lane0) / per_lane : 0);
-                if ((size_t)lanes > fit) lanes = (int)fit;
-            }
+        size_t free_b = 0, total_b = 0;
+        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+            size_t per_lane = L->chunk * ((size_t)36 << 20);
+            if (const char* env = getenv("ZKAMD_LANE_BYTES"))
+                if (atoll(env) > 0) per_lane = (size_t)atoll(env);
+            const size_t reserve = (size_t)2 << 30;
+            const size_t avail = free_b > reserve ? free_b - reserve : 0;
+            const size_t lane0 = p->work.abc.p ? 0 : per_lane;       // nothing more to allocate once it has proved a chunk
+            const size_t fit = 1 + (avail > lane0 ? (avail - lane0) / per_lane : 0);
+            if ((size_t)lanes > fit) lanes = (int)fit;
         }
 #endif
-        if (lanes < 1) lanes = 1;
-        for (int l = 1; l < lanes; l++) {
-            L->Pl[l] = params_clone_for_lane(p);
-            L->Rl[l] = r1cs_clone_for_lane(circuit);
-            if (!L->Pl[l] || !L->Rl[l]) {   // no room for another set of workspaces: run with the lanes there are
-                delete L->Pl[l];
-                delete L->Rl[l];
-                L->Pl[l] = nullptr;
-                L->Rl[l] = nullptr;
-                break;
-            }
-            L->n_lanes = l + 1;
+    }
+    for (int l = 1; l < lanes; l++) {
+        L->Pl[l] = params_clone_for_lane(p);
+        L->Rl[l] = r1cs_clone_for_lane(circuit);
+        if (!L->Pl[l] || !L->Rl[l]) {   // no room for another set of workspaces: run with the lanes there are
+            delete L->Pl[l];
+            delete L->Rl[l];
+            L->Pl[l] = nullptr;
+            L->Rl[l] = nullptr;
+            break;
         }
-        L->live_lanes = L->n_lanes;
-        try {
-            L->t_gpu = std::thread([L] { L->run_gpu_witness(0); });
-            for (int l = 1; l < L->n_lanes; l++) L->t_lane[l] = std::thread([L, l] { L->run_gpu_witness(l); });
-        } catch (const std::system_error& e) {
-            zk_pipeline_free(L);
-            return fail(ZK_ERR_OUT_OF_MEMORY, std::string("cannot start a pipeline worker: ") + e.what());
-        }
-    } else {
-        for (int k = 0; k < 2; k++) {
-            zk_status rc = L->buf[k].ensure(L->chunk * L->nv * 32);
-            if (rc != ZK_OK) {
-                delete L;
-                return rc;
-            }
-        }
-        try {
-            L->t_wit = std::thread([L] { L->run_wit(); });
-            L->t_gpu = std::thread([L] { L->run_gpu(); });
-        } catch (const std::system_error& e) {
-            zk_pipeline_free(L);
-            return fail(ZK_ERR_OUT_OF_MEMORY, std::string("cannot start a pipeline worker: ") + e.what());
-        }
+        L->n_lanes = l + 1;
+    }
+    L->Q.open(L->n_lanes);
+    try {
+        for (int l = 0; l < L->n_lanes; l++)
+            L->t_lane[l] = std::thread([L, l] {
+                PipelineLane lane{L, l};
+                zkpipe::lane_run(L->Q, l, lane);
+            });
+    } catch (const std::system_error& e) {
+        zk_pipeline_free(L);
+        return fail(ZK_ERR_OUT_OF_MEMORY, std::string("cannot start a pipeline worker: ") + e.what());
     }
     *out = L;
     return ZK_OK;
 } ZK_ABI_CATCH
 
-int zk_pipeline_lanes(const zk_pipeline* L) {
-    if (!L) return 0;
-    std::lock_guard<std::mutex> lk(const_cast<zk_pipeline*>(L)->mu);
-    return L->live_lanes;
-}
+int zk_pipeline_lanes(const zk_pipeline* L) { return L ? L->Q.lanes() : 0; }
 
 zk_status zk_pipeline_submit(zk_pipeline* L, size_t n, const zk_transfer_statement* st, const uint8_t* rs, uint8_t* proofs_out) try {
     if (!L || !rs || !proofs_out || (!st && n)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    std::lock_guard<std::mutex> lk(L->mu);
-    for (size_t first = 0; first < n; first += L->chunk) {
-        const size_t np = std::min(L->chunk, n - first);
-        L->q_wit.push_back(zk_pipeline::Job{st + first, rs + first * 64, proofs_out + first * 192, np, first, -1});
-        L->in_flight++;
-    }
-    L->cv.notify_all();
+    std::vector<zkpipe::Job> jobs;
+    for (size_t first = 0; first < n; first += L->chunk)
+        jobs.push_back(zkpipe::Job{st + first, rs + first * 64, proofs_out + first * 192, std::min(L->chunk, n - first), first});
+    L->Q.submit(jobs.data(), jobs.size());
     return ZK_OK;
 } ZK_ABI_CATCH
 
 zk_status zk_pipeline_wait(zk_pipeline* L) try {
     if (!L) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
-    std::unique_lock<std::mutex> lk(L->mu);
-    L->cv.wait(lk, [&] { return L->in_flight == 0; });
-    const zk_status rc = L->err;
-    if (rc != ZK_OK) g_err = L->err_msg;
-    L->err = ZK_OK;   // the stream is usable again after the failure has been reported
-    L->err_msg.clear();
-    return rc;
+    return L->Q.wait(&g_err);
 } ZK_ABI_CATCH
 
 void zk_pipeline_free(zk_pipeline* L) {
     if (!L) return;
-    {
-        std::unique_lock<std::mutex> lk(L->mu);
-        L->cv.wait(lk, [&] { return L->in_flight == 0; });
-        L->stop = true;
-        L->cv.notify_all();
-    }
-    if (L->t_wit.joinable()) L->t_wit.join();
-    if (L->t_gpu.joinable()) L->t_gpu.join();
-    for (int l = 1; l < zk_pipeline::MAX_LANES; l++) {
+    L->Q.close();
+    for (int l = 0; l < zk_pipeline::MAX_LANES; l++) {
         if (L->t_lane[l].joinable()) L->t_lane[l].join();
-        delete L->Pl[l];
-        delete L->Rl[l];
+        if (l) delete L->Pl[l];   // (lane 0 works on the caller's handles)
+        if (l) delete L->Rl[l];
     }
     delete L;
 }
