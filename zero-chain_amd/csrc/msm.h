@@ -13,6 +13,10 @@
 //   * with a multiple available at every bit position the scalar is recoded in width-c NAF:
 //     odd signed digits |d| < 2^(c-1) at arbitrary positions, on average one non-zero digit
 //     per c + 1 bits (bellman: one per c bits) over only 2^(c-2) buckets (bellman: 2^c - 1).
+//   * the same memory buys a larger digit set: the tables bound to a circuit also hold m * 2^k * P_i for the odd m = 3, 5, ...
+//     (slice 255 j + k for m = 2 j + 1: 3.7 -> 29.9 GB for the Transfer key with eight), a digit m * b (b odd, b < 2^(c-1))
+//     goes into bucket b through the slice of m, and a scalar has a digit per c + 1 + g bits, g = 0.6 / 1.25 / 1.85 for two /
+//     four / eight multiples (MsmRecode, msm_wnaf_mult below) - buckets, reduction and tail exactly as they were.
 //   * (digit, point) pairs are counting-sorted by bucket (histogram with returned ranks ->
 //     per-job exclusive scan -> scatter).  A bucket is cut into tasks of <= seg points and
 //     the tasks of the whole launch are ordered by length, so the 64 lanes of a wave walk
@@ -119,15 +123,10 @@ struct MsmConsts {
     static constexpr uint32_t R[8] = ZK_FR_P_32;
 };
 
-// Width-c NAF of one scalar.  f(slot, position, odd magnitude in [1, 2^(c-1)), negative) is
-// called for every non-zero digit, slot = 0, 1, 2 ... in order of increasing position.
-// Scalars above (r - 1) / 2 are replaced by r - s with every sign flipped
-// (s * P == (r - s) * (-P)), so the recoded value is < 2^254 and the last digit sits at a
-// position <= 254.  The words are consumed through a 64-bit shift buffer, so no dynamically
-// indexed register array is needed.
-template <class Fn>
-ZK_DI void msm_wnaf(const uint32_t* __restrict__ sp, uint32_t c, Fn&& f) {
-    uint32_t s[8];
+// The words a scalar is recoded from: s itself, or r - s with every sign flipped (`neg`) for s above (r - 1) / 2
+// (s * P == (r - s) * (-P)), so the recoded value is < 2^254 and the last digit sits at a position <= 254.  False: the
+// scalar has no digits.
+ZK_DI bool msm_wnaf_words(const uint32_t* __restrict__ sp, uint32_t (&s)[8], bool& neg) {
     const uint4* q = reinterpret_cast<const uint4*>(sp);
     uint4 lo = q[0], hi = q[1];
     s[0] = lo.x; s[1] = lo.y; s[2] = lo.z; s[3] = lo.w;
@@ -155,10 +154,22 @@ ZK_DI void msm_wnaf(const uint32_t* __restrict__ sp, uint32_t c, Fn&& f) {
     uint32_t t_or = 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) t_or |= t[i];
-    if (!zero_or || bo || !t_or) return;
-    const bool neg = lt != 0;
+    if (!zero_or || bo || !t_or) return false;
+    neg = lt != 0;
 #pragma unroll
     for (int i = 0; i < 8; i++) s[i] = neg ? t[i] : s[i];
+    return true;
+}
+
+// Width-c NAF of one scalar.  f(slot, position, odd magnitude in [1, 2^(c-1)), negative) is
+// called for every non-zero digit, slot = 0, 1, 2 ... in order of increasing position.
+// The sign normalisation is msm_wnaf_words'.  The words are consumed through a 64-bit shift buffer, so no dynamically
+// indexed register array is needed.
+template <class Fn>
+ZK_DI void msm_wnaf(const uint32_t* __restrict__ sp, uint32_t c, Fn&& f) {
+    uint32_t s[8];
+    bool neg;
+    if (!msm_wnaf_words(sp, s, neg)) return;
     const uint32_t half = 1u << (c - 1), mask = (1u << c) - 1;
     uint64_t buf = 0;
     uint32_t nbits = 0, pos = 0, carry = 0, slot = 0;
@@ -199,6 +210,108 @@ ZK_DI void msm_wnaf(const uint32_t* __restrict__ sp, uint32_t c, Fn&& f) {
                 f(slot++, pos + z, mag, (carry != 0) != neg);
                 buf >>= c;
                 pos += z + c;
+            }
+        }
+    }
+}
+
+// Table multiples.  A table may hold, behind its 255 slices 2^k P, the slices of m 2^k P for the odd m = 3, 5, ... ,
+// 2 n_mult - 1 (slice 255 j + k = m_j 2^k P, m_j = 2 j + 1).  The digit set grows to D = { +- m b : m = m_j, b odd,
+// b < 2^(c-1) } over the SAME buckets - a digit m b goes into bucket b through the slice of m - so the zero runs between the
+// digits grow.  At an odd residual k with more than W + 1 bits left (W = c + ext) the step is WIDE: for w = W down to c,
+// rho = k mod 2^w and the candidates rho, rho - 2^w, the smaller magnitude first; the first candidate in D is the digit, its
+// multiple the smallest m that divides it with a quotient below 2^(c-1), and the recoding goes on with (k - d) / 2^w (the
+// carry stays 0 or 1).  w = c always finds the plain NAF digit.  Near the top of the scalar the step is the plain one of
+// msm_wnaf.  The choice depends on the low W bits of the odd residual alone: lut[(k mod 2^W) >> 1] = (w - c) | negative
+// candidate << 3 | j << 4, 2^(W-1) bytes per (c, n_mult, ext) that stay in L2 (msm_mult_choice makes them on the host).
+constexpr uint32_t MSM_MULT_MAX = 8;
+struct MsmRecode {
+    const uint8_t* lut;     // null: one multiple, the plain msm_wnaf
+    uint32_t n_mult, ext;
+};
+__host__ ZK_DI uint32_t msm_mult_ext(uint32_t n_mult) { return n_mult <= 1 ? 0u : n_mult == 2 ? 2u : 3u; }
+// v: the low W = c + ext bits of an odd residual
+__host__ ZK_DI uint8_t msm_mult_choice(uint32_t v, uint32_t c, uint32_t n_mult, uint32_t ext) {
+    const uint32_t half = 1u << (c - 1);
+    for (uint32_t w = c + ext; w >= c; w--) {
+        const uint32_t rho = v & ((1u << w) - 1u), other = (1u << w) - rho;
+        for (uint32_t t = 0; t < 2; t++) {
+            const uint32_t negative = (rho < other) == (t == 0) ? 0u : 1u, mag = negative ? other : rho;
+            for (uint32_t j = 0; j < n_mult; j++) {
+                const uint32_t m = 2 * j + 1;
+                if (mag % m == 0 && mag / m < half) return (uint8_t)((w - c) | (negative << 3) | (j << 4));
+            }
+        }
+    }
+    return 0;   // (not reached: at w = c the candidate of the smaller magnitude is below 2^(c-1))
+}
+// f(slot, slice = 255 j + position, odd bucket magnitude in [1, 2^(c-1)), negative), digits in order of increasing position
+template <class Fn>
+ZK_DI void msm_wnaf_mult(const uint32_t* __restrict__ sp, uint32_t c, const MsmRecode& rc, Fn&& f) {
+    uint32_t s[8];
+    bool neg;
+    if (!msm_wnaf_words(sp, s, neg)) return;
+    uint32_t len = 0;   // bits of the value: a wide step needs more than W + 1 of them from its digit on
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+        if (s[i]) len = 32u * i + 32u - (uint32_t)__builtin_clz(s[i]);
+    const uint32_t W = c + rc.ext, half = 1u << (c - 1), mask = (1u << c) - 1, maskw = (1u << W) - 1;
+    uint64_t buf = 0;
+    uint32_t nbits = 0, pos = 0, carry = 0, slot = 0;
+    // the digit at position p, the odd residual's low bits at the bottom of buf; returns the bits it consumed
+    auto step = [&](uint32_t p) -> uint32_t {
+        uint32_t w = c, mag, j = 0;
+        if (len > p + W + 1) {
+            const uint32_t val = ((uint32_t)buf & maskw) + carry;   // odd, < 2^W
+            const uint32_t ch = rc.lut[val >> 1];
+            w = c + (ch & 7u);
+            j = ch >> 4;
+            const uint32_t rho = val & ((1u << w) - 1u), m = 2 * j + 1;
+            carry = (ch >> 3) & 1u;
+            mag = carry ? (1u << w) - rho : rho;
+            uint32_t inv = m;   // m^-1 mod 2^32 (m m = 1 mod 8; every step doubles the bits): the division is exact
+#pragma unroll
+            for (int it = 0; it < 4; it++) inv *= 2u - m * inv;
+            mag *= inv;
+        } else {
+            const uint32_t val = ((uint32_t)buf & mask) + carry;   // odd
+            carry = val > half ? 1u : 0u;
+            mag = carry ? (1u << c) - val : val;
+        }
+        f(slot++, p + MSM_NPOS * j, mag, (carry != 0) != neg);
+        return w;
+    };
+#pragma unroll
+    for (int i = 0; i < 8; i++) {
+        buf |= (uint64_t)s[i] << nbits;   // nbits <= 32 here
+        nbits += 32;
+        if (i < 7) {
+            // more than 32 bits stay buffered below a digit, so a wide window (c + ext <= 22) is always there
+            while (nbits > 32) {
+                uint64_t tt = carry ? ~buf : buf;
+                uint32_t z = tt ? (uint32_t)__builtin_ctzll(tt) : 64u;
+                uint32_t room = nbits - 32;
+                if (z >= room) {   // only zero digits up to the refill point
+                    buf >>= room;
+                    pos += room;
+                    nbits = 32;
+                    break;
+                }
+                buf >>= z;
+                const uint32_t w = step(pos + z);
+                buf >>= w;
+                pos += z + w;
+                nbits -= z + w;
+            }
+        } else {
+            // last word: bits above the buffer are genuine zeros of the scalar
+            while (buf != 0 || carry) {
+                uint64_t tt = carry ? ~buf : buf;
+                uint32_t z = (uint32_t)__builtin_ctzll(tt);   // tt != 0: the top two bits of s are clear
+                buf >>= z;
+                const uint32_t w = step(pos + z);
+                buf >>= w;
+                pos += z + w;
             }
         }
     }
@@ -261,11 +374,12 @@ ZK_DI bool msm_vb_digit(const uint32_t* __restrict__ sp, uint32_t c, uint32_t di
     }
     return true;
 }
-// digits of scalar i of a job, in either mode: f(slot, bit position of the table slice, odd magnitude, negative)
+// digits of scalar i of a job, in either mode: f(slot, table slice (the bit position; behind 255 j for multiple j), odd magnitude, negative)
 template <class Fn>
-ZK_DI void msm_digits(const MsmJob& job, uint32_t i, uint32_t c, Fn&& f) {
+ZK_DI void msm_digits(const MsmJob& job, uint32_t i, uint32_t c, const MsmRecode& rc, Fn&& f) {
     if (job.vb_digit == 0) {
-        msm_wnaf(job.scalars + (size_t)i * 8, c, f);
+        if (rc.lut) msm_wnaf_mult(job.scalars + (size_t)i * 8, c, rc, f);
+        else msm_wnaf(job.scalars + (size_t)i * 8, c, f);
     } else {
         uint32_t mag;
         bool negative;
@@ -293,7 +407,7 @@ constexpr uint32_t MSM_COARSE_SCALARS = 1024;  // scalars per workgroup of passe
 
 static __global__ void __launch_bounds__(256)
 k_msm_coarse_count(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_log, uint32_t n_coarse, uint32_t* coarse_cnt,
-                   uint32_t* blockbase, uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}) {
+                   uint32_t* blockbase, uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}, const MsmRecode rc = MsmRecode{}) {
     ZK_SHARED uint32_t h[MSM_COARSE_MAX];
     const MsmJob job = jobs[blockIdx.y];
     const uint32_t tid = threadIdx.x;
@@ -303,7 +417,7 @@ k_msm_coarse_count(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_lo
     for (uint32_t e = 0; e < per_wg / 256; e++) {
         const uint32_t i = blockIdx.x * per_wg + e * 256 + tid;
         if (i >= job.n || msm_job_pos(job, sels, blockIdx.y, i) < 0) continue;
-        msm_digits(job, i, c, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[(mag >> 1) >> fine_log], 1u); });
+        msm_digits(job, i, c, rc, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[(mag >> 1) >> fine_log], 1u); });
     }
     __syncthreads();
     uint32_t* bb = blockbase + ((size_t)blockIdx.y * gridDim.x + blockIdx.x) * n_coarse;
@@ -345,7 +459,7 @@ k_msm_coarse_scan(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, u
 static __global__ void __launch_bounds__(256)
 k_msm_coarse_scatter(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_log, uint32_t n_coarse,
                      const uint32_t* __restrict__ coarse_off, const uint32_t* __restrict__ blockbase, uint2* __restrict__ rec,
-                     uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}) {
+                     uint32_t per_wg, const MsmSelSet sels = MsmSelSet{}, const MsmRecode rc = MsmRecode{}) {
     ZK_SHARED uint32_t h[MSM_COARSE_MAX];
     const MsmJob job = jobs[blockIdx.y];
     const uint32_t tid = threadIdx.x;
@@ -362,7 +476,7 @@ k_msm_coarse_scatter(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t fine_
         const int32_t pos = msm_job_pos(job, sels, blockIdx.y, i);
         if (pos < 0) continue;
         const uint32_t tbase = job.table_base + (uint32_t)pos, tstride = job.n_table;
-        msm_digits(job, i, c, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {
+        msm_digits(job, i, c, rc, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {
             const uint32_t b = mag >> 1;
             const uint32_t slot = atomicAdd(&h[b >> fine_log], 1u);
             jrec[slot] = make_uint2(b & fmask, ((tbase + bit * tstride) << 1) | (negative ? 1u : 0u));
@@ -463,9 +577,12 @@ constexpr uint32_t MSM_SORT_THREADS = 64;     // the test-only emulation runs on
 #else
 constexpr uint32_t MSM_SORT_THREADS = 1024;
 #endif
-static __global__ void __launch_bounds__(MSM_SORT_THREADS)
+// (two workgroups of sixteen waves per CU: 64 VGPRs - the recoding over the multiples took 76 without the second bound, one
+//  workgroup per CU, and every sort 2 ms longer)
+static __global__ void __launch_bounds__(MSM_SORT_THREADS, 8)
 k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint32_t* off, uint32_t* toff,
-               uint32_t* ntasks, uint32_t* pairs, uint32_t seg, uint32_t dbg, const MsmSelSet sels = MsmSelSet{}) {
+               uint32_t* ntasks, uint32_t* pairs, uint32_t seg, uint32_t dbg, const MsmSelSet sels = MsmSelSet{},
+               const MsmRecode rc = MsmRecode{}) {
     ZK_DYN_SHARED(uint32_t, h);   // [nb] histogram, then running slot cursors
     ZK_SHARED uint32_t part[MSM_SORT_THREADS];
     ZK_SHARED uint32_t tpart[MSM_SORT_THREADS];
@@ -475,7 +592,7 @@ k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint3
     __syncthreads();
     for (uint32_t i = tid; i < job.n; i += nt) {
         if (msm_job_pos(job, sels, blockIdx.x, i) < 0) continue;
-        msm_digits(job, i, c, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[mag >> 1], 1u); });
+        msm_digits(job, i, c, rc, [&](uint32_t, uint32_t, uint32_t mag, bool) { atomicAdd(&h[mag >> 1], 1u); });
     }
     __syncthreads();
     // exclusive scans of the counts (pair slots) and of the task counts; thread t owns buckets [t*per, ..)
@@ -520,7 +637,7 @@ k_msm_sort_lds(const MsmJob* __restrict__ jobs, uint32_t c, uint32_t* cnt, uint3
         const int32_t pos = msm_job_pos(job, sels, blockIdx.x, i);
         if (pos < 0) continue;
         const uint32_t tbase = job.table_base + (uint32_t)pos, tstride = job.n_table;
-        msm_digits(job, i, c, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {
+        msm_digits(job, i, c, rc, [&](uint32_t, uint32_t bit, uint32_t mag, bool negative) {
             uint32_t slot = atomicAdd(&h[mag >> 1], 1u);
             if ((dbg & 1u) && slot != 0xffffffffu) return;   // diagnostics: everything but the scattered store
             jpairs[slot] = ((tbase + bit * tstride) << 1) | (negative ? 1u : 0u);
@@ -1588,37 +1705,47 @@ ZK_DI Affine<F> to_affine(const XYZZ<F>& p) {
 // point, [slot][field][point].  Points at infinity (legal bases, mapped out) and - for unchecked keys
 // - a chain that runs into infinity are carried through as (0, 0).
 constexpr uint32_t MSM_TABLE_CHUNK = 16;
+// n_mult > 1: behind the 255 slices of P those of 3 P, 5 P, ... (slice 255 j + k = (2 j + 1) 2^k P): 3 P = 2 P + P,
+// 5 P = 3 P + 2 P, ... with the complete addition, then the same chain per multiple over the same scratch.  j0: the first
+// multiple whose slices are made (the ones before it are in place: MsmGroup::add_multiples).
 template <class F>
 static __global__ void __launch_bounds__(128)
-k_msm_build_table(Affine<F>* table, uint32_t n, uint32_t npos, F* scratch) {
+k_msm_build_table(Affine<F>* table, uint32_t n, uint32_t npos, F* scratch, uint32_t n_mult, uint32_t j0) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     const Affine<F> p0 = table[i];   // slice 0 was uploaded by the host
-    XYZZ<F> cur = p0.is_inf() ? XYZZ<F>::inf() : XYZZ<F>{p0.x, p0.y, F::one(), F::one()};
+    XYZZ<F> mult = p0.is_inf() ? XYZZ<F>::inf() : XYZZ<F>{p0.x, p0.y, F::one(), F::one()};
+    const XYZZ<F> two = n_mult > 1 ? xdbl(mult) : XYZZ<F>::inf();
     auto slot = [&](uint32_t j, uint32_t f) -> F& { return scratch[((size_t)j * 5 + f) * n + i]; };
-    for (uint32_t k0 = 1; k0 < npos; k0 += MSM_TABLE_CHUNK) {
-        const uint32_t nc = npos - k0 < MSM_TABLE_CHUNK ? npos - k0 : MSM_TABLE_CHUNK;
-        F run = F::one();
-        for (uint32_t j = 0; j < nc; j++) {
-            cur = xdbl(cur);
-            slot(j, 0) = cur.x;
-            slot(j, 1) = cur.y;
-            slot(j, 2) = cur.zz;
-            slot(j, 3) = cur.zzz;
-            slot(j, 4) = run;                                   // product of the zzz before this one
-            if (!cur.is_inf()) run = mul(run, cur.zzz);
-        }
-        F inv_run = inv_fast(run);
-        for (uint32_t j = nc; j-- > 0;) {
-            const XYZZ<F> q{slot(j, 0), slot(j, 1), slot(j, 2), slot(j, 3)};
-            Affine<F> a{F::zero(), F::zero()};
-            if (!q.is_inf()) {
-                const F izzz = mul(inv_run, slot(j, 4));
-                inv_run = mul(inv_run, q.zzz);
-                const F izz = mul(sqr(q.zz), sqr(izzz));       // zz^2 / zzz^2 = 1 / zz
-                a = Affine<F>{mul(q.x, izz), mul(q.y, izzz)};
+    for (uint32_t jm = 0; jm < n_mult; jm++) {
+        if (jm) mult = xadd(mult, two);
+        if (jm < j0) continue;
+        XYZZ<F> cur = mult;
+        Affine<F>* tj = table + (size_t)jm * npos * n;
+        for (uint32_t k0 = jm ? 0u : 1u; k0 < npos; k0 += MSM_TABLE_CHUNK) {   // (slice 0 of a multiple is the multiple itself)
+            const uint32_t nc = npos - k0 < MSM_TABLE_CHUNK ? npos - k0 : MSM_TABLE_CHUNK;
+            F run = F::one();
+            for (uint32_t j = 0; j < nc; j++) {
+                if (k0 + j) cur = xdbl(cur);
+                slot(j, 0) = cur.x;
+                slot(j, 1) = cur.y;
+                slot(j, 2) = cur.zz;
+                slot(j, 3) = cur.zzz;
+                slot(j, 4) = run;                                   // product of the zzz before this one
+                if (!cur.is_inf()) run = mul(run, cur.zzz);
             }
-            table[(size_t)(k0 + j) * n + i] = a;
+            F inv_run = inv_fast(run);
+            for (uint32_t j = nc; j-- > 0;) {
+                const XYZZ<F> q{slot(j, 0), slot(j, 1), slot(j, 2), slot(j, 3)};
+                Affine<F> a{F::zero(), F::zero()};
+                if (!q.is_inf()) {
+                    const F izzz = mul(inv_run, slot(j, 4));
+                    inv_run = mul(inv_run, q.zzz);
+                    const F izz = mul(sqr(q.zz), sqr(izzz));       // zz^2 / zzz^2 = 1 / zz
+                    a = Affine<F>{mul(q.x, izz), mul(q.y, izzz)};
+                }
+                tj[(size_t)(k0 + j) * n + i] = a;
+            }
         }
     }
 }

@@ -30,6 +30,9 @@ namespace zkrt {
 // G2: the same in Fq2, where the full addition no longer fits the register file).  `group` 1 / 2.
 // group: 1 = G1 jobs of a batch (level 1 of their reduction in assembly), 2 = G2, 3 = the small A jobs of a split batch,
 // 4 = a stand-alone G1 handle (zk_msm_create: compiled reduction)
+// Over a table with multiples (msm.h MsmRecode) a scalar has 254 / (c + 1 + g) digits, g = 0.6 / 1.25 / 1.85 bits for 2 / 4 / 8
+// multiples; the widths are NOT taken from that: with it the G2 set came out at 12 and ran 3.4 ms per chunk slower than at the
+// 13 it has without (profiles/r28_table_multiples.txt (c)), so the bound sets keep the widths of one multiple.
 inline uint32_t pick_window(size_t n, int group) {
     const char* env = getenv(group == 2 ? "ZKAMD_WINDOW_BITS_G2" : group == 3 ? "ZKAMD_WINDOW_BITS_G1A" : "ZKAMD_WINDOW_BITS_G1");
     if (!env) env = getenv("ZKAMD_WINDOW_BITS");
@@ -156,7 +159,10 @@ struct MsmGroup {
 
     uint32_t c = 0, maxd = 0, nb = 0;
     size_t n_points = 0;
-    DevBuf table;
+    // the odd multiples of every slice the table holds (msm.h MsmRecode; 1: the doublings alone), the extra window bits of the
+    // recoding over them and its choice table for this group's c (made by the first launch set: ensure_recode)
+    uint32_t n_mult = 1, ext = 0;
+    DevBuf table, lut;
     DevBuf jobs_d, cnt, off, toff, ntasks, hist, tclass, sorted, heavy, light, blockbase, coarse, tbase, rank, pairs, tsums, red_r, red_w, red_t, result, redo;
     DPoint* res_dev = nullptr;
     PinBuf pin_jobs;
@@ -165,22 +171,38 @@ struct MsmGroup {
 
     // the recoding width and what follows from it.  with_table = false: variable-base mode - only the bases themselves are
     // kept (slice 0), every job takes ONE digit of every scalar (msm.h msm_digits)
-    zk_status set_geometry(uint32_t c_, size_t n, bool with_table) {
+    zk_status set_geometry(uint32_t c_, size_t n, bool with_table, uint32_t n_mult_ = 1) {
+        if (n_mult_ < 1 || n_mult_ > zkdev::MSM_MULT_MAX || (n_mult_ > 1 && !with_table))
+            return fail(ZK_ERR_INVALID_ARGUMENT, "internal: table multiples out of range");
         c = c_;
         maxd = with_table ? zkdev::msm_max_digits(c) : 1u;
         nb = 1u << (c - 2);
         n_points = n;
+        set_multiples(n_mult_);
         const uint32_t npos = with_table ? zkdev::MSM_NPOS : 1u;
-        if ((uint64_t)n_points * npos >= (1ull << 31)) return fail(ZK_ERR_INVALID_ARGUMENT, "doubling table too large");
-        bytes = sizeof(DAffine) * n_points * npos;
+        // a pair is an entry's index and a sign bit: 31 bits for the index
+        if ((uint64_t)n_points * npos * n_mult >= (1ull << 31)) return fail(ZK_ERR_INVALID_ARGUMENT, "doubling table too large");
+        bytes = sizeof(DAffine) * n_points * npos * n_mult;
         return ZK_OK;
     }
-    // the same bases (borrowed doubling table) under another recoding width; workspaces are this object's own
+    // the same bases (borrowed doubling table, with its multiples) under another recoding width; workspaces are this object's own
     void alias(const MsmGroup& o, uint32_t c_) {
-        (void)set_geometry(c_, o.n_points, true);   // (the table it borrows passed the size test when it was built)
-        bytes = 0;                                    // (... and is accounted for by its owner)
+        (void)set_geometry(c_, o.n_points, true, o.n_mult);   // (the table it borrows passed the size test when it was built)
+        bytes = 0;                                              // (... and is accounted for by its owner)
         table.borrow(o.table);
     }
+    void set_multiples(uint32_t n_mult_) {
+        n_mult = n_mult_;
+        ext = zkdev::msm_mult_ext(n_mult);
+        if (c + ext > 22) ext = c < 22 ? 22 - c : 0;   // (the recoding's buffer holds 32 bits: msm.h msm_wnaf_mult)
+        lut.release();
+    }
+    // A table built with one multiple gets the slices of the others: a new allocation, the slices in place copied, the chains of
+    // 3 P, 5 P, ... made (a key bound by a proof made alone meets its first batch).  Groups that borrowed the table alias again.
+    zk_status add_multiples(uint32_t n_mult_);
+    // the choice table of the recoding over the multiples (none for one multiple), and what the sort kernels get
+    zk_status ensure_recode();
+    zkdev::MsmRecode recode() const { return zkdev::MsmRecode{lut.as<uint8_t>(), n_mult, ext}; }
     // Slice 0 of the table from the reference's uncompressed encodings (n x 96 / 192 bytes on the HOST), decoded on the
     // device: upload into `raw`, k_decode_uncompressed into the table, `map` (n entries) = position or -1 for a point at
     // infinity.  Everything is enqueued on st; decode_finish() reads the verdict once the stream has been waited for.
@@ -201,11 +223,13 @@ struct MsmGroup {
     zk_status table_enqueue(DevBuf& scratch, hipStream_t st);
     // the table of doublings over a slice 0 that is already in place; checked: curve + subgroup test of every base first
     zk_status finish_build(bool checked, const char* what, bool with_table);
-    zk_status build(const std::vector<HAffine>& pts, uint32_t c_, bool checked, const char* what, bool with_table = true);
+    zk_status build(const std::vector<HAffine>& pts, uint32_t c_, bool checked, const char* what, bool with_table = true,
+                    uint32_t n_mult_ = 1);
 
     // A derived base set: slice 0 = [pts | entries [from, from + count) of slice 0 of `o`], then the table of doublings.  A point
     // at infinity among pts stays (0, 0) through the table, as in a key file: the caller maps it out.
-    zk_status build_with_tail(const std::vector<HAffine>& pts, const MsmGroup& o, size_t from, size_t count, uint32_t c_);
+    zk_status build_with_tail(const std::vector<HAffine>& pts, const MsmGroup& o, size_t from, size_t count, uint32_t c_,
+                              uint32_t n_mult_ = 1);
 
     // jobs[i].pair_base is filled in here.  Everything, including the copy of the results (one XYZZ
     // per job) into `out`, is enqueued on `st`; collect() waits for it.
@@ -251,7 +275,8 @@ private:
     zk_status tail(const MsmPlan& p, hipStream_t st);
     // the end of the *_to_host functions: the launch is checked, `stage` (n points in the host's layout) goes to `out`
     zk_status copy_to_host(const DevBuf& stage, size_t n, HPoint* out, hipStream_t st);
-    // diagnostics of the hooks build (ZKAMD_DEBUG_REDO, ZKAMD_DEBUG_HEAVY)
+    // diagnostics of the hooks build (ZKAMD_DEBUG_REDO, ZKAMD_DEBUG_HEAVY, ZKAMD_DEBUG_PAIRS)
+    void dump_pairs(const MsmJob& job0, hipStream_t st, const char* dir);
     void dump_redo(const MsmPlan& p, hipStream_t st, bool after_level1);
     void dump_heavy(const MsmPlan& p, hipStream_t st);
     // the counters behind the two class arrays of `hist` (its layout: msm_plan.h Bytes::hist)

@@ -56,9 +56,40 @@ template <class HF, class DF>
 zk_status MsmGroup<HF, DF>::launch_table_build(DevBuf& scratch, hipStream_t st) {
     ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF) * n_points));   // chunk of un-normalised slices + prefix products
     ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3((unsigned)((n_points + 127) / 128)), dim3(128), 0, st, table.as<DAffine>(),
-              (uint32_t)n_points, zkdev::MSM_NPOS, scratch.as<DF>());
+              (uint32_t)n_points, zkdev::MSM_NPOS, scratch.as<DF>(), n_mult, 0u);
     HIP_TRY(hipGetLastError());
     return ZK_OK;
+}
+
+template <class HF, class DF>
+zk_status MsmGroup<HF, DF>::add_multiples(uint32_t n_mult_) {
+    if (n_mult_ <= n_mult || !n_points) return ZK_OK;
+    if (n_mult != 1 || !table.owned || n_mult_ > zkdev::MSM_MULT_MAX) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: multiples cannot be added to this table");
+    if ((uint64_t)n_points * zkdev::MSM_NPOS * n_mult_ >= (1ull << 31)) return fail(ZK_ERR_INVALID_ARGUMENT, "doubling table too large");
+    const size_t one = sizeof(DAffine) * n_points * zkdev::MSM_NPOS;
+    DevBuf grown, scratch;
+    grown.is_public = true;
+    ZK_TRY(grown.ensure(one * n_mult_));
+    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF) * n_points));
+    HIP_TRY(hipMemcpyAsync(grown.p, table.p, one, hipMemcpyDeviceToDevice, g_stream));
+    ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3((unsigned)((n_points + 127) / 128)), dim3(128), 0, g_stream, grown.as<DAffine>(),
+              (uint32_t)n_points, zkdev::MSM_NPOS, scratch.as<DF>(), n_mult_, 1u);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    std::swap(table.p, grown.p);       // (the table with one multiple goes with `grown`)
+    std::swap(table.cap, grown.cap);
+    set_multiples(n_mult_);
+    bytes = one * n_mult_;
+    return ensure_recode();
+}
+
+template <class HF, class DF>
+zk_status MsmGroup<HF, DF>::ensure_recode() {
+    if (n_mult <= 1 || lut.p) return ZK_OK;
+    std::vector<uint8_t> h((size_t)1 << (c + ext - 1));
+    for (size_t v = 0; v < h.size(); v++) h[v] = zkdev::msm_mult_choice((uint32_t)(2 * v + 1), c, n_mult, ext);
+    lut.is_public = true;   // a function of (c, n_mult, ext) alone
+    return lut.upload(h);
 }
 
 template <class HF, class DF>
@@ -74,13 +105,15 @@ zk_status MsmGroup<HF, DF>::finish_build(bool checked, const char* what, bool wi
         DevBuf scratch;   // freed after the build
         ZK_TRY(launch_table_build(scratch, g_stream));
         HIP_TRY(hipStreamSynchronize(g_stream));
+        ZK_TRY(ensure_recode());
     }
     return ZK_OK;
 }
 
 template <class HF, class DF>
-zk_status MsmGroup<HF, DF>::build(const std::vector<typename MsmGroup<HF, DF>::HAffine>& pts, uint32_t c_, bool checked, const char* what, bool with_table) {
-    ZK_TRY(set_geometry(c_, pts.size(), with_table));
+zk_status MsmGroup<HF, DF>::build(const std::vector<typename MsmGroup<HF, DF>::HAffine>& pts, uint32_t c_, bool checked, const char* what, bool with_table,
+                                  uint32_t n_mult_) {
+    ZK_TRY(set_geometry(c_, pts.size(), with_table, n_mult_));
     table.is_public = true;   // bases of a key or of a multiexp: public points, 4.2 GB for the transfer key - freed without the wipe
     ZK_TRY(table.ensure(bytes ? bytes : 1));
     if (!n_points) return ZK_OK;
@@ -99,9 +132,9 @@ zk_status MsmGroup<HF, DF>::build(const std::vector<typename MsmGroup<HF, DF>::H
 
 template <class HF, class DF>
 zk_status MsmGroup<HF, DF>::build_with_tail(const std::vector<typename MsmGroup<HF, DF>::HAffine>& pts, const MsmGroup& o, size_t from,
-                                            size_t count, uint32_t c_) {
+                                            size_t count, uint32_t c_, uint32_t n_mult_) {
     if (from + count > o.n_points) return fail(ZK_ERR_INVALID_ARGUMENT, "internal: tail outside the borrowed table");
-    ZK_TRY(set_geometry(c_, pts.size() + count, true));
+    ZK_TRY(set_geometry(c_, pts.size() + count, true, n_mult_));
     table.is_public = true;   // images of a key's bases under public maps
     ZK_TRY(table.ensure(bytes ? bytes : 1));
     if (!pts.empty()) {
@@ -132,9 +165,11 @@ zk_status MsmGroup<HF, DF>::enqueue(std::vector<MsmJob>& jobs, std::vector<typen
     if (msm_plan(p, IS_G2, c, nb, maxd, jobs.data(), nj, asm_loop<DF>(), asm_reduce<DF>(), MsmTunables::read(IS_G2)) != ZK_OK)
         return fail(p.status, p.refusal);
     for (size_t k = 0; k < nj; k++) jobs[k].pair_base = p.pair_base[k];
+    ZK_TRY(ensure_recode());
     ZK_TRY(reserve(p, to_host));
     ZK_TRY(upload_jobs(jobs, p, st));
     ZK_TRY(sort_pairs(p, st, sels ? *sels : zkdev::MsmSelSet{}));
+    if (hook_env("ZKAMD_DEBUG_PAIRS")) dump_pairs(jobs[0], st, hook_env("ZKAMD_DEBUG_PAIRS"));
     ZK_TRY(order_tasks(p, st));
     ZK_TRY(accumulate(p, st));
     {
@@ -185,7 +220,7 @@ zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st, const z
         ProfScope ps("msm_sort_lds", st);
         ZK_LAUNCH_SYNC(zkdev::k_msm_sort_lds, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), (size_t)nb * 4, st, dj, c,
                        cnt.as<uint32_t>(), off.as<uint32_t>(), toff.as<uint32_t>(), ntasks.as<uint32_t>(),
-                       pairs.as<uint32_t>(), p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u, sel_set);
+                       pairs.as<uint32_t>(), p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u, sel_set, recode());
         return ZK_OK;
     }
     // two-level counting sort, every per-digit atomic in LDS (msm.h)
@@ -199,11 +234,11 @@ zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st, const z
     {
         ProfScope ps("msm_sort_coarse", st);
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_count, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse, coarse_cnt,
-                       blockbase.as<uint32_t>(), per_wg, sel_set);
+                       blockbase.as<uint32_t>(), per_wg, sel_set, recode());
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
                        (const uint32_t*)coarse_cnt, coarse_off, (uint32_t*)nullptr, n_coarse);
         ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scatter, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse,
-                       (const uint32_t*)coarse_off, (const uint32_t*)blockbase.as<uint32_t>(), rank.as<uint2>(), per_wg, sel_set);
+                       (const uint32_t*)coarse_off, (const uint32_t*)blockbase.as<uint32_t>(), rank.as<uint2>(), per_wg, sel_set, recode());
     }
     {
         ProfScope ps("msm_sort_fine", st);
@@ -374,6 +409,32 @@ void MsmGroup<HF, DF>::dump_redo(const MsmPlan& p, hipStream_t st, bool after_le
         fprintf(stderr, "[redo]   task %u: n = %u, equal pair words %u, opposite pair words %u, first %u %u %u\n", ti, dsc.z, dup, opp,
                 pw.size() > 0 ? pw[0] : 0, pw.size() > 1 ? pw[1] : 0, pw.size() > 2 ? pw[2] : 0);
     }
+}
+
+// diagnostics: the first job of the first launch set of every width - its scalars, its map and the pairs the sort counted for
+// it - into <dir>/pairs_<g1|g2>_c<width>.bin = [c, n_mult, ext, n, pairs, has map | n x 8 words | n map entries], so that the
+// count can be held against a recoding of the same scalars made elsewhere (profiles/r28_table_multiples.txt)
+template <class HF, class DF>
+void MsmGroup<HF, DF>::dump_pairs(const MsmJob& job0, hipStream_t st, const char* dir) {
+    static uint32_t seen = 0;
+    if (job0.vb_digit || c >= 32 || (seen >> c & 1u)) return;
+    seen |= 1u << c;
+    (void)hipStreamSynchronize(st);
+    std::vector<uint32_t> h(nb), sc((size_t)job0.n * 8);
+    std::vector<int32_t> mp(job0.map ? job0.n : 0);
+    (void)hipMemcpy(h.data(), cnt.p, (size_t)nb * 4, hipMemcpyDeviceToHost);
+    (void)hipMemcpy(sc.data(), job0.scalars, sc.size() * 4, hipMemcpyDeviceToHost);
+    if (job0.map) (void)hipMemcpy(mp.data(), job0.map, mp.size() * 4, hipMemcpyDeviceToHost);
+    uint32_t pairs_job0 = 0;
+    for (uint32_t x : h) pairs_job0 += x;
+    const std::string path = std::string(dir) + "/pairs_" + (IS_G2 ? "g2" : "g1") + "_c" + std::to_string(c) + ".bin";
+    FILE* f = fopen(path.c_str(), "wb");
+    if (!f) return;
+    const uint32_t head[6] = {c, n_mult, ext, job0.n, pairs_job0, job0.map ? 1u : 0u};
+    fwrite(head, 4, 6, f);
+    fwrite(sc.data(), 4, sc.size(), f);
+    fwrite(mp.data(), 4, mp.size(), f);
+    fclose(f);
 }
 
 // diagnostics: the heavy list of the set and the partials of its buckets

@@ -411,8 +411,53 @@ zk_status derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>&
     return ZK_OK;
 }
 
-zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
-    if (P->bind.drv.ready && P->bind.drv.circuit == R->sys.id) return ZK_OK;
+// ZKAMD_TABLE_MULTIPLES = 1 | 2 | 4 | 8: the odd multiples of every slice the bound tables carry (msm.h MsmRecode).  Table memory
+// and bind time grow with it, the (digit, point) pairs of every full-width scalar shrink.  The key's own tables keep one.
+// A key carries them from its first launch set of ZKAMD_TABLE_MULTIPLES_MIN jobs on (default 129: the batch form of a set) or
+// from the pipeline made over it: a proof made alone binds the key as fast as it did and holds no larger tables.
+#ifndef ZK_TABLE_MULTIPLES_DEFAULT
+#define ZK_TABLE_MULTIPLES_DEFAULT 8
+#endif
+uint32_t table_multiples() {
+    const char* env = getenv("ZKAMD_TABLE_MULTIPLES");
+    const int v = env ? atoi(env) : 0;
+    return v == 1 || v == 2 || v == 4 || v == 8 ? (uint32_t)v : ZK_TABLE_MULTIPLES_DEFAULT;
+}
+size_t table_multiples_min() {
+    const char* env = getenv("ZKAMD_TABLE_MULTIPLES_MIN");
+    return env && atol(env) > 0 ? (size_t)atol(env) : 129;
+}
+
+// The multiples of the two bound tables, once per binding, when its first batch arrives.  A table that does not fit stays as it
+// is (each table recodes by what it holds); the host trace says what was taken.
+zk_status add_table_multiples(zk_params* P) {
+    zk_params::Binding& B = P->bind;
+    const uint32_t asked = table_multiples();
+    if (B.drv.multiples_tried || !B.g1d.table.owned) return ZK_OK;
+    B.drv.multiples_tried = true;
+    if (asked <= 1) return ZK_OK;
+    ZK_TRY(use_device(P->key.device));
+    const auto t0 = std::chrono::steady_clock::now();
+    zk_status st = hook_env("ZKAMD_INJECT_TABLE_OOM") ? fail(ZK_ERR_OUT_OF_MEMORY, "injected: the table with its multiples does not fit")
+                                                     : B.g1d.add_multiples(asked);
+    if (st == ZK_OK && B.prs.ready) st = B.g2p.add_multiples(asked);
+    if (st != ZK_OK && st != ZK_ERR_OUT_OF_MEMORY) return st;
+    B.g1d_lone.alias(B.g1d, B.g1d_lone.c);
+    if (B.prs.ready) {
+        B.g1da.alias(B.g1d, B.g1da.c);
+        B.g2p_lone.alias(B.g2p, B.g2p_lone.c);
+    }
+    if (getenv("ZKAMD_TRACE_HOST"))
+        fprintf(stderr, "[zkamd] table multiples: %u asked%s, G1 table %u per slice %.2f GB, G2 table %u per slice %.2f GB, %.1f ms\n", asked,
+                st == ZK_OK ? "" : " (out of memory)", B.g1d.n_mult, (double)B.g1d.bytes / 1e9, B.g2p.n_mult, (double)B.g2p.bytes / 1e9,
+                std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    return ZK_OK;
+}
+
+// batch: the caller has a launch set of table_multiples_min() jobs or more, or is making a pipeline
+zk_status ensure_derived(zk_params* P, zk_r1cs* R, bool batch) {
+    if (P->bind.drv.ready && P->bind.drv.circuit == R->sys.id) return batch ? add_table_multiples(P) : ZK_OK;
+    P->bind.drv.multiples_tried = false;
     const uint32_t n_in = R->sys.n_in, n_aux = R->sys.n_aux, nv = n_in + n_aux, n_con = R->sys.n_con, n_rows = n_con + n_in, k = P->key.log_m;
     const size_t m = P->key.m;
     if (!P->tab.g1.table.owned || R->sys.h_row_ptr[2].size() != (size_t)n_con + 1 || n_in != P->key.n_ic || n_aux != P->key.n_l ||
@@ -543,12 +588,8 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
 #endif
     const zk_params::Key& K = P->key;
     const bool values = merge_values_on();   // (the widths of a run with the switch off stay those of a set without pairs)
-    const uint32_t c_set = pick_window(live + K.n_b1 - (values ? std::min<size_t>(X.q[QL].expect + X.q[QB1].expect, live) : 0), 1);
-    ZK_TRY(P->bind.g1d.build_with_tail(pts, P->tab.g1, K.off_a, P->tab.g1.n_points - K.off_a, c_set));
-    P->bind.g1d_lone.alias(P->bind.g1d, P->tab.g1_lone.c);
+    std::vector<HG2A> pts2;
     if (X.ready) {
-        P->bind.g1da.alias(P->bind.g1d, values ? pick_window(K.n_a - std::min(X.q[QA].expect, K.n_a), 3) : P->tab.g1a.c);
-        std::vector<HG2A> pts2;
         pts2.swap(pb.b2);
         pts2.resize(K.n_b2 + 2, HG2A::inf());
         if (K.vk_bytes.size() < 864 || zkhost::g2_from_uncompressed(K.vk_bytes.data() + 192, &pts2[K.n_b2]) != zkhost::DEC_OK ||
@@ -558,6 +599,14 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
 #ifdef ZK_TEST_HOOKS
         X.hook_g2.assign(pts2.begin() + X.q[BOUND_G2_ORDER[0]].xbase, pts2.end());
 #endif
+    }
+    // The two bound tables, as they were: the odd multiples of their slices (msm.h MsmRecode) come with the first batch
+    // (add_table_multiples), and the widths stay those of one multiple (msm_group.h pick_window).
+    const uint32_t c_set = pick_window(live + K.n_b1 - (values ? std::min<size_t>(X.q[QL].expect + X.q[QB1].expect, live) : 0), 1);
+    ZK_TRY(P->bind.g1d.build_with_tail(pts, P->tab.g1, K.off_a, P->tab.g1.n_points - K.off_a, c_set));
+    P->bind.g1d_lone.alias(P->bind.g1d, P->tab.g1_lone.c);
+    if (X.ready) {
+        P->bind.g1da.alias(P->bind.g1d, values ? pick_window(K.n_a - std::min(X.q[QA].expect, K.n_a), 3) : P->tab.g1a.c);
         const uint32_t c2 = values ? pick_window(K.n_b2 - std::min(X.q[QB2].expect, K.n_b2), 2) : P->tab.g2.c;
         ZK_TRY(P->bind.g2p.build(pts2, c2, false, "pair bases (G2)"));
         P->bind.g2p_lone.alias(P->bind.g2p, getenv("ZKAMD_WINDOW_BITS_G2") || c2 <= 10 ? c2 : 10u);
@@ -581,7 +630,7 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R) {
         for (uint32_t l = 3; l <= zkpairs::RUN_MAX; l++)
             fprintf(stderr, "[zkamd] value runs: bases of %u members: a %u, b_g2 %u, l %u, b_g1 %u\n", l, X.q[QA].xn[l - 3], X.q[QB2].xn[l - 3],
                     X.q[QL].xn[l - 3], X.q[QB1].xn[l - 3]);
-    return ZK_OK;
+    return batch ? add_table_multiples(P) : ZK_OK;
 }
 
 }  // namespace

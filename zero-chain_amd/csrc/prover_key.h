@@ -310,6 +310,7 @@ struct zk_params {
             uint32_t off_a = 0, off_b1 = 0;
             std::vector<int32_t> pos;   // [Lambda | E | D]: position in slice 0, or -1 for a base that came out as the identity
             double bind_ms = 0;
+            bool multiples_tried = false;   // the tables were asked for their multiples once (prover_binding.h add_table_multiples)
         } drv;
         MsmG1 g1d, g1d_lone;
         // Value pairs of the (key, circuit) pair the derived set was built for (value_pairs.h; prover_binding.h derived_pairs): one

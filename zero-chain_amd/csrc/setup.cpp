@@ -44,7 +44,7 @@ zk_status build_generator_table(const zkhost::Affine<HF>& g, DevBuf& table) {
     ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3(1), dim3(128), 0, g_stream, (const uint32_t*)stage.as<uint32_t>(),
               table.as<zkdev::Affine<DF>>(), 1u);
     ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3(1), dim3(128), 0, g_stream, table.as<zkdev::Affine<DF>>(), 1u, zkdev::MSM_NPOS,
-              scratch.as<DF>());
+              scratch.as<DF>(), 1u, 0u);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));
     return ZK_OK;

@@ -217,7 +217,7 @@ zk_status build_ic_table(zk_vk* V) {
               V->ic_table.as<DG1A>(), (uint32_t)n);
     ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(zkdev::Fq) * n));
     ZK_LAUNCH(zkdev::k_msm_build_table<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, V->ic_table.as<DG1A>(), (uint32_t)n,
-              zkdev::MSM_NPOS, scratch.as<zkdev::Fq>());
+              zkdev::MSM_NPOS, scratch.as<zkdev::Fq>(), 1u, 0u);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(g_stream));
     return ZK_OK;

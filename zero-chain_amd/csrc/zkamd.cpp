@@ -520,7 +520,7 @@ zk_status r1cs_load(uint32_t n_in, uint32_t n_aux, uint32_t n_con, const zk_csr*
 zk_status prove_from_z(zk_params* P, zk_r1cs* R, size_t np, int slot, const uint8_t* rs, uint8_t* proofs_out, bool derived) {
     const uint32_t nv = R->sys.n_in + R->sys.n_aux, n_rows = R->sys.n_con + R->sys.n_in;
     if (derived) {
-        ZK_TRY(ensure_derived(P, R));
+        ZK_TRY(ensure_derived(P, R, np >= table_multiples_min()));
         derived = P->bind.drv.ready && P->bind.drv.circuit == R->sys.id;
     }
     ZK_TRY(R->work.abc.ensure(3 * np * (size_t)n_rows * 32));
@@ -1514,7 +1514,7 @@ zk_status zk_pipeline_create(zk_params* p, zk_r1cs* circuit, zk_pipeline** out) 
     ZK_TRY(route_check(p, circuit, zkpairs::TRANSFER));
     (void)zkwit::tables();
     // the derived bases of the pair before the lanes borrow the key's tables: every lane binds to the same set
-    ZK_TRY(ensure_derived(p, circuit));
+    ZK_TRY(ensure_derived(p, circuit, true));
     zk_pipeline* L = new (std::nothrow) zk_pipeline();
     if (!L) return fail(ZK_ERR_OUT_OF_MEMORY, "host allocation failed");
     L->Pl[0] = p;
@@ -1857,3 +1857,5 @@ zk_status zk_synchronize(void) try {
 } ZK_ABI_CATCH
 
 }  // extern "C"
+
+#include "msm_hooks.h"   // (test hooks of the table multiples: -DZK_TEST_HOOKS only)
