@@ -1250,6 +1250,46 @@ def verifier_rlc(lib, n=20, seed=8, capfd=None):
         params.close()
 
 
+def verifier_rlc_sizes(lib, capfd, sizes=(8, 10, 11, 143, 257), seed=8):
+    """The combined check at the chunk sizes where one of its buffers or its product tree takes another shape - n + 2 Miller
+    functions multiplied in groups of twelve: 10 (one group, straight into the final exponentiation's operand), 12 (a full
+    group), 13 (two levels), 145 (three levels, both halves of the tree's workspace), 259 (two blocks of partial sums of the
+    C's with one point in the second, two leaves of the seed's hash) - on sixteen distinct proofs tiled to n: all accepted by
+    the combined check itself (the debug line of the hooks build), and with the last C taken from another statement the
+    verdicts of both forms name that proof alone."""
+    E = g.Bls12Engine()
+    n_in, n_aux = 3, 12
+    circ = synth.ChainCircuit(seed, n_in, n_aux)
+    P = g.generate_parameters(E, circ.r1cs, *helpers.TOXIC, scalars_only=True)
+    pk = params_io.write_parameters_from_scalars(P.sc, n_in, threads=4)
+    params = zk.Parameters.read(pk, checked=False, lib=lib)
+    pvk = zk.prepare_verifying_key(params)
+    try:
+        rng = synth.SplitMix64(seed + 31)
+        proofs16, inputs16 = [], []
+        for i in range(16):
+            inp, aux = circ.witness(seed * 1000 + i)
+            asg = g.assign(E, circ.r1cs, inp, aux)
+            proofs16.append(helpers.expected_proof_trapdoor(P, asg, rng.field(bls.R_MOD), rng.field(bls.R_MOD)))
+            inputs16.append(list(asg.inputs[1:]))
+        assert len(set(proofs16)) == 16 and len({tuple(x) for x in inputs16}) > 1
+        for n in sizes:
+            proofs, inputs = [proofs16[i % 16] for i in range(n)], [inputs16[i % 16] for i in range(n)]
+            capfd.readouterr()
+            good = zk.verify_proofs(pvk, proofs, inputs, rlc=True)
+            assert "chunk of %d proofs: combined check passed, every proof well-formed: yes" % n in capfd.readouterr().err, n
+            assert good == zk.verify_proofs(pvk, proofs, inputs) == [True] * n, n
+            bad = list(proofs)
+            bad[n - 1] = proofs[n - 1][:144] + proofs[n - 2][144:]
+            assert proofs[n - 1][144:] != proofs[n - 2][144:]
+            want = [i != n - 1 for i in range(n)]
+            assert zk.verify_proofs(pvk, bad, inputs, rlc=True) == want, n
+            assert zk.verify_proofs(pvk, bad, inputs) == want, n
+    finally:
+        pvk.close()
+        params.close()
+
+
 def scalars_to_bytes_list(values):
     return zk.scalars_to_bytes(values)
 

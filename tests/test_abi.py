@@ -260,6 +260,6 @@ def test_shipped_library_carries_no_test_hook():
         assert name in hooks, name
     assert b"zk_hook_field_op" not in shipped
     assert b"zk_hook_field_op" in hooks
-    for name in (b"zk_hook_ntt_plan", b"zk_hook_ntt_chain", b"zk_hook_ntt_table"):
+    for name in (b"zk_hook_ntt_plan", b"zk_hook_ntt_chain", b"zk_hook_ntt_table", b"zk_hook_rlc_coefs"):
         assert name not in shipped, name
         assert name in hooks, name

@@ -834,6 +834,11 @@ def test_verifier_rlc(gpu_hooks_lib, monkeypatch, capfd):
     pc.verifier_rlc(gpu_hooks_lib, n=40, capfd=capfd)
 
 
+def test_verifier_rlc_sizes(gpu_hooks_lib, monkeypatch, capfd):
+    monkeypatch.setenv("ZKAMD_DEBUG_RLC", "1")
+    pc.verifier_rlc_sizes(gpu_hooks_lib, capfd)
+
+
 def test_verifier_rlc_full_chunk(gpu_lib):
     """The combined check at the bench's size: 1024 transfer proofs from statements, all accepted in one check; with three
     of them damaged the verdicts are the per-proof verifier's (the chunk falls back)."""

@@ -25,6 +25,7 @@
 #include "anon_block_exec.h"
 #include "asset_block_exec.h"
 #include "verify_plan.h"
+#include "verify_rlc.h"
 
 using namespace zkrt;
 using zkdev::F12;
@@ -118,6 +119,64 @@ zk_status read_g2(Reader& r, HG2A* out, const char* what) {
 constexpr size_t COEF_WORDS = (size_t)zkdev::PAIRING_NCOEF * 72;
 constexpr size_t VERIFY_CHUNK = 8192;   // proofs per launch set
 
+// The lane's three streams around a chunk: main forks into (side, copy), each says when it is done, main waits for both
+struct ForkJoin {
+    hipEvent_t done[2] = {nullptr, nullptr};   // side, copy: created on first use
+    ~ForkJoin() {
+        for (int k = 0; k < 2; k++)
+            if (done[k]) (void)hipEventDestroy(done[k]);
+    }
+    zk_status fork() {
+        for (int k = 0; k < 2; k++)
+            if (!done[k]) HIP_TRY(hipEventCreate(&done[k]));
+        HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
+        HIP_TRY(hipStreamWaitEvent(g_stream2, g_ev_fork, 0));
+        HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_ev_fork, 0));
+        return ZK_OK;
+    }
+    zk_status side_done() {
+        HIP_TRY(hipEventRecord(done[0], g_stream2));
+        return ZK_OK;
+    }
+    zk_status copy_done() {
+        HIP_TRY(hipEventRecord(done[1], g_copy_stream));
+        return ZK_OK;
+    }
+    zk_status join() {
+        HIP_TRY(hipStreamWaitEvent(g_stream, done[0], 0));
+        HIP_TRY(hipStreamWaitEvent(g_stream, done[1], 0));
+        return ZK_OK;
+    }
+};
+
+// The workspaces of the random-linear-combination check alone (verify_chunk_rlc; skip, f, ok and prep_b it shares with the
+// per-proof path)
+struct RlcWork {
+    typedef zkdev::XYZZ<zkdev::Fq32> P32;
+    DevBuf rho, s, exp;     // the coefficients of the chunk (verify_rlc.h Coefs)
+    DevBuf pts;             // rho_i A_i | acc | C sum: the G1 side of the n + 2 pairs
+    DevBuf c, csum;         // rho_i C_i, and their sum in front of its partial sums of 256
+    DevBuf acc, inf, all;   // sum_j s_j ic_j; is acc / the C sum the point at infinity; is every proof well-formed
+    DevBuf want, prod;      // e(alpha, beta)^S; the two halves of the product tree's workspace
+    DevBuf fe, ab_lambda;   // once per key (ensure_rlc_fe, ensure_rlc_ab_lambda)
+    zk_status reserve(size_t n, uint32_t n_ic) {
+        const size_t m = n + 2;
+        ZK_TRY(rho.ensure(n * 16));
+        ZK_TRY(s.ensure((size_t)n_ic * 32));
+        ZK_TRY(exp.ensure(32));
+        ZK_TRY(pts.ensure(m * 96));
+        ZK_TRY(c.ensure(n * sizeof(P32)));
+        ZK_TRY(csum.ensure(((n + 255) / 256 + 1) * sizeof(P32)));
+        ZK_TRY(acc.ensure(sizeof(DG1)));
+        ZK_TRY(inf.ensure(8));
+        ZK_TRY(all.ensure(4));
+        ZK_TRY(want.ensure(sizeof(F12)));
+        ZK_TRY(prod.ensure(2 * prod_half(m) * sizeof(F12)));
+        return ZK_OK;
+    }
+    static size_t prod_half(size_t m) { return m / 12 + 2; }   // (the first level of m functions leaves (m + 11) / 12 products)
+};
+
 }  // namespace
 
 struct zk_vk {
@@ -131,25 +190,18 @@ struct zk_vk {
     // per-batch workspaces
     DevBuf in_g1, in_g2, fl_g1, fl_g2, aff_g1, aff_g2, st_g1, st_g2, scal, part, acc, acc_inf, host_bad, skip, valid, f, ok;
     DevBuf coop_stage;   // the cooperative line preparation's un-reduced coefficients (coop_verify.cpp)
-    DevBuf ic_win;       // the 8-bit window table of the ic bases (pairing.h k_inputs_window_table), built on first use
-    DevBuf lines28[2];   // prep[] in the multiexps' representation, for the Miller loop on rows (coop_pairing.cpp); built on first use
+    DevBuf ic_win;       // the 8-bit window table of the ic bases (pairing.h k_inputs_window_table): ensure_ic_win
+    DevBuf lines28[2];   // prep[] in the multiexps' representation, for the Miller loop on rows (coop_pairing.cpp): ensure_lines28
     DevBuf prep_b;   // line coefficients of the batch's own B points (the lane-parallel Miller loop reads every pair prepared)
-    // the random-linear-combination check (verify_chunk_rlc): rho_i, the n_ic input scalars, rho_i A_i | acc | C sum, rho_i C_i and
-    // its partial sums, the accumulator, flags, the exponent and e(alpha, beta)^S, the product tree, two Fq12 ones
-    DevBuf rlc_rho, rlc_s, rlc_pts, rlc_c, rlc_csum, rlc_acc, rlc_inf, rlc_all, rlc_exp, rlc_want, rlc_prod, rlc_fe;
-    DevBuf rlc_ab_lambda;   // e(alpha, beta)^lambda, lambda = -x^2 (the coefficients are a_i + b_i lambda: pairing.h k_rlc_scale)
+    RlcWork rlc;
     zkxt::IntoXyBufs xt;    // IntoXY of the extrinsics' points (xt_inputs.h)
     DevBuf block;           // the block executor's ledger layout, scan results and public inputs (block_exec.h; public chain state)
     PinBuf block_rows;      // ... and the rows of public inputs of a round on their way into verify_batch
     // the G1 decoder and the input accumulator run beside the G2 decoder on the lane's side streams
-    hipEvent_t ev_join[2] = {nullptr, nullptr};
+    ForkJoin streams;
     // Blake2s over e(alpha, beta), the prepared -gamma / -delta coefficients and ic: the domain separation of the combined
     // check's coefficients (the same batch bytes under another key draw other rho_i)
     uint8_t key_digest[32] = {0};
-    ~zk_vk() {
-        for (int k = 0; k < 2; k++)
-            if (ev_join[k]) (void)hipEventDestroy(ev_join[k]);
-    }
 };
 
 namespace {
@@ -189,9 +241,9 @@ zk_status check_points(const std::vector<zkhost::Affine<HF>>& pts, const char* w
     ZK_TRY(d.ensure(n * sizeof(zkdev::Affine<DF>)));
     ZK_TRY(flags.ensure(4 * n));
     const unsigned blocks = (unsigned)((n + 127) / 128);
-    ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3(blocks), dim3(128), 0, g_stream, (const uint32_t*)stage.as<uint32_t>(),
+    ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3(blocks), dim3(128), 0, g_stream, stage.as<const uint32_t>(),
               d.as<zkdev::Affine<DF>>(), (uint32_t)n);
-    ZK_LAUNCH(zkdev::k_check_points<DF>, dim3(blocks), dim3(128), 0, g_stream, (const zkdev::Affine<DF>*)d.as<zkdev::Affine<DF>>(),
+    ZK_LAUNCH(zkdev::k_check_points<DF>, dim3(blocks), dim3(128), 0, g_stream, d.as<const zkdev::Affine<DF>>(),
               (uint32_t)n, 1u, flags.as<uint32_t>());
     HIP_TRY(hipGetLastError());
     std::vector<uint32_t> f(n);
@@ -213,7 +265,7 @@ zk_status build_ic_table(zk_vk* V) {
     DevBuf stage, scratch;
     ZK_TRY(upload(stage, V->ic.data(), n * sizeof(HG1A)));
     const unsigned blocks = (unsigned)((n + 127) / 128);
-    ZK_LAUNCH(zkdev::k_import_affine<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, (const uint32_t*)stage.as<uint32_t>(),
+    ZK_LAUNCH(zkdev::k_import_affine<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, stage.as<const uint32_t>(),
               V->ic_table.as<DG1A>(), (uint32_t)n);
     ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(zkdev::Fq) * n));
     ZK_LAUNCH(zkdev::k_msm_build_table<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, V->ic_table.as<DG1A>(), (uint32_t)n,
@@ -269,7 +321,7 @@ zk_status vk_prepare(const uint8_t* bytes, size_t len, int device, zk_vk** out) 
         DevBuf q, co;
         ZK_TRY(upload(q, neg, sizeof(neg)));
         ZK_TRY(co.ensure(2 * COEF_WORDS * 4));
-        ZK_LAUNCH(zkdev::k_g2_prepare, dim3(1), dim3(64), 0, g_stream, (const uint32_t*)q.as<uint32_t>(), co.as<uint32_t>(), 2u);
+        ZK_LAUNCH(zkdev::k_g2_prepare, dim3(1), dim3(64), 0, g_stream, q.as<const uint32_t>(), co.as<uint32_t>(), 2u);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));
         for (int k = 0; k < 2; k++) {
@@ -288,10 +340,10 @@ zk_status vk_prepare(const uint8_t* bytes, size_t len, int device, zk_vk** out) 
         ZK_TRY(upload(sk, &skip, 4));
         ZK_TRY(f.ensure(3 * sizeof(F12)));
         ZK_TRY(val.ensure(sizeof(F12)));
-        ZK_LAUNCH(zkdev::k_miller_loop, dim3(1, 3), dim3(64), 0, g_stream, (const uint32_t*)p0.as<uint32_t>(),
-                  (const uint32_t*)q0.as<uint32_t>(), (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
-                  (const uint32_t*)nullptr, (const uint32_t*)sk.as<uint32_t>(), f.as<F12>(), 1u);
-        ZK_LAUNCH(zkdev::k_final_exp, dim3(1), dim3(64), 0, g_stream, (const F12*)f.as<F12>(), (const uint32_t*)V->gam.as<uint32_t>(),
+        ZK_LAUNCH(zkdev::k_miller_loop, dim3(1, 3), dim3(64), 0, g_stream, p0.as<const uint32_t>(),
+                  q0.as<const uint32_t>(), (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr,
+                  (const uint32_t*)nullptr, sk.as<const uint32_t>(), f.as<F12>(), 1u);
+        ZK_LAUNCH(zkdev::k_final_exp, dim3(1), dim3(64), 0, g_stream, f.as<const F12>(), V->gam.as<const uint32_t>(),
                   (const F12*)nullptr, (const uint32_t*)nullptr, (uint32_t*)nullptr, val.as<F12>(), 1u);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(g_stream));
@@ -309,10 +361,10 @@ zk_status vk_prepare(const uint8_t* bytes, size_t len, int device, zk_vk** out) 
 void vk_digest(zk_vk* V) {
     static const uint8_t pers[8] = {'z', 'k', 'a', 'm', 'd', 'v', 'k', 'd'};
     zkhash::Blake2s h(pers);
-    h.update((const uint8_t*)V->h_alpha_beta.data(), V->h_alpha_beta.size() * 4);
+    h.update(V->h_alpha_beta.data(), V->h_alpha_beta.size() * 4);
     for (int k = 0; k < 2; k++) {
         h.update_u64be(V->h_prep[k].size());
-        h.update((const uint8_t*)V->h_prep[k].data(), V->h_prep[k].size() * 4);
+        h.update(V->h_prep[k].data(), V->h_prep[k].size() * 4);
     }
     h.update_u64be(V->ic.size());
     for (const HG1A& p : V->ic) {
@@ -493,6 +545,53 @@ zk_status stage_own_affine(zk_vk* V, size_t n, const uint8_t* own_affine) {
     HIP_TRY(hipStreamSynchronize(g_stream));   // (a1 / a2 are about to go out of scope: pageable sources of asynchronous copies)
     return ZK_OK;
 }
+// The four device tables of a key that are built on first use, once per key, each on the stream of the stage that reads it:
+// the window table of the ic bases (public) ...
+zk_status ensure_ic_win(zk_vk* V, hipStream_t st) {
+    if (V->ic_win.cap) return ZK_OK;
+    V->ic_win.is_public = true;
+    ZK_TRY(V->ic_win.ensure((size_t)V->n_ic * 32 * 256 * sizeof(DG1A)));
+    ZK_LAUNCH(zkdev::k_inputs_window_table, dim3((unsigned)(V->n_ic * 32 * 256 / 64)), dim3(64), 0, st, V->ic_table.as<const DG1A>(), V->ic_win.as<DG1A>(),
+              V->n_ic);
+    return ZK_OK;
+}
+// ... the key's prepared lines in the rows' representation (public) ...
+zk_status ensure_lines28(zk_vk* V, hipStream_t st) {
+    for (int k = 0; k < 2; k++) {
+        if ((k == 0 ? V->gamma_inf : V->delta_inf) || V->lines28[k].cap) continue;
+        V->lines28[k].is_public = true;
+        ZK_TRY(V->lines28[k].ensure(zkcoop::LINE_TABLE_BYTES));
+        zkcoop::verify_import_coefs(V->prep[k].as<const uint32_t>(), V->lines28[k].p, (uint32_t)zkcoop::VERIFY_NCOEF * 6, st);
+    }
+    return ZK_OK;
+}
+// ... [product | 1 | 1], what k_final_exp_wide multiplies for the one item of the combined check ...
+zk_status ensure_rlc_fe(zk_vk* V, hipStream_t st) {
+    if (V->rlc.fe.cap) return ZK_OK;
+    static const std::vector<uint32_t> ones = [] {   // (static: the pageable source of an asynchronous copy)
+        std::vector<uint32_t> o(3 * 144, 0);
+        static const uint32_t R32[12] = ZK_FQ_R_32;
+        for (int k = 1; k < 3; k++) memcpy(&o[(size_t)k * 144], R32, 48);
+        return o;
+    }();
+    ZK_TRY(V->rlc.fe.ensure(ones.size() * 4));
+    HIP_TRY(hipMemcpyAsync(V->rlc.fe.p, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, st));
+    return ZK_OK;
+}
+// ... and e(alpha, beta)^lambda (the coefficients are a_i + b_i lambda: verify_rlc.h, pairing.h k_rlc_scale); the call that
+// builds it waits for it
+zk_status ensure_rlc_ab_lambda(zk_vk* V, hipStream_t st) {
+    if (V->rlc.ab_lambda.cap) return ZK_OK;
+    const zkhost::Fr lambda = zkrlc::lambda();
+    DevBuf dl;
+    ZK_TRY(dl.ensure(32));
+    HIP_TRY(hipMemcpy(dl.p, lambda.l, 32, hipMemcpyHostToDevice));
+    ZK_TRY(V->rlc.ab_lambda.ensure(sizeof(F12)));
+    ZK_LAUNCH_SYNC(zkdev::k_f12_pow_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, st, V->alpha_beta.as<const F12>(), dl.as<const uint32_t>(), 255u,
+                   V->rlc.ab_lambda.as<F12>());
+    HIP_TRY(hipStreamSynchronize(st));
+    return ZK_OK;
+}
 // acc[p] = ic_0 + sum_j x_pj ic_j for the n proofs of the chunk, on `st`
 zk_status enqueue_inputs(zk_vk* V, size_t n, const VerifyPlan& pl, hipStream_t st) {
     const uint32_t ni = V->n_ic - 1;
@@ -508,11 +607,7 @@ zk_status enqueue_inputs(zk_vk* V, size_t n, const VerifyPlan& pl, hipStream_t s
     // on lanes: the products of the pieces of every scalar with its base ...
     const bool sixteen = pl.inputs == VInputs::SIXTEEN;
     if (pl.inputs == VInputs::WINDOWS) {   // (four chains of eight additions per scalar)
-        if (!V->ic_win.cap) {
-            V->ic_win.is_public = true;
-            ZK_TRY(V->ic_win.ensure((size_t)V->n_ic * 32 * 256 * sizeof(DG1A)));
-            ZK_LAUNCH(zkdev::k_inputs_window_table, dim3((unsigned)(V->n_ic * 32 * 256 / 64)), dim3(64), 0, st, table, V->ic_win.as<DG1A>(), V->n_ic);
-        }
+        ZK_TRY(ensure_ic_win(V, st));
         ZK_LAUNCH(zkdev::k_inputs_mul_win<4>, dim3((unsigned)((4 * n * ni + 63) / 64)), dim3(64), 0, st, V->ic_win.as<const DG1A>(), scal, part,
                   V->n_ic, (uint32_t)n);
     } else if (pl.inputs_mul && sixteen) {
@@ -536,13 +631,7 @@ zk_status enqueue_pairing(zk_vk* V, size_t n, const VerifyPlan& pl) {
     const F12* alpha_beta = V->alpha_beta.as<const F12>();
     uint32_t* ok = V->ok.as<uint32_t>();
     const unsigned b64 = (unsigned)((n + 63) / 64), bw = (unsigned)((n + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS);
-    if (pl.pairing == VPairing::ROWS)   // the key's prepared lines in the rows' representation, once per key
-        for (int k = 0; k < 2; k++) {
-            if ((k == 0 ? V->gamma_inf : V->delta_inf) || V->lines28[k].cap) continue;
-            V->lines28[k].is_public = true;
-            ZK_TRY(V->lines28[k].ensure(zkcoop::LINE_TABLE_BYTES));
-            zkcoop::verify_import_coefs(V->prep[k].as<const uint32_t>(), V->lines28[k].p, (uint32_t)zkcoop::VERIFY_NCOEF * 6, g_stream);
-        }
+    if (pl.pairing == VPairing::ROWS) ZK_TRY(ensure_lines28(V, g_stream));
     {
         ProfScope ps("verify_miller");
         if (pl.pairing == VPairing::ROWS)
@@ -604,17 +693,12 @@ zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t*
     ZK_TRY(V->ok.ensure(n * 4));
     // three independent bundles of serial chains - the G2 decoder, the G1 decoder, the input accumulator - side by side
     // on the lane's three streams (each is a few dozen waves; one after the other they were 60 % of a verification)
-    for (int k = 0; k < 2; k++)
-        if (!V->ev_join[k]) HIP_TRY(hipEventCreate(&V->ev_join[k]));
-    HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
-    HIP_TRY(hipStreamWaitEvent(g_stream2, g_ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_ev_fork, 0));
+    ZK_TRY(V->streams.fork());
     ZK_TRY(enqueue_head(V, n, pl, g_stream, g_stream2));
-    HIP_TRY(hipEventRecord(V->ev_join[0], g_stream2));
+    ZK_TRY(V->streams.side_done());
     ZK_TRY(enqueue_inputs(V, n, pl, g_copy_stream));
-    HIP_TRY(hipEventRecord(V->ev_join[1], g_copy_stream));
-    HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[0], 0));
-    HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[1], 0));
+    ZK_TRY(V->streams.copy_done());
+    ZK_TRY(V->streams.join());
     ZK_LAUNCH(zkdev::k_verify_flags, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, g_stream, V->st_g1.as<const uint32_t>(),
               V->st_g2.as<const uint32_t>(), V->acc_inf.as<const uint32_t>(), V->host_bad.as<const uint32_t>(), V->skip.as<uint32_t>(),
               V->valid.as<uint32_t>(), (uint32_t)n);
@@ -624,6 +708,70 @@ zk_status verify_chunk(zk_vk* V, size_t n, const uint8_t* proofs, const uint8_t*
     HIP_TRY(hipStreamSynchronize(g_stream));
     HIP_TRY(hipMemcpy(okv.data(), V->ok.p, n * 4, hipMemcpyDeviceToHost));
     for (size_t i = 0; i < n; i++) ok_out[i] = okv[i] ? 1 : 0;
+    return ZK_OK;
+}
+
+// The stages of the combined check (verify_chunk_rlc), each on the stream it is given.  Behind the decoder of A | C: both
+// scaled by rho_i, the C's summed
+zk_status rlc_enqueue_scale(zk_vk* V, size_t n, hipStream_t st) {
+    typedef RlcWork::P32 P32;
+    const uint32_t *aff_g1 = V->aff_g1.as<const uint32_t>(), *rho = V->rlc.rho.as<const uint32_t>();
+    uint32_t* pts = V->rlc.pts.as<uint32_t>();
+    P32 *c = V->rlc.c.as<P32>(), *csum = V->rlc.csum.as<P32>();
+    const uint32_t nb1 = (uint32_t)((n + 255) / 256);
+    ProfScope ps("verify_rlc_scale", st);
+    ZK_LAUNCH(zkdev::k_rlc_scale, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, st, aff_g1, rho, pts, c, (uint32_t)n);
+    ZK_LAUNCH_SYNC(zkdev::k_g1_sum, dim3(nb1), dim3(64), 0, st, V->rlc.c.as<const P32>(), (uint32_t)n, csum + 1);
+    ZK_LAUNCH_SYNC(zkdev::k_g1_sum, dim3(1), dim3(64), 0, st, V->rlc.csum.as<const P32>() + 1, nb1, csum);
+    return ZK_OK;
+}
+// What the product is compared with, e(alpha, beta)^S = e(alpha, beta)^(sum a_i) (e(alpha, beta)^lambda)^(sum b_i) over
+// `nbits` bits, and the accumulator sum_j s_j ic_j
+zk_status rlc_enqueue_want(zk_vk* V, uint32_t nbits, hipStream_t st) {
+    ZK_TRY(ensure_rlc_ab_lambda(V, st));   // (ahead of the scope: its one-off is not a stage time)
+    const DG1A* table = V->ic_table.as<const DG1A>();
+    const uint32_t *s = V->rlc.s.as<const uint32_t>(), *exp = V->rlc.exp.as<const uint32_t>();
+    const F12 *alpha_beta = V->alpha_beta.as<const F12>(), *ab_lambda = V->rlc.ab_lambda.as<const F12>();
+    ProfScope ps("verify_inputs", st);
+    ZK_LAUNCH_SYNC(zkdev::k_rlc_inputs, dim3(1), dim3(zkdev::RLC_IN_THREADS), 0, st, table, s, V->rlc.acc.as<DG1>(), V->n_ic);
+    ZK_LAUNCH_SYNC(zkdev::k_f12_pow2_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, st, alpha_beta, ab_lambda, exp, nbits, V->rlc.want.as<F12>());
+    return ZK_OK;
+}
+// On the main stream, behind the others: the two shared points behind the rho_i A_i, the flags, the key's line tables behind
+// the batch's (pairs n and n + 1), ONE Miller loop over the m = n + 2 pairs, the product of its m functions as a tree of
+// groups of twelve, ONE final exponentiation
+zk_status rlc_enqueue_pairing(zk_vk* V, size_t n) {
+    const size_t m = n + 2;
+    ZK_TRY(ensure_rlc_fe(V, g_stream));
+    const uint32_t *st_g1 = V->st_g1.as<const uint32_t>(), *st_g2 = V->st_g2.as<const uint32_t>(), *host_bad = V->host_bad.as<const uint32_t>();
+    const uint32_t *inf = V->rlc.inf.as<const uint32_t>(), *pts = V->rlc.pts.as<const uint32_t>(), *skip = V->skip.as<const uint32_t>();
+    const uint32_t *prep_b = V->prep_b.as<const uint32_t>(), *gam = V->gam.as<const uint32_t>(), *none = nullptr;
+    const F12 *fe = V->rlc.fe.as<const F12>(), *want = V->rlc.want.as<const F12>();
+    uint32_t* key_lines = V->prep_b.as<uint32_t>() + n * COEF_WORDS;
+    ZK_LAUNCH(zkdev::k_rlc_shared_points, dim3(1), dim3(64), 0, g_stream, V->rlc.acc.as<const DG1>(), V->rlc.csum.as<const RlcWork::P32>(),
+              V->rlc.pts.as<uint32_t>(), V->rlc.inf.as<uint32_t>(), (uint32_t)n);
+    ZK_LAUNCH(zkdev::k_rlc_flags, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, g_stream, st_g1, st_g2, host_bad, inf, V->skip.as<uint32_t>(),
+              V->rlc.all.as<uint32_t>(), (uint32_t)n);
+    HIP_TRY(hipMemcpyAsync(key_lines, V->prep[0].p, COEF_WORDS * 4, hipMemcpyDeviceToDevice, g_stream));
+    HIP_TRY(hipMemcpyAsync(key_lines + COEF_WORDS, V->prep[1].p, COEF_WORDS * 4, hipMemcpyDeviceToDevice, g_stream));
+    {
+        ProfScope ps("verify_miller");
+        ZK_LAUNCH_SYNC(zkdev::k_miller_loop_wide, dim3((unsigned)((m + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS), 1), dim3(zkdev::W3_THREADS), 0,
+                       g_stream, pts, prep_b, none, none, none, none, skip, V->f.as<F12>(), (uint32_t)m);
+    }
+    ProfScope ps("verify_final");
+    const F12* src = V->f.as<const F12>();
+    F12* half[2] = {V->rlc.prod.as<F12>(), V->rlc.prod.as<F12>() + RlcWork::prod_half(m)};
+    int which = 0;
+    for (uint32_t cnt = (uint32_t)m; cnt > 1; which ^= 1) {
+        const uint32_t groups = (cnt + 11) / 12;
+        F12* dst = groups == 1 ? V->rlc.fe.as<F12>() : half[which];   // (the last product: the final exponentiation's operand)
+        ZK_LAUNCH_SYNC(zkdev::k_f12_prod_wide, dim3((groups + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS), dim3(zkdev::W3_THREADS), 0, g_stream, src,
+                       cnt, dst, groups);
+        src = dst;
+        cnt = groups;
+    }
+    ZK_LAUNCH_SYNC(zkdev::k_final_exp_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, g_stream, fe, gam, want, none, V->ok.as<uint32_t>(), (F12*)nullptr, 1u);
     return ZK_OK;
 }
 
@@ -640,204 +788,37 @@ zk_status verify_chunk_rlc(zk_vk* V, size_t n, const uint8_t* proofs, const uint
     if (V->gamma_inf || V->delta_inf || !ni) return ZK_OK;   // degenerate keys: the per-proof path knows them
     const Staged staged(n, proofs);
     const std::vector<uint32_t> bad(n, 0);
-    static const uint64_t RMOD[4] = ZK_FR_P_64;
-    for (size_t i = 0; i < n; i++)   // a refused encoding, an input that is not a canonical Fr: undecided
+    for (size_t i = 0; i < n; i++)   // a refused encoding, an input that is not a canonical Fr: undecided, nothing hashed
         if (staged.enc[i] || !inputs_canonical(inputs + i * ni * 32, ni)) return ZK_OK;
-    // seed = Blake2s(n | digests of the leaves), a leaf = 256 consecutive proofs with their inputs: the leaves are hashed by
-    // the host threads side by side (7 MB in one stream was 7 ms of the 8192-proof call), the seed does not depend on how many
-    uint8_t seed[32];
-    static const uint8_t pers[8] = {'z', 'k', 'a', 'm', 'd', 'r', 'l', 'c'};
-    const unsigned nth = host_threads(n, 16);
-    {
-        const size_t LEAF = 256, n_leaves = (n + LEAF - 1) / LEAF;
-        std::vector<uint8_t> dig(n_leaves * 32);
-        auto leaf_work = [&](unsigned t) {
-            for (size_t l = n_leaves * t / nth; l < n_leaves * (t + 1) / nth; l++) {
-                const size_t lo = l * LEAF, cnt = std::min(LEAF, n - lo);
-                zkhash::Blake2s h(pers);
-                h.update_u64be(l);
-                h.update(proofs + lo * 192, cnt * 192);
-                h.update(inputs + lo * (size_t)ni * 32, cnt * (size_t)ni * 32);
-                h.finish(&dig[l * 32]);
-            }
-        };
-        run_threads(nth, leaf_work);
-        zkhash::Blake2s h(pers);
-        h.update(V->key_digest, 32);
-        h.update_u64be(n);
-        h.update(dig.data(), dig.size());
-        h.finish(seed);
-    }
-    // rho_i = a_i + b_i lambda with (a_i, b_i) = 2 x 64 bits of Blake2s(seed, i); lambda = -x^2 mod r (pairing.h k_rlc_scale)
-    std::vector<uint32_t> rho(n * 4);
-    zkhost::Fr lambda_m;
-    {
-        const unsigned __int128 x2 = (unsigned __int128)ZK_BLS_X_ABS * ZK_BLS_X_ABS;
-        zkhost::Fr l = zkhost::Fr::zero();
-        l.l[0] = (uint64_t)x2;
-        l.l[1] = (uint64_t)(x2 >> 64);
-        uint64_t bo = 0;
-        for (int k = 0; k < 4; k++) {   // r - x^2
-            const unsigned __int128 d = (unsigned __int128)RMOD[k] - l.l[k] - bo;
-            l.l[k] = (uint64_t)d;
-            bo = (uint64_t)(d >> 64) & 1u;
-        }
-        lambda_m = l.to_mont();
-    }
-    struct Part {
-        std::vector<zkhost::Fr> s;
-        unsigned __int128 sa = 0, sb = 0;
-    };
-    std::vector<Part> part(nth);
-    for (auto& pt : part) pt.s.assign(ni + 1, zkhost::Fr::zero());
-    auto work = [&](unsigned t) {
-        for (size_t i = n * t / nth; i < n * (t + 1) / nth; i++) {
-            uint8_t d[32];
-            zkhash::Blake2s h;
-            h.update(seed, 32);
-            h.update_u64be(i);
-            h.finish(d);
-            memcpy(&rho[i * 4], d, 16);
-            if (!(rho[i * 4] | rho[i * 4 + 1] | rho[i * 4 + 2] | rho[i * 4 + 3])) rho[i * 4] = 1;
-            uint64_t ab[2];
-            memcpy(ab, &rho[i * 4], 16);
-            part[t].sa += ab[0];
-            part[t].sb += ab[1];
-            zkhost::Fr a = zkhost::Fr::zero(), b = zkhost::Fr::zero();
-            a.l[0] = ab[0];
-            b.l[0] = ab[1];
-            const zkhost::Fr rm = a.to_mont() + b.to_mont() * lambda_m;   // rho_i R
-            part[t].s[0] = part[t].s[0] + rm;
-            for (uint32_t j = 0; j < ni; j++) {
-                zkhost::Fr x;
-                memcpy(x.l, inputs + (i * ni + j) * 32, 32);   // plain: rho R * x / R = rho x, plain
-                part[t].s[1 + j] = part[t].s[1 + j] + rm * x;
-            }
-        }
-    };
-    run_threads(nth, work);
-    std::vector<uint32_t> sv((size_t)(ni + 1) * 8), ev(8, 0);
-    unsigned __int128 sa = 0, sb = 0;
-    for (unsigned t = 0; t < nth; t++) {
-        sa += part[t].sa;
-        sb += part[t].sb;
-    }
-    for (uint32_t j = 0; j <= ni; j++) {
-        zkhost::Fr a = zkhost::Fr::zero();
-        for (unsigned t = 0; t < nth; t++) a = a + part[t].s[j];
-        if (j == 0) a = a.from_mont();   // sum of rho_i R -> plain; the others are plain already
-        memcpy(&sv[(size_t)j * 8], a.l, 32);
-    }
-    // the exponent of e(alpha, beta) in the same decomposed form: sum a_i | sum b_i (< n 2^64 each), for
-    // e(alpha, beta)^(sum a_i) * (e(alpha, beta)^lambda)^(sum b_i)
-    memcpy(&ev[0], &sa, 16);
-    memcpy(&ev[4], &sb, 16);
+    // (alive until the streams have been waited for: the pageable source of asynchronous copies, as staged and bad are)
+    const zkrlc::Coefs co = zkrlc::coefs(V->key_digest, n, ni, proofs, inputs, host_threads(n, 16),
+                                         [](unsigned nth, auto& work) { run_threads(nth, work); });
     const size_t m = n + 2;
     ZK_TRY(upload_staged(V, n, staged, &bad));
-    ZK_TRY(upload(V->rlc_rho, rho.data(), rho.size() * 4));
-    ZK_TRY(upload(V->rlc_s, sv.data(), sv.size() * 4));
-    ZK_TRY(upload(V->rlc_exp, ev.data(), 32));
+    ZK_TRY(V->rlc.reserve(n, V->n_ic));
+    HIP_TRY(hipMemcpyAsync(V->rlc.rho.p, co.rho.data(), co.rho.size() * 4, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(hipMemcpyAsync(V->rlc.s.p, co.s.data(), co.s.size() * 4, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(hipMemcpyAsync(V->rlc.exp.p, co.exp, 32, hipMemcpyHostToDevice, g_stream));
+    HIP_TRY(hipMemsetAsync(V->rlc.all.p, 0xff, 4, g_stream));
+    ZK_TRY(V->streams.fork());
+    // the workspaces shared with the per-proof path, for the m pairs
     ZK_TRY(V->skip.ensure(m * 4));
     ZK_TRY(V->f.ensure(3 * m * sizeof(F12)));
     ZK_TRY(V->ok.ensure(4));
-    ZK_TRY(V->prep_b.ensure(m * COEF_WORDS * 4));   // (the key's two tables behind the n of the batch: before enqueue_head reserves n)
-    ZK_TRY(V->rlc_pts.ensure(m * 96));
-    ZK_TRY(V->rlc_c.ensure(n * sizeof(zkdev::XYZZ<zkdev::Fq32>)));
-    ZK_TRY(V->rlc_csum.ensure(((n + 255) / 256 + 1) * sizeof(zkdev::XYZZ<zkdev::Fq32>)));
-    ZK_TRY(V->rlc_acc.ensure(sizeof(DG1)));
-    ZK_TRY(V->rlc_inf.ensure(8));
-    ZK_TRY(V->rlc_all.ensure(4));
-    ZK_TRY(V->rlc_want.ensure(sizeof(F12)));
-    ZK_TRY(V->rlc_prod.ensure(2 * (m / 12 + 2) * sizeof(F12)));
-    if (!V->rlc_fe.cap) {   // [product | 1 | 1]: what k_final_exp_wide multiplies for its one item
-        std::vector<uint32_t> ones(3 * 144, 0);
-        static const uint32_t R32[12] = ZK_FQ_R_32;
-        for (int k = 1; k < 3; k++) memcpy(&ones[(size_t)k * 144], R32, 48);
-        ZK_TRY(upload(V->rlc_fe, ones.data(), ones.size() * 4));
-    }
-    for (int k = 0; k < 2; k++)
-        if (!V->ev_join[k]) HIP_TRY(hipEventCreate(&V->ev_join[k]));
-    HIP_TRY(hipMemsetAsync(V->rlc_all.p, 0xff, 4, g_stream));
-    HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
-    HIP_TRY(hipStreamWaitEvent(g_stream2, g_ev_fork, 0));
-    HIP_TRY(hipStreamWaitEvent(g_copy_stream, g_ev_fork, 0));
-    // main stream: B decoded, its lines prepared (the r-torsion test rides on the preparation); side stream: A and C decoded ...
+    ZK_TRY(V->prep_b.ensure(m * COEF_WORDS * 4));   // (the key's two tables behind the n of the batch: BEFORE enqueue_head reserves n)
+    // main stream: B decoded, its lines prepared (the r-torsion test rides on the preparation); side stream: A and C decoded
     ZK_TRY(enqueue_head(V, n, verify_plan_lane_head(n, own_proofs, tun, true), g_stream, g_stream2));
-    {   // ... scaled by rho_i, the C's summed
-        ProfScope ps("verify_rlc_scale", g_stream2);
-        typedef zkdev::XYZZ<zkdev::Fq32> P32;
-        ZK_LAUNCH(zkdev::k_rlc_scale, dim3((unsigned)((2 * n + 63) / 64)), dim3(64), 0, g_stream2, (const uint32_t*)V->aff_g1.as<uint32_t>(),
-                  (const uint32_t*)V->rlc_rho.as<uint32_t>(), V->rlc_pts.as<uint32_t>(), V->rlc_c.as<P32>(), (uint32_t)n);
-        const uint32_t nb1 = (uint32_t)((n + 255) / 256);
-        ZK_LAUNCH_SYNC(zkdev::k_g1_sum, dim3(nb1), dim3(64), 0, g_stream2, (const P32*)V->rlc_c.as<P32>(), (uint32_t)n, V->rlc_csum.as<P32>() + 1);
-        ZK_LAUNCH_SYNC(zkdev::k_g1_sum, dim3(1), dim3(64), 0, g_stream2, (const P32*)(V->rlc_csum.as<P32>() + 1), nb1, V->rlc_csum.as<P32>());
-    }
-    HIP_TRY(hipEventRecord(V->ev_join[0], g_stream2));
-    {   // copy stream: e(alpha, beta)^S and the accumulator sum_j s_j ic_j
-        ProfScope ps("verify_inputs", g_copy_stream);
-        ZK_LAUNCH_SYNC(zkdev::k_rlc_inputs, dim3(1), dim3(zkdev::RLC_IN_THREADS), 0, g_copy_stream, (const DG1A*)V->ic_table.as<DG1A>(),
-                       (const uint32_t*)V->rlc_s.as<uint32_t>(), V->rlc_acc.as<DG1>(), V->n_ic);
-        if (!V->rlc_ab_lambda.cap) {   // once per key: e(alpha, beta)^lambda
-            uint32_t lam[8];
-            const zkhost::Fr lp = lambda_m.from_mont();
-            memcpy(lam, lp.l, 32);
-            DevBuf dl;
-            ZK_TRY(dl.ensure(32));
-            HIP_TRY(hipMemcpy(dl.p, lam, 32, hipMemcpyHostToDevice));
-            ZK_TRY(V->rlc_ab_lambda.ensure(sizeof(F12)));
-            ZK_LAUNCH_SYNC(zkdev::k_f12_pow_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, g_copy_stream, (const F12*)V->alpha_beta.as<F12>(),
-                           (const uint32_t*)dl.as<uint32_t>(), 255u, V->rlc_ab_lambda.as<F12>());
-            HIP_TRY(hipStreamSynchronize(g_copy_stream));
-        }
-        uint32_t nbits = 128;
-        while (nbits > 1 && !(((ev[(nbits - 1) >> 5] | ev[4 + ((nbits - 1) >> 5)]) >> ((nbits - 1) & 31)) & 1u)) nbits--;
-        ZK_LAUNCH_SYNC(zkdev::k_f12_pow2_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, g_copy_stream, (const F12*)V->alpha_beta.as<F12>(),
-                       (const F12*)V->rlc_ab_lambda.as<F12>(), (const uint32_t*)V->rlc_exp.as<uint32_t>(), nbits, V->rlc_want.as<F12>());
-    }
-    HIP_TRY(hipEventRecord(V->ev_join[1], g_copy_stream));
-    HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[0], 0));
-    HIP_TRY(hipStreamWaitEvent(g_stream, V->ev_join[1], 0));
-    ZK_LAUNCH(zkdev::k_rlc_shared_points, dim3(1), dim3(64), 0, g_stream, (const DG1*)V->rlc_acc.as<DG1>(),
-              (const zkdev::XYZZ<zkdev::Fq32>*)V->rlc_csum.as<zkdev::XYZZ<zkdev::Fq32>>(), V->rlc_pts.as<uint32_t>(), V->rlc_inf.as<uint32_t>(),
-              (uint32_t)n);
-    ZK_LAUNCH(zkdev::k_rlc_flags, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, g_stream, (const uint32_t*)V->st_g1.as<uint32_t>(),
-              (const uint32_t*)V->st_g2.as<uint32_t>(), (const uint32_t*)V->host_bad.as<uint32_t>(), (const uint32_t*)V->rlc_inf.as<uint32_t>(),
-              V->skip.as<uint32_t>(), V->rlc_all.as<uint32_t>(), (uint32_t)n);
-    // the key's prepared -gamma and -delta behind the batch's own lines: pairs n and n + 1
-    HIP_TRY(hipMemcpyAsync(V->prep_b.as<uint32_t>() + n * COEF_WORDS, V->prep[0].p, COEF_WORDS * 4, hipMemcpyDeviceToDevice, g_stream));
-    HIP_TRY(hipMemcpyAsync(V->prep_b.as<uint32_t>() + (n + 1) * COEF_WORDS, V->prep[1].p, COEF_WORDS * 4, hipMemcpyDeviceToDevice, g_stream));
-    {
-        ProfScope ps("verify_miller");
-        ZK_LAUNCH_SYNC(zkdev::k_miller_loop_wide, dim3((unsigned)((m + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS), 1), dim3(zkdev::W3_THREADS), 0,
-                       g_stream, (const uint32_t*)V->rlc_pts.as<uint32_t>(), (const uint32_t*)V->prep_b.as<uint32_t>(), (const uint32_t*)nullptr,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)V->skip.as<uint32_t>(),
-                       V->f.as<F12>(), (uint32_t)m);
-    }
-    {
-        ProfScope ps("verify_final");
-        // the product of the n + 2 Miller functions: a tree of groups of twelve
-        const F12* src = V->f.as<F12>();
-        F12* bufs[2] = {V->rlc_prod.as<F12>(), V->rlc_prod.as<F12>() + (m / 12 + 2)};
-        uint32_t cnt = (uint32_t)m;
-        int which = 0;
-        while (cnt > 1) {
-            const uint32_t groups = (cnt + 11) / 12;
-            F12* dst = groups == 1 ? V->rlc_fe.as<F12>() : bufs[which];
-            ZK_LAUNCH_SYNC(zkdev::k_f12_prod_wide, dim3((groups + zkdev::W3_GROUPS - 1) / zkdev::W3_GROUPS), dim3(zkdev::W3_THREADS), 0, g_stream,
-                           src, cnt, dst, groups);
-            src = dst;
-            cnt = groups;
-            which ^= 1;
-        }
-        ZK_LAUNCH_SYNC(zkdev::k_final_exp_wide, dim3(1), dim3(zkdev::W3_THREADS), 0, g_stream, (const F12*)V->rlc_fe.as<F12>(),
-                       (const uint32_t*)V->gam.as<uint32_t>(), (const F12*)V->rlc_want.as<F12>(), (const uint32_t*)nullptr, V->ok.as<uint32_t>(),
-                       (F12*)nullptr, 1u);
-    }
+    ZK_TRY(rlc_enqueue_scale(V, n, g_stream2));
+    ZK_TRY(V->streams.side_done());
+    ZK_TRY(rlc_enqueue_want(V, co.nbits, g_copy_stream));
+    ZK_TRY(V->streams.copy_done());
+    ZK_TRY(V->streams.join());
+    ZK_TRY(rlc_enqueue_pairing(V, n));
     HIP_TRY(hipGetLastError());
     uint32_t okv = 0, allv = 0;
     HIP_TRY(hipStreamSynchronize(g_stream));
     HIP_TRY(hipMemcpy(&okv, V->ok.p, 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(&allv, V->rlc_all.p, 4, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&allv, V->rlc.all.p, 4, hipMemcpyDeviceToHost));
     *decided = okv == 1 && allv != 0;
     if (hook_env("ZKAMD_DEBUG_RLC"))   // tests: was the chunk really decided by the combined check?
         fprintf(stderr, "[rlc] chunk of %zu proofs: combined check %s, every proof well-formed: %s\n", n, okv == 1 ? "passed" : "FAILED",
@@ -1138,6 +1119,20 @@ zk_status zk_hook_verify_plan(size_t n, size_t n_inputs, int own_proofs, int hav
     const uint64_t f[9] = {(uint64_t)p.decode, p.b_torsion_in_decoder, p.subgroup_tests, (uint64_t)p.prepare, p.prep_b_points, (uint64_t)p.inputs,
                            p.inputs_mul, (uint64_t)p.pairing, verify_takes_combined(form, n, tun)};
     std::copy(f, f + 9, out);
+    return ZK_OK;
+} ZK_ABI_CATCH
+// ... and the coefficients of the combined check of a chunk (verify_rlc.h) on `threads` host threads, no GPU involved: rho_out
+// 16 n bytes, s_out 32 (n_inputs + 1), exp_out 32
+zk_status zk_hook_rlc_coefs(const uint8_t key_digest[32], size_t n, size_t n_inputs, const uint8_t* proofs, const uint8_t* inputs, unsigned threads,
+                            uint8_t* rho_out, uint8_t* s_out, uint8_t* exp_out, uint32_t* nbits_out) try {
+    if (!key_digest || !n || !proofs || (n_inputs && !inputs) || !rho_out || !s_out || !exp_out || !nbits_out)
+        return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    const zkrlc::Coefs co =
+        zkrlc::coefs(key_digest, n, (uint32_t)n_inputs, proofs, inputs, threads, [](unsigned nth, auto& work) { run_threads(nth, work); });
+    memcpy(rho_out, co.rho.data(), co.rho.size() * 4);
+    memcpy(s_out, co.s.data(), co.s.size() * 4);
+    memcpy(exp_out, co.exp, 32);
+    *nbits_out = co.nbits;
     return ZK_OK;
 } ZK_ABI_CATCH
 // ... and zk_elgamal_ledger_apply's arguments through the scan that can forget (asset_block_exec.h): flag bit 2 is LEDGER_CLEAR,
