@@ -2,6 +2,7 @@
 sizes) suites.  Every function takes `lib` (a ZkLib over one build of the C ABI) and compares
 the HIP path's bytes with the oracle's on the same seeded inputs."""
 import ctypes as C
+import functools
 import os
 
 import numpy as np
@@ -303,7 +304,7 @@ def _bad_uncompressed(group):
 
 
 def msm_decoder_refusals(lib, oneshot_every=1):
-    """The device decoder of the bases (msm.h k_decode_uncompressed) behind zk_msm_create / zk_msm_create_variable and the
+    """The device decoder of the bases (msm_point_kernels.h k_decode_uncompressed) behind zk_msm_create / zk_msm_create_variable and the
     one-shot entries zk_msm_g1 / zk_msm_g2: every malformed encoding of the reference's tests is refused with IoError and
     the index of the offending base; what only `into_affine` (checked) refuses passes unchecked and fails checked."""
     for group in (1, 2):
@@ -362,6 +363,57 @@ def msm_oneshot(lib, n1=700, n2=90, seeds=(5, 6)):
             with pytest.raises(zk.ZkError) as e:
                 zk.multiexp(group, b"".join(pts[k] for k in ks), np.frombuffer(b"".join(int(x).to_bytes(32, "little") for x in sc), dtype=np.uint8), lib=lib)
             assert e.value.variant == "InvalidArgument" and "scalar 3" in str(e.value)
+
+
+# the launch-set forms of msm_sort_paths: (environment, window width)
+SORT_PATHS = {
+    "lds_c9": ({"ZKAMD_FEW_JOBS": "1"}, 9),                                       # the LDS sort, 128 buckets: the threads past the last bucket meet the clamp of the scan ranges
+    "lds_c14": ({"ZKAMD_FEW_JOBS": "1"}, 14),                                     # the LDS sort, 4 096 buckets: four per thread
+    "two_level_16_bins": ({"ZKAMD_NO_LDS_SORT": "1", "ZKAMD_SORT_FINE_LOG": "3"}, 9),   # 16 coarse bins, two workgroups of scalars, the second ragged
+    "two_level_one_bin": ({"ZKAMD_NO_LDS_SORT": "1"}, 9),                         # one bin: the degenerate coarse scan
+}
+SORT_N_JOBS, SORT_N, SORT_N_BASES = 3, 1300, 40
+
+
+@functools.lru_cache(maxsize=None)
+def _sort_paths_jobs():
+    """3 jobs of 1 300 random scalars mapped onto 40 bases (base 2 the identity), a few map entries -1, one scalar 0; the
+    reference per job is the oracle's sum with the scalars of every base added up first (40 multiplications per job)."""
+    import test_table_multiples as tm
+    _, bases = tm._bases(1, SORT_N_BASES, 2)
+    rng = synth.SplitMix64(2028)
+    mp = [rng.below(SORT_N_BASES) for _ in range(SORT_N)]
+    for i in (0, 517, 1023, 1024, 1299):
+        mp[i] = -1
+    jobs = [[rng.field(bls.R_MOD) for _ in range(SORT_N)] for _ in range(SORT_N_JOBS)]
+    jobs[1][700] = 0
+    pts = [bls.g1_from_uncompressed(bases[96 * i:96 * (i + 1)]) for i in range(SORT_N_BASES)]
+    assert pts[2] is None
+    want = []
+    for sc in jobs:
+        per_base = [0] * SORT_N_BASES
+        for s, m in zip(sc, mp):
+            if m >= 0:
+                per_base[m] += s
+        want.append(bls.g1_uncompressed(bls.G1.to_affine(bls.msm_naive(bls.G1, pts, [t % bls.R_MOD for t in per_base]))))
+    return bases, mp, jobs, want
+
+
+def msm_sort_paths(lib, monkeypatch, path, seg, mults=(1, 8)):
+    """Both sorts of the (digit, point) pairs (msm_sort.h: in one workgroup's LDS, in two levels) and the task order at small
+    shapes, through zk_hook_mult_msm: every launch-set form of SORT_PATHS must give the oracle's bytes over one multiple and
+    over eight (three extra window bits).  seg: None, or ZKAMD_MSM_SEG - 4 cuts the buckets into several tasks, so that the
+    second scanned value, the task offsets and the heavy / light lists are no longer trivial."""
+    import test_table_multiples as tm
+    env, c = SORT_PATHS[path]
+    for name, value in env.items():
+        monkeypatch.setenv(name, value)
+    if seg is not None:
+        monkeypatch.setenv("ZKAMD_MSM_SEG", str(seg))
+    bases, mp, jobs, want = _sort_paths_jobs()
+    for n_mult in mults:
+        got, _ = tm._mult_msm(lib, 1, c, n_mult, bases, scalars=jobs, mp=mp, ext=3 if n_mult == 8 else None)
+        assert got == want, (path, seg, n_mult, [p for p in range(SORT_N_JOBS) if got[p] != want[p]])
 
 
 def prover_device_pointers(lib, alloc, seed=4, n_in=3, n_aux=14, n_proofs=5):

@@ -86,6 +86,13 @@ def test_prover_small_checked(emu_lib, monkeypatch):
     pc.prover_small(emu_lib, 1, 3, 10, 12)
 
 
+def test_prover_small_normalised_on_the_device(emu_lib, monkeypatch):
+    """the emulation twin of test_gpu_parity.test_prover_small_normalised_on_the_device (k_xyzz_normalize_export2)"""
+    monkeypatch.setenv("ZKAMD_WINDOW_BITS", "5")
+    monkeypatch.setenv("ZKAMD_HOST_NORMALIZE_MAX", "0")
+    pc.prover_small(emu_lib, 1, 3, 10, 12)
+
+
 def test_prover_montgomery_inputs_two_pass_ntt(emu_lib, monkeypatch):
     monkeypatch.setenv("ZKAMD_WINDOW_BITS", "6")
     pc.prover_small(emu_lib, 7, 4, 300, 330, checked=False, montgomery=True)   # m = 512: two NTT passes
@@ -156,6 +163,13 @@ def test_msm_two_level_sort_path(emu_lib, monkeypatch):
     pc.msm_golden_vectors(emu_lib, 2, 60, 6)                  # 16 buckets in 2 bins
     monkeypatch.setenv("ZKAMD_WINDOW_BITS", "7")
     pc.prover_small(emu_lib, 5, 3, 10, 12)
+
+
+@pytest.mark.parametrize("seg", [None, 4], ids=["seg_default", "seg_4"])
+@pytest.mark.parametrize("path", sorted(pc.SORT_PATHS))
+def test_msm_sort_paths(emu_lib, monkeypatch, path, seg):
+    """The emulation twin of test_gpu_parity.test_msm_sort_paths: the same jobs, forms and reference on 64-thread workgroups."""
+    pc.msm_sort_paths(emu_lib, monkeypatch, path, seg)
 
 
 @pytest.mark.parametrize("form", LAUNCH_SET_FORMS)

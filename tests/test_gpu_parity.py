@@ -122,6 +122,13 @@ def test_prover_small(gpu_lib):
     pc.prover_small(gpu_lib, 7, 4, 300, 330, checked=False, montgomery=True)
 
 
+def test_prover_small_normalised_on_the_device(gpu_lib, monkeypatch):
+    """ZKAMD_HOST_NORMALIZE_MAX=0: A and C of a proof made alone take their affine form on the device, side by side in one
+    launch (msm_point_kernels.h k_xyzz_normalize_export2) - by default only chunks of 17 to 32 proofs take that kernel."""
+    monkeypatch.setenv("ZKAMD_HOST_NORMALIZE_MAX", "0")
+    pc.prover_small(gpu_lib, 1, 3, 10, 12)
+
+
 def test_prover_blinding_edges(gpu_lib):
     pc.prover_blinding_edges(gpu_lib)
 
@@ -745,6 +752,14 @@ def test_msm_decoder_refusals(gpu_lib):
 
 def test_msm_oneshot_entries(gpu_lib):
     pc.msm_oneshot(gpu_lib)
+
+
+@pytest.mark.parametrize("seg", [None, 4], ids=["seg_default", "seg_4"])
+@pytest.mark.parametrize("path", sorted(pc.SORT_PATHS))
+def test_msm_sort_paths(gpu_hooks_lib, monkeypatch, path, seg):
+    """Both sorts and the task order at small shapes, every launch-set form over one and over eight table multiples
+    (parity_cases.msm_sort_paths)."""
+    pc.msm_sort_paths(gpu_hooks_lib, monkeypatch, path, seg)
 
 
 def test_msm_oneshot_2p16_vs_bellman_algorithm(gpu_lib):

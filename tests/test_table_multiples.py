@@ -1,4 +1,4 @@
-"""Table multiples (csrc/msm.h MsmRecode, msm_wnaf_mult, k_msm_build_table): a bound table holds, behind the 255 slices 2^k P
+"""Table multiples (csrc/msm_types.h MsmRecode, msm_recode.h msm_wnaf_mult, msm_point_kernels.h k_msm_build_table): a bound table holds, behind the 255 slices 2^k P
 of every base, the slices of m 2^k P for the odd m = 3, 5, ..., and a scalar is recoded over the digits +- m b (b odd,
 b < 2^(c-1)): digit m b goes into bucket b through the slice of m.  The group element a multiexp computes cannot change; what
 can go wrong is the recoding (a digit that does not sum back to the scalar, a bucket past the histogram, a slice past the
@@ -35,7 +35,7 @@ DEFAULT_EXT = {1: 0, 2: 2, 4: 3, 8: 3}
 
 
 def _max_digits(c):
-    return 254 // c + 2          # msm.h msm_max_digits
+    return 254 // c + 2          # msm_types.h msm_max_digits
 
 
 # ----------------------------------------------------------------------------------------------

@@ -1,4 +1,4 @@
-"""Value runs (csrc/value_pairs.h RUN_MAX, ntt.h k_build_scalars, msm.h MsmSelSet): a stretch of up to RUN_MAX linked variables
+"""Value runs (csrc/value_pairs.h RUN_MAX, ntt.h k_build_scalars, msm_types.h MsmSelSet): a stretch of up to RUN_MAX linked variables
 that hold the same value in a proof is ONE term of a multiexp over the sum of their bases.
 
     z P_1 + ... + z P_l = z (P_1 + ... + P_l)

@@ -25,11 +25,11 @@ products take it as it is (v_mad_i64_i32, arithmetic shifts of the column accumu
 (its limbs reach 2^30 and it is squared).  The accumulator's y is held as W = sigma Y with sigma = -1 after every
 second step: W' = R^ T' + W PPP with R^ = S2^ - W, S2^ = sigma (+-py) ZZZ, T' = X' - Q gives -sigma Y' without a
 single negation, and sigma is uniform over the wave (a function of the step index), so it costs one s_not_b64 per
-step folded into the lanes' negate mask.  The C++ wrapper (msm.h) converts the four coordinates back to the unsigned
+step folded into the lanes' negate mask.  The C++ wrapper (msm_asm_g1.h, msm_asm_g2.h) converts the four coordinates back to the unsigned
 weakly normalised form of dev_field.h after the loop.
 
 Special cases need no code in the loop: P == 0 (mod p) makes ZZ' == 0 (mod p), and a ZZ that is 0 (mod p) stays
-0 through every later product, so ONE test per task after the loop (the C++ wrapper in msm.h) sends the task to
+0 through every later product, so ONE test per task after the loop (the C++ wrapper in msm_asm_g1.h / msm_asm_g2.h) sends the task to
 the generic kernel for a second pass.
 
 Everything emitted here is executed for one lane by tools/sim_madd_asm.py against big-integer arithmetic before it
@@ -563,7 +563,7 @@ def render(R, e, name, what, first_clobber=64):
     # ..._CLOBBERS_MIN: only the registers the loop names.  The pads it never touches stay with the compiler, which then has
     # somewhere to keep the few values that live across the loop; with EVERY VGPR clobbered they go to scratch memory, and a
     # kernel that uses scratch runs under the runtime's scratch-wave limit (the scratch-free second form of the kernels,
-    # msm.h k_msm_accumulate_g2asm*_sf, selected per device at load time: zkamd.cpp calibrate_kernel_forms)
+    # msm_asm_g2.h k_msm_accumulate_g2asm*_sf, selected per device at load time: zkamd.cpp calibrate_kernel_forms)
     used = used_vgprs(e.lines)
     assert max(used) < R.n_vgpr
     clob_min = ["v%d" % i for i in range(first_clobber, R.n_vgpr) if i in used] + ["s%d" % i for i in R.clob_s] + ["vcc", "scc", "memory"]

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Generate zero-chain_amd/csrc/red_asm.h: level 1 of the bucket reduction of the G1 multiexp (msm.h, pass 6) as ONE
+"""Generate zero-chain_amd/csrc/red_asm.h: level 1 of the bucket reduction of the G1 multiexp (msm_asm_g1.h, pass 6) as ONE
 straight-line gfx950 assembly loop with a hand-made register allocation.
 
 What it replaces: k_msm_suffix_buckets + the first k_msm_segsum - compiled XYZZ full additions

@@ -44,7 +44,7 @@ void combine(const zkdev::XYZZ<F>* Y, zkdev::XYZZ<F>* out, uint32_t nbits, uint3
 
 // Many-jobs launch sets (a chunk of proofs): everything above level 1 in one launch, one workgroup of rows per job.
 // out[j] = sum_t W_t + 2 L sum_t t S_t over the T nodes of job j (S at S[(j T + t) s_stride], W at W[j T + t]; T a power
-// of two).  w_is_a: the assembly level 1 (msm.h k_msm_reduce1_g1asm) leaves A = (W - S) / 2 in W's place.
+// of two).  w_is_a: the assembly level 1 (msm_asm_g1.h k_msm_reduce1_g1asm) leaves A = (W - S) / 2 in W's place.
 template <class F>
 void upper(const zkdev::XYZZ<F>* S, uint32_t s_stride, const zkdev::XYZZ<F>* W, zkdev::XYZZ<F>* out, uint32_t T, uint32_t log2_2l,
            bool w_is_a, uint32_t nj, hipStream_t st);

@@ -1,9 +1,65 @@
 // The G1 instantiation of the MSM group (msm_group.h): its kernels - the generated assembly loops of the accumulation and of
-// level 1 of the bucket reduction among them - are compiled here and nowhere else.
+// level 1 of the bucket reduction among them - are compiled here and nowhere else.  So are the kernels of the sort and of the
+// task order, which both groups run through msm_sort_pairs / msm_order_tasks below.
 #define ZK_MSM_GROUP_INSTANTIATE 1
 #include "msm_group_impl.h"
+#include "msm_sort.h"
+#include "msm_asm_g1.h"
 
 namespace zkrt {
+
+zk_status msm_sort_pairs(const MsmPlan& p, hipStream_t st, const MsmSortBufs& w, uint32_t nb, uint32_t c, const zkdev::MsmRecode& rc,
+                         const zkdev::MsmSelSet& sel_set) {
+    const size_t nj = p.nj;
+    const MsmJob* dj = w.jobs;
+    if (p.lds_sort) {
+        // histogram + scan + scatter of a job inside one workgroup's LDS
+        ProfScope ps("msm_sort_lds", st);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_sort_lds, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), (size_t)nb * 4, st, dj, c, w.cnt, w.off, w.toff,
+                       w.ntasks, w.pairs, p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u, sel_set, rc);
+        return ZK_OK;
+    }
+    // two-level counting sort, every per-digit atomic in LDS (msm_sort.h)
+    const uint32_t fine_log = p.fine_log, fine = 1u << fine_log, n_coarse = p.n_coarse, per_wg = zkdev::MSM_COARSE_SCALARS;
+    const dim3 gridc(p.coarse_wgs, (unsigned)nj);
+    uint32_t* coarse_cnt = w.coarse;
+    uint32_t* coarse_off = coarse_cnt + nj * (size_t)n_coarse;
+    uint32_t* bin_tasks = coarse_off + nj * (size_t)n_coarse;
+    uint32_t* bin_tbase = bin_tasks + nj * (size_t)n_coarse;
+    HIP_TRY(hipMemsetAsync(coarse_cnt, 0, nj * (size_t)n_coarse * 4, st));
+    {
+        ProfScope ps("msm_sort_coarse", st);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_count, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse, coarse_cnt, w.blockbase, per_wg, sel_set, rc);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
+                       (const uint32_t*)coarse_cnt, coarse_off, (uint32_t*)nullptr, n_coarse);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scatter, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse,
+                       (const uint32_t*)coarse_off, (const uint32_t*)w.blockbase, w.rank, per_wg, sel_set, rc);
+    }
+    {
+        ProfScope ps("msm_sort_fine", st);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_fine_sort, dim3(n_coarse, (unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st, dj,
+                       (const uint2*)w.rank, (const uint32_t*)coarse_cnt, (const uint32_t*)coarse_off, fine, nb, w.cnt, w.off, w.toff,
+                       bin_tasks, w.pairs, p.seg);
+        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
+                       (const uint32_t*)bin_tasks, bin_tbase, w.ntasks, n_coarse);
+        ZK_LAUNCH(zkdev::k_msm_task_offsets, dim3((nb + 255) / 256, (unsigned)nj), dim3(256), 0, st, w.toff,
+                  (const uint32_t*)bin_tbase, nb, fine_log, n_coarse);
+    }
+    return ZK_OK;
+}
+
+zk_status msm_order_tasks(const MsmPlan& p, hipStream_t st, const MsmSortBufs& w, uint32_t nb) {
+    const uint32_t nj = (uint32_t)p.nj;
+    const dim3 gridb((nb + 255) / 256, nj);
+    uint32_t* lenhist = w.hist;
+    uint32_t* cursor = lenhist + p.n_class;
+    ProfScope ps("msm_task_sort", st);
+    ZK_LAUNCH_SYNC(zkdev::k_msm_task_hist, gridb, dim3(256), 0, st, w.cnt, lenhist, nb, p.seg);
+    ZK_LAUNCH_SYNC(zkdev::k_msm_task_base, dim3(1), dim3(zkdev::MSM_SORT_THREADS), 0, st, lenhist, w.tclass, w.n_tasks, nj, p.seg);
+    ZK_LAUNCH_SYNC(zkdev::k_msm_task_place, gridb, dim3(256), 0, st, w.cnt, w.off, w.toff, w.tbase, w.tclass, cursor, w.sorted, w.n_heavy,
+                   w.heavy, nb, nj, p.merge_inline, p.seg, w.n_light, w.light);
+    return ZK_OK;
+}
 
 #ifdef ZK_HAVE_RED_ASM
 template <>
@@ -81,9 +137,7 @@ zk_status calibrate_g1_reduce(const zkdev::Affine<zkdev::Fq28>* table, uint32_t 
     return ZK_OK;
 }
 
-template struct MsmGroup<zkhost::Fq, zkdev::Fq>;
-template zk_status check_points_dev<zkhost::Fq, zkdev::Fq>(const zkdev::Affine<zkdev::Fq>*, size_t, const char*);
-template zk_status check_points_host<zkhost::Fq, zkdev::Fq>(const std::vector<zkhost::Affine<zkhost::Fq>>&, const char*);
+ZK_MSM_GROUP_DEFINE(zkhost::Fq, zkdev::Fq)
 
 }  // namespace zkrt
 

@@ -2,6 +2,7 @@
 // its two forms among them - are compiled here and nowhere else.
 #define ZK_MSM_GROUP_INSTANTIATE 1
 #include "msm_group_impl.h"
+#include "msm_asm_g2.h"
 
 namespace zkrt {
 
@@ -64,8 +65,6 @@ zk_status calibrate_g2_accumulate(const zkdev::Affine<DevFq2>* table, uint32_t n
     return ZK_OK;
 }
 
-template struct MsmGroup<zkhost::Fq2, DevFq2>;
-template zk_status check_points_dev<zkhost::Fq2, DevFq2>(const zkdev::Affine<DevFq2>*, size_t, const char*);
-template zk_status check_points_host<zkhost::Fq2, DevFq2>(const std::vector<zkhost::Affine<zkhost::Fq2>>&, const char*);
+ZK_MSM_GROUP_DEFINE(zkhost::Fq2, DevFq2)
 
 }  // namespace zkrt

@@ -1,6 +1,6 @@
 // The MSM group (moved out of zkamd.cpp in round 6): the doubling table of a set of bases + the bucket pipeline over a list of
 // jobs (sort, accumulation, bucket reduction), a class template over the host / device field pair.  It is instantiated twice
-// - G1 on Fq28, G2 on Fq2x - and each instantiation compiles ~25 kernels (msm.h), among them the generated assembly loops:
+// - G1 on Fq28, G2 on Fq2x - and each instantiation compiles ~25 kernels (overview: msm.h), among them the generated assembly loops:
 // msm_g1.cpp and msm_g2.cpp hold one explicit instantiation each (ZK_MSM_GROUP_INSTANTIATE), every other unit sees them as
 // `extern template` and compiles none of their kernels - an edit of the prover's host logic no longer rebuilds them, and the
 // three units compile side by side.
@@ -17,7 +17,7 @@
 #include "gpu_rt.h"
 #include "host_common.h"
 #include "host_math.h"
-#include "msm.h"
+#include "msm_types.h"
 #include "coop_tail.h"
 #include "msm_plan.h"
 
@@ -30,7 +30,7 @@ namespace zkrt {
 // G2: the same in Fq2, where the full addition no longer fits the register file).  `group` 1 / 2.
 // group: 1 = G1 jobs of a batch (level 1 of their reduction in assembly), 2 = G2, 3 = the small A jobs of a split batch,
 // 4 = a stand-alone G1 handle (zk_msm_create: compiled reduction)
-// Over a table with multiples (msm.h MsmRecode) a scalar has 254 / (c + 1 + g) digits, g = 0.6 / 1.25 / 1.85 bits for 2 / 4 / 8
+// Over a table with multiples (msm_types.h MsmRecode) a scalar has 254 / (c + 1 + g) digits, g = 0.6 / 1.25 / 1.85 bits for 2 / 4 / 8
 // multiples; the widths are NOT taken from that: with it the G2 set came out at 12 and ran 3.4 ms per chunk slower than at the
 // 13 it has without (profiles/r28_table_multiples.txt (c)), so the bound sets keep the widths of one multiple.
 inline uint32_t pick_window(size_t n, int group) {
@@ -58,39 +58,21 @@ inline uint32_t pick_window(size_t n, int group) {
 // On-curve + subgroup validation of an array of decoded points (Parameters::read(checked = true):
 // core/pairing/src/bls12_381/ec.rs:675-688), one GPU thread per point.
 template <class HF, class DF>
-zk_status check_points_dev(const zkdev::Affine<DF>* d_pts, size_t n, const char* what) {
-    if (!n) return ZK_OK;
-    DevBuf flags;
-    ZK_TRY(flags.ensure(4 * n));
-    ZK_LAUNCH(zkdev::k_check_points<DF>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, g_stream, d_pts, (uint32_t)n, 1u,
-              flags.as<uint32_t>());
-    HIP_TRY(hipGetLastError());
-    std::vector<uint32_t> f(n);
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    HIP_TRY(hipMemcpy(f.data(), flags.p, 4 * n, hipMemcpyDeviceToHost));
-    for (size_t i = 0; i < n; i++)
-        if (f[i])
-            return fail(ZK_ERR_IO, std::string(what) + ": point " + std::to_string(i) +
-                                       (f[i] & 1 ? " is not on the curve" : " is not in the correct subgroup"));
-    return ZK_OK;
-}
+zk_status check_points_dev(const zkdev::Affine<DF>* d_pts, size_t n, const char* what);
 template <class HF, class DF>
-zk_status check_points_host(const std::vector<zkhost::Affine<HF>>& pts, const char* what) {
-    if (pts.empty()) return ZK_OK;
-    DevBuf stage, d;
-    ZK_TRY(stage.ensure(pts.size() * sizeof(zkhost::Affine<HF>)));
-    ZK_TRY(d.ensure(pts.size() * sizeof(zkdev::Affine<DF>)));
-    HIP_TRY(hipMemcpy(stage.p, pts.data(), pts.size() * sizeof(zkhost::Affine<HF>), hipMemcpyHostToDevice));
-    ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3((unsigned)((pts.size() + 127) / 128)), dim3(128), 0, g_stream,
-              (const uint32_t*)stage.as<uint32_t>(), d.as<zkdev::Affine<DF>>(), (uint32_t)pts.size());
-    HIP_TRY(hipGetLastError());
-    zk_status st = check_points_dev<HF, DF>(d.as<zkdev::Affine<DF>>(), pts.size(), what);
-    HIP_TRY(hipStreamSynchronize(g_stream));
-    return st;
-}
+zk_status check_points_host(const std::vector<zkhost::Affine<HF>>& pts, const char* what);
+// The other point kernels two units need, behind host functions (DF = zkdev::Fq or DevFq2; all four are defined in
+// msm_group_impl.h and instantiated by msm_g1.cpp / msm_g2.cpp, where alone their kernels are compiled):
+// dst[i] = the host-layout affine point i of d_src, n points, enqueued on st
+template <class DF>
+zk_status import_affine_dev(const void* d_src, zkdev::Affine<DF>* dst, size_t n, hipStream_t st);
+// the doublings - and, behind them, those of the odd multiples j0 <= j < n_mult - of the n points in slice 0 of `table`,
+// npos slices each, enqueued on st; `scratch` is sized here and must outlive the launch
+template <class DF>
+zk_status build_table_dev(zkdev::Affine<DF>* table, size_t n, uint32_t npos, DevBuf& scratch, uint32_t n_mult, uint32_t j0, hipStream_t st);
 
-// Which form of the two scratch-using assembly kernels a device runs (msm.h: the G2 accumulation loop and level 1 of the G1
-// reduction; 0 = the first form, 84 - 144 B of scratch per lane; 1 = the scratch-free second form).  Decided per device
+// Which form of the two scratch-using assembly kernels a device runs (msm_asm_g2.h: the G2 accumulation loop; msm_asm_g1.h:
+// level 1 of the G1 reduction; 0 = the first form, 84 - 144 B of scratch per lane; 1 = the scratch-free second form).  Decided per device
 // when the first key is loaded there (calibrate_kernel_forms below); ZKAMD_KERNEL_FORM = scratch | free overrides.
 struct KernelForms {
     bool done = false;
@@ -108,14 +90,14 @@ inline uint32_t kernel_form(int which) {
     return g_forms[g_device & 63].form[which];   // (written once, before the device's first proving launch)
 }
 
-// The accumulation kernels run the generated assembly loops (msm.h k_msm_accumulate_g1asm / _g2asm) from
+// The accumulation kernels run the generated assembly loops (msm_asm_g1.h k_msm_accumulate_g1asm / msm_asm_g2.h _g2asm) from
 // ZKAMD_ASM_MIN_PAIRS pairs per launch set on, unless the build has none (the x86 emulation build).
 template <class DF>
 constexpr bool asm_loop() { return false; }
 template <class DF>
 void launch_asm_loop(const zkdev::Affine<DF>*, const uint32_t*, const uint4*, const uint32_t*, zkdev::XYZZ<DF>*, uint32_t*,
                             uint32_t*, unsigned, hipStream_t) {}
-// Level 1 of the bucket reduction as the generated assembly loop (msm.h k_msm_reduce1_g1asm): G1 only, unless
+// Level 1 of the bucket reduction as the generated assembly loop (msm_asm_g1.h k_msm_reduce1_g1asm): G1 only, unless
 // the build has none (the x86 emulation build).
 template <class DF>
 constexpr bool asm_reduce() { return false; }
@@ -144,6 +126,23 @@ void launch_asm_loop<zkdev::Fq2x>(const zkdev::Affine<zkdev::Fq2x>* table, const
                                   unsigned blocks, hipStream_t st);
 #endif
 
+// The sort and the task order of a launch set do not depend on the group: plain functions over the plan of the set and the
+// pointers of the group's workspaces, defined in msm_g1.cpp next to the kernels they launch (msm_sort.h), called by both groups.
+struct MsmSortBufs {
+    const MsmJob* jobs;
+    uint32_t *cnt, *off, *toff, *ntasks, *pairs, *blockbase, *coarse;
+    uint2* rank;
+    uint32_t *hist, *tclass, *tbase;   // hist: [length histogram | cursors] of the task order (msm_plan.h Bytes::hist)
+    uint4* sorted;
+    uint32_t *heavy, *light;           // light: null where the set lists no light buckets
+    uint32_t *n_tasks, *n_heavy, *n_light;
+};
+// the (digit, point) pairs of every job sorted by bucket: cnt / off of every bucket, toff = its first task
+zk_status msm_sort_pairs(const MsmPlan& p, hipStream_t st, const MsmSortBufs& w, uint32_t nb, uint32_t c, const zkdev::MsmRecode& rc,
+                         const zkdev::MsmSelSet& sel_set);
+// the tasks of the set in classes of equal length, longest first (`sorted`), and the heavy / light lists of the merge
+zk_status msm_order_tasks(const MsmPlan& p, hipStream_t st, const MsmSortBufs& w, uint32_t nb);
+
 template <class HF, class DF>
 struct MsmGroup {
     typedef zkhost::Affine<HF> HAffine;
@@ -159,7 +158,7 @@ struct MsmGroup {
 
     uint32_t c = 0, maxd = 0, nb = 0;
     size_t n_points = 0;
-    // the odd multiples of every slice the table holds (msm.h MsmRecode; 1: the doublings alone), the extra window bits of the
+    // the odd multiples of every slice the table holds (msm_types.h MsmRecode; 1: the doublings alone), the extra window bits of the
     // recoding over them and its choice table for this group's c (made by the first launch set: ensure_recode)
     uint32_t n_mult = 1, ext = 0;
     DevBuf table, lut;
@@ -167,10 +166,10 @@ struct MsmGroup {
     DPoint* res_dev = nullptr;
     PinBuf pin_jobs;
     size_t bytes = 0;
-    DevBuf dstat;   // [first refused encoding | points at infinity] of the last decode_enqueue (msm.h k_decode_uncompressed)
+    DevBuf dstat;   // [first refused encoding | points at infinity] of the last decode_enqueue (msm_point_kernels.h k_decode_uncompressed)
 
     // the recoding width and what follows from it.  with_table = false: variable-base mode - only the bases themselves are
-    // kept (slice 0), every job takes ONE digit of every scalar (msm.h msm_digits)
+    // kept (slice 0), every job takes ONE digit of every scalar (msm_recode.h msm_digits)
     zk_status set_geometry(uint32_t c_, size_t n, bool with_table, uint32_t n_mult_ = 1) {
         if (n_mult_ < 1 || n_mult_ > zkdev::MSM_MULT_MAX || (n_mult_ > 1 && !with_table))
             return fail(ZK_ERR_INVALID_ARGUMENT, "internal: table multiples out of range");
@@ -194,7 +193,7 @@ struct MsmGroup {
     void set_multiples(uint32_t n_mult_) {
         n_mult = n_mult_;
         ext = zkdev::msm_mult_ext(n_mult);
-        if (c + ext > 22) ext = c < 22 ? 22 - c : 0;   // (the recoding's buffer holds 32 bits: msm.h msm_wnaf_mult)
+        if (c + ext > 22) ext = c < 22 ? 22 - c : 0;   // (the recoding's buffer holds 32 bits: msm_recode.h msm_wnaf_mult)
         lut.release();
     }
     // A table built with one multiple gets the slices of the others: a new allocation, the slices in place copied, the chains of
@@ -233,7 +232,7 @@ struct MsmGroup {
 
     // jobs[i].pair_base is filled in here.  Everything, including the copy of the results (one XYZZ
     // per job) into `out`, is enqueued on `st`; collect() waits for it.
-    // sels: the pair slots of the set's jobs whose bases follow the bytes of this call's proofs (msm.h MsmSelSet), or null.
+    // sels: the pair slots of the set's jobs whose bases follow the bytes of this call's proofs (msm_types.h MsmSelSet), or null.
     zk_status enqueue(std::vector<MsmJob>& jobs, std::vector<HPoint>& out, hipStream_t st, bool to_host = true,
                       const zkdev::MsmSelSet* sels = nullptr);
     // out[i] = affine form of src[i] (host layout, zz = zzz = 1), enqueued on st
@@ -269,6 +268,12 @@ private:
     zk_status upload_jobs(const std::vector<MsmJob>& jobs, const MsmPlan& p, hipStream_t st);
     zk_status sort_pairs(const MsmPlan& p, hipStream_t st, const zkdev::MsmSelSet& sel_set);
     zk_status order_tasks(const MsmPlan& p, hipStream_t st);
+    MsmSortBufs sort_bufs(const MsmPlan& p) const {
+        return MsmSortBufs{jobs_d.as<MsmJob>(), cnt.as<uint32_t>(), off.as<uint32_t>(), toff.as<uint32_t>(), ntasks.as<uint32_t>(),
+                           pairs.as<uint32_t>(), blockbase.as<uint32_t>(), coarse.as<uint32_t>(), rank.as<uint2>(), hist.as<uint32_t>(),
+                           tclass.as<uint32_t>(), tbase.as<uint32_t>(), sorted.as<uint4>(), heavy.as<uint32_t>(),
+                           p.use_light ? light.as<uint32_t>() : nullptr, counter(p, N_TASKS), counter(p, N_HEAVY), counter(p, N_LIGHT)};
+    }
     zk_status accumulate(const MsmPlan& p, hipStream_t st);
     zk_status merge_partials(const MsmPlan& p, hipStream_t st);
     zk_status level1(const MsmPlan& p, hipStream_t st);
@@ -304,10 +309,13 @@ zk_status calibrate_g1_reduce(const zkdev::Affine<zkdev::Fq28>* table, uint32_t 
 #ifndef ZK_MSM_GROUP_INSTANTIATE
 extern template struct MsmGroup<zkhost::Fq, zkdev::Fq>;
 extern template struct MsmGroup<zkhost::Fq2, DevFq2>;
-extern template zk_status check_points_dev<zkhost::Fq, zkdev::Fq>(const zkdev::Affine<zkdev::Fq>*, size_t, const char*);
-extern template zk_status check_points_dev<zkhost::Fq2, DevFq2>(const zkdev::Affine<DevFq2>*, size_t, const char*);
-extern template zk_status check_points_host<zkhost::Fq, zkdev::Fq>(const std::vector<zkhost::Affine<zkhost::Fq>>&, const char*);
-extern template zk_status check_points_host<zkhost::Fq2, DevFq2>(const std::vector<zkhost::Affine<zkhost::Fq2>>&, const char*);
 #endif
+// (msm_g1.cpp / msm_g2.cpp: the group and the four point functions above, over the unit's field)
+#define ZK_MSM_GROUP_DEFINE(HF, DF)                                                                                         \
+    template struct MsmGroup<HF, DF>;                                                                                       \
+    template zk_status check_points_dev<HF, DF>(const zkdev::Affine<DF>*, size_t, const char*);                             \
+    template zk_status check_points_host<HF, DF>(const std::vector<zkhost::Affine<HF>>&, const char*);                      \
+    template zk_status import_affine_dev<DF>(const void*, zkdev::Affine<DF>*, size_t, hipStream_t);                         \
+    template zk_status build_table_dev<DF>(zkdev::Affine<DF>*, size_t, uint32_t, DevBuf&, uint32_t, uint32_t, hipStream_t);
 
 }  // namespace zkrt

@@ -1,9 +1,62 @@
 // The member functions of MsmGroup (msm_group.h) that launch kernels: included by msm_g1.cpp and msm_g2.cpp only, so that no
-// other unit instantiates - and compiles - the ~25 kernels each of them pulls in.
+// other unit instantiates - and compiles - the ~25 kernels each of them pulls in.  The passes both groups launch are included
+// here; the sort (msm_sort.h) and the wrappers of the generated loops (msm_asm_g1.h / msm_asm_g2.h) by the one unit that
+// launches them.
 #pragma once
 #include "msm_group.h"
+#include "msm_accumulate.h"
+#include "msm_reduce.h"
+#include "msm_point_kernels.h"
 
 namespace zkrt {
+
+template <class DF>
+zk_status import_affine_dev(const void* d_src, zkdev::Affine<DF>* dst, size_t n, hipStream_t st) {
+    if (!n) return ZK_OK;
+    ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, (const uint32_t*)d_src, dst, (uint32_t)n);
+    HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class DF>
+zk_status build_table_dev(zkdev::Affine<DF>* table, size_t n, uint32_t npos, DevBuf& scratch, uint32_t n_mult, uint32_t j0, hipStream_t st) {
+    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF) * n));   // chunk of un-normalised slices + prefix products
+    ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, st, table, (uint32_t)n, npos, scratch.as<DF>(),
+              n_mult, j0);
+    HIP_TRY(hipGetLastError());
+    return ZK_OK;
+}
+
+template <class HF, class DF>
+zk_status check_points_dev(const zkdev::Affine<DF>* d_pts, size_t n, const char* what) {
+    if (!n) return ZK_OK;
+    DevBuf flags;
+    ZK_TRY(flags.ensure(4 * n));
+    ZK_LAUNCH(zkdev::k_check_points<DF>, dim3((unsigned)((n + 127) / 128)), dim3(128), 0, g_stream, d_pts, (uint32_t)n, 1u,
+              flags.as<uint32_t>());
+    HIP_TRY(hipGetLastError());
+    std::vector<uint32_t> f(n);
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(hipMemcpy(f.data(), flags.p, 4 * n, hipMemcpyDeviceToHost));
+    for (size_t i = 0; i < n; i++)
+        if (f[i])
+            return fail(ZK_ERR_IO, std::string(what) + ": point " + std::to_string(i) +
+                                       (f[i] & 1 ? " is not on the curve" : " is not in the correct subgroup"));
+    return ZK_OK;
+}
+template <class HF, class DF>
+zk_status check_points_host(const std::vector<zkhost::Affine<HF>>& pts, const char* what) {
+    if (pts.empty()) return ZK_OK;
+    DevBuf stage, d;
+    ZK_TRY(stage.ensure(pts.size() * sizeof(zkhost::Affine<HF>)));
+    ZK_TRY(d.ensure(pts.size() * sizeof(zkdev::Affine<DF>)));
+    HIP_TRY(hipMemcpy(stage.p, pts.data(), pts.size() * sizeof(zkhost::Affine<HF>), hipMemcpyHostToDevice));
+    ZK_TRY(import_affine_dev<DF>(stage.p, d.as<zkdev::Affine<DF>>(), pts.size(), g_stream));
+    zk_status st = check_points_dev<HF, DF>(d.as<zkdev::Affine<DF>>(), pts.size(), what);
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    return st;
+}
+
 
 // one machine-filling launch, three times, the first not counted: the best of the other two in ms (the load-time
 // comparisons of msm_g1.cpp / msm_g2.cpp)
@@ -54,11 +107,7 @@ zk_status MsmGroup<HF, DF>::decode_enqueue(const uint8_t* bases, size_t n, uint3
 
 template <class HF, class DF>
 zk_status MsmGroup<HF, DF>::launch_table_build(DevBuf& scratch, hipStream_t st) {
-    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF) * n_points));   // chunk of un-normalised slices + prefix products
-    ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3((unsigned)((n_points + 127) / 128)), dim3(128), 0, st, table.as<DAffine>(),
-              (uint32_t)n_points, zkdev::MSM_NPOS, scratch.as<DF>(), n_mult, 0u);
-    HIP_TRY(hipGetLastError());
-    return ZK_OK;
+    return build_table_dev<DF>(table.as<DAffine>(), n_points, zkdev::MSM_NPOS, scratch, n_mult, 0u, st);
 }
 
 template <class HF, class DF>
@@ -70,11 +119,8 @@ zk_status MsmGroup<HF, DF>::add_multiples(uint32_t n_mult_) {
     DevBuf grown, scratch;
     grown.is_public = true;
     ZK_TRY(grown.ensure(one * n_mult_));
-    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF) * n_points));
     HIP_TRY(hipMemcpyAsync(grown.p, table.p, one, hipMemcpyDeviceToDevice, g_stream));
-    ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3((unsigned)((n_points + 127) / 128)), dim3(128), 0, g_stream, grown.as<DAffine>(),
-              (uint32_t)n_points, zkdev::MSM_NPOS, scratch.as<DF>(), n_mult_, 1u);
-    HIP_TRY(hipGetLastError());
+    ZK_TRY(build_table_dev<DF>(grown.as<DAffine>(), n_points, zkdev::MSM_NPOS, scratch, n_mult_, 1u, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
     std::swap(table.p, grown.p);       // (the table with one multiple goes with `grown`)
     std::swap(table.cap, grown.cap);
@@ -117,14 +163,11 @@ zk_status MsmGroup<HF, DF>::build(const std::vector<typename MsmGroup<HF, DF>::H
     table.is_public = true;   // bases of a key or of a multiexp: public points, 4.2 GB for the transfer key - freed without the wipe
     ZK_TRY(table.ensure(bytes ? bytes : 1));
     if (!n_points) return ZK_OK;
-    unsigned blocks = (unsigned)((n_points + 127) / 128);
     {
         DevBuf stage;
         ZK_TRY(stage.ensure(sizeof(HAffine) * n_points));
         HIP_TRY(hipMemcpy(stage.p, pts.data(), sizeof(HAffine) * n_points, hipMemcpyHostToDevice));
-        ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3(blocks), dim3(128), 0, g_stream, (const uint32_t*)stage.as<uint32_t>(),
-                  table.as<DAffine>(), (uint32_t)n_points);
-        HIP_TRY(hipGetLastError());
+        ZK_TRY(import_affine_dev<DF>(stage.p, table.as<DAffine>(), n_points, g_stream));
         HIP_TRY(hipStreamSynchronize(g_stream));
     }
     return finish_build(checked, what, with_table);
@@ -142,9 +185,7 @@ zk_status MsmGroup<HF, DF>::build_with_tail(const std::vector<typename MsmGroup<
         stage.is_public = true;
         ZK_TRY(stage.ensure(sizeof(HAffine) * pts.size()));
         HIP_TRY(hipMemcpy(stage.p, pts.data(), sizeof(HAffine) * pts.size(), hipMemcpyHostToDevice));
-        ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3((unsigned)((pts.size() + 127) / 128)), dim3(128), 0, g_stream,
-                  (const uint32_t*)stage.as<uint32_t>(), table.as<DAffine>(), (uint32_t)pts.size());
-        HIP_TRY(hipGetLastError());
+        ZK_TRY(import_affine_dev<DF>(stage.p, table.as<DAffine>(), pts.size(), g_stream));
         HIP_TRY(hipStreamSynchronize(g_stream));
     }
     if (count)
@@ -210,65 +251,14 @@ zk_status MsmGroup<HF, DF>::upload_jobs(const std::vector<MsmJob>& jobs, const M
     return ZK_OK;
 }
 
-// the (digit, point) pairs of every job sorted by bucket: cnt / off of every bucket, toff = its first task
+// the sort and the task order: the group's workspaces handed to the plain functions of msm_g1.cpp (msm_group.h)
 template <class HF, class DF>
 zk_status MsmGroup<HF, DF>::sort_pairs(const MsmPlan& p, hipStream_t st, const zkdev::MsmSelSet& sel_set) {
-    const size_t nj = p.nj;
-    const MsmJob* dj = jobs_d.as<MsmJob>();
-    if (p.lds_sort) {
-        // histogram + scan + scatter of a job inside one workgroup's LDS
-        ProfScope ps("msm_sort_lds", st);
-        ZK_LAUNCH_SYNC(zkdev::k_msm_sort_lds, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), (size_t)nb * 4, st, dj, c,
-                       cnt.as<uint32_t>(), off.as<uint32_t>(), toff.as<uint32_t>(), ntasks.as<uint32_t>(),
-                       pairs.as<uint32_t>(), p.seg, hook_env("ZKAMD_DEBUG_SORT") ? (uint32_t)atoi(hook_env("ZKAMD_DEBUG_SORT")) : 0u, sel_set, recode());
-        return ZK_OK;
-    }
-    // two-level counting sort, every per-digit atomic in LDS (msm.h)
-    const uint32_t fine_log = p.fine_log, fine = 1u << fine_log, n_coarse = p.n_coarse, per_wg = zkdev::MSM_COARSE_SCALARS;
-    const dim3 gridc(p.coarse_wgs, (unsigned)nj);
-    uint32_t* coarse_cnt = coarse.as<uint32_t>();
-    uint32_t* coarse_off = coarse_cnt + nj * (size_t)n_coarse;
-    uint32_t* bin_tasks = coarse_off + nj * (size_t)n_coarse;
-    uint32_t* bin_tbase = bin_tasks + nj * (size_t)n_coarse;
-    HIP_TRY(hipMemsetAsync(coarse_cnt, 0, nj * (size_t)n_coarse * 4, st));
-    {
-        ProfScope ps("msm_sort_coarse", st);
-        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_count, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse, coarse_cnt,
-                       blockbase.as<uint32_t>(), per_wg, sel_set, recode());
-        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
-                       (const uint32_t*)coarse_cnt, coarse_off, (uint32_t*)nullptr, n_coarse);
-        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scatter, gridc, dim3(256), 0, st, dj, c, fine_log, n_coarse,
-                       (const uint32_t*)coarse_off, (const uint32_t*)blockbase.as<uint32_t>(), rank.as<uint2>(), per_wg, sel_set, recode());
-    }
-    {
-        ProfScope ps("msm_sort_fine", st);
-        ZK_LAUNCH_SYNC(zkdev::k_msm_fine_sort, dim3(n_coarse, (unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st, dj,
-                       (const uint2*)rank.as<uint2>(), (const uint32_t*)coarse_cnt, (const uint32_t*)coarse_off, fine, nb,
-                       cnt.as<uint32_t>(), off.as<uint32_t>(), toff.as<uint32_t>(), bin_tasks, pairs.as<uint32_t>(), p.seg);
-        ZK_LAUNCH_SYNC(zkdev::k_msm_coarse_scan, dim3((unsigned)nj), dim3(zkdev::MSM_SORT_THREADS), 0, st,
-                       (const uint32_t*)bin_tasks, bin_tbase, ntasks.as<uint32_t>(), n_coarse);
-        ZK_LAUNCH(zkdev::k_msm_task_offsets, dim3((nb + 255) / 256, (unsigned)nj), dim3(256), 0, st, toff.as<uint32_t>(),
-                  (const uint32_t*)bin_tbase, nb, fine_log, n_coarse);
-    }
-    return ZK_OK;
+    return msm_sort_pairs(p, st, sort_bufs(p), nb, c, recode(), sel_set);
 }
-
-// the tasks of the set in classes of equal length, longest first (`sorted`), and the heavy / light lists of the merge
 template <class HF, class DF>
 zk_status MsmGroup<HF, DF>::order_tasks(const MsmPlan& p, hipStream_t st) {
-    const uint32_t nj = (uint32_t)p.nj;
-    const dim3 gridb((nb + 255) / 256, nj);
-    uint32_t* lenhist = hist.as<uint32_t>();
-    uint32_t* cursor = lenhist + p.n_class;
-    ProfScope ps("msm_task_sort", st);
-    ZK_LAUNCH_SYNC(zkdev::k_msm_task_hist, gridb, dim3(256), 0, st, cnt.as<uint32_t>(), lenhist, nb, p.seg);
-    ZK_LAUNCH_SYNC(zkdev::k_msm_task_base, dim3(1), dim3(zkdev::MSM_SORT_THREADS), 0, st, lenhist, tclass.as<uint32_t>(), counter(p, N_TASKS),
-                   nj, p.seg);
-    ZK_LAUNCH_SYNC(zkdev::k_msm_task_place, gridb, dim3(256), 0, st, cnt.as<uint32_t>(), off.as<uint32_t>(),
-                   toff.as<uint32_t>(), tbase.as<uint32_t>(), tclass.as<uint32_t>(), cursor, sorted.as<uint4>(), counter(p, N_HEAVY),
-                   heavy.as<uint32_t>(), nb, nj, p.merge_inline, p.seg, counter(p, N_LIGHT),
-                   p.use_light ? light.as<uint32_t>() : (uint32_t*)nullptr);
-    return ZK_OK;
+    return msm_order_tasks(p, st, sort_bufs(p), nb);
 }
 
 // tsums[t] = the sum of the points of task t
@@ -277,7 +267,7 @@ zk_status MsmGroup<HF, DF>::accumulate(const MsmPlan& p, hipStream_t st) {
     ProfScope ps(IS_G2 ? "msm_accumulate_g2" : "msm_accumulate_g1", st);
     const unsigned blocks = (unsigned)((p.total_tasks + 127) / 128);
     if (p.acc_asm) {
-        // the generated assembly loop (msm.h, madd_asm.h), then the compiled loop over the few tasks it flagged
+        // the generated assembly loop (msm_asm_g1.h / msm_asm_g2.h, madd_asm.h), then the compiled loop over the few tasks it flagged
         launch_asm_loop(table.as<DAffine>(), pairs.as<uint32_t>(), sorted.as<uint4>(), counter(p, N_TASKS), tsums.as<DPoint>(),
                         counter(p, N_REDO), redo.as<uint32_t>(), blocks, st);
         if (hook_env("ZKAMD_DEBUG_REDO")) dump_redo(p, st, false);

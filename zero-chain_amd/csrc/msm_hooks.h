@@ -1,8 +1,9 @@
-// Test hooks of the table multiples (msm.h MsmRecode; tests/test_table_multiples.py): the recoding of single scalars, a group
+// Test hooks of the table multiples (msm_types.h MsmRecode; tests/test_table_multiples.py): the recoding of single scalars, a group
 // built with multiples - its table entries and launch sets over it - and what ensure_derived bound.  Included by zkamd.cpp
 // under -DZK_TEST_HOOKS only; the multiples and the extra window bits are run-time arguments here.
 #pragma once
 #ifdef ZK_TEST_HOOKS
+#include "msm_recode.h"
 
 namespace zkdev {
 
@@ -46,7 +47,7 @@ inline bool hook_mult_args(uint32_t c, uint32_t n_mult, uint32_t ext) {
 }
 
 // A group over n_bases encoded points with n_mult multiples per slice (extra window bits ext), then - in this order - the table
-// entries (multiple, slice, base) asked for and n_jobs jobs of n scalars through one map (msm.h MsmSelRange over them as in
+// entries (multiple, slice, base) asked for and n_jobs jobs of n scalars through one map (msm_types.h MsmSelRange over them as in
 // zk_hook_msm_select).  A base that is the identity is mapped out, as the key's decoder does it.
 template <class Group, class HA, class HP, class Dec, class Enc>
 zk_status hook_mult_msm(Dec&& decode, Enc&& encode, size_t enc_bytes, uint32_t c, uint32_t n_mult, uint32_t ext, uint32_t n_bases, const uint8_t* bases,

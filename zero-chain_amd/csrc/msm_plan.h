@@ -9,7 +9,7 @@
 #include <algorithm>
 #include <vector>
 #include "../../include/zkamd.h"
-#include "msm.h"
+#include "msm_types.h"
 #include "coop_tail.h"
 
 namespace zkrt {
@@ -113,7 +113,7 @@ inline zk_status msm_plan(MsmPlan& p, bool is_g2, uint32_t c, uint32_t nb, uint3
     p.nj = nj;
     uint64_t total = 0, total_tasks = 0;
     for (size_t k = 0; k < nj; k++) total += (uint64_t)jobs[k].n * maxd;
-    // points per accumulation task (msm.h): a task is a serial chain of ~10 us per point, so the
+    // points per accumulation task (msm_accumulate.h): a task is a serial chain of ~10 us per point, so the
     // long form is for launches that keep the GPU busy for tens of milliseconds anyway
     // ... and the short form (32) is for one proof at a time, where the longest task IS the launch: 5.33 -> 4.80 ms
     // per proof (at 2^20 points it costs 1 % with the table and doubles the variable-base time: kept at 64 there)
@@ -140,8 +140,8 @@ inline zk_status msm_plan(MsmPlan& p, bool is_g2, uint32_t c, uint32_t nb, uint3
     p.n_buckets = nj * (size_t)nb;
     if (p.n_buckets >= (1ull << 32)) return p.refuse("too many buckets in one launch");
     p.n_class = nj * (size_t)seg;
-    // the latency-optimised form of the launch set (many-workgroup sort, bit-plane tail of the bucket reduction: msm.h
-    // passes 1-3 and 5c, coop_tail.h planes / combine): one or a few jobs - and the digit positions of ONE variable-base
+    // the latency-optimised form of the launch set (many-workgroup sort, bit-plane tail of the bucket reduction: msm_sort.h
+    // passes 1-3, msm_reduce.h pass 5c, coop_tail.h planes / combine): one or a few jobs - and the digit positions of ONE variable-base
     // multiexp, a dozen or two jobs over the same large scalar vector, which are as far from filling the machine per job
     // as a lone job is.  Every other set is a chunk of proofs, which folds what is above level 1 on rows too, one
     // workgroup per job (coop_tail.h upper).
@@ -209,7 +209,7 @@ inline zk_status msm_plan(MsmPlan& p, bool is_g2, uint32_t c, uint32_t nb, uint3
     p.lds_sort = (size_t)nb * 4 <= 65536 && !few && !tun.no_lds_sort;
     MsmPlan::Bytes& b = p.bytes;
     if (!p.lds_sort) {
-        // two-level counting sort, every per-digit atomic in LDS (msm.h)
+        // two-level counting sort, every per-digit atomic in LDS (msm_sort.h)
         uint32_t fine_log = tun.sort_fine_log;
         while (fine_log < c - 2 && (nb >> fine_log) > zkdev::MSM_COARSE_MAX) fine_log++;
         if (fine_log > c - 2) fine_log = c - 2;

@@ -391,7 +391,7 @@ k_r1cs_eval(R1csMat ma, R1csMat mb, R1csMat mc, const uint32_t* __restrict__ z, 
 // (value_pairs.h count_merges).  A term of l >= 2 members is emitted by its LAST variable into the pair slot that variable
 // owns, with l in the byte beside the slot (sel_w: the [pa | pb2] slots of the witness vector, sel_c: the [pl | pb1 | (fold:
 // pa)] slots of the C job, per proof); the other members' own slots get 0, and a pair slot that is 0 has the byte 0.  The sort
-// of the job picks the base of l members by the byte (msm.h MsmSelSet).
+// of the job picks the base of l members by the byte (msm_types.h MsmSelSet).
 constexpr uint32_t PAIR_WALK_MAX = 32;
 constexpr uint32_t PAIR_RUN_CAP = 8;   // (a byte per member in a 64-bit word, a nibble per query for the length: pair_decide)
 // Which queries keep the term of variable i of the witness zp, whose value is raw (canonical) - bits: A, B2, L, B1 - and in

@@ -24,7 +24,8 @@
 // (mod.rs:102-160; 3 * (q^4 - q^2 + 1) / r == (x - 1)^2 (x + q)(x^2 + q^2 - 1) + 3), through its own chain:
 //   easy part (q^6 - 1)(q^2 + 1), then  a = f^((x-1)^2),  b = a^(x+q),  c = b^(x^2+q^2-1),  c * f^3.
 #pragma once
-#include "msm.h"
+#include "msm_inverse.h"
+#include "msm_points.h"
 
 namespace zkdev {
 
@@ -70,7 +71,7 @@ ZK_DI void fq_st(uint32_t* p, const Fq32& a) {
     for (int i = 0; i < 12; i++) p[i] = a.l[i];
 }
 
-// a^e for a public 12-word exponent, MSB first (out of line, rolled loops: see fq_pow_qm2 in msm.h)
+// a^e for a public 12-word exponent, MSB first (out of line, rolled loops: see fq_pow_qm2 in msm_inverse.h)
 template <class F>
 ZK_POW_ATTR F pow12(const F& a, const uint32_t* e) {
     F r = a;

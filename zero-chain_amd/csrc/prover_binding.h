@@ -411,7 +411,7 @@ zk_status derived_pairs(zk_params* P, const zk_r1cs* R, const std::vector<HG1A>&
     return ZK_OK;
 }
 
-// ZKAMD_TABLE_MULTIPLES = 1 | 2 | 4 | 8: the odd multiples of every slice the bound tables carry (msm.h MsmRecode).  Table memory
+// ZKAMD_TABLE_MULTIPLES = 1 | 2 | 4 | 8: the odd multiples of every slice the bound tables carry (msm_types.h MsmRecode).  Table memory
 // and bind time grow with it, the (digit, point) pairs of every full-width scalar shrink.  The key's own tables keep one.
 // A key carries them from its first launch set of ZKAMD_TABLE_MULTIPLES_MIN jobs on (default 129: the batch form of a set) or
 // from the pipeline made over it: a proof made alone binds the key as fast as it did and holds no larger tables.
@@ -600,7 +600,7 @@ zk_status ensure_derived(zk_params* P, zk_r1cs* R, bool batch) {
         X.hook_g2.assign(pts2.begin() + X.q[BOUND_G2_ORDER[0]].xbase, pts2.end());
 #endif
     }
-    // The two bound tables, as they were: the odd multiples of their slices (msm.h MsmRecode) come with the first batch
+    // The two bound tables, as they were: the odd multiples of their slices (msm_types.h MsmRecode) come with the first batch
     // (add_table_multiples), and the widths stay those of one multiple (msm_group.h pick_window).
     const uint32_t c_set = pick_window(live + K.n_b1 - (values ? std::min<size_t>(X.q[QL].expect + X.q[QB1].expect, live) : 0), 1);
     ZK_TRY(P->bind.g1d.build_with_tail(pts, P->tab.g1, K.off_a, P->tab.g1.n_points - K.off_a, c_set));

@@ -448,7 +448,7 @@ zk_status params_load(const uint8_t* pk, size_t len, int checked, int device, zk
 
     P->key.vk_bytes.assign(pk, pk + (len - r.left));
     // The query vectors are only LOCATED here; their 10 MB of encodings are gathered in table order and decoded on the
-    // device (msm.h k_decode_uncompressed: round 5 - the host loop it replaces was a quarter of the load).
+    // device (msm_point_kernels.h k_decode_uncompressed: round 5 - the host loop it replaces was a quarter of the load).
     // G1 table order: h | l | a | alpha_g1 | delta_g1 | b_g1 | beta_g1   (the tails carry the scalars 1, r / 1)
     // G2 table order: b_g2 | beta_g2 | delta_g2                            (scalars 1, s)
     struct Section {

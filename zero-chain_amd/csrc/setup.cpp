@@ -5,6 +5,7 @@
 
 #include "handles.h"
 #include "setup.h"
+#include "msm_group.h"   // (import_affine_dev, build_table_dev: the prover's table kernels, msm_g1.cpp / msm_g2.cpp)
 
 using namespace zkrt;
 using zkhost::Fr;
@@ -40,12 +41,8 @@ zk_status build_generator_table(const zkhost::Affine<HF>& g, DevBuf& table) {
     DevBuf stage, scratch;
     ZK_TRY(upload(stage, &g, sizeof(g)));
     ZK_TRY(table.ensure(sizeof(zkdev::Affine<DF>) * zkdev::MSM_NPOS));
-    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(DF)));
-    ZK_LAUNCH(zkdev::k_import_affine<DF>, dim3(1), dim3(128), 0, g_stream, (const uint32_t*)stage.as<uint32_t>(),
-              table.as<zkdev::Affine<DF>>(), 1u);
-    ZK_LAUNCH(zkdev::k_msm_build_table<DF>, dim3(1), dim3(128), 0, g_stream, table.as<zkdev::Affine<DF>>(), 1u, zkdev::MSM_NPOS,
-              scratch.as<DF>(), 1u, 0u);
-    HIP_TRY(hipGetLastError());
+    ZK_TRY(import_affine_dev<DF>(stage.p, table.as<zkdev::Affine<DF>>(), 1, g_stream));
+    ZK_TRY(build_table_dev<DF>(table.as<zkdev::Affine<DF>>(), 1, zkdev::MSM_NPOS, scratch, 1u, 0u, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
     return ZK_OK;
 }

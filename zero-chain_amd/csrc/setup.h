@@ -11,7 +11,8 @@
 //     (k_msm_build_table, the prover's table kernel) and a multiplication is the sum of the entries at the set
 //     bits - one thread per scalar, ~127 mixed additions, then one inversion to the affine form the file holds.
 #pragma once
-#include "msm.h"
+#include "msm_inverse.h"
+#include "msm_points.h"
 #include "ntt.h"
 
 namespace zkdev {

@@ -203,7 +203,7 @@ inline std::vector<int32_t> chains_of(const std::vector<std::vector<Fr>>& probes
 
 // The longest stretch of a run that becomes ONE term z (P_1 + ... + P_l): a run is cut into blocks of RUN_MAX members (ntt.h
 // k_build_scalars has the rule).  Every size follows from it: RUN_MAX - 2 more bases per link (prover_binding.h derived_pairs), as
-// many alternates per pair slot (msm.h MsmSelRange::alt), one bit per length in the words of k_build_scalars.  2 ... 8; 2 is the
+// many alternates per pair slot (msm_types.h MsmSelRange::alt), one bit per length in the words of k_build_scalars.  2 ... 8; 2 is the
 // rule of pairs alone.  (ZK_RUN_MAX: a second library for measurements.)
 #ifndef ZK_RUN_MAX
 #define ZK_RUN_MAX 4

@@ -18,6 +18,8 @@
 #include "host_math.h"
 #include "blake2s.h"
 #include "pairing.h"
+#include "msm_point_kernels.h"   // (k_import_affine / k_check_points over the saturated Fq2: this unit is their one user)
+#include "msm_group.h"           // (check_points_host, import_affine_dev, build_table_dev over G1: msm_g1.cpp)
 #include "coop_verify.h"
 #include "xt_inputs.h"
 #include "ledger.h"
@@ -231,13 +233,14 @@ zk_status upload_frobenius(zk_vk* V) {
     return ZK_OK;
 }
 
-// on-curve and subgroup validation of decoded key points (into_affine): the prover's kernel
-template <class HF, class DF>
-zk_status check_points(const std::vector<zkhost::Affine<HF>>& pts, const char* what) {
+// on-curve and subgroup validation of decoded key points (into_affine): the prover's kernel.  G1 points go through the
+// prover's own function (check_points_host, msm_g1.cpp); the G2 points of a key live on the saturated Fq2 here.
+zk_status check_points_g2(const std::vector<HG2A>& pts, const char* what) {
+    typedef zkdev::Fq2 DF;
     if (pts.empty()) return ZK_OK;
     const size_t n = pts.size();
     DevBuf stage, d, flags;
-    ZK_TRY(upload(stage, pts.data(), n * sizeof(zkhost::Affine<HF>)));
+    ZK_TRY(upload(stage, pts.data(), n * sizeof(HG2A)));
     ZK_TRY(d.ensure(n * sizeof(zkdev::Affine<DF>)));
     ZK_TRY(flags.ensure(4 * n));
     const unsigned blocks = (unsigned)((n + 127) / 128);
@@ -264,13 +267,8 @@ zk_status build_ic_table(zk_vk* V) {
     ZK_TRY(V->ic_table.ensure(sizeof(DG1A) * n * zkdev::MSM_NPOS));
     DevBuf stage, scratch;
     ZK_TRY(upload(stage, V->ic.data(), n * sizeof(HG1A)));
-    const unsigned blocks = (unsigned)((n + 127) / 128);
-    ZK_LAUNCH(zkdev::k_import_affine<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, stage.as<const uint32_t>(),
-              V->ic_table.as<DG1A>(), (uint32_t)n);
-    ZK_TRY(scratch.ensure((size_t)zkdev::MSM_TABLE_CHUNK * 5 * sizeof(zkdev::Fq) * n));
-    ZK_LAUNCH(zkdev::k_msm_build_table<zkdev::Fq>, dim3(blocks), dim3(128), 0, g_stream, V->ic_table.as<DG1A>(), (uint32_t)n,
-              zkdev::MSM_NPOS, scratch.as<zkdev::Fq>(), 1u, 0u);
-    HIP_TRY(hipGetLastError());
+    ZK_TRY(import_affine_dev<zkdev::Fq>(stage.p, V->ic_table.as<DG1A>(), n, g_stream));
+    ZK_TRY(build_table_dev<zkdev::Fq>(V->ic_table.as<DG1A>(), n, zkdev::MSM_NPOS, scratch, 1u, 0u, g_stream));
     HIP_TRY(hipStreamSynchronize(g_stream));
     return ZK_OK;
 }
@@ -308,8 +306,8 @@ zk_status vk_prepare(const uint8_t* bytes, size_t len, int device, zk_vk** out) 
         g1.push_back(alpha_g1);
         g1.push_back(beta_g1);
         g1.push_back(delta_g1);
-        ZK_TRY((check_points<zkhost::Fq, zkdev::Fq>(g1, "vk (G1: ic | alpha | beta | delta)")));
-        ZK_TRY((check_points<zkhost::Fq2, zkdev::Fq2>(std::vector<HG2A>{beta_g2, gamma_g2, delta_g2}, "vk (G2: beta | gamma | delta)")));
+        ZK_TRY((check_points_host<zkhost::Fq, zkdev::Fq>(g1, "vk (G1: ic | alpha | beta | delta)")));
+        ZK_TRY(check_points_g2(std::vector<HG2A>{beta_g2, gamma_g2, delta_g2}, "vk (G2: beta | gamma | delta)"));
     }
     ZK_TRY(upload_frobenius(V));
     ZK_TRY(build_ic_table(V));
@@ -419,7 +417,7 @@ zk_status vk_read_prepared(const uint8_t* bytes, size_t len, int device, zk_vk**
         ZK_TRY(read_g1(r, &tmp, "ic", false));
         V->ic.push_back(tmp);
     }
-    ZK_TRY((check_points<zkhost::Fq, zkdev::Fq>(V->ic, "ic")));
+    ZK_TRY((check_points_host<zkhost::Fq, zkdev::Fq>(V->ic, "ic")));
     ZK_TRY(upload(V->alpha_beta, V->h_alpha_beta.data(), 144 * 4));
     ZK_TRY(upload_frobenius(V));
     ZK_TRY(build_ic_table(V));

@@ -3,8 +3,8 @@
 // What it replaces in the reference (all behind core/proofs/src/confidential.rs:149, in the
 // un-vendored bellman 0.1.0 crate; restated in SURVEY.md Appendix A):
 //   create_proof step 3  (EvaluationDomain H pipeline)   -> ntt.h kernels, NttPlan below
-//   create_proof step 4  (8 x multiexp)                  -> msm.h kernels, MsmGroup below
-//   create_proof step 6  (final fold, into_affine)       -> k_ct_scale_add (coop_tail.cpp) / k_xyzz_normalize_export (msm.h)
+//   create_proof step 4  (8 x multiexp)                  -> the msm_*.h kernels (overview: msm.h), MsmGroup below
+//   create_proof step 6  (final fold, into_affine)       -> k_ct_scale_add (coop_tail.cpp) / k_xyzz_normalize_export (msm_point_kernels.h)
 //   Parameters::read                                     -> prover_key.h params_load
 //   Proof::write                                         -> host_math.h g1/g2_to_compressed
 #include <stdio.h>
@@ -123,7 +123,7 @@ struct ChunkRun {
         }
         HIP_TRY(hipEventRecord(g_ev_fork, g_stream));
         HIP_TRY(hipStreamWaitEvent(side, g_ev_fork, 0));
-        // the bytes of the jobs' pair slots: the lengths of their terms pick the bases (msm.h MsmSelSet)
+        // the bytes of the jobs' pair slots: the lengths of their terms pick the bases (msm_types.h MsmSelSet)
         const CJobLayout& L = plan.layout;
         zkdev::MsmSelSet sels = {};
         if (pairs && RUN_W) sels.r[0] = {P->work.sel_w.as<uint8_t>() + L.pa, P->maps.alt_b2.as<int32_t>(), 0u, (uint32_t)np, L.sel_w, L.w_pair_b2, L.pb2, RUN_W};
@@ -201,7 +201,7 @@ struct ChunkRun {
             }
             (split ? P->work.jobs1a : P->work.jobs1).push_back(ja);
         }
-        // the ranges of jobs whose pair slots follow the bytes (msm.h MsmSelSet): the C' jobs, the A jobs
+        // the ranges of jobs whose pair slots follow the bytes (msm_types.h MsmSelSet): the C' jobs, the A jobs
         const CJobLayout& L = plan.layout;
         zkdev::MsmSelSet sc = {}, sa = {};
         if (pairs && RUN_W) {
@@ -744,7 +744,7 @@ zk_status msm_create(int group, const uint8_t* bases, size_t n, int window_bits,
     M->device = device;
     uint32_t c = 0;
     ZK_TRY(msm_configure(M, group, n, window_bits, variable, &c));
-    // the encodings are decoded on the device (msm.h k_decode_uncompressed: 0.1 ms for 2^20 points, the host loop it
+    // the encodings are decoded on the device (msm_point_kernels.h k_decode_uncompressed: 0.1 ms for 2^20 points, the host loop it
     // replaces 0.11 s); points at infinity are legal multiexp bases: they are mapped out (map = -1)
     DevBuf raw;
     uint32_t n_inf = 0;
@@ -1436,7 +1436,7 @@ zk_status zk_hook_value_runs(const zk_params* p, uint32_t info[12], int32_t* lin
     return ZK_OK;
 } ZK_ABI_CATCH
 // Test hook: n_jobs multiexp jobs over the bases of a G1 handle, each of n scalars (plain words) through one map, with the
-// bytes and alternates of msm.h MsmSelRange over the slots [sel_first, sel_first + sel_n) (sel: sel_n bytes per job, or
+// bytes and alternates of msm_types.h MsmSelRange over the slots [sel_first, sel_first + sel_n) (sel: sel_n bytes per job, or
 // null: jobs without them); out: n_jobs uncompressed points
 zk_status zk_hook_msm_select(zk_msm* M, uint32_t n_jobs, uint32_t n, const uint8_t* scalars, const int32_t* map, const uint8_t* sel,
                              const int32_t* alt, uint32_t sel_first, uint32_t sel_n, uint32_t alt_w, uint8_t* out) try {
