@@ -1138,7 +1138,7 @@ def fq_inverse_on_rows(lib, n=600, seed=77):
 
 def verifier_forms_agree(lib, seed=6, n_in=4, n_aux=10, n_con=13):
     """A handful of proofs is verified on rows (coop_verify.cpp: the accumulator and the lines of B; coop_pairing.cpp: the
-    Miller loops and the final exponentiation with an Fq12 value on six rows): the verdicts are those of the eighteen-lane
+    Miller loops and the final exponentiation with an Fq12 value on twelve rows): the verdicts are those of the eighteen-lane
     kernels and of the one-lane head on the same batch - accepted proofs included, i.e. the 12 x 381-bit comparison with
     e(alpha, beta) comes out equal on every form."""
     r1, asg, P, pk = helpers.small_case(seed, n_in, n_aux, n_con)

@@ -16,6 +16,9 @@
 //
 // Reference: core/pairing/src/bls12_381/mod.rs:47-96 (miller_loop, ell), :98-160 (final_exponentiation), fq12.rs:70-155,
 // fq6.rs, fq2.rs (the tower's products), fq12.rs:42-60 (frobenius_map).
+#ifdef ZK_TEST_HOOKS
+#include "host_common.h"
+#endif
 #include "gpu_rt.h"
 #include "coop_curve.h"
 #include "coop_verify.h"
@@ -63,7 +66,7 @@ ZK_DI CLanes c12_x3(const CLanes& a) {   // limb-wise, un-normalised (limbs belo
     return r;
 }
 // coefficient i of the first operand as it enters row k's sum: f_i, or xi f_i = (a0 - a1) + (a0 + a1) u when it wraps;
-// components below 4 p in, below 9 p out
+// components below 4 p in; out: the first below 9 p (below 4 p where it does not wrap), the second below 8 p
 ZK_DI void c12_operand(const C12Slot& s, uint32_t i, bool wrap, CFq& A0, CFq& A1) {
     const CFq a0 = c12_get(s, i, 0), a1 = c12_get(s, i, 1);
     A0 = c12_sel(wrap, sub_b<4>(a0, a1), a0);
@@ -71,7 +74,8 @@ ZK_DI void c12_operand(const C12Slot& s, uint32_t i, bool wrap, CFq& A0, CFq& A1
 }
 
 // Row (k, c)'s component of f g (operand components below 4 p; result below 2 p).  Magnitudes: a term is at most
-// 9 x 4 + 10 x 4 = 76 p^2, six pairs of them 456 (< 2000); every limb that enters is weakly normalised, so a round's column is
+// 9 x 4 + 10 x 4 = 76 p^2 (the second operand of c12_operand stays below 8 p: neg_b<9> has one p to spare), six pairs of them 456
+// (< 2000); every limb that enters is weakly normalised, so a round's column is
 // 12 x 2^56 + the reduction's 2^56 < 2^60 and its carry fits the 32-bit lane of coop_products.
 ZK_C12_FN CFq c12_mul(C12Lds& lds, uint32_t k, uint32_t c, const CFq& F, const CFq& G) {
     c12_put(lds.f, k, c, F);
@@ -95,7 +99,8 @@ ZK_C12_FN CFq c12_mul(C12Lds& lds, uint32_t k, uint32_t c, const CFq& F, const C
 }
 // Row (k, c)'s component of f (L0 + L2 w^2 + L3 w^3): f_k L0 + F_(k-2) L2 + F_(k-3) L3.  ln: the step's [L0 | L2 | L3]
 // [component][lane]; L0 is a line's constant term as the preparation left it (below 64 p), L2 and L3 are products (below
-// 2 p): 4 x 64 + 5 x 64 + 2 (9 x 2 + 10 x 2) = 652.
+// 2 p): the term of f_k does not wrap, its components stay below 4 p and the negated one (10 p - a) is at most 10 p, so the sum is
+// at most 4 x 64 + 10 x 64 + 2 (9 x 2 + 10 x 2) = 972 p^2.
 ZK_C12_FN CFq c12_line(C12Lds& lds, uint32_t k, uint32_t c, const CFq& f, const CLanes (&ln)[3][2][COOP_W]) {
     c12_put(lds.f, k, c, f);
     __syncthreads();
@@ -127,8 +132,10 @@ ZK_C12_FN CFq c12_line(C12Lds& lds, uint32_t k, uint32_t c, const CFq& f, const 
 // four terms - three Fq products scaled by 3 limb-wise and -+2 z times one - so that the rows of a wave run one stream:
 //     even: c0 = (a0 + a1)(a0 - a1) + (b0 + b1)(b0 - b1) - 2 b0 b1,   c1 = 2 a0 a1 + (b0 + b1)(b0 - b1) + 2 b0 b1
 //     odd:  c0 = 2 a0 b0 - 2 a1 b1,                                   c1 = 2 a1 b0 + 2 a0 b1
-// Magnitudes (units of p; z below 4 - a conjugate may come in -, a below 9 on the rows of w^1; the subtractions take the bound
-// of the worst row): at most 3 (8 x 14 + 8 x 9 + 19 x 4) + 9 = 789 p^2; columns 3 x 3 x 2^56 + 2 x 2^56 < 2^60.
+// Magnitudes (units of p; z below 4 - a conjugate, at most 3, may come in).  On the rows of w^1 a is xi z_2: a0 below 9, a1
+// below 8; elsewhere both below 4.  The subtractions take the bound of the worst row - sub_b<9>: a1 < 8; neg_b<18>: 2 a0 < 18;
+// neg_b<8>: 2 z < 8; each has room left, none is exact.  Even rows: at most 3 (8 x 14 + 8 x 9 + 19 x 4) + 9 = 789 p^2; the rows
+// of w^1: 3 (18 x 4 + 19 x 4) + 9 = 453; columns 3 x 3 x 2^56 + 2 x 2^56 < 2^60.  (tests/test_c12_ops.py reaches these bounds.)
 ZK_C12_FN CFq c12_cyc_sqr(C12Lds& lds, uint32_t k, uint32_t c, const CFq& z) {
     c12_put(lds.f, k, c, z);
     __syncthreads();
@@ -161,15 +168,15 @@ ZK_DI CFq c12_partner(C12Lds& lds, uint32_t k, uint32_t c, const CFq& v) {
 ZK_DI CFq c12_mul_fq2(C12Lds& lds, uint32_t k, uint32_t c, const CFq& a, int j, const CFq& g0, const CFq& g1) {
     const CFq p = c12_partner(lds, k, c, a);
     const CFq a0 = c12_sel(c == 0, a, p), a1r = c12_sel(c == 0, p, a);
-    const CFq a1 = (j & 1) ? neg_b<4>(a1r) : a1r;                              // < 5
-    const CLanes x[1][2] = {{a0.l, c12_sel(c == 0, neg_b<5>(a1), a1).l}};
+    const CFq a1 = (j & 1) ? neg_b<4>(a1r) : a1r;                              // at most 5: 5 p itself for a component 0
+    const CLanes x[1][2] = {{a0.l, c12_sel(c == 0, neg_b<7>(a1), a1).l}};
     const CLanes y[1][2] = {{c12_sel(c == 0, g0, g1).l, c12_sel(c == 0, g1, g0).l}};
     CFq o[1];
     coop_products<1, 2>(x, y, o);
     return o[0];
 }
 ZK_DI CFq c12_one(uint32_t k, uint32_t c) { return (k == 0 && c == 0) ? CFq::one() : CFq::zero(); }
-// a^(q^6): w -> -w  (below 3 p)
+// a^(q^6): w -> -w  (a below 2 p; at most 3 p, and 3 p itself only for a row of zero limbs)
 ZK_DI CFq c12_conj(uint32_t k, const CFq& a) { return (k & 1u) ? neg_b<2>(a) : a; }
 // position of component c of the coefficient of w^k in the F12 words of pairing.h (c0.c0 c0.c1 c0.c2 c1.c0 c1.c1 c1.c2, 24
 // words each: c0 then c1)
@@ -301,7 +308,133 @@ k_c12_final_exp(const uint32_t* __restrict__ f_in, const uint32_t* __restrict__ 
     if (ok && threadIdx.x == 0) ok[item] = lds.flag;
 }
 
+#ifdef ZK_TEST_HOOKS
+// ---- test hook (tests/c12_cases.py, tests/test_c12_ops.py): ONE function of this file on the twelve rows of a workgroup.
+// Row (k, c) loads its component of every operand with coop_load from the Fq28 slots of its case as they are - no import, no
+// reduction, no check of any bound: the caller decides every limb - and stores what the function returns with coop_store as
+// it is.  A slot is that of field_hooks.cpp: 16 words, the 14 limbs and 2 pad words (ignored on input, zero on output); an
+// Fq12 value is 12 slots in the order of the rows, slot 2 k + c.  One workgroup per case, grid n.
+//
+//   op (slots in -> out)                          the function
+//   C12_MUL (f 12 + g 12 -> 12)                   c12_mul(f, g)
+//   C12_SQR (12 -> 12)                            c12_mul(f, f), as the Miller loop squares
+//   C12_LINE (f 12 + 6 -> 12)                     c12_line; the six slots are [L0 | L2 | L3][component], put into LDS as
+//                                                 k_c12_miller lays a step out
+//   C12_CYC_SQR (12 -> 12)                        c12_cyc_sqr
+//   C12_MUL_FQ2_J<j> (a 12 + 24 -> 12)            c12_mul_fq2(a, j, g0, g1), j = 0 1 2; row r's own g0, g1 in slots 12 + 2 r,
+//                                                 13 + 2 r
+//   C12_CONJ (12 -> 12)                           c12_conj
+//   C12_CONJ_MUL (f 12 + g 12 -> 12)              c12_mul(c12_conj(f), g)
+//   C12_EXP_X (12 -> 12)                          c12_exp_x
+//   C12_INV (f 12 + 24 -> 12)                     c12_inv; the C12Frob constants in the order of the key's table: component e
+//                                                 of xi^(k (q^j - 1) / 6) in slot 12 + ((j - 1) 6 + k) 2 + e
+//   C12_EXPORT (12 -> 144 words)                  coop_export at c12_pos(k, c): the F12 words of pairing.h
+// X(name, slots in, words out per case); tests/c12_cases.py holds the same table in the same order.
+#define ZK_HK_C12_OPS(X)        \
+    X(C12_MUL, 24, 192)         \
+    X(C12_SQR, 12, 192)         \
+    X(C12_LINE, 18, 192)        \
+    X(C12_CYC_SQR, 12, 192)     \
+    X(C12_MUL_FQ2_J0, 36, 192)  \
+    X(C12_MUL_FQ2_J1, 36, 192)  \
+    X(C12_MUL_FQ2_J2, 36, 192)  \
+    X(C12_CONJ, 12, 192)        \
+    X(C12_CONJ_MUL, 24, 192)    \
+    X(C12_EXP_X, 12, 192)       \
+    X(C12_INV, 36, 192)         \
+    X(C12_EXPORT, 12, 144)
+
+enum C12HookOp : uint32_t {
+#define X(name, ni, wo) HK_##name,
+    ZK_HK_C12_OPS(X)
+#undef X
+    HK_C12_COUNT
+};
+struct C12HkSlot {
+    Fq28 f;
+    uint32_t pad[2];
+};
+static_assert(sizeof(C12HkSlot) == 64, "a slot is 16 words");
+
+static __global__ void __launch_bounds__(C12_ROWS * COOP_W)
+k_c12_op(uint32_t op, uint32_t ni, uint32_t wo, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    ZK_SHARED C12LdsInv lds;
+    ZK_SHARED CLanes ln[3][2][COOP_W];
+    const uint32_t row = coop_row_in_block(), k = row >> 1, c = row & 1u, item = blockIdx.x;
+    if (item >= n) return;
+    const C12HkSlot* a = (const C12HkSlot*)in + (size_t)item * ni;
+    const CFq f = coop_load(a[row].f);
+    CFq r = f;
+    switch (op) {
+    case HK_C12_MUL: r = c12_mul(lds, k, c, f, coop_load(a[12 + row].f)); break;
+    case HK_C12_SQR: r = c12_mul(lds, k, c, f, f); break;
+    case HK_C12_LINE:
+        if (row < 6) ln[row >> 1][row & 1u][c12_l()] = coop_load(a[12 + row].f).l;
+        __syncthreads();
+        r = c12_line(lds, k, c, f, ln);
+        break;
+    case HK_C12_CYC_SQR: r = c12_cyc_sqr(lds, k, c, f); break;
+    case HK_C12_MUL_FQ2_J0: r = c12_mul_fq2(lds, k, c, f, 0, coop_load(a[12 + 2 * row].f), coop_load(a[13 + 2 * row].f)); break;
+    case HK_C12_MUL_FQ2_J1: r = c12_mul_fq2(lds, k, c, f, 1, coop_load(a[12 + 2 * row].f), coop_load(a[13 + 2 * row].f)); break;
+    case HK_C12_MUL_FQ2_J2: r = c12_mul_fq2(lds, k, c, f, 2, coop_load(a[12 + 2 * row].f), coop_load(a[13 + 2 * row].f)); break;
+    case HK_C12_CONJ: r = c12_conj(k, f); break;
+    case HK_C12_CONJ_MUL: r = c12_mul(lds, k, c, c12_conj(k, f), coop_load(a[12 + row].f)); break;
+    case HK_C12_EXP_X: r = c12_exp_x(lds, k, c, f); break;
+    case HK_C12_INV: {
+        C12Frob fr;
+        for (uint32_t j = 0; j < 2; j++)
+            for (uint32_t e = 0; e < 2; e++) fr.g[j][e] = coop_load(a[12 + (j * 6 + k) * 2 + e].f);
+        r = c12_inv(lds, k, c, f, fr);
+        break;
+    }
+    default: break;   // HK_C12_EXPORT
+    }
+    if (op == HK_C12_EXPORT) {
+        coop_export(f, out + (size_t)item * wo + c12_pos(k, c));
+        return;
+    }
+    C12HkSlot* o = (C12HkSlot*)out + (size_t)item * C12_ROWS + row;
+    coop_store(o->f, r);
+#ifndef ZK_EMU
+    if (coop_lane() >= 14) o->pad[coop_lane() - 14] = 0u;
+#else
+    o->pad[0] = o->pad[1] = 0u;
+#endif
+}
+#endif
+
 }  // namespace zkdev
+
+#ifdef ZK_TEST_HOOKS
+// NOT part of include/zkamd.h (absent from libzkamd.so): n cases of op through k_c12_op, host arrays in and out
+using namespace zkrt;
+extern "C" zk_status zk_hook_c12_op(uint32_t op, size_t n, const uint32_t* in, uint32_t* out) try {
+    static const uint32_t shape[][2] = {
+#define X(name, ni, wo) {ni, wo},
+        ZK_HK_C12_OPS(X)
+#undef X
+    };
+    static_assert(sizeof(shape) / sizeof(shape[0]) == zkdev::HK_C12_COUNT, "one entry of the shape table per op");
+    if (op >= zkdev::HK_C12_COUNT) return fail(ZK_ERR_INVALID_ARGUMENT, "unknown Fq12 op");
+    if (!in || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    if (n > (1u << 16)) return fail(ZK_ERR_INVALID_ARGUMENT, "too many cases");
+    const size_t in_bytes = n * shape[op][0] * 64, out_bytes = n * shape[op][1] * 4;
+    ZK_TRY(use_device(0));
+    DevBuf a, b;
+    a.is_public = b.is_public = true;
+    ZK_TRY(a.ensure(in_bytes));
+    ZK_TRY(b.ensure(out_bytes));
+    HIP_TRY(hipMemcpy(a.p, in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b.p, 0xa5, out_bytes));   // (a word no thread writes is not mistaken for a result)
+    ZK_LAUNCH_SYNC(zkdev::k_c12_op, dim3((unsigned)n), dim3(zkdev::C12_ROWS * zkdev::COOP_W), 0, g_stream, op, shape[op][0], shape[op][1],
+                   a.as<uint32_t>(), b.as<uint32_t>(), (uint32_t)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(hipMemcpy(out, b.p, out_bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_ABI_CATCH
+#endif
 
 namespace zkcoop {
 using zkdev::COOP_W;

@@ -13,6 +13,9 @@
 // Reference: core/bellman-verifier/src/verifier.rs:32-63 (the accumulator), core/pairing/src/bls12_381/mod.rs:335-359,
 // :98-160 (G2Prepared::from_affine: the doubling / addition steps and their coefficient scaling), ec.rs:296-526.
 #include <stdlib.h>
+#ifdef ZK_TEST_HOOKS
+#include "host_common.h"
+#endif
 #include "gpu_rt.h"
 #include "coop_curve.h"
 #include "coop_verify.h"
@@ -190,8 +193,8 @@ ZK_DI void cv_double_step(CFq2& X, CFq2& Y, CFq2& Z, CvLine& l) {
     cv_sqr4<2, 2, 2, 4>(X, Y, Z, add(Y, Z), A, B, zz, t2);                 // X^2, Y^2, Z^2, (Y + Z)^2
     const CFq2 E = add(dbl(A), A);                                         // 3 A            < 6
     cv_sqr4<2, 4, 6, 8>(B, add(X, B), E, add(X, E), C, t1, G, t3);         // B^2, (X + B)^2, E^2, (X + E)^2
-    const CFq2 D = dbl(sub_b<2>(sub_b<2>(t1, A), C));                      // 4 X Y^2        < 16
-    const CFq2 x3 = sub_b<32>(G, dbl(D));                                  //                < 35
+    const CFq2 D = dbl(sub_b<2>(sub_b<2>(t1, A), C));                      // 4 X Y^2        < 16 (and > 4: A, C < 2)
+    const CFq2 x3 = sub_b<32>(G, dbl(D));                                  //                < 35 (2 D > 8: in fact < 27)
     const CFq2 z3 = sub_b<2>(sub_b<2>(t2, B), zz);                         // 2 Y Z          < 8
     const CFq2 c8 = dbl(dbl(dbl(C)));                                      //                < 16
     CFq2 p0, p1, p2;
@@ -595,9 +598,108 @@ k_cv_test_inverse(const uint32_t* __restrict__ in, uint32_t* __restrict__ out, u
     if (i >= n) return;
     coop_export(inv(coop_import(in + (size_t)i * 12), powtab[coop_row_in_block()]), out + (size_t)i * 12);
 }
+
+// test hook (tests/cv_step_cases.py, tests/test_cv_line_steps.py): ONE step of the line preparation on limbs the caller
+// chooses.  A case is 6 (a doubling: X, Y, Z) or 12 (an addition: X, Y, Z, x_Q, y_Q, y_Q^2) slots of field_hooks.cpp's layout
+// (16 words: the 14 limbs and 2 pad words), an Fq2 value its c0 then its c1, loaded with coop_load as they are; out is 12
+// slots: X3, Y3, Z3 as the step leaves them, then the line as cv_put stores it (coop_store, no reduction).  The one-row forms run four cases to a wave
+// (rows past n return before any row operation); the four-row forms run one case per workgroup, and the row that stores is
+// row (case mod 4), so that over a launch every one of the four replicated copies of the running point is read back.
+// X(name, slots in); tests/cv_step_cases.py holds the same table in the same order.
+#define ZK_HK_CV_OPS(X)      \
+    X(CV_DOUBLE_STEP, 6)     \
+    X(CV_ADD_STEP, 12)       \
+    X(CVQ_DOUBLE_STEP, 6)    \
+    X(CVQ_ADD_STEP, 12)
+enum CvHookOp : uint32_t {
+#define X(name, ni) HK_##name,
+    ZK_HK_CV_OPS(X)
+#undef X
+    HK_CV_COUNT
+};
+struct CvHkSlot {
+    Fq28 f;
+    uint32_t pad[2];
+};
+static_assert(sizeof(CvHkSlot) == 64, "a slot is 16 words");
+ZK_DI CFq2 cv_hk_load(const CvHkSlot* a) { return CFq2{coop_load(a[0].f), coop_load(a[1].f)}; }
+ZK_DI void cv_hk_store(CvHkSlot* o, const CFq2& X, const CFq2& Y, const CFq2& Z, const CvLine& l) {
+    const CFq v[12] = {X.c0, X.c1, Y.c0, Y.c1, Z.c0, Z.c1, l.a.c0, l.a.c1, l.b.c0, l.b.c1, l.c.c0, l.c.c1};   // (the line: cv_put's order)
+#pragma unroll
+    for (int s = 0; s < 12; s++) {
+        coop_store(o[s].f, v[s]);
+#ifndef ZK_EMU
+        if (coop_lane() >= 14) o[s].pad[coop_lane() - 14] = 0u;
+#else
+        o[s].pad[0] = o[s].pad[1] = 0u;
+#endif
+    }
+}
+static __global__ void __launch_bounds__(CV_THIN * COOP_W)
+k_cv_test_step(uint32_t op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    const uint32_t i = coop_row();
+    if (i >= n) return;
+    const CvHkSlot* a = (const CvHkSlot*)in + (size_t)i * (op == HK_CV_DOUBLE_STEP ? 6 : 12);
+    CFq2 X = cv_hk_load(a), Y = cv_hk_load(a + 2), Z = cv_hk_load(a + 4);
+    CvLine l;
+    if (op == HK_CV_DOUBLE_STEP)
+        cv_double_step(X, Y, Z, l);
+    else
+        cv_add_step(X, Y, Z, cv_hk_load(a + 6), cv_hk_load(a + 8), cv_hk_load(a + 10), l);
+    cv_hk_store((CvHkSlot*)out + (size_t)i * 12, X, Y, Z, l);
+}
+static __global__ void __launch_bounds__(4 * COOP_W)
+k_cvq_test_step(uint32_t op, const uint32_t* __restrict__ in, uint32_t* __restrict__ out, uint32_t n) {
+    ZK_SHARED QuadLds lds;
+    const uint32_t i = blockIdx.x, r = coop_row_in_block();
+    if (i >= n) return;
+    const CvHkSlot* a = (const CvHkSlot*)in + (size_t)i * (op == HK_CVQ_DOUBLE_STEP ? 6 : 12);
+    CFq2 X = cv_hk_load(a), Y = cv_hk_load(a + 2), Z = cv_hk_load(a + 4);
+    CvLine l;
+    if (op == HK_CVQ_DOUBLE_STEP)
+        cvq_double_step(lds, r, X, Y, Z, l);
+    else
+        cvq_add_step(lds, r, X, Y, Z, cv_hk_load(a + 6), cv_hk_load(a + 8), cv_hk_load(a + 10), l);
+    if (r == (i & 3u)) cv_hk_store((CvHkSlot*)out + (size_t)i * 12, X, Y, Z, l);
+}
 #endif
 
 }  // namespace zkdev
+
+#ifdef ZK_TEST_HOOKS
+// NOT part of include/zkamd.h (absent from libzkamd.so): n cases of one line-preparation step, host arrays in and out
+using namespace zkrt;
+extern "C" zk_status zk_hook_cv_step(uint32_t op, size_t n, const uint32_t* in, uint32_t* out) try {
+    static const uint32_t slots_in[] = {
+#define X(name, ni) ni,
+        ZK_HK_CV_OPS(X)
+#undef X
+    };
+    static_assert(sizeof(slots_in) / sizeof(slots_in[0]) == zkdev::HK_CV_COUNT, "one entry per op");
+    if (op >= zkdev::HK_CV_COUNT) return fail(ZK_ERR_INVALID_ARGUMENT, "unknown line-step op");
+    if (!in || !out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    if (n == 0) return ZK_OK;
+    if (n > (1u << 16)) return fail(ZK_ERR_INVALID_ARGUMENT, "too many cases");
+    const size_t in_bytes = n * slots_in[op] * 64, out_bytes = n * 12 * 64;
+    ZK_TRY(use_device(0));
+    DevBuf a, b;
+    a.is_public = b.is_public = true;
+    ZK_TRY(a.ensure(in_bytes));
+    ZK_TRY(b.ensure(out_bytes));
+    HIP_TRY(hipMemcpy(a.p, in, in_bytes, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemset(b.p, 0xa5, out_bytes));   // (a word no thread writes is not mistaken for a result)
+    if (op == zkdev::HK_CV_DOUBLE_STEP || op == zkdev::HK_CV_ADD_STEP)
+        ZK_LAUNCH(zkdev::k_cv_test_step, dim3((unsigned)((n + zkdev::CV_THIN - 1) / zkdev::CV_THIN)), dim3(zkdev::CV_THIN * zkdev::COOP_W), 0, g_stream,
+                  op, a.as<uint32_t>(), b.as<uint32_t>(), (uint32_t)n);
+    else
+        ZK_LAUNCH_SYNC(zkdev::k_cvq_test_step, dim3((unsigned)n), dim3(4 * zkdev::COOP_W), 0, g_stream, op, a.as<uint32_t>(), b.as<uint32_t>(),
+                       (uint32_t)n);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(g_stream));
+    HIP_TRY(hipMemcpy(out, b.p, out_bytes, hipMemcpyDeviceToHost));
+    return ZK_OK;
+} ZK_ABI_CATCH
+#endif
 
 namespace zkcoop {
 using zkdev::COOP_W;

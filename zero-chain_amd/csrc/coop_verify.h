@@ -27,7 +27,7 @@ size_t g2_prepare_stage_bytes(uint32_t n);
 // (out may be null: the cooperative Miller loop reads the stage itself)
 void verify_g2_prepare(const uint32_t* q, void* stage, uint32_t* out, uint32_t n, uint32_t* st_flags, hipStream_t st);
 
-// ---- coop_pairing.cpp: the Miller loops and the final exponentiation with an Fq12 value on six rows; same arguments and
+// ---- coop_pairing.cpp: the Miller loops and the final exponentiation with an Fq12 value on twelve rows; same arguments and
 // the same words out as pairing.h's k_miller_loop_wide / k_final_exp_wide, except that the line coefficients come in the
 // multiexps' representation: lines0 = the stage of verify_g2_prepare ([n][68][6] field elements), lines1 / lines2 = the
 // key's prepared -gamma / -delta converted once by verify_import_coefs ([68][6]; count = 408 field elements of 12 words).
