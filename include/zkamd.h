@@ -82,6 +82,7 @@
  *   zk_anonymous_witness, zk_anonymous_witness_gpu   value half of AnonymousTransfer::synthesize          circuit/anonymous_transfer.rs:40-54, 56-337
  *   zk_anonymous_prove_batch        synthesize + create_random_proof              anonymous.rs:147-165
  *   zk_anonymous_derive             the derivations at the head of gen_proof      anonymous.rs:97-146
+ *   zk_anonymous_derive_dev         the same, the point work in two kernels, with check_proof's public inputs   anonymous.rs:97-146, 213-264
  *   zk_r1cs_check_batch, zk_transfer_check_batch, zk_anonymous_check_batch
  *                                   TestConstraintSystem::which_is_unsatisfied / is_satisfied   core/proofs/src/circuit/test.rs:253-272
  *   zk_r1cs_stage                   - (the namespace half of which_is_unsatisfied's answer, circuit/test.rs:253-272: the part of a
@@ -558,6 +559,29 @@ typedef struct {   /* AnonymousXt, anonymous.rs:351-359 */
     uint8_t right_ciphertext[32], nonce[32], rsk[32], rvk[32];
 } zk_anonymous_xt;
 zk_status zk_anonymous_derive(const zk_anonymous_request* req, size_t n, zk_anonymous_statement* statements_out, uint8_t* rsk_out);
+/* zk_anonymous_derive_dev: zk_anonymous_derive as a stage on `device` (csrc/anon_derive.h), the front end of
+ *   zk_anonymous_gen_proof_batch reachable on its own.  statements_out (n) and rsk_out (n x 32) are byte for byte what
+ *   zk_anonymous_derive writes.  inputs_out (may be NULL) is n x 104 x 32 bytes: the public inputs of check_proof
+ *   (anonymous.rs:213-264) as plain little-endian Fr, x then y of the twelve enc_keys, the twelve left ciphertexts, the balances'
+ *   left halves, their right halves, the right ciphertext, rvk, g_epoch and the nonce - the order zk_verify_batch takes them for
+ *   this circuit.  Neither the reference nor zk_anonymous_derive hands them out: with them zk_verify_batch checks a proof of a
+ *   derived statement without deriving again.
+ *   Up to ZKAMD_ANON_DERIVE_HOST_MAX requests (read per call; 0 = always the kernels) the whole derivation runs on the
+ *   zk_set_host_threads pool, as zk_anonymous_derive's.  Above it the host keeps what reads the spending key - the checks of the
+ *   indices and the three scalars, pgk = [sk] G, dec_key, rsk, and u = randomness dec_key - amount in Fs - and the device does the
+ *   rest in two launches: every DISTINCT encoding of the batch decoded and tested for prime order once, [randomness] key for the
+ *   recipient and the decoys and [dec_key] g_epoch with a scalar per lane, five multiplications by G per request over a resident
+ *   table, then one lane per output point.  The spending key never reaches the device: what travels is what the statement carries
+ *   to the witness kernels anyway (randomness, alpha, dec_key), with u and the amount.  Those buffers live for the call and are
+ *   zeroed before it returns (zk_memory_stats counts them), on failure too; host copies are wiped.  The host form multiplies
+ *   without branching on a scalar; the device form is NOT constant-time: a zero digit of a lane's scalar skips that lane's addition.
+ *   Both forms write the same bytes and refuse the same requests: ZK_ERR_INVALID_ARGUMENT with zk_anonymous_derive's message for
+ *   the lowest failing request - its indices, then its three scalars, then the first of its points, in the order recipient,
+ *   decoys, g_epoch, enc_balances_left[i], enc_balances_right[i], that does not decode or lies outside the prime-order subgroup.
+ *   After a refusal the outputs hold nothing to rely on.  n == 0 is ZK_OK and touches nothing; a NULL req, statements_out or
+ *   rsk_out with n > 0 is "null argument"; a device out of range is ZK_ERR_INVALID_ARGUMENT in either form. */
+zk_status zk_anonymous_derive_dev(const zk_anonymous_request* req, size_t n, int device, zk_anonymous_statement* statements_out,
+                                  uint8_t* rsk_out, uint8_t* inputs_out);
 /* the two scans (declared with zk_elgamal_decrypt above, where their results are) */
 zk_status zk_confidential_scan(zk_elgamal_table* t, size_t n, const zk_confidential_xt* xts, const uint8_t dec_key[32], uint64_t limit,
                                zk_confidential_scan_result* out);

@@ -26,7 +26,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 __all__ = ["transfer_check", "anonymous_check", "Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
            "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "jubjub_base_mul_dev", "hd_master", "hd_xpgk", "hd_derive", "HD_XKEY_BYTES", "HD_XSK", "HD_XPGK", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
-           "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
+           "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_derive_dev", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
            "ZK_NTT_COSET", "ZK_NTT_IN_BITREV", "ZK_NTT_OUT_BITREV", "shard_bounds", "gather_proofs", "prove_sharded"]
@@ -1540,6 +1540,23 @@ def anonymous_derive(requests, lib=None):
     rsk = np.zeros(32 * n, dtype=np.uint8)
     lib.check(lib.zk_anonymous_derive(requests, n, st, _ptr(rsk)))
     return st, [rsk[32 * i:32 * i + 32].tobytes() for i in range(n)]
+
+
+def anonymous_derive_dev(requests, device=0, want_inputs=False, lib=None):
+    """zk_anonymous_derive_dev: (statements, [rsk bytes]) as anonymous_derive's, the point work in two kernels on `device` above
+    ZKAMD_ANON_DERIVE_HOST_MAX requests; with want_inputs also the public inputs of check_proof, 104 Fr ints per request, in the
+    order verify_proofs takes them for this circuit."""
+    lib = lib or _lib.load()
+    n = len(requests)
+    st = (_lib.AnonymousStatement * n)()
+    rsk = np.zeros(32 * n, dtype=np.uint8)
+    inputs = np.zeros(104 * 32 * n, dtype=np.uint8) if want_inputs else None
+    lib.check(lib.zk_anonymous_derive_dev(requests, n, int(device), st, _ptr(rsk), _ptr(inputs) if want_inputs else None))
+    rsks = [rsk[32 * i:32 * i + 32].tobytes() for i in range(n)]
+    if not want_inputs:
+        return st, rsks
+    flat = bytes_to_scalars(inputs)
+    return st, rsks, [flat[104 * i:104 * (i + 1)] for i in range(n)]
 
 
 def anonymous_gen_proofs(params, matrices, pvk, requests, rs):

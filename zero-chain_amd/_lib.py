@@ -165,6 +165,7 @@ _PROTOS = {
     "zk_transfer_r1cs_fingerprint": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "zk_anonymous_r1cs_load": (C.c_int32, [C.c_int, C.POINTER(C.c_void_p)]),
     "zk_anonymous_derive": (C.c_int32, [C.POINTER(AnonymousRequest), C.c_size_t, C.POINTER(AnonymousStatement), C.c_void_p]),
+    "zk_anonymous_derive_dev": (C.c_int32, [C.POINTER(AnonymousRequest), C.c_size_t, C.c_int, C.POINTER(AnonymousStatement), C.c_void_p, C.c_void_p]),
     "zk_anonymous_gen_proof_batch": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(AnonymousRequest), C.c_void_p,
                                                  C.POINTER(AnonymousXt)]),
     "zk_anonymous_r1cs_fingerprint": (C.c_int32, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),

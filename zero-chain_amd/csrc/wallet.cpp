@@ -13,7 +13,8 @@
 //   ExtendedSpendingKey / ExtendedProofGenerationKey     zface/src/derive/mod.rs:48-228 (master, derive_child, read / write; hd_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
 // the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h),
-// its two combines (elgamal_scan.h, balance_keys.h) and the two of the key derivation's fixed-base multiplier (hd_keys.h).
+// its two combines (elgamal_scan.h, balance_keys.h), the two of the key derivation's fixed-base multiplier (hd_keys.h) and the two
+// of the anonymous transfer's request -> statement stage (anon_derive.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -646,6 +647,8 @@ zk_status anonymous_derive(const zk_anonymous_request* rq, size_t n, zk_anonymou
 
 }  // namespace
 
+#include "anon_derive.h"    // (the same derivation as a stage with a device form: one point kernel with three lane kinds, a combine)
+
 extern "C" {
 
 zk_status zk_anonymous_derive(const zk_anonymous_request* req, size_t n, zk_anonymous_statement* statements_out, uint8_t* rsk_out) try {
@@ -653,32 +656,34 @@ zk_status zk_anonymous_derive(const zk_anonymous_request* req, size_t n, zk_anon
     return anonymous_derive(req, n, statements_out, rsk_out, nullptr);
 } ZK_ABI_CATCH
 
+zk_status zk_anonymous_derive_dev(const zk_anonymous_request* req, size_t n, int device, zk_anonymous_statement* statements_out, uint8_t* rsk_out,
+                                  uint8_t* inputs_out) try {
+    if (n == 0) return ZK_OK;
+    if (!req || !statements_out || !rsk_out) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
+    return zkanon::derive(req, n, device, statements_out, rsk_out, inputs_out, nullptr);
+} ZK_ABI_CATCH
+
 zk_status zk_anonymous_gen_proof_batch(zk_params* p, zk_r1cs* circuit, zk_vk* vk, size_t n, const zk_anonymous_request* req,
                                        const uint8_t* rs, zk_anonymous_xt* out) try {
     if (!p || !circuit || !vk || (n && (!req || !rs || !out))) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
     if (n == 0) return ZK_OK;
-    const size_t n_pts = 4 * ZK_ANONYMOUS_SIZE + 4, n_pub = 2 * n_pts;
+    const size_t n_pub = zkanon::N_PUB;
     std::vector<zk_anonymous_statement> st(n);
-    std::vector<AnonDerived> der(n);
-    std::vector<uint8_t> rsk(n * 32), proofs(n * 192), ok(n), inputs(n * n_pub * 32);
+    std::vector<uint8_t> rsk(n * 32), proofs(n * 192), ok(n), inputs(n * n_pub * 32), tail(n * 96);
     WipeOnExit wipe_st{st.data(), n * sizeof(zk_anonymous_statement)}, wipe_rsk{rsk.data(), rsk.size()};
-    ZK_TRY(anonymous_derive(req, n, st.data(), rsk.data(), der.data()));
+    // the statements, the 104 coordinates of check_proof and the three points the statement does not carry, from the one stage
+    // (anon_derive.h), on the circuit's device - the key's too, or zk_anonymous_prove_batch refuses the pair
+    ZK_TRY(zkanon::derive(req, n, circuit->sys.device, st.data(), rsk.data(), inputs.data(), tail.data()));
     ZK_TRY(zk_anonymous_prove_batch(p, circuit, n, st.data(), rs, proofs.data()));
     for (size_t i = 0; i < n; i++) {
         zk_anonymous_xt& x = out[i];
         memset(&x, 0, sizeof(x));
         memcpy(x.proof, &proofs[i * 192], 192);
-        for (size_t k = 0; k < n_pts; k++) {
-            const zkhost::Fr px = der[i].pub[k].x.from_mont(), py = der[i].pub[k].y.from_mont();
-            memcpy(&inputs[(i * n_pub + 2 * k) * 32], px.l, 32);
-            memcpy(&inputs[(i * n_pub + 2 * k + 1) * 32], py.l, 32);
-        }
         memcpy(x.enc_keys, st[i].enc_keys, sizeof(x.enc_keys));
         memcpy(x.left_ciphertexts, st[i].left_ciphertexts, sizeof(x.left_ciphertexts));
-        const zkwit::JPoint* tail = &der[i].pub[4 * ZK_ANONYMOUS_SIZE];
-        jubjub_encode(tail[0].x, tail[0].y, x.right_ciphertext);
-        jubjub_encode(tail[1].x, tail[1].y, x.rvk);
-        jubjub_encode(tail[3].x, tail[3].y, x.nonce);
+        memcpy(x.right_ciphertext, &tail[96 * i], 32);
+        memcpy(x.rvk, &tail[96 * i + 32], 32);
+        memcpy(x.nonce, &tail[96 * i + 64], 32);
         memcpy(x.rsk, &rsk[i * 32], 32);
     }
     // check_proof (anonymous.rs:213-264)
