@@ -53,6 +53,8 @@
  *   zk_spending_key_from_seed       SpendingKey::from_seed                        core/proofs/src/no_std_aliases/keys.rs:45-58
  *   zk_jubjub_base_mul              EncryptionKey::from_decryption_key            no_std_aliases/keys.rs:250-261
  *   zk_elgamal_encrypt              elgamal::Ciphertext::encrypt                  no_std_aliases/elgamal.rs:46-63
+ *   zk_elgamal_encrypt_dev          Ciphertext::encrypt / neg_encrypt and MultiCiphertexts::encrypt for groups of keys, in two kernels
+ *                                   no_std_aliases/elgamal.rs:46-63, core/proofs/src/crypto_components.rs:60-125, 168-217
  *   zk_elgamal_table_create, zk_elgamal_decrypt, zk_elgamal_table_free
  *                                   elgamal::Ciphertext::decrypt (the brute-force walk) no_std_aliases/elgamal.rs:85-108
  *   zk_elgamal_add                  elgamal::Ciphertext::add / sub                no_std_aliases/elgamal.rs:139-158
@@ -369,6 +371,23 @@ zk_status zk_spending_key_from_seed(const uint8_t* seed, size_t len, uint8_t spe
 zk_status zk_jubjub_base_mul(const uint8_t* scalars, size_t n, uint8_t* points_out);
 zk_status zk_elgamal_encrypt(const uint32_t* values, const uint8_t* randomness, const uint8_t* enc_keys, size_t n,
                              uint8_t* left_out, uint8_t* right_out);
+/* zk_elgamal_encrypt_dev: the same encryption for n GROUPS of k keys as a stage on `device` (csrc/elgamal_encrypt.h).  Group i has
+ *   one randomness r_i: right_i = [r_i]G, left_ij = [v_ij]G + [r_i]pk_ij, G the generator of zk_elgamal_encrypt.
+ *   k = 1 with v >= 0 is Ciphertext::encrypt; a negative value is Ciphertext::neg_encrypt (crypto_components.rs:181-187); k = 3 with
+ *   (amount, amount, fee) under (sender, recipient, sender) is MultiCiphertexts::<Confidential>::encrypt (crypto_components.rs:60-125);
+ *   k = 12 with -amount at the sender, +amount at the recipient and 0 elsewhere is the anonymous one (:168-217).
+ *   values: n x k, |v| < 2^32; randomness: n x 32 bytes, canonical Fs, little-endian; enc_keys: n x k x 32 bytes.
+ *   Outputs: left_out n x k x 32 and right_out n x 32 bytes, Point::write of the affine result (the identity is 01 00 .. 00);
+ *   status_out: n x k bytes.  Keys pass Point::read and as_prime_order, exactly as zk_jubjub_into_xy decides: status_out[i k + j]
+ *   is 0 or the ZK_INTO_XY_* code of that key.  A refused key is a status, never an error: it zeroes its own 32 bytes of left_out
+ *   and touches nothing else - right_i and the other lefts of its group are written as usual.
+ *   ZK_ERR_INVALID_ARGUMENT, nothing written, the index in zk_last_error: k outside 1 .. 16, a value outside (-2^32, 2^32), a
+ *   randomness that is not canonical, a NULL pointer with n > 0.  n == 0 touches nothing.
+ *   Two forms that write the same bytes: host threads for device < 0 or n k <= ZKAMD_ENCRYPT_HOST_MAX (README), else two kernels
+ *   per slice of 4096 groups on `device` - every distinct key decoded once, [r_i]G once per group.  The randomness is the
+ *   sender's secret: every device buffer that held it is zeroed before the call returns.  The device form is not constant-time. */
+zk_status zk_elgamal_encrypt_dev(size_t n, size_t k, const int64_t* values, const uint8_t* randomness, const uint8_t* enc_keys,
+                                 int device, uint8_t* left_out, uint8_t* right_out, uint8_t* status_out);
 zk_status zk_transfer_derive(const zk_transfer_request* req, size_t n, zk_transfer_statement* statements_out, uint8_t* rsk_out);
 /* The balance query at the head of a transfer (zface/src/utils/getter.rs:135-174): the encrypted balance and the pending
  * transfer are added (zk_elgamal_add) and the sum is decrypted (zk_elgamal_decrypt).

@@ -46,7 +46,8 @@ def param_type(ctype, dims):
     const = ctype.startswith("const ")
     core = ctype[6:] if const else ctype
     stars = core.count("*")
-    core = base_type(core.replace("*", ""))
+    pointee_i64 = stars > 0 and core.replace("*", "").strip() == "int64_t"   # (behind a pointer no struct is sized: the real type)
+    core = "i64" if pointee_i64 else base_type(core.replace("*", ""))
     if dims:
         assert stars == 0
         for d in reversed(dims):

@@ -25,7 +25,7 @@ from ._lib import (ZkError, ZkLib, ZK_FR_MONTGOMERY, ZK_NTT_INVERSE, ZK_NTT_COSE
 
 __all__ = ["transfer_check", "anonymous_check", "Parameters", "Proof", "generate_parameters", "generate_random_parameters", "PreparedVerifyingKey", "prepare_verifying_key", "verify_proof", "verify_proofs", "read_proofs",
            "verify_transfer_batch", "jubjub_into_xy", "redjubjub_sign", "redjubjub_verify", "REDJUBJUB_REASONS", "verify_confidential_xts", "verify_anonymous_xts", "execute_confidential_block", "execute_anonymous_block", "execute_asset_block", "ASSET_KINDS", "BLOCK_TAKEN", "g_epoch", "BLOCK_VERDICTS", "BLOCK_ROLLOVER_DUE", "BLOCK_ROLLED", "INTO_XY_REASONS", "SCAN_SENDER", "SCAN_RECIPIENT", "CONFIDENTIAL_XT_POINTS", "ANONYMOUS_XT_POINTS", "ProvingAssignment", "create_proof", "create_random_proof", "create_proofs", "create_proofs_dev", "stream", "bind_host_to_device", "KernelTimer", "kernel_forms",
-           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "jubjub_base_mul_dev", "hd_master", "hd_xpgk", "hd_derive", "HD_XKEY_BYTES", "HD_XSK", "HD_XPGK", "elgamal_encrypt", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
+           "multiexp", "multiexp_cache_release", "memory_stats", "MultiexpContext", "ConstraintMatrices", "create_proofs_from_witness", "fs_rand", "spending_key_from_seed", "jubjub_base_mul", "jubjub_base_mul_dev", "hd_master", "hd_xpgk", "hd_derive", "HD_XKEY_BYTES", "HD_XSK", "HD_XPGK", "elgamal_encrypt", "elgamal_encrypt_dev", "ElGamalTable", "ScanKeys", "scan_confidential_keys", "scan_anonymous_keys", "balances_keys", "balance", "BALANCE_POINTS", "elgamal_add", "ledger_apply", "LEDGER_SUBTRACT", "LEDGER_SKIP", "LEDGER_SCAN_WIDTH", "balance_query", "ELGAMAL_DECRYPT_LIMIT", "ZERO_CIPHERTEXT", "transfer_requests", "transfer_derive", "gen_proofs", "xt_fields", "gen_proof", "XT_FIELDS",
            "FS_MODULUS", "transfer_statements", "transfer_witness", "transfer_witness_gpu", "transfer_r1cs_fingerprint", "anonymous_r1cs_fingerprint", "ANONYMOUS_N_INPUTS", "ANONYMOUS_N_AUX", "anonymous_statements", "anonymous_requests", "anonymous_derive", "anonymous_derive_dev", "anonymous_gen_proofs", "anonymous_witness", "anonymous_witness_gpu", "anonymous_prove_batch",
            "transfer_prove_batch", "TransferPipeline", "set_host_threads", "TRANSFER_N_INPUTS", "TRANSFER_N_AUX", "EvaluationDomain", "XorShiftRng", "fr_rand", "ZkError", "FR_MODULUS",
            "scalars_to_bytes", "bytes_to_scalars", "load_library", "ZK_FR_MONTGOMERY", "ZK_NTT_INVERSE",
@@ -1035,6 +1035,28 @@ def elgamal_encrypt(values, randomness, enc_keys, lib=None):
         lib.check(lib.zk_elgamal_encrypt(_ptr(vb), _ptr(rb), _ptr(kb), n, _ptr(left), _ptr(right)))
     lb, rbb = left.tobytes(), right.tobytes()
     return [lb[i:i + 32] for i in range(0, 32 * n, 32)], [rbb[i:i + 32] for i in range(0, 32 * n, 32)]
+
+
+def elgamal_encrypt_dev(values, randomness, enc_keys, k=1, device=0, lib=None):
+    """zk_elgamal_encrypt_dev: len(randomness) groups of k keys, one Fs randomness per group - values (ints with |v| < 2^32, a
+    negative one is neg_encrypt) and enc_keys (32-byte encodings) flat, group after group.  Host threads up to
+    ZKAMD_ENCRYPT_HOST_MAX lefts, else two kernels on `device`.  Returns (lefts, rights, statuses): n k and n encodings, and per
+    key 0 or its ZK_INTO_XY_* status - a refused key has 32 zero bytes for its left and changes nothing else."""
+    lib = lib or _lib.load()
+    n, k = len(randomness), int(k)
+    if not (len(values) == n * k and len(enc_keys) == n * k):
+        raise ValueError("values and enc_keys must hold k entries per randomness")
+    vb = np.asarray([int(v) for v in values], dtype=np.int64)
+    rb = scalars_to_bytes(randomness)
+    kb = _u8(b"".join(bytes(e) for e in enc_keys), 32 * n * k)
+    left, right, st = np.zeros(32 * n * k, dtype=np.uint8), np.zeros(32 * n, dtype=np.uint8), np.zeros(n * k, dtype=np.uint8)
+    try:
+        if n:
+            lib.check(lib.zk_elgamal_encrypt_dev(n, k, _ptr(vb), _ptr(rb), _ptr(kb), int(device), _ptr(left), _ptr(right), _ptr(st)))
+    finally:
+        rb[:] = 0
+    lb, rbb = left.tobytes(), right.tobytes()
+    return [lb[i:i + 32] for i in range(0, 32 * n * k, 32)], [rbb[i:i + 32] for i in range(0, 32 * n, 32)], [int(s) for s in st]
 
 
 ELGAMAL_DECRYPT_LIMIT = 1000000                                  # the reference's bound, elgamal.rs:100

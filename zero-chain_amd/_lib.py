@@ -187,6 +187,7 @@ _PROTOS = {
     "zk_spending_key_from_seed": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zk_jubjub_base_mul": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "zk_elgamal_encrypt": (C.c_int32, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "zk_elgamal_encrypt_dev": (C.c_int32, [C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "zk_elgamal_table_create": (C.c_int32, [C.c_uint32, C.c_int, C.POINTER(C.c_void_p)]),
     "zk_elgamal_decrypt": (C.c_int32, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_void_p,
                                        C.c_void_p]),

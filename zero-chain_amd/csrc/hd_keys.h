@@ -61,11 +61,12 @@ constexpr size_t SLICE = (size_t)1 << 20;   // lanes per launch
 
 // ---- device
 // [scalar in SLOT_SCALAR] G, extended with T.  tab: TAB_WORDS.  STAGED: every lane of the block takes part (two barriers per window).
+// windows: how many the scalar can occupy, its top digit's carry included (elgamal_encrypt.h: 6 for a 32-bit value).
 template <bool STAGED>
-ZK_DI EP fixed_mul(const Lds& L, const uint32_t* tab, uint32_t* stage) {
+ZK_DI EP fixed_mul(const Lds& L, const uint32_t* tab, uint32_t* stage, uint32_t windows = (uint32_t)WINDOWS) {
     EP acc = zkxt::ep_neutral();
 #pragma unroll 1
-    for (uint32_t w = 0; w < (uint32_t)WINDOWS; w++) {
+    for (uint32_t w = 0; w < windows; w++) {
         const uint32_t* win = tab + (size_t)w * WINDOW_WORDS;
         if constexpr (STAGED) {
             __syncthreads();   // the readers of the window before are done

@@ -13,8 +13,9 @@
 //   ExtendedSpendingKey / ExtendedProofGenerationKey     zface/src/derive/mod.rs:48-228 (master, derive_child, read / write; hd_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
 // the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h),
-// its two combines (elgamal_scan.h, balance_keys.h), the two of the key derivation's fixed-base multiplier (hd_keys.h) and the two
-// of the anonymous transfer's request -> statement stage (anon_derive.h).
+// its two combines (elgamal_scan.h, balance_keys.h), the two of the key derivation's fixed-base multiplier (hd_keys.h), the two
+// of the anonymous transfer's request -> statement stage (anon_derive.h) and the two of the encryption under many keys
+// (elgamal_encrypt.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -648,8 +649,14 @@ zk_status anonymous_derive(const zk_anonymous_request* rq, size_t n, zk_anonymou
 }  // namespace
 
 #include "anon_derive.h"    // (the same derivation as a stage with a device form: one point kernel with three lane kinds, a combine)
+#include "elgamal_encrypt.h"   // (encryption under many keys as such a stage: the same lane bodies, a combine of its own)
 
 extern "C" {
+
+zk_status zk_elgamal_encrypt_dev(size_t n, size_t k, const int64_t* values, const uint8_t* randomness, const uint8_t* enc_keys, int device,
+                                 uint8_t* left_out, uint8_t* right_out, uint8_t* status_out) try {
+    return zkenc::encrypt(n, k, values, randomness, enc_keys, device, left_out, right_out, status_out);
+} ZK_ABI_CATCH
 
 zk_status zk_anonymous_derive(const zk_anonymous_request* req, size_t n, zk_anonymous_statement* statements_out, uint8_t* rsk_out) try {
     if (n && (!req || !statements_out || !rsk_out)) return fail(ZK_ERR_INVALID_ARGUMENT, "null argument");
