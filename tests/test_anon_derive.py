@@ -98,10 +98,16 @@ def test_thirteen_requests_with_shared_encodings(lib, monkeypatch):
 
 
 def test_several_slices(emu_lib, monkeypatch):
-    """the slice loop, with the emulation build's hook: five requests in slices of two, a refusal in the last slice"""
+    """the slice loop, with the emulation build's hook: five requests in slices of two, a refusal in the last slice.  It covers the
+    pool indices: a slice's variable lanes read dk for g_epoch and r for the rest through the slice's pool, the second request of a
+    slice at its own five scalars; beside the model, the nonce and a decoy's left of every request are recomputed here."""
     monkeypatch.setenv("ZKAMD_DEBUG_ANON_SLICE", "2")
     rqs = [ad.request(k) for k in range(5)]
-    check(monkeypatch, emu_lib, rqs)
+    st, _, inputs = check(monkeypatch, emu_lib, rqs)
+    for i, rq in enumerate(rqs):   # the nonce [dk] g_epoch and a decoy's left [r] key, from the request's own scalars
+        d, m = ad.statement_dict(st[i]), next(m for m in range(12) if m not in (rq["s_index"], rq["t_index"]))
+        assert inputs[i][2 * 51:2 * 52] == list(jj.mul(jj.read_point(rq["g_epoch"]), d["dec_key"]))
+        assert d["left_ciphertexts"][m] == jj.write_point(jj.mul(jj.read_point(d["enc_keys"][m]), rq["randomness"]))
     rqs[4] = dict(rqs[4], g_epoch=sc.NOT_A_POINT)
     refused(monkeypatch, emu_lib, rqs, "request 4: g_epoch is not a Jubjub point")
 
@@ -259,14 +265,17 @@ def test_key_derived_device_memory_is_returned_and_wiped(lib, monkeypatch):
 
 
 def test_the_kernels_keep_their_tables_in_lds():
-    """the code object's metadata: both kernels of the stage, no scratch memory, LDS within the 36 864 B of k_rj_check and k_keys_points"""
+    """the code object's metadata: both kernels of the derived-point stage (csrc/derive_stage.h), the pair that serves this entry and
+    zk_elgamal_encrypt_dev and has no per-entry sibling left - no scratch memory, LDS within the 36 864 B of k_rj_check and k_keys_points"""
     import importlib.util
     from zero_chain_amd import _lib
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(root, "tools", "kernel_resources.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    res = {n: r for n, r in mod.kernel_resources(_lib.LIB_PATH).items() if "k_anon_points" in n or "k_anon_combine" in n}
+    every = mod.kernel_resources(_lib.LIB_PATH)
+    assert not [n for n in every if "k_anon_" in n or "k_enc_" in n]
+    res = {n: r for n, r in every.items() if "k_derive_points" in n or "k_derive_combine" in n}
     assert len(res) == 2, sorted(res)
     assert all(r["scratch"] == 0 for r in res.values()), res
     assert all(r["lds"] <= 36864 for r in res.values()), res

@@ -93,7 +93,8 @@ def test_the_old_entry_writes_the_same_bytes(lib, monkeypatch):
 # ---------------------------------------------------------------------------------------------- edges
 def test_value_edges(lib, monkeypatch):
     """0 (no fixed-base value lane: left = [r]pk), +-1, +-(2^32 - 1), +-2^30 (only the sixth window is not zero); one group per
-    value, all under one key and one randomness, so that lefts differ by the value alone"""
+    value, all under one key and one randomness, so that lefts differ by the value alone; and a call whose values are all zero (k = 2,
+    one group): left_j = [r]pk_j"""
     values = [0, 1, -1, ec.TOP, -ec.TOP, 1 << 30, -(1 << 30)]
     r, key = ec.randomness(6, 1)[0], ec.keys(20, 1)[0]
     lefts, rights, _ = check(monkeypatch, lib, (values, [r] * 7, [key] * 7, 1))
@@ -102,6 +103,10 @@ def test_value_edges(lib, monkeypatch):
     # the same as ONE group of seven keys
     lefts7, rights7, _ = check(monkeypatch, lib, (values, [r], [key] * 7, 7))
     assert lefts7 == lefts and rights7 == rights[:1]
+    # every value zero: the descriptors end in the group's padding, with no value lane behind it
+    keys2 = ec.keys(21, 2)
+    lefts0, _, _ = check(monkeypatch, lib, ([0, 0], [r], keys2, 2))
+    assert lefts0 == [jj.write_point(jj.mul(jj.read_point(key_j), r)) for key_j in keys2]
 
 
 def test_scalar_edges(lib, monkeypatch):

@@ -6,7 +6,7 @@ what zk_anonymous_gen_proof_batch costs with it: ONE JSON line.
   256, 1024, 4096 on 16 host threads.  Per n, wall ms (host clock around the entry, which ends in a device synchronise; one warm
   repetition discarded, median of five with min and max, the columns taken in turn inside every repetition):
     host      ZKAMD_ANON_DERIVE_HOST_MAX huge: anonymous_derive_one on the host threads
-    device    ZKAMD_ANON_DERIVE_HOST_MAX=0: the host part, k_anon_points, k_anon_combine
+    device    ZKAMD_ANON_DERIVE_HOST_MAX=0: the host part, k_derive_points, k_derive_combine (csrc/derive_stage.h)
     default   the variable unset
   and the totals of the device form's stages (HIP events, zk_profile_*) in runs of their own: anon_derive_host (the checks, [sk]G,
   the hash, the Fs products: events on an idle stream, so host time), anon_derive_upload, anon_derive_points, anon_derive_combine,

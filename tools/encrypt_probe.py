@@ -8,7 +8,7 @@ the same items in the same process: ONE JSON line.
   device synchronise; one warm repetition discarded, median of five with min and max, the columns taken in turn inside every
   repetition):
     host      ZKAMD_ENCRYPT_HOST_MAX huge: the host threads
-    device    ZKAMD_ENCRYPT_HOST_MAX=0: k_enc_points, k_enc_combine
+    device    ZKAMD_ENCRYPT_HOST_MAX=0: k_derive_points, k_derive_combine (csrc/derive_stage.h)
     default   the variable unset
     old       ONE call of zk_elgamal_encrypt over the n k items, the randomness of a group repeated for each of its keys
   and the totals of the device form's stages (HIP events, zk_profile_*) in runs of their own: encrypt_upload, encrypt_points,

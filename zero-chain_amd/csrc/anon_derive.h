@@ -1,6 +1,6 @@
 // The request -> statement derivation of the anonymous transfer (core/proofs/src/anonymous.rs:97-146; wallet.cpp
 // anonymous_derive_one is the host form) as a stage with a device form: zk_anonymous_derive_dev, and the front end of
-// zk_anonymous_gen_proof_batch.  Included by wallet.cpp below hd_keys.h and the host form, and by no other unit.
+// zk_anonymous_gen_proof_batch.  Included by wallet.cpp below hd_keys.h and the host form, and by elgamal_encrypt.h.
 //
 // Per request the host form decodes 36 points (a square root and a multiplication by the group order each), multiplies 13 times
 // by a scalar of its own and four times by G, and encodes 16 points.  The device form keeps on the host only what reads the
@@ -8,42 +8,33 @@
 //   host    (zk_set_host_threads pool) the index and scalar checks in the host form's order, pgk = [sk]G, dk = BLAKE2s("zech_bdk",
 //           pgk) & mask, rsk = sk + alpha, and u = r dk - amount in Fs.  THE SPENDING KEY NEVER REACHES THE DEVICE (the rule of
 //           hd_keys.h): what travels is what the statement already carries to the witness kernels - randomness, alpha, dec_key -
-//           with u, the amount and the public pgk.  Then the DISTINCT 32-byte encodings of the slice (Encodings below: the
+//           with u, the amount and the public pgk.  Then the DISTINCT 32-byte encodings of the slice (zkstage::Encodings: the
 //           recipient keys, decoys, g_epoch - normally one for the batch - and the 24 balance halves; the identity's encoding, the
 //           balance of a fresh account, is one lane like any other).
-//   device  two launches per slice of requests on the library stream, one wave per block, nothing in scratch memory:
-//     k_anon_points    three lane kinds, split at wave boundaries (the first two counts are padded to 64: a wave takes one path)
-//         decode       lanes [0, D): wallet_stage.h point_lane's first kind - read_point + is_prime_order, x | y in Montgomery
-//                      form and a zkxt::INTO_XY_* status (~2 800 dependent products)
-//         variable     12 per request: point_lane's second kind with BoothMul, the lane's own scalar - [r] key for the recipient
-//                      and the ten decoys, [dk] g_epoch for the nonce (~3 350 with read_point; all lanes add at the same 85 positions)
-//         fixed        5 per request: hd_keys.h fixed_mul over the resident positional table (device_table) - [dk]G the sender's
-//                      key, [u]G the sender's left ciphertext ([r][dk]G - [amount]G as ONE multiplication), [amount]G, [r]G the
-//                      right ciphertext, [alpha]G + pgk = rvk (the addend as a table entry, ext_add_affine) (~300)
-//                      The variable and fixed lanes leave X Y Z T; LDS is k_keys_points': 17 slots x 32 x 64 = 34 816 B.
-//     k_anon_combine   one lane per output point, 16 per request: a source (+ an addend: [amount]G on the recipient's lane), one
-//                      inversion (~330), Point::write's bytes and x | y in Montgomery form.  LDS: pow_windows' 16 slots, 32 768 B.
-//   The choice between this and a launch each of k_keys_points, k_base_mul and a combine: the lane bodies ARE those kernels'
-//   (point_lane, BoothMul, fixed_mul, unchanged), so the one point kernel costs no new arithmetic, keeps their LDS budget and
-//   no scratch (tests/test_anon_derive.py reads both off the code object), saves a launch and k_base_mul's inversion per fixed
-//   lane, and lets the short fixed lanes fill the machine beside the long chains instead of after them.
+//   device  derive_stage.h's two launches per slice of requests, the lanes of a request described as data:
+//         decode       every DISTINCT encoding of the slice
+//         variable     12 per request: [r] key for the recipient and the ten decoys, [dk] g_epoch for the nonce - r and dk read from
+//                      the request's five pool scalars, which are uploaded once
+//         fixed        5 per request, 43 windows each, one per pool scalar: [dk]G the sender's key, [u]G the sender's left
+//                      ciphertext ([r][dk]G - [amount]G as ONE multiplication), [amount]G, [r]G the right ciphertext,
+//                      [alpha]G + pgk = rvk (the addend as a table entry)
+//         combine      16 per request, 24 words each: a source (+ an addend: [amount]G on the recipient's lane); no lane answers
+//                      for a decode lane - the host reads their coordinates and statuses itself
 //   host    the statuses walked in the host form's order - per request the recipient, decoys 0 .. 9, g_epoch, then
 //           enc_balances_left[i], enc_balances_right[i] for i = 0 .. 11 - and the lowest failing request reported with the host
 //           form's message; then the statement, rsk and the 104 public coordinates of check_proof (anonymous.rs:213-264).
 // Both forms write the same bytes and refuse the same requests with the same status and message.
-// Secrets: the scalars, the projective points and everything derived from them live in DevBufs of the call, zeroed before they
-// are released (zk_memory_stats counts them), on success and on every failure; host copies are wiped on every way out.  The
+// Secrets: the scalars, the projective points and everything derived from them live in the DevBufs of the call's Stage, zeroed
+// before they are released (zk_memory_stats counts them), on success and on every failure; host copies are wiped on every way out.  The
 // device form is NOT constant-time: a zero digit of a lane's scalar skips that lane's addition; the host form multiplies with
 // jubjub_var_mul / jubjub_fixed_mul, whose steps do not depend on the scalar.
 #pragma once
-#include "hd_keys.h"
+#include "derive_stage.h"
 
 namespace zkanon {
 
-using zkdev::Fr;
 using zkrt::fail;
-using zkxt::EP;
-using zkxt::Lds;
+using zkstage::NONE;
 
 // ZKAMD_ANON_DERIVE_HOST_MAX: requests up to which the host form runs (read per call; 0 = always the kernels).  Measured
 // (profiles/r32_anon_derive_probe.json, 16 host threads, the 104 public inputs written): the device form is 3.23 ms at 1 request
@@ -52,66 +43,15 @@ using zkxt::Lds;
 constexpr size_t HOST_MAX = 0;
 constexpr size_t N_SET = ZK_ANONYMOUS_SIZE, N_PTS = 4 * N_SET + 4, N_PUB = 2 * N_PTS;
 constexpr size_t ENC_PER_REQ = 3 * N_SET;       // recipient, ten decoys, g_epoch, 24 balance halves
-constexpr uint32_t VAR_PER_REQ = 12, FIX_PER_REQ = 5, OUT_PER_REQ = 16, NO_ADDEND = 0xffffffffu;
-constexpr uint32_t FIX_DK = 0, FIX_U = 1, FIX_AMOUNT = 2, FIX_R = 3, FIX_ALPHA = 4;
+constexpr uint32_t VAR_PER_REQ = 12, FIX_PER_REQ = 5, OUT_PER_REQ = 16;
+constexpr uint32_t FIX_DK = 0, FIX_U = 1, FIX_AMOUNT = 2, FIX_R = 3, FIX_ALPHA = 4;   // the pool scalars of a request, and the fixed lane of each
 constexpr uint32_t OUT_RIGHT = 12, OUT_RVK = 13, OUT_NONCE = 14, OUT_SENDER = 15, OUT_WORDS = 24;
 constexpr size_t SLICE = 4096;   // requests per pair of launches
 static_assert(N_PUB == 104 && ENC_PER_REQ == 36, "the public inputs of check_proof, the decodings of a request");
-static_assert(zkhd::SLOT_SCALAR == zkscan::KEYS_SLOT_SCALAR && zkhd::LDS_WORDS * 4 == zkscan::KEYS_LDS_BYTES && zkscan::KEYS_LDS_BYTES <= 36864,
-              "one LDS layout for the three lane kinds, in k_rj_check's budget");
 
 inline size_t host_max() {
     const char* e = getenv("ZKAMD_ANON_DERIVE_HOST_MAX");
     return e && *e ? (size_t)strtoull(e, nullptr, 10) : HOST_MAX;
-}
-
-// ---- device
-ZK_DI EP ld_ep(const uint32_t* p) { return EP{zkrj::ld_fr(p), zkrj::ld_fr(p + 8), zkrj::ld_fr(p + 16), zkrj::ld_fr(p + 24)}; }
-// enc: d64 x 8 words (n_dec used).  venc, vsc: n_var x 8 words, a base's encoding and the lane's plain scalar.  tab: zkhd::TAB_WORDS.
-// fsc: n_fix x 8 plain words; addends: a table entry (24 words) per request, added on its FIX_ALPHA lane.  xy: n_dec x 16 words,
-// status: n_dec words (point_lane's).  proj: (n_var + n_fix) x 32 words, X Y Z T.
-static __global__ void __launch_bounds__(64)
-k_anon_points(const uint32_t* enc, uint32_t n_dec, uint32_t d64, const uint32_t* venc, const uint32_t* vsc, uint32_t n_var, uint32_t v64,
-              const uint32_t* tab, const uint32_t* fsc, const uint32_t* addends, uint32_t n_fix, uint32_t* xy, uint32_t* status, uint32_t* proj) {
-    ZK_SHARED uint32_t table[zkscan::KEYS_LDS_SLOTS * 8 * 64];
-    const Lds L{table + threadIdx.x};
-    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-    if (t < d64 + v64) {
-        zkscan::point_lane(L, enc, n_dec, d64, venc, n_var, zkscan::BoothMul{vsc}, xy, status, proj);
-        return;
-    }
-    const uint32_t f = t - d64 - v64;
-    if (f >= n_fix) return;
-    L.st(zkhd::SLOT_SCALAR, zkrj::ld_fr(fsc + (size_t)f * 8));
-    EP p = zkhd::fixed_mul<false>(L, tab, nullptr);
-    if (f % FIX_PER_REQ == FIX_ALPHA) {
-        const uint32_t* a = addends + (size_t)(f / FIX_PER_REQ) * zkhd::ENTRY_WORDS;
-        p = zkrj::ext_add_affine(p, zkrj::ld_fr(a), zkrj::ld_fr(a + 8), zkrj::ld_fr(a + 16), false, true);
-    }
-    uint32_t* o = proj + ((size_t)n_var + f) * 32;
-    zkscan::st_fr(o, p.X);
-    zkscan::st_fr(o + 8, p.Y);
-    zkscan::st_fr(o + 16, p.Z);
-    zkscan::st_fr(o + 24, p.T);
-}
-// src: n x 2 words, the lane's source in proj and its addend there (or NO_ADDEND).  out: n x OUT_WORDS words - Point::write's 8,
-// then x | y in Montgomery form.  (Z is never zero where the request is accepted: the addition law is complete on prime-order points.)
-static __global__ void __launch_bounds__(64)
-k_anon_combine(const uint32_t* proj, const uint32_t* src, uint32_t n, uint32_t* out) {
-    ZK_SHARED uint32_t table[16 * 8 * 64];
-    const uint32_t t = blockIdx.x * 64 + threadIdx.x;
-    if (t >= n) return;
-    const Lds L{table + threadIdx.x};
-    EP p = ld_ep(proj + (size_t)src[2 * t] * 32);
-    const uint32_t a = src[2 * t + 1];
-    if (a != NO_ADDEND) p = zkxt::ext_add(p, ld_ep(proj + (size_t)a * 32), zkxt::jubjub_d2());
-    constexpr zkxt::PowDigits EI = zkxt::digits_inverse();
-    const Fr zi = zkxt::pow_windows(L, p.Z, EI);
-    const Fr x = mul(p.X, zi), y = mul(p.Y, zi);
-    uint32_t* o = out + (size_t)t * OUT_WORDS;
-    zkscan::st_fr(o, zkxt::point_words(x, y));
-    zkscan::st_fr(o + 8, x);
-    zkscan::st_fr(o + 16, y);
 }
 
 // ---- host side
@@ -140,37 +80,6 @@ inline void fs_sub_small_ct(const uint64_t a[4], uint32_t v, uint64_t out[4]) {
     zkrj::fs_reduce_ct(neg);
     zkrj::fs_add_ct(a, neg, out);
 }
-
-// the distinct 32-byte encodings of a slice, in the order they are first met
-struct Encodings {
-    std::vector<uint32_t> cell;   // index + 1; 0 = empty
-    std::vector<uint8_t> enc;
-    size_t mask;
-    explicit Encodings(size_t expected) {
-        size_t cap = 16;
-        while (cap < 2 * expected + 2) cap <<= 1;
-        cell.assign(cap, 0);
-        mask = cap - 1;
-        enc.reserve(expected * 32);
-    }
-    size_t size() const { return enc.size() / 32; }
-    uint32_t put(const uint8_t* b) {
-        uint64_t w[4];
-        memcpy(w, b, 32);
-        uint64_t h = w[0] * 0x9e3779b97f4a7c15ull;
-        h = ((h ^ (h >> 29)) + w[1]) * 0xbf58476d1ce4e5b9ull;
-        h = ((h ^ (h >> 31)) + w[2]) * 0x94d049bb133111ebull;
-        h = ((h ^ (h >> 30)) + w[3]) * 0x9e3779b97f4a7c15ull;
-        for (size_t at = (h ^ (h >> 32)) & mask;; at = (at + 1) & mask) {
-            const uint32_t c = cell[at];
-            if (c && !memcmp(&enc[(size_t)(c - 1) * 32], b, 32)) return c - 1;
-            if (!c) {
-                enc.insert(enc.end(), b, b + 32);
-                return (cell[at] = (uint32_t)size()) - 1;
-            }
-        }
-    }
-};
 
 // the fields of a request in the order the host form decodes them: k = 0 the recipient, 1 .. 10 the decoys, 11 g_epoch, then
 // enc_balances_left[i], enc_balances_right[i] at 12 + 2 i, 13 + 2 i
@@ -263,86 +172,54 @@ inline zk_status derive_device(const zk_anonymous_request* rq, size_t n, int dev
     // ---- slices of the requests below the first one refused
     size_t slice = SLICE;
     if (const char* e = zkrt::hook_env("ZKAMD_DEBUG_ANON_SLICE")) slice = std::max<size_t>(1, (size_t)strtoull(e, nullptr, 10));   // test hook: several slices of a few requests
-    zkrt::DevBuf in, out;   // scalars and their multiples: zeroed before they go back, on every way out of this function
-    std::vector<uint32_t> hin, back, ids;   // hin: the slice as it is uploaded, scalars among it; back: coordinates, statuses, encodings - public
-    struct WipeWords {
-        std::vector<uint32_t>& v;
-        ~WipeWords() {
-            if (!v.empty()) explicit_bzero(v.data(), v.size() * 4);
-        }
-    } wipe_hin{hin};
+    zkstage::Stage S;   // the scalars and their multiples, on the device and in the upload's host copy: gone on every way out of this function
+    std::vector<uint32_t> ids;
     for (size_t first = 0; first < good; first += slice) {
         const size_t np = std::min(slice, good - first);
         // the distinct encodings, and where each field of each request went
-        Encodings E(np * ENC_PER_REQ);
+        zkstage::Encodings E(np * ENC_PER_REQ);
         ids.resize(np * ENC_PER_REQ);
         for (size_t i = 0; i < np; i++)
             for (size_t k = 0; k < ENC_PER_REQ; k++) ids[i * ENC_PER_REQ + k] = E.put(field_of(rq[first + i], k));
-        const size_t nd = E.size(), d64 = (nd + 63) / 64 * 64, nv = np * VAR_PER_REQ, v64 = (nv + 63) / 64 * 64, nf = np * FIX_PER_REQ, nc = np * OUT_PER_REQ;
-        // in: encodings | bases | their scalars | fixed scalars | pgk entries | combine sources
-        const size_t w_venc = d64 * 8, w_vsc = w_venc + nv * 8, w_fsc = w_vsc + nv * 8, w_add = w_fsc + nf * 8, w_src = w_add + np * zkhd::ENTRY_WORDS,
-                     in_words = w_src + nc * 2;
-        // out: coordinates | statuses (padded to 4) | the combine's output || the projective points (not read back)
-        const size_t w_st = nd * 16, w_cout = w_st + (nd + 3) / 4 * 4, back_words = w_cout + nc * OUT_WORDS, w_proj = back_words,
-                     out_words = w_proj + (nv + nf) * 32;
-        if (!hin.empty()) explicit_bzero(hin.data(), hin.size() * 4);   // (before assign() may move it)
-        hin.assign(in_words, 0);
-        back.resize(std::max(back.size(), back_words));
-        memcpy(hin.data(), E.enc.data(), nd * 32);
+        const size_t nv = np * VAR_PER_REQ, nf = np * FIX_PER_REQ;
+        S.begin({E.size(), nv, nf, nf, np, np * OUT_PER_REQ, OUT_WORDS, false, "anon_derive_upload", "anon_derive_points", "anon_derive_combine",
+                 "anon_derive_download"});
+        memcpy(S.enc, E.enc.data(), E.size() * 32);
         ZK_TRY(zkrt::for_each_status(np, 64, [&](size_t i) -> zk_status {
             const zk_anonymous_request& q = rq[first + i];
             const Head& h = heads[first + i];
-            for (size_t k = 0; k < VAR_PER_REQ; k++) {   // the lane of field k: the recipient, the decoys, g_epoch
-                memcpy(&hin[w_venc + (i * VAR_PER_REQ + k) * 8], field_of(q, k), 32);
-                memcpy(&hin[w_vsc + (i * VAR_PER_REQ + k) * 8], k == 11 ? h.dk : h.r, 32);
+            const uint32_t var0 = (uint32_t)(i * VAR_PER_REQ), pool0 = (uint32_t)(i * FIX_PER_REQ), fix0 = (uint32_t)nv + pool0;
+            for (uint32_t k = 0; k < VAR_PER_REQ; k++) {   // the lane of field k: the recipient, the decoys, g_epoch
+                memcpy(S.venc + (var0 + k) * 8, field_of(q, k), 32);
+                S.vidx[var0 + k] = pool0 + (k == 11 ? FIX_DK : FIX_R);
             }
-            uint32_t* fs = &hin[w_fsc + i * FIX_PER_REQ * 8];
-            memcpy(fs + 8 * FIX_DK, h.dk, 32);
-            memcpy(fs + 8 * FIX_U, h.u, 32);
-            fs[8 * FIX_AMOUNT] = q.amount;
-            memcpy(fs + 8 * FIX_R, h.r, 32);
-            memcpy(fs + 8 * FIX_ALPHA, h.alpha, 32);
-            memcpy(&hin[w_add + i * zkhd::ENTRY_WORDS], h.pgk_entry, 96);
-            const uint32_t var0 = (uint32_t)(i * VAR_PER_REQ), fix0 = (uint32_t)(nv + i * FIX_PER_REQ);
-            uint32_t* src = &hin[w_src + i * OUT_PER_REQ * 2];
-            for (size_t m = 0; m < N_SET; m++) {
-                src[2 * m] = m == q.s_index ? fix0 + FIX_U : var0 + (uint32_t)key_field(q, m);
-                src[2 * m + 1] = m == q.t_index ? fix0 + FIX_AMOUNT : NO_ADDEND;
+            uint32_t* sc = S.pool + pool0 * 8;
+            memcpy(sc + 8 * FIX_DK, h.dk, 32);
+            memcpy(sc + 8 * FIX_U, h.u, 32);
+            sc[8 * FIX_AMOUNT] = q.amount;
+            memcpy(sc + 8 * FIX_R, h.r, 32);
+            memcpy(sc + 8 * FIX_ALPHA, h.alpha, 32);
+            memcpy(S.addends + i * zkhd::ENTRY_WORDS, h.pgk_entry, 96);
+            for (uint32_t j = 0; j < FIX_PER_REQ; j++) {   // [scalar j]G into slot fix0 + j, the request's pgk added to [alpha]G
+                const uint32_t d[4] = {pool0 + j, (uint32_t)zkhd::WINDOWS, j == FIX_ALPHA ? (uint32_t)i : NONE, fix0 + j};
+                memcpy(S.fix + (pool0 + j) * 4, d, 16);
             }
-            const uint32_t rest[4][2] = {{OUT_RIGHT, fix0 + FIX_R}, {OUT_RVK, fix0 + FIX_ALPHA}, {OUT_NONCE, var0 + 11}, {OUT_SENDER, fix0 + FIX_DK}};
-            for (const auto& o : rest) {
-                src[2 * o[0]] = o[1];
-                src[2 * o[0] + 1] = NO_ADDEND;
-            }
+            auto source = [&](size_t lane, uint32_t from, uint32_t addend) {
+                const uint32_t d[4] = {from, addend, 0, NONE};
+                memcpy(S.src + (i * OUT_PER_REQ + lane) * 4, d, 16);
+            };
+            for (size_t m = 0; m < N_SET; m++)
+                source(m, m == q.s_index ? fix0 + FIX_U : var0 + (uint32_t)key_field(q, m), m == q.t_index ? fix0 + FIX_AMOUNT : NONE);
+            source(OUT_RIGHT, fix0 + FIX_R, NONE);
+            source(OUT_RVK, fix0 + FIX_ALPHA, NONE);
+            source(OUT_NONCE, var0 + 11, NONE);
+            source(OUT_SENDER, fix0 + FIX_DK, NONE);
             return ZK_OK;
         }));
-        ZK_TRY(in.ensure(in_words * 4));
-        ZK_TRY(out.ensure(out_words * 4));
-        const uint32_t* d_in = in.as<const uint32_t>();
-        uint32_t* d_out = out.as<uint32_t>();
-        {
-            zkrt::ProfScope ps("anon_derive_upload");
-            HIP_TRY(hipMemcpyAsync(in.p, hin.data(), in_words * 4, hipMemcpyHostToDevice, zkrt::g_stream));
-        }
-        {
-            zkrt::ProfScope ps("anon_derive_points");
-            ZK_LAUNCH(k_anon_points, dim3((unsigned)(d64 / 64 + v64 / 64 + (nf + 63) / 64)), dim3(64), 0, zkrt::g_stream, d_in, (uint32_t)nd, (uint32_t)d64,
-                      d_in + w_venc, d_in + w_vsc, (uint32_t)nv, (uint32_t)v64, tab, d_in + w_fsc, d_in + w_add, (uint32_t)nf, d_out, d_out + w_st, d_out + w_proj);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            zkrt::ProfScope ps("anon_derive_combine");
-            ZK_LAUNCH(k_anon_combine, dim3((unsigned)((nc + 63) / 64)), dim3(64), 0, zkrt::g_stream, d_out + w_proj, d_in + w_src, (uint32_t)nc, d_out + w_cout);
-        }
-        HIP_TRY(hipGetLastError());
-        {
-            zkrt::ProfScope ps("anon_derive_download");
-            HIP_TRY(hipMemcpyAsync(back.data(), out.p, back_words * 4, hipMemcpyDeviceToHost, zkrt::g_stream));
-        }
-        HIP_TRY(hipStreamSynchronize(zkrt::g_stream));
+        ZK_TRY(S.run(tab));
 
         // ---- the statuses in the host form's order, then what the request's outputs are made of
-        const uint32_t *xy = back.data(), *status = back.data() + w_st, *cout = back.data() + w_cout;
+        const uint32_t *xy = S.xy, *status = S.dstatus, *cout = S.out;
         ZK_TRY(zkrt::for_each_status(np, 64, [&](size_t i) -> zk_status {
             const size_t g = first + i;
             const zk_anonymous_request& q = rq[g];

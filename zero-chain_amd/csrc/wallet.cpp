@@ -13,9 +13,9 @@
 //   ExtendedSpendingKey / ExtendedProofGenerationKey     zface/src/derive/mod.rs:48-228 (master, derive_child, read / write; hd_keys.h)
 // Proving itself (witness kernels, row evaluations, the multiexps) is zkamd.cpp's; the only kernels of this unit are the two of
 // the signature check (redjubjub.h), the two point kernels of the scans' and the balance query's one point stage (wallet_stage.h),
-// its two combines (elgamal_scan.h, balance_keys.h), the two of the key derivation's fixed-base multiplier (hd_keys.h), the two
-// of the anonymous transfer's request -> statement stage (anon_derive.h) and the two of the encryption under many keys
-// (elgamal_encrypt.h).
+// its two combines (elgamal_scan.h, balance_keys.h), the two of the key derivation's fixed-base multiplier (hd_keys.h) and the two
+// of the derived-point stage (derive_stage.h) behind the anonymous transfer's request -> statement derivation (anon_derive.h) and the
+// encryption under many keys (elgamal_encrypt.h).
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -648,8 +648,8 @@ zk_status anonymous_derive(const zk_anonymous_request* rq, size_t n, zk_anonymou
 
 }  // namespace
 
-#include "anon_derive.h"    // (the same derivation as a stage with a device form: one point kernel with three lane kinds, a combine)
-#include "elgamal_encrypt.h"   // (encryption under many keys as such a stage: the same lane bodies, a combine of its own)
+#include "anon_derive.h"    // (the same derivation with a device form: its lanes through derive_stage.h's point kernel and combine)
+#include "elgamal_encrypt.h"   // (encryption under many keys with a device form: its lanes through the same two kernels)
 
 extern "C" {
 
